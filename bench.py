@@ -27,6 +27,12 @@ Rank 0 prints ONE JSON line.
            (MI355X_MICROARCH.md).  "mfma_per_alg_mac" = MFMA issue time per algorithmic product in fp16-pass units.
   cpu_baseline  BASELINE.md section 3 "B0": oracle/xvec_cpu_baseline.c (C + OpenMP restatement of Kaldi's semantics -
            "port", NOT Kaldi) file in / file out, one thread and every host core; rank 0, N=1 only, ~12 s.
+
+A plain run sets up, warms up, times the K steps and prints the headline (metric, value, unit, dtype, ms_per_step, config);
+`dtype` comes from one untimed profiled step after the timed region.  `--full` adds everything else above: the roofline and
+per-kernel times (a one-lane context, K steps more), parity against the fp32 oracle and fp16x3, and with one GPU the sustained
+rate, the other arithmetics and configurations and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step
+computed as DIR/<name>.npy (float32; inputs are seeded, so runs with the same arguments see the same inputs).
 """
 import argparse
 import importlib
@@ -44,7 +50,19 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 PRECISION_NOTES = {"default": None, "bf16x3": 3, "fp16x3": 3, "fp16x2": 2, "fp16mx": 1.25, "fp16mx2": 1.5, "auto": None, "bf16": 1, "fp16": 1}
 KERNEL_PASSES = {"bf16x3": 3, "fp16x3": 3, "fp16x2": 2, "fp16mx": 1.25, "fp16mx2": 1.5, "fp16x3e": 3, "bf16": 1, "fp16": 1}
 PEAK_TFLOPS = 2500.0  # dense bf16/fp16 MFMA, MI355X_MICROARCH.md "Peak BF16/FP16 MFMA ~2.5 PF dense"
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
+
+def dump_output(torch, path, name, t, budget):
+    """Writes the (rows, cols) device tensor `t` as <path>/<name>.npy in float32.  Larger than `budget` bytes: a fixed, seeded
+    sample of its rows (the same rows for the same shape in every run), kept in their original order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    row_bytes = t.shape[1] * 4
+    if t.shape[0] * row_bytes > budget:
+        keep = np.sort(np.random.default_rng(0).choice(t.shape[0], max(1, budget // row_bytes), replace=False))
+        t = t.index_select(0, torch.from_numpy(keep).to(t.device))
+    np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def arithmetic_name(ctx):
@@ -325,7 +343,14 @@ def main():
                     help="batches in flight inside the engine during the timed region (2 = the engine's default, what the command-line "
                          "tools run: consecutive steps alternate between two streams, so the tail kernels of one batch overlap the next "
                          "batch's; the per-kernel durations of the roofline always come from a one-lane context)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline too: roofline and per-kernel times, parity against the fp32 "
+                         "oracle and fp16x3, and (one GPU) the sustained rate, other arithmetics and configurations, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; past 64 MB a fixed, seeded sample of rows)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -395,7 +420,7 @@ def main():
             return P.Context(device_blob=(wt.data_ptr(), wt.numel()), device=local_rank)
         return P.Context(blob=wt.numpy().tobytes(), device=local_rank)
     ctx = make_ctx(args.lanes)
-    ctx_prof = make_ctx(1) if args.lanes != 1 else ctx
+    ctx_prof = make_ctx(1) if args.full and args.lanes != 1 else ctx
     os.environ["XVEC_LANES"] = str(args.lanes)
     del wt
 
@@ -465,6 +490,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        # the output buffer the last timed step wrote (steps rotate over `outs`); each rank writes its own share of the job
+        name = ("frame_outputs" if frame_level else "embeddings") + ("_rank%d" % rank if world > 1 else "")
+        dump_output(torch, args.dump_outputs, name, outs[(step_no[0] - 1) % len(outs)], DUMP_BYTES // world)
     # Per-kernel durations: the same K steps once more, now with a (start, stop) HIP event pair stamped by every dispatch
     # on the launch stream.  Kept out of the timed region above because the event bookkeeping itself costs ~4 % of a step
     # (18 events per step: the profiled steps run at `profiled_ms_per_step`); kernel durations are not affected by it.
@@ -476,16 +505,23 @@ def main():
 
     def step1():
         ctx_prof.forward_batch_device(feats.data_ptr(), offs, o_prof.data_ptr(), o_prof.shape[1], None)
-    # one batch in flight, untimed warm-up then K steps without the event bookkeeping (`single_lane`), then K steps with it
-    for _ in range(max(2, args.warmup)):
+    if args.full:
+        # one batch in flight, untimed warm-up then K steps without the event bookkeeping (`single_lane`), then K steps with it
+        for _ in range(max(2, args.warmup)):
+            step1()
+        dt_one = time_steps(torch, step1, args.steps)
+        ctx_prof.set_profiling(True)
+        tp0 = time.perf_counter()
+        for _ in range(args.steps):
+            step1()
+        torch.cuda.synchronize()
+        dt_prof = time.perf_counter() - tp0
+    else:
+        # a plain run profiles ONE untimed step, alone on the GPU, for `dtype` (the arithmetic of the dominant kernel)
+        torch.cuda.synchronize()
+        ctx_prof.set_profiling(True)
         step1()
-    dt_one = time_steps(torch, step1, args.steps)
-    ctx_prof.set_profiling(True)
-    tp0 = time.perf_counter()
-    for _ in range(args.steps):
-        step1()
-    torch.cuda.synchronize()
-    dt_prof = time.perf_counter() - tp0
+        torch.cuda.synchronize()
     ctx_prof.set_profiling(False)
     prof = ctx_prof.profile_report()
     tt = torch.tensor([dt], dtype=torch.float64, device=cdev)
@@ -503,7 +539,7 @@ def main():
         dom = max(groups, key=lambda k: groups[k]["ms"]) if groups else None
         total_prof_ms = sum(ms / max(1, c) for (_, c, ms) in prof)
         roofline = {"bound": "mfma", "achieved": 0.0, "peak": PEAK_TFLOPS, "unit": "TFLOP/s", "frac": 0.0, "traffic": None}
-        if dom:
+        if dom and args.full:
             g = groups[dom]
             achieved = g["flops"] / (g["ms"] * 1e-3) / 1e12
             pname = re.search(r"<(\w+),", dom)
@@ -545,21 +581,22 @@ def main():
                                           "alg_tflops": v["flops"] / (v["ms"] * 1e-3) / 1e12,
                                           "frac": v["flops"] / (v["ms"] * 1e-3) / 1e12 / PEAK_TFLOPS}
                                       for k, v in groups.items()}}
-        # ---- parity spot check against the oracle on the same inputs (not timed) ------------------------------
-        n2 = H.nm.Nnet3.from_bytes(net.to_bytes(True))
-        n2.apply_nnet_config(cfg_line)
-        ev = H.xo.GraphEvaluator(n2, np.float32)
-        # pooled output: EVERY chunk of the step against the fp32 oracle (256 x 400 frames: ~3 s of numpy); frame-level: two chunks
-        nchk = min(2, B) if frame_level else B
-        f_host = feats[:int(offs[nchk])].cpu().numpy()
-        parity_mean = None
-        if frame_level:
-            ref = np.concatenate([H.xo.compute_all_frames(ev, f_host[offs[i]:offs[i + 1]]) for i in range(nchk)])
-            parity = H.rel_err(outs[0][:int(offs[nchk])].cpu().numpy(), ref)
-        else:
-            ref = np.stack([ev.compute(f_host[offs[i]:offs[i + 1]])[0] for i in range(nchk)])
-            e_ = np.abs(out[:nchk].cpu().numpy().astype(np.float64) - ref).max(axis=1) / np.abs(ref).max(axis=1)
-            parity, parity_mean = float(e_.max()), float(e_.mean())
+        if args.full:
+            # ---- parity spot check against the oracle on the same inputs (not timed) ------------------------------
+            n2 = H.nm.Nnet3.from_bytes(net.to_bytes(True))
+            n2.apply_nnet_config(cfg_line)
+            ev = H.xo.GraphEvaluator(n2, np.float32)
+            # pooled output: EVERY chunk of the step against the fp32 oracle (256 x 400 frames: ~3 s of numpy); frame-level: two chunks
+            nchk = min(2, B) if frame_level else B
+            f_host = feats[:int(offs[nchk])].cpu().numpy()
+            parity_mean = None
+            if frame_level:
+                ref = np.concatenate([H.xo.compute_all_frames(ev, f_host[offs[i]:offs[i + 1]]) for i in range(nchk)])
+                parity = H.rel_err(outs[0][:int(offs[nchk])].cpu().numpy(), ref)
+            else:
+                ref = np.stack([ev.compute(f_host[offs[i]:offs[i + 1]])[0] for i in range(nchk)])
+                e_ = np.abs(out[:nchk].cpu().numpy().astype(np.float64) - ref).max(axis=1) / np.abs(ref).max(axis=1)
+                parity, parity_mean = float(e_.max()), float(e_.mean())
         kernel_precs = sorted(set(m for k in groups for m in re.findall(r"<(\w+),", k)))
         res = {
             "metric": "utterance-embeddings/sec (400-frame chunks)", "value": value, "unit": "utt/s",
@@ -578,16 +615,19 @@ def main():
                        # is stamped with)
                        "library": P.lib().xv_version().decode()},
             "frames_per_sec": world * total_rows * args.steps / dt,
-            "roofline": roofline,
-            "parity_rel_err_vs_oracle_fp32": parity,          # worst chunk
-            "parity_rel_err_vs_oracle_fp32_mean": parity_mean,
-            "parity_chunks_vs_oracle": nchk,
-            "kernels_ms_per_step": {l: ms / max(1, c) for (l, c, ms) in prof},
-            # the same K steps with ONE batch in flight (the context the per-kernel durations come from; rounds 1-4 reported this as
-            # `value`): what the second lane's overlap of one batch's tail kernels with the next batch's GEMMs is worth
-            "single_lane": {"lanes": 1, "value": B * args.steps / dt_one, "unit": "utt/s (this rank)", "ms_per_step": dt_one / args.steps * 1e3},
         }
-        if not frame_level and PRECISION_NOTES[args.precision] != 1 and not args.no_parity_sweep:
+        if args.full:
+            res.update({
+                "roofline": roofline,
+                "parity_rel_err_vs_oracle_fp32": parity,          # worst chunk
+                "parity_rel_err_vs_oracle_fp32_mean": parity_mean,
+                "parity_chunks_vs_oracle": nchk,
+                "kernels_ms_per_step": {l: ms / max(1, c) for (l, c, ms) in prof},
+                # the same K steps with ONE batch in flight (the context the per-kernel durations come from; rounds 1-4 reported this as
+                # `value`): what the second lane's overlap of one batch's tail kernels with the next batch's GEMMs is worth
+                "single_lane": {"lanes": 1, "value": B * args.steps / dt_one, "unit": "utt/s (this rank)", "ms_per_step": dt_one / args.steps * 1e3},
+            })
+        if args.full and not frame_level and PRECISION_NOTES[args.precision] != 1 and not args.no_parity_sweep:
             # every chunk of the step against the three-pass arithmetic on the same inputs: worst chunk of max|d| / max|ref|
             cx = P.Context(model, device=local_rank, precision=P.PRECISIONS["fp16x3"])
             ox = torch.empty_like(out)
@@ -596,7 +636,7 @@ def main():
             d_ = (out - ox).abs().amax(dim=1) / ox.abs().amax(dim=1)
             res["parity_worst_vs_fp16x3"] = {"value": float(d_.max()), "mean": float(d_.mean()), "chunks": int(d_.numel())}
             del cx, ox
-        extras = world == 1 and not args.no_extra_modes
+        extras = args.full and world == 1 and not args.no_extra_modes
         if extras:
             # sustained: the same step for >= 3 s of wall clock (the timed region above is ~30 ms)
             n_sus = max(args.steps, int(3.2 / (dt / args.steps)))
@@ -681,7 +721,7 @@ def main():
                 except Exception as e:   # noqa: BLE001
                     oc[key] = {"error": str(e)}
             res["other_configs"] = oc
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(args.topology, int(np.mean(lens)), args.cpu_seconds)
             except Exception as e:   # noqa: BLE001

@@ -503,23 +503,17 @@ def test_the_reference_feature_pipeline_is_recognised_as_text_and_nothing_else_i
            "select-voiced-frames ark:- scp,s,cs:data/sre10/split8/3/vad.scp ark:- |")
     assert R(ref) == {"feats": "scp:data/sre10/split8/3/feats.scp", "vad": "scp,s,cs:data/sre10/split8/3/vad.scp", "cmn_window": 300,
                       "min_cmn_window": 100, "center": True}
-    # the text the scripts of the reference hold, with their shell variables filled in: every one of them is recognised
-    import glob
-    import re
-    root = "/root/reference/egs/sre/v2/sid"
-    if os.path.isdir(root):
-        seen = 0
-        for f in glob.glob(root + "/nnet3*/**/*.sh", recursive=True):
-            for m in re.finditer(r'feats?="(ark:apply-cmvn-sliding[^"]*)"', open(f).read()):
-                s = m.group(1)
-                for var, val in (("${sdata}", "data/x/split4/1"), ("$sdata", "data/x/split4/1"), ("$norm_vars", "false"),
-                                 ("$center", "true"), ("$cmn_window", "300")):
-                    s = s.replace(var, val)
-                got = R(s)
-                assert got and got["feats"] == "scp:data/x/split4/1/feats.scp" and got["cmn_window"] == 300 and got["center"], (f, s, got)
-                assert got["vad"] in ("", "scp,s,cs:data/x/split4/1/vad.scp"), (f, got)
-                seen += 1
-        assert seen >= 10, seen
+    # the text the scripts of the reference hold, with their shell variables filled in (tests/golden/feature_pipelines/cases.json,
+    # tests/golden/make_feature_pipeline_goldens.py): every one of them is recognised
+    import json
+    seen = 0
+    for c in json.load(open(os.path.join(H.GOLDEN, "feature_pipelines", "cases.json"))):
+        f, s = c["source"], c["rspecifier"]
+        got = R(s)
+        assert got and got["feats"] == "scp:data/x/split4/1/feats.scp" and got["cmn_window"] == 300 and got["center"], (f, s, got)
+        assert got["vad"] in ("", "scp,s,cs:data/x/split4/1/vad.scp"), (f, got)
+        seen += 1
+    assert seen >= 10, seen
     # variations the device front-end implements
     assert R("ark:apply-cmvn-sliding --norm-vars=false --center=false --cmn-window=200 --min-cmn-window=50 ark:/x/raw.ark ark:- |") == \
         {"feats": "ark:/x/raw.ark", "vad": "", "cmn_window": 200, "min_cmn_window": 50, "center": False}

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 out=$R/gpurun_out/$1; var=$2; va=$3; vb=$4; shift 4
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --no-cpu-baseline --no-extra-modes --no-parity-sweep $*"
+B="$R/bench.py --full --no-cpu-baseline --no-extra-modes --no-parity-sweep $*"
 for rep in 1 2 3; do
   for v in $va $vb; do
     env $var=$v python3 $B --steps 40 --warmup 5 > "$out/bench_${var}_${v}_$rep.json" 2> "$out/bench_${var}_${v}_$rep.err"

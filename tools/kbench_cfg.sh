@@ -2,7 +2,7 @@
 # GPU box: per-kernel times of the other BASELINE configurations (3: v5 c-vector, 5: v3 senone head fp16 ragged)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 out=$R/gpurun_out/${1:-cfg}; mkdir -p $out
-run() { label=$1; shift; python3 $R/bench.py --no-cpu-baseline --no-extra-modes "$@" > $out/$label.json 2> $out/$label.err
+run() { label=$1; shift; python3 $R/bench.py --full --no-cpu-baseline --no-extra-modes "$@" > $out/$label.json 2> $out/$label.err
   python3 - <<PY
 import json
 try:

@@ -5,7 +5,7 @@ out=$R/gpurun_out/$1; shift; mkdir -p $out
 for spec in "$@"; do
   IFS=: read label prec envs <<< "$spec"
   ( IFS=,; for kv in $envs; do export "$kv"; done
-    python3 $R/bench.py --precision $prec --no-cpu-baseline --no-extra-modes > $out/$label.json 2> $out/$label.err )
+    python3 $R/bench.py --full --precision $prec --no-cpu-baseline --no-extra-modes > $out/$label.json 2> $out/$label.err )
   python3 - <<PY
 import json
 try:
