@@ -284,6 +284,39 @@ xv_status xv_backend_apply(int device, const float* x, int32_t n, int32_t dim, c
 xv_status xv_segment_mean(int device, const float* x, int32_t n, int32_t dim, const int32_t* seg_off, const int32_t* idx,
                           int32_t n_seg, int32_t acc64, float* out);
 
+/* ---- PLDA back-end (stage 7 of egs/sre/v2/run_sre10.sh: ivector-compute-lda, ivector-compute-plda, ivector-plda-scoring)
+ * Device kernels behind host buffers, fp64 arithmetic on fp32 vectors, deterministic (fixed reduction orders, no float
+ * atomics).  device_ms (optional, may be NULL) receives the kernel time between two events around the launches.
+ *   xv_scatter_stats   segment s = rows idx[seg_off[s] .. seg_off[s+1]) of x [n][dim] (seg_off[0] == 0, offsets do not
+ *                      decrease, every index in [0, n)): s_tot[dim][dim] = sum of x_i x_i^T over every listed row,
+ *                      sums[n_seg][dim] = per-segment sums (list order), s_bet[dim][dim] = sum_s sums_s sums_s^T / n_s.
+ *                      Any output may be NULL.  dim up to 3000 and beyond (the workspace is dim^2 doubles per row chunk).
+ *   xv_plda_transform  Kaldi's Plda::TransformIvector: y = offset + transform x (fp64, transform [dim][dim] row-major),
+ *                      scale = sqrt(dim / sum_d y_d^2 / (psi_d + 1/num_i)) (simple != 0: sqrt(dim) / |y|), y *= scale
+ *                      when normalize != 0; y[n][dim] stored as fp32, scale[n] (optional) as fp64.  dim <= 512.
+ *   xv_plda_score      Kaldi's Plda::LogLikelihoodRatio of trial i = (enrolment row trials[2i] of u [n_u][dim] with
+ *                      num_u examples, test row trials[2i+1] of v [n_v][dim]) into scores[i] (fp64).  An index out of
+ *                      range is XV_ERR_ARG.  dim <= 512.
+ *   xv_lda_estimate    host only (no GPU needed): ivector-compute-lda from the scatter statistics of n mean-subtracted
+ *                      vectors; out[lda_dim][dim + 1] = [L | -L mean]; n_floored (optional) = eigenvalues floored in the
+ *                      normalising transform.
+ *   xv_plda_estimate   host only: ivector-compute-plda's EM (num_em_iters iterations) from per-speaker sums / counts and
+ *                      the scatter statistics of the same rows; mean[dim], transform[dim][dim], psi[dim] (descending);
+ *                      n_floored (optional) = between-class eigenvalues floored at zero.
+ * The device entries fail with XV_ERR_DEVICE when no gfx950 device is usable. */
+xv_status xv_scatter_stats(int device, const float* x, int32_t n, int32_t dim, const int32_t* seg_off, const int32_t* idx,
+                           int32_t n_seg, double* s_tot, double* sums, double* s_bet, float* device_ms);
+xv_status xv_plda_transform(int device, const float* x, int32_t n, int32_t dim, const double* transform, const double* offset,
+                            const double* psi, const double* num, int32_t normalize, int32_t simple, float* y, double* scale,
+                            float* device_ms);
+xv_status xv_plda_score(int device, const float* u, const double* num_u, int32_t n_u, const float* v, int32_t n_v, int32_t dim,
+                        const double* psi, const int32_t* trials, int64_t n_trials, double* scores, float* device_ms);
+xv_status xv_lda_estimate(int32_t dim, int64_t n, const double* s_tot, const double* s_bet, const float* mean,
+                          double total_covariance_factor, double covariance_floor, int32_t lda_dim, float* out, int32_t* n_floored);
+xv_status xv_plda_estimate(int32_t dim, int32_t n_spk, const double* sums, const int32_t* counts, const double* s_tot,
+                           const double* s_bet, int32_t num_em_iters, double* mean, double* transform, double* psi,
+                           int32_t* n_floored);
+
 /* ---- kernel-level entry (unit tests of the HIP GEMM against a plain fp32 reference) ------------------- */
 typedef struct {
   const void* hi;   /* device plane (bf16 / fp16) at logical row 0 */

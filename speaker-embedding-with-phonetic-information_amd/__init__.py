@@ -94,7 +94,8 @@ ABI_SYMBOLS = [
     "xv_calibrate_table", "xv_ctx_set_calibration", "xv_ctx_model_fingerprint", "xv_ctx_share_calibration",
     "xv_ctx_set_calibration_file", "xv_calibration_file_read", "xv_calibration_file_publish", "xv_recognize_feature_pipeline", "xv_ctx_set_lite_layers", "xv_ctx_lite_layers",
     "xv_extract_table", "xv_frontend_cmvn_select", "xv_plan_chunks", "xv_ctx_create_broadcast", "xv_kernel_tdnn_gemm",
-    "xv_backend_apply", "xv_segment_mean", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
+    "xv_backend_apply", "xv_segment_mean", "xv_scatter_stats", "xv_plda_transform", "xv_plda_score", "xv_lda_estimate",
+    "xv_plda_estimate", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
 ]
 
 _lib = None
@@ -561,6 +562,113 @@ def segment_mean(x, segments, acc64=False, device=0):
     _check(L.xv_segment_mean(device, x.ctypes.data, n, dim, off.ctypes.data, idx.ctypes.data if idx.size else None,
                              len(segments), 1 if acc64 else 0, out.ctypes.data))
     return out
+
+
+def _segments(segments):
+    import numpy as np
+    off = np.zeros(len(segments) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(s) for s in segments])
+    idx = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int32) for s in segments]) if len(segments) else
+                               np.zeros(0, np.int32), dtype=np.int32)
+    return off, idx
+
+
+def scatter_stats(x, segments, device=0, return_ms=False):
+    """Scatter statistics of the PLDA back-end on the device (fp64): segment s holds the rows x[segments[s]].  Returns
+    (s_tot, sums, s_bet): sum of x_i x_i^T over every listed row [dim, dim], per-segment sums [n_seg, dim] and
+    sum_s sums_s sums_s^T / n_s [dim, dim]; with return_ms also the kernel time."""
+    import numpy as np
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    n, dim = x.shape
+    off, idx = _segments(segments)
+    s_tot = np.empty((dim, dim)); s_bet = np.empty((dim, dim)); sums = np.empty((len(segments), dim))
+    ms = ctypes.c_float(0)
+    L = lib()
+    L.xv_scatter_stats.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _check(L.xv_scatter_stats(device, x.ctypes.data if n else None, n, dim, off.ctypes.data, idx.ctypes.data if idx.size else None,
+                              len(segments), s_tot.ctypes.data, sums.ctypes.data if len(segments) else None, s_bet.ctypes.data,
+                              ctypes.byref(ms)))
+    return (s_tot, sums, s_bet, ms.value) if return_ms else (s_tot, sums, s_bet)
+
+
+def plda_transform(x, transform, offset, psi, num=None, normalize=True, simple=False, device=0, return_ms=False):
+    """Kaldi's Plda::TransformIvector on the device for every row of x [n, dim] (num: example count per row, default 1).
+    Returns (y float32 [n, dim], scale float64 [n]) (and the kernel time with return_ms)."""
+    import numpy as np
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    n, dim = x.shape
+    t = np.ascontiguousarray(transform, dtype=np.float64)
+    off = np.ascontiguousarray(offset, dtype=np.float64)
+    ps = np.ascontiguousarray(psi, dtype=np.float64)
+    if t.shape != (dim, dim) or off.shape != (dim,) or ps.shape != (dim,):
+        raise XvError(XV_ERR_ARG, "PLDA model shapes do not match the vectors' dimension %d" % dim)
+    num = np.ascontiguousarray(np.ones(n) if num is None else num, dtype=np.float64)
+    y = np.empty((n, dim), np.float32)
+    scale = np.empty(n, np.float64)
+    ms = ctypes.c_float(0)
+    L = lib()
+    L.xv_plda_transform.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 4 + \
+        [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _check(L.xv_plda_transform(device, x.ctypes.data, n, dim, t.ctypes.data, off.ctypes.data, ps.ctypes.data, num.ctypes.data,
+                               1 if normalize else 0, 1 if simple else 0, y.ctypes.data, scale.ctypes.data, ctypes.byref(ms)))
+    return (y, scale, ms.value) if return_ms else (y, scale)
+
+
+def plda_score(u, num_u, v, psi, trials, device=0, return_ms=False):
+    """Kaldi's Plda::LogLikelihoodRatio on the device: trials [m, 2] of (enrolment row of u, test row of v), u [n_u, dim]
+    transformed enrolment vectors with example counts num_u, v [n_v, dim] transformed test vectors.  Returns float64 [m]."""
+    import numpy as np
+    u = np.ascontiguousarray(u, dtype=np.float32)
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    num_u = np.ascontiguousarray(num_u, dtype=np.float64)
+    ps = np.ascontiguousarray(psi, dtype=np.float64)
+    tr = np.ascontiguousarray(np.asarray(trials, dtype=np.int32).reshape(-1, 2))
+    dim = u.shape[1]
+    scores = np.empty(len(tr), np.float64)
+    ms = ctypes.c_float(0)
+    L = lib()
+    L.xv_plda_score.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+    _check(L.xv_plda_score(device, u.ctypes.data, num_u.ctypes.data, u.shape[0], v.ctypes.data, v.shape[0], dim, ps.ctypes.data,
+                           tr.ctypes.data if len(tr) else None, len(tr), scores.ctypes.data if len(tr) else None, ctypes.byref(ms)))
+    return (scores, ms.value) if return_ms else scores
+
+
+def lda_estimate(s_tot, s_bet, n, mean, lda_dim, total_covariance_factor=0.0, covariance_floor=1e-6):
+    """ivector-compute-lda's estimator on the host (no GPU needed) from the scatter statistics of n mean-subtracted
+    vectors: the [lda_dim, dim + 1] float32 matrix [L | -L mean]."""
+    import numpy as np
+    s_tot = np.ascontiguousarray(s_tot, dtype=np.float64)
+    s_bet = np.ascontiguousarray(s_bet, dtype=np.float64)
+    mean = np.ascontiguousarray(mean, dtype=np.float32)
+    dim = s_tot.shape[0]
+    out = np.empty((lda_dim, dim + 1), np.float32)
+    fl = ctypes.c_int32(0)
+    L = lib()
+    L.xv_lda_estimate.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
+                                  ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    _check(L.xv_lda_estimate(dim, n, s_tot.ctypes.data, s_bet.ctypes.data, mean.ctypes.data, total_covariance_factor,
+                             covariance_floor, lda_dim, out.ctypes.data if lda_dim > 0 else None, ctypes.byref(fl)))
+    return out
+
+
+def plda_estimate(sums, counts, s_tot, s_bet, num_em_iters=10):
+    """ivector-compute-plda's EM on the host (no GPU needed) from per-speaker sums [n_spk, dim], counts [n_spk] and the
+    scatter statistics of the same rows.  Returns (mean, transform, psi), float64."""
+    import numpy as np
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    s_tot = np.ascontiguousarray(s_tot, dtype=np.float64)
+    s_bet = np.ascontiguousarray(s_bet, dtype=np.float64)
+    n_spk, dim = sums.shape
+    mean = np.empty(dim); transform = np.empty((dim, dim)); psi = np.empty(dim)
+    fl = ctypes.c_int32(0)
+    L = lib()
+    L.xv_plda_estimate.argtypes = [ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 4 + [ctypes.c_int32] + [ctypes.c_void_p] * 4
+    _check(L.xv_plda_estimate(dim, n_spk, sums.ctypes.data, counts.ctypes.data, s_tot.ctypes.data, s_bet.ctypes.data, num_em_iters,
+                              mean.ctypes.data, transform.ctypes.data, psi.ctypes.data, ctypes.byref(fl)))
+    return mean, transform, psi
 
 
 def kernel_tdnn_gemm(desc):

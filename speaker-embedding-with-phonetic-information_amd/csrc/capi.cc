@@ -16,6 +16,8 @@
 #include "fuse_pipe.h"
 #include "multi_gpu.h"
 #include "nnet3_raw.h"
+#include "plda.h"
+#include "plda_kernels.h"
 #include "program.h"
 #include "table_extract.h"
 
@@ -546,6 +548,77 @@ xv_status xv_segment_mean(int device, const float* x, int32_t n, int32_t dim, co
   if (n_seg > 0 && seg_off[n_seg] > 0 && !idx) return Fail(XV_ERR_ARG, "xv_segment_mean: null index list");
   return Guard([&] {
     xv::SegmentMean(device, x, n, dim, seg_off, idx, n_seg, acc64 != 0, out);
+    return XV_OK;
+  });
+}
+
+xv_status xv_scatter_stats(int device, const float* x, int32_t n, int32_t dim, const int32_t* seg_off, const int32_t* idx,
+                           int32_t n_seg, double* s_tot, double* sums, double* s_bet, float* device_ms) {
+  if (n < 0 || dim < 1 || n_seg < 0 || !seg_off || (n > 0 && !x)) return Fail(XV_ERR_ARG, "xv_scatter_stats: bad argument");
+  if (seg_off[0] != 0) return Fail(XV_ERR_ARG, "xv_scatter_stats: segment offsets must start at 0");
+  for (int s = 0; s < n_seg; ++s)
+    if (seg_off[s + 1] < seg_off[s]) return Fail(XV_ERR_ARG, "xv_scatter_stats: segment offsets must not decrease");
+  if (seg_off[n_seg] > 0 && !idx) return Fail(XV_ERR_ARG, "xv_scatter_stats: null index list");
+  for (int i = 0; i < seg_off[n_seg]; ++i)
+    if (idx[i] < 0 || idx[i] >= n) return Fail(XV_ERR_ARG, "xv_scatter_stats: row index out of range");
+  return Guard([&] {
+    xv::ScatterStats(device, x, n, dim, seg_off, idx, n_seg, s_tot, sums, s_bet, device_ms);
+    return XV_OK;
+  });
+}
+
+xv_status xv_plda_transform(int device, const float* x, int32_t n, int32_t dim, const double* transform, const double* offset,
+                            const double* psi, const double* num, int32_t normalize, int32_t simple, float* y, double* scale,
+                            float* device_ms) {
+  if (n < 0 || dim < 1 || !transform || !offset || !psi || (n > 0 && (!x || !num || !y)))
+    return Fail(XV_ERR_ARG, "xv_plda_transform: bad argument");
+  if (dim > xv::kPldaMaxDim) return Fail(XV_ERR_ARG, "xv_plda_transform: dimension larger than " + std::to_string(xv::kPldaMaxDim));
+  return Guard([&] {
+    xv::PldaTransform(device, x, n, dim, transform, offset, psi, num, normalize != 0, simple != 0, y, scale, device_ms);
+    return XV_OK;
+  });
+}
+
+xv_status xv_plda_score(int device, const float* u, const double* num_u, int32_t n_u, const float* v, int32_t n_v, int32_t dim,
+                        const double* psi, const int32_t* trials, int64_t n_trials, double* scores, float* device_ms) {
+  if (n_u < 0 || n_v < 0 || dim < 1 || n_trials < 0 || !psi || (n_trials > 0 && (!u || !num_u || !v || !trials || !scores)))
+    return Fail(XV_ERR_ARG, "xv_plda_score: bad argument");
+  if (dim > xv::kPldaMaxDim) return Fail(XV_ERR_ARG, "xv_plda_score: dimension larger than " + std::to_string(xv::kPldaMaxDim));
+  for (int64_t i = 0; i < n_trials; ++i)
+    if (trials[2 * i] < 0 || trials[2 * i] >= n_u || trials[2 * i + 1] < 0 || trials[2 * i + 1] >= n_v)
+      return Fail(XV_ERR_ARG, "xv_plda_score: trial " + std::to_string(i) + " indexes a row that does not exist");
+  return Guard([&] {
+    xv::PldaScore(device, u, num_u, n_u, v, n_v, dim, psi, trials, (long)n_trials, scores, device_ms);
+    return XV_OK;
+  });
+}
+
+xv_status xv_lda_estimate(int32_t dim, int64_t n, const double* s_tot, const double* s_bet, const float* mean,
+                          double total_covariance_factor, double covariance_floor, int32_t lda_dim, float* out, int32_t* n_floored) {
+  if (dim < 1 || n < 1 || !s_tot || !s_bet || !mean || !out) return Fail(XV_ERR_ARG, "xv_lda_estimate: bad argument");
+  if (lda_dim < 1 || lda_dim > dim)
+    return Fail(XV_ERR_ARG, "LDA dimension " + std::to_string(lda_dim) + " is out of range for input dimension " + std::to_string(dim));
+  return Guard([&] {
+    const int f = xv::LdaFromStats(dim, (long)n, s_tot, s_bet, mean, total_covariance_factor, covariance_floor, lda_dim, out);
+    if (n_floored) *n_floored = f;
+    return XV_OK;
+  });
+}
+
+xv_status xv_plda_estimate(int32_t dim, int32_t n_spk, const double* sums, const int32_t* counts, const double* s_tot,
+                           const double* s_bet, int32_t num_em_iters, double* mean, double* transform, double* psi,
+                           int32_t* n_floored) {
+  if (dim < 1 || n_spk < 1 || num_em_iters < 0 || !sums || !counts || !s_tot || !s_bet || !mean || !transform || !psi)
+    return Fail(XV_ERR_ARG, "xv_plda_estimate: bad argument");
+  for (int k = 0; k < n_spk; ++k)
+    if (counts[k] < 1) return Fail(XV_ERR_ARG, "xv_plda_estimate: every speaker needs at least one vector");
+  return Guard([&] {
+    xv::Plda p;
+    const int f = xv::PldaFromStats(dim, n_spk, sums, counts, s_tot, s_bet, num_em_iters, &p);
+    std::copy(p.mean.begin(), p.mean.end(), mean);
+    std::copy(p.transform.begin(), p.transform.end(), transform);
+    std::copy(p.psi.begin(), p.psi.end(), psi);
+    if (n_floored) *n_floored = f;
     return XV_OK;
   });
 }

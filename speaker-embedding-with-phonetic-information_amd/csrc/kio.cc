@@ -477,7 +477,11 @@ void SkipScalar(Input& in, bool binary) {
   }
 }
 
-static void ReadTextNumbers(Input& in, std::vector<float>* vals, std::vector<int>* row_ends) {
+static inline float ParseNumber(const char* s, char** end, float*) { return strtof(s, end); }
+static inline double ParseNumber(const char* s, char** end, double*) { return strtod(s, end); }
+
+template <typename T>
+static void ReadTextNumbers(Input& in, std::vector<T>* vals, std::vector<int>* row_ends) {
   // grammar: ws* '[' (number | newline)* ']' ; a newline (or ']') after >=1 numbers closes a row
   int c;
   while ((c = in.Peek()) >= 0 && isspace(c)) in.Get();
@@ -491,7 +495,7 @@ static void ReadTextNumbers(Input& in, std::vector<float>* vals, std::vector<int
       if (!tok.empty()) {
         const char* s = tok.c_str();
         char* end = nullptr;
-        float v = strtof(s, &end);
+        T v = ParseNumber(s, &end, (T*)nullptr);
         if (end == s) throw KioError("bad number '" + tok + "' in text matrix");
         vals->push_back(v);
         tok.clear();
@@ -789,6 +793,102 @@ void WriteMatrix(Output& out, bool binary, const Matrix& m) {
     }
     out.Puts("]\n");
   }
+}
+
+void ReadVectorDouble(Input& in, bool binary, std::vector<double>* v) {
+  v->clear();
+  if (binary) {
+    std::string tok;
+    ReadToken(in, true, &tok);
+    int32_t n = ReadInt32(in, true);
+    if (n < 0) throw KioError("negative vector dimension");
+    if (tok == "DV") {
+      ReadGrow(in, v, (size_t)n);
+    } else if (tok == "FV") {
+      std::vector<float> f;
+      ReadGrow(in, &f, (size_t)n);
+      v->assign(f.begin(), f.end());
+    } else {
+      throw KioError("expected FV or DV, got " + tok);
+    }
+    return;
+  }
+  std::vector<int> ends;
+  ReadTextNumbers(in, v, &ends);
+}
+
+void ReadMatrixDouble(Input& in, bool binary, int* rows, int* cols, std::vector<double>* m) {
+  m->clear();
+  if (binary) {
+    std::string tok;
+    ReadToken(in, true, &tok);
+    if (tok != "FM" && tok != "DM") throw KioError("expected FM or DM, got " + tok + " in " + in.Name());
+    int32_t r = ReadInt32(in, true), c = ReadInt32(in, true);
+    if (r < 0 || c < 0) throw KioError("negative matrix dimension");
+    *rows = r;
+    *cols = c;
+    if (tok == "DM") {
+      ReadGrow(in, m, (size_t)r * c);
+    } else {
+      std::vector<float> f;
+      ReadGrow(in, &f, (size_t)r * c);
+      m->assign(f.begin(), f.end());
+    }
+    return;
+  }
+  std::vector<int> ends;
+  ReadTextNumbers(in, m, &ends);
+  *rows = (int)ends.size();
+  *cols = *rows ? ends[0] : 0;
+  for (int r = 0; r < *rows; ++r)
+    if (ends[r] != (r + 1) * *cols) throw KioError("ragged text matrix in " + in.Name());
+}
+
+// Text doubles carry all 17 significant digits: a model written as text reads back bit-identical.
+static void PutDoubleText(Output& out, double v) {
+  char buf[48];
+  if (isnan(v)) snprintf(buf, sizeof buf, "nan");
+  else if (isinf(v)) snprintf(buf, sizeof buf, v > 0 ? "inf" : "-inf");
+  else snprintf(buf, sizeof buf, "%.17g", v);
+  out.Puts(buf);
+}
+
+void WriteVectorDouble(Output& out, bool binary, const double* v, int n) {
+  if (binary) {
+    out.Puts("DV ");
+    WriteInt32(out, true, n);
+    out.Write(v, (size_t)n * 8);
+  } else {
+    out.Puts(" [ ");
+    for (int i = 0; i < n; ++i) {
+      PutDoubleText(out, v[i]);
+      out.Put(' ');
+    }
+    out.Puts("]\n");
+  }
+}
+
+void WriteMatrixDouble(Output& out, bool binary, const double* m, int rows, int cols) {
+  if (binary) {
+    out.Puts("DM ");
+    WriteInt32(out, true, rows);
+    WriteInt32(out, true, cols);
+    out.Write(m, (size_t)rows * cols * 8);
+    return;
+  }
+  if (rows == 0) {
+    out.Puts(" [ ]\n");
+    return;
+  }
+  out.Puts(" [");
+  for (int r = 0; r < rows; ++r) {
+    out.Puts("\n  ");
+    for (int c = 0; c < cols; ++c) {
+      PutDoubleText(out, m[(size_t)r * cols + c]);
+      out.Put(' ');
+    }
+  }
+  out.Puts("]\n");
 }
 
 // ------------------------------------------------------------------------------------- specifiers
@@ -1213,6 +1313,44 @@ std::vector<TokenList> ReadTokenVectorTable(const std::string& rspecifier) {
     else line.push_back((char)c);
   }
   flush();
+  in.Close();
+  return out;
+}
+
+std::unordered_map<std::string, std::string> ReadTokenTable(const std::string& rspecifier) {
+  std::unordered_map<std::string, std::string> out;
+  for (const TokenList& e : ReadTokenVectorTable(rspecifier)) {
+    if (e.tokens.size() != 1)
+      throw KioError("bad line in token table " + rspecifier + " (expected 'key token'): " + e.key);
+    out[e.key] = e.tokens[0];
+  }
+  return out;
+}
+
+std::unordered_map<std::string, int32_t> ReadInt32Table(const std::string& rspecifier) {
+  RspecifierOptions o = ParseRspecifier(rspecifier);
+  if (o.is_scp) throw KioError("int32 tables are read from archives (ark:...), not scp: " + rspecifier);
+  Input in;
+  in.Open(o.rxfilename);
+  std::unordered_map<std::string, int32_t> out;
+  std::string key;
+  while (ReadKey(in, &key)) {
+    int32_t v;
+    if (in.Peek() == 0) {
+      ReadBinaryHeader(in);
+      v = ReadInt32(in, true);
+    } else {
+      const std::string w = ReadTextWord(in);
+      char* end = nullptr;
+      const long l = strtol(w.c_str(), &end, 10);
+      if (end == w.c_str() || *end) throw KioError("bad int32 value '" + w + "' for key " + key + " in " + rspecifier);
+      v = (int32_t)l;
+    }
+    int c;
+    while ((c = in.Peek()) >= 0 && c != '\n' && isspace(c)) in.Get();
+    if (in.Peek() == '\n') in.Get();
+    out[key] = v;
+  }
   in.Close();
   return out;
 }

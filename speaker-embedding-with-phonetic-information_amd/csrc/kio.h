@@ -134,6 +134,12 @@ void ExpandCompressedView(const Matrix& view, Matrix* out);
 void SkipBinaryMatrix(Input& in, int* rows, int* cols);
 // Reads FV / DV (binary) or " [ ... ]" (text).
 void ReadVector(Input& in, bool binary, std::vector<float>* v);
+// Double-precision objects (the PLDA model): readers accept FV/DV, FM/DM and text; writers write DV/DM, or text with
+// 17 significant digits.
+void ReadVectorDouble(Input& in, bool binary, std::vector<double>* v);
+void ReadMatrixDouble(Input& in, bool binary, int* rows, int* cols, std::vector<double>* m);
+void WriteVectorDouble(Output& out, bool binary, const double* v, int n);
+void WriteMatrixDouble(Output& out, bool binary, const double* m, int rows, int cols);
 void WriteToken(Output& out, bool binary, const char* tok);
 void WriteInt32(Output& out, bool binary, int32_t v);
 void WriteFloat(Output& out, bool binary, float v);
@@ -270,6 +276,10 @@ struct TokenList {
   std::vector<std::string> tokens;
 };
 std::vector<TokenList> ReadTokenVectorTable(const std::string& rspecifier);
+// "key token" per line (utt2spk, "ark:$data/sre_combined/utt2spk"); any other number of tokens is an error.
+std::unordered_map<std::string, std::string> ReadTokenTable(const std::string& rspecifier);
+// Random-access int32 table, text ("key 12") or binary entries (num_utts.ark, what ivector-mean writes with Int32Writer).
+std::unordered_map<std::string, int32_t> ReadInt32Table(const std::string& rspecifier);
 
 // Whole-file Kaldi objects (with the optional binary header): mean.vec, transform.mat.
 void ReadVectorObject(const std::string& rxfilename, std::vector<float>* v);

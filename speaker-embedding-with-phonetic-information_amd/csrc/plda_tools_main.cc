@@ -1,0 +1,565 @@
+// ivector-compute-lda / ivector-compute-plda / ivector-copy-plda / ivector-plda-scoring / compute-eer - drop-in command lines
+// for the back-end stage of the recipes (stage 7 of egs/sre/v2/run_sre10.sh:221-252; v5/run_sre10.sh:105-137,
+// v2/run_sre16.sh:76-116), one executable dispatching on its name:
+//   ivector-compute-lda [--dim=100 --total-covariance-factor=0.0 --covariance-floor=1e-6 --binary=true]
+//                       <ivector-rspecifier> <utt2spk-rspecifier> <lda-matrix-out>                      run_sre10.sh:229-231
+//   ivector-compute-plda [--num-em-iters=10 --binary=true] <spk2utt-rspecifier> <ivector-rspecifier> <plda-out>   :234-236
+//   ivector-copy-plda [--smoothing=0.0 --binary=true] <plda-in> <plda-out>                                       :243
+//   ivector-plda-scoring [--normalize-length=true --simple-length-normalization=false --num-utts=<rspecifier>]
+//                        <plda> <train-ivector-rspecifier> <test-ivector-rspecifier> <trials-rxfilename> <scores-wxfilename>
+//                                                                                                           :240-246
+//   compute-eer <scores-rxfilename>    ("score target|nontarget" lines; the EER in percent on stdout)           :252
+// The statistics over the vectors, the PLDA transform of the vectors and the per-trial scores run on the HIP device
+// (plda.h); without a GPU these tools fail (exit 255).  compute-eer is host arithmetic only.  Semantics are upstream
+// Kaldi's [UPSTREAM, recalled] (ivectorbin/*.cc, ivector/plda.cc); log lines and exit codes follow the Kaldi idiom
+// (0 iff something was written, 1 if nothing was, 255 on an error).
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <map>
+#include <sstream>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "backend.h"
+#include "kio.h"
+#include "plda.h"
+
+namespace {
+
+std::string g_prog = "ivector-plda-scoring";
+
+void LogLine(const char* level, int line, const std::string& msg) {
+  fprintf(stderr, "%s (%s[xvec-hip-0.1]:main():plda_tools_main.cc:%d) %s\n", level, g_prog.c_str(), line, msg.c_str());
+}
+#define XLOG(msg)                       \
+  do {                                  \
+    std::ostringstream _o;              \
+    _o << msg;                          \
+    LogLine("LOG", __LINE__, _o.str()); \
+  } while (0)
+#define XWARN(msg)                          \
+  do {                                      \
+    std::ostringstream _o;                  \
+    _o << msg;                              \
+    LogLine("WARNING", __LINE__, _o.str()); \
+  } while (0)
+
+struct Args {
+  std::vector<std::string> pos;
+  bool binary = true;
+  int lda_dim = 100;                    // ivector-compute-lda --dim
+  double total_covariance_factor = 0.0;
+  double covariance_floor = 1e-6;
+  int num_em_iters = 10;                // ivector-compute-plda
+  double smoothing = 0.0;               // ivector-copy-plda
+  bool normalize_length = true;         // ivector-plda-scoring
+  bool simple_length_norm = false;
+  std::string num_utts;
+  int device = -1;
+};
+
+bool ParseBool(const std::string& v, bool* out) {
+  if (v == "true" || v == "t" || v == "1" || v.empty()) *out = true;
+  else if (v == "false" || v == "f" || v == "0") *out = false;
+  else return false;
+  return true;
+}
+
+bool ParseDouble(const std::string& v, double* out) {
+  char* end = nullptr;
+  *out = strtod(v.c_str(), &end);
+  return !v.empty() && end && *end == 0;
+}
+
+bool ParseInt(const std::string& v, int* out) {
+  char* end = nullptr;
+  const long l = strtol(v.c_str(), &end, 10);
+  *out = (int)l;
+  return !v.empty() && end && *end == 0;
+}
+
+int PickDevice(int requested) {
+  if (requested >= 0) return requested;
+  const char* e = getenv("XVEC_DEVICE");
+  return (e && *e) ? atoi(e) : 0;
+}
+
+// A whole vector table, packed; every vector must have the dimension of the first one.
+struct Packed {
+  std::vector<std::string> keys;
+  std::vector<float> data;
+  int dim = 0;
+  int n() const { return (int)keys.size(); }
+};
+
+void ReadAll(const std::string& rspecifier, Packed* p, long* n_err) {
+  xv::SequentialVectorReader r(rspecifier);
+  std::string key, err;
+  std::vector<float> v;
+  while (r.Next(&key, &v, &err)) {
+    if (!err.empty()) {
+      XWARN("Failed to read vector for key " << key << ": " << err);
+      ++*n_err;
+      continue;
+    }
+    if (p->dim == 0) p->dim = (int)v.size();
+    if ((int)v.size() != p->dim || p->dim == 0)
+      throw xv::KioError("vector " + key + " has dimension " + std::to_string(v.size()) + ", expected " + std::to_string(p->dim));
+    p->keys.push_back(key);
+    p->data.insert(p->data.end(), v.begin(), v.end());
+  }
+  const int st = r.Close();
+  if (st != 0) throw xv::KioError("the input pipe of " + rspecifier + " exited with status " + std::to_string(st));
+}
+
+// Rows of `p` grouped into segments (in the order of `groups`), for the scatter kernel.
+struct Segments {
+  std::vector<int32_t> off = {0}, idx;
+  void Add(const std::vector<int32_t>& rows) {
+    idx.insert(idx.end(), rows.begin(), rows.end());
+    off.push_back((int32_t)idx.size());
+  }
+  int n() const { return (int)off.size() - 1; }
+};
+
+void WriteFloatMatrixObject(const std::string& wx, bool binary, int rows, int cols, const std::vector<float>& data) {
+  xv::Matrix m;
+  m.rows = rows;
+  m.cols = cols;
+  m.data = data;
+  xv::Output out;
+  out.Open(wx);
+  if (binary) out.Write("\0B", 2);
+  xv::WriteMatrix(out, binary, m);
+  out.Close();
+}
+
+int ComputeLda(const Args& a) {
+  if (a.pos.size() != 3) return -2;
+  const int dev = PickDevice(a.device);
+  Packed p;
+  long n_err = 0;
+  ReadAll(a.pos[0], &p, &n_err);
+  const std::unordered_map<std::string, std::string> utt2spk = xv::ReadTokenTable(a.pos[1]);
+  // the utterances with a speaker, packed; speakers in order of first appearance
+  std::vector<float> x;
+  std::map<std::string, int> spk_index;
+  std::vector<std::vector<int32_t>> spk_rows;
+  int n_done = 0;
+  for (int i = 0; i < p.n(); ++i) {
+    auto it = utt2spk.find(p.keys[i]);
+    if (it == utt2spk.end()) {
+      XWARN("No speaker for utterance " << p.keys[i]);
+      ++n_err;
+      continue;
+    }
+    auto s = spk_index.emplace(it->second, (int)spk_rows.size());
+    if (s.second) spk_rows.emplace_back();
+    spk_rows[s.first->second].push_back(n_done++);
+    x.insert(x.end(), p.data.begin() + (size_t)i * p.dim, p.data.begin() + (size_t)(i + 1) * p.dim);
+  }
+  XLOG("Read " << n_done << " utterances, " << n_err << " with errors.");
+  if (n_done == 0) throw xv::KioError("Did not read any utterances.");
+  const int dim = p.dim;
+  if (a.lda_dim < 1 || a.lda_dim > dim)
+    throw xv::KioError("--dim=" + std::to_string(a.lda_dim) + " is out of range: the iVectors have dimension " + std::to_string(dim));
+  // global mean (fp64 accumulation) and its subtraction, on the device
+  std::vector<int32_t> all_off = {0, n_done}, all_idx(n_done);
+  for (int i = 0; i < n_done; ++i) all_idx[i] = i;
+  std::vector<float> mean(dim), xc(x.size());
+  xv::SegmentMean(dev, x.data(), n_done, dim, all_off.data(), all_idx.data(), 1, /*acc64=*/true, mean.data());
+  double mn = 0;
+  for (float m : mean) mn += (double)m * m;
+  XLOG("2-norm of iVector mean is " << sqrt(mn));
+  xv::BackendOptions o;
+  o.mean = mean.data();
+  xv::BackendApply(dev, x.data(), n_done, dim, o, xc.data(), nullptr);
+  Segments seg;
+  for (const auto& rows : spk_rows) seg.Add(rows);
+  std::vector<double> s_tot((size_t)dim * dim), s_bet((size_t)dim * dim);
+  XLOG("Computing within-class covariance.");
+  xv::ScatterStats(dev, xc.data(), n_done, dim, seg.off.data(), seg.idx.data(), seg.n(), s_tot.data(), nullptr, s_bet.data());
+  std::vector<float> lda((size_t)a.lda_dim * (dim + 1));
+  const int floored = xv::LdaFromStats(dim, n_done, s_tot.data(), s_bet.data(), mean.data(), a.total_covariance_factor,
+                                       a.covariance_floor, a.lda_dim, lda.data());
+  if (floored > 0) XWARN("Floored " << floored << " eigenvalues of covariance");
+  WriteFloatMatrixObject(a.pos[2], a.binary, a.lda_dim, dim + 1, lda);
+  XLOG("Wrote LDA transform to " << a.pos[2]);
+  return 0;
+}
+
+int ComputePlda(const Args& a) {
+  if (a.pos.size() != 3) return -2;
+  const int dev = PickDevice(a.device);
+  const std::vector<xv::TokenList> spk2utt = xv::ReadTokenVectorTable(a.pos[0]);
+  Packed p;
+  long n_read_err = 0;
+  ReadAll(a.pos[1], &p, &n_read_err);
+  std::unordered_map<std::string, int> row;
+  for (int i = 0; i < p.n(); ++i) row.emplace(p.keys[i], i);
+  Segments seg;
+  std::vector<int32_t> counts;
+  long num_spk_done = 0, num_spk_err = 0, num_utt_done = 0, num_utt_err = 0;
+  for (const xv::TokenList& e : spk2utt) {
+    if (e.tokens.empty()) throw xv::KioError("Speaker with no utterances.");
+    std::vector<int32_t> rows;
+    for (const std::string& utt : e.tokens) {
+      auto it = row.find(utt);
+      if (it == row.end()) {
+        XWARN("No iVector present in input for utterance " << utt);
+        ++num_utt_err;
+      } else {
+        rows.push_back(it->second);
+        ++num_utt_done;
+      }
+    }
+    if (rows.empty()) {
+      XWARN("Not producing output for speaker " << e.key << " since no utterances had iVectors");
+      ++num_spk_err;
+    } else {
+      seg.Add(rows);
+      counts.push_back((int32_t)rows.size());
+      ++num_spk_done;
+    }
+  }
+  XLOG("Accumulated stats from " << num_spk_done << " speakers (" << num_spk_err << " with no utterances), consisting of "
+                                 << num_utt_done << " utterances (" << num_utt_err << " absent from input).");
+  if (num_spk_done == 0) throw xv::KioError("No stats accumulated, unable to estimate PLDA.");
+  if (num_spk_done == num_utt_done) throw xv::KioError("No speakers with multiple utterances, unable to estimate PLDA.");
+  const int dim = p.dim;
+  std::vector<double> s_tot((size_t)dim * dim), s_bet((size_t)dim * dim), sums((size_t)seg.n() * dim);
+  xv::ScatterStats(dev, p.data.data(), p.n(), dim, seg.off.data(), seg.idx.data(), seg.n(), s_tot.data(), sums.data(), s_bet.data());
+  xv::Plda plda;
+  std::vector<std::string> log;
+  const int floored = xv::PldaFromStats(dim, seg.n(), sums.data(), counts.data(), s_tot.data(), s_bet.data(), a.num_em_iters,
+                                        &plda, &log);
+  for (const std::string& l : log) XLOG(l);
+  if (floored > 0) XWARN("Floored " << floored << " eigenvalues of between-class variance to zero.");
+  xv::WritePlda(a.pos[2], a.binary, plda);
+  return 0;
+}
+
+std::string VecText(const std::vector<double>& v) {
+  std::ostringstream o;
+  o << " [ ";
+  for (double x : v) o << x << " ";
+  o << "]";
+  return o.str();
+}
+
+int CopyPlda(const Args& a) {
+  if (a.pos.size() != 2) return -2;
+  xv::Plda plda;
+  xv::ReadPlda(a.pos[0], &plda);
+  if (a.smoothing != 0.0) {
+    if (a.smoothing < 0.0 || a.smoothing > 1.0) throw xv::KioError("--smoothing must be in [0, 1]");
+    XLOG("Smoothing within-class covariance by " << a.smoothing << ", Psi is initially: " << VecText(plda.psi));
+    plda.SmoothWithinClassCovariance(a.smoothing);
+    XLOG("New value of Psi is " << VecText(plda.psi));
+  }
+  xv::WritePlda(a.pos[1], a.binary, plda);
+  return 0;
+}
+
+// Splits on blanks (" \t\r\n"), empty fields dropped.
+void SplitFields(const std::string& line, std::vector<std::string>* f) {
+  f->clear();
+  size_t i = 0;
+  while (i < line.size()) {
+    while (i < line.size() && strchr(" \t\r\n", line[i])) ++i;
+    size_t j = i;
+    while (j < line.size() && !strchr(" \t\r\n", line[j])) ++j;
+    if (j > i) f->push_back(line.substr(i, j - i));
+    i = j;
+  }
+}
+
+// Lines of an rxfilename, read in blocks.
+class LineReader {
+ public:
+  explicit LineReader(const std::string& rx) { in_.Open(rx); }
+  bool Next(std::string* line) {
+    line->clear();
+    for (;;) {
+      if (pos_ == len_) {
+        len_ = in_.ReadUpTo(buf_, sizeof buf_);
+        pos_ = 0;
+        if (len_ == 0) return !line->empty();
+      }
+      const char* nl = (const char*)memchr(buf_ + pos_, '\n', len_ - pos_);
+      if (nl) {
+        line->append(buf_ + pos_, nl - (buf_ + pos_));
+        pos_ = nl - buf_ + 1;
+        return true;
+      }
+      line->append(buf_ + pos_, len_ - pos_);
+      pos_ = len_;
+    }
+  }
+  int Close() { return in_.Close(); }
+
+ private:
+  xv::Input in_;
+  char buf_[1 << 16];
+  size_t pos_ = 0, len_ = 0;
+};
+
+int PldaScoring(const Args& a) {
+  if (a.pos.size() != 5) return -2;
+  const int dev = PickDevice(a.device);
+  xv::Plda plda;
+  xv::ReadPlda(a.pos[0], &plda);
+  const int dim = plda.dim;
+  std::unordered_map<std::string, int32_t> num_utts;
+  if (!a.num_utts.empty()) num_utts = xv::ReadInt32Table(a.num_utts);
+
+  // one table -> transformed vectors on the device
+  struct Side {
+    Packed p;
+    std::vector<double> num;
+    std::vector<float> y;
+    std::unordered_map<std::string, int> row;
+  } train, test;
+  auto load = [&](const std::string& rspec, bool is_train, Side* s, long* n_err) {
+    Packed raw;
+    long read_err = 0;
+    ReadAll(rspec, &raw, &read_err);
+    if (raw.n() > 0 && raw.dim != dim)
+      throw xv::KioError("iVector dimension " + std::to_string(raw.dim) + " does not match the PLDA dimension " + std::to_string(dim));
+    s->p.dim = dim;
+    for (int i = 0; i < raw.n(); ++i) {
+      const std::string& key = raw.keys[i];
+      if (s->row.count(key))
+        throw xv::KioError(std::string("Duplicate ") + (is_train ? "training iVector found for speaker " : "test iVector found for utterance ") + key);
+      double n = 1.0;
+      if (is_train && !a.num_utts.empty()) {
+        auto it = num_utts.find(key);
+        if (it == num_utts.end()) {
+          XWARN("Number of utterances not given for speaker " << key);
+          ++*n_err;
+          continue;
+        }
+        n = it->second;
+        if (n < 1) throw xv::KioError("number of utterances for speaker " + key + " is not positive");
+      }
+      s->row.emplace(key, s->p.n());
+      s->p.keys.push_back(key);
+      s->p.data.insert(s->p.data.end(), raw.data.begin() + (size_t)i * dim, raw.data.begin() + (size_t)(i + 1) * dim);
+      s->num.push_back(n);
+    }
+    std::vector<double> scale(s->p.n());
+    s->y.resize(s->p.data.size());
+    xv::PldaTransform(dev, s->p.data.data(), s->p.n(), dim, plda.transform.data(), plda.offset.data(), plda.psi.data(),
+                      s->num.data(), a.normalize_length, a.simple_length_norm, s->y.data(), scale.data());
+    double tot = 0;
+    for (double x : scale) tot += x;
+    return tot;
+  };
+  long n_train_err = 0, n_test_err = 0;
+  XLOG("Reading train iVectors");
+  const double train_scale = load(a.pos[1], true, &train, &n_train_err);
+  XLOG("Read " << train.p.n() << " training iVectors, errors on " << n_train_err);
+  if (train.p.n() == 0) throw xv::KioError("No training iVectors present.");
+  XLOG("Average renormalization scale on training iVectors was " << train_scale / train.p.n());
+  XLOG("Reading test iVectors");
+  const double test_scale = load(a.pos[2], false, &test, &n_test_err);
+  XLOG("Read " << test.p.n() << " test iVectors.");
+  if (test.p.n() == 0) throw xv::KioError("No test iVectors present.");
+  XLOG("Average renormalization scale on test iVectors was " << test_scale / test.p.n());
+
+  // trials, in input order; lines whose keys are missing are skipped
+  using Clock = std::chrono::steady_clock;
+  auto secs = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+  const Clock::time_point t0 = Clock::now();
+  LineReader lr(a.pos[3]);
+  std::string line;
+  std::vector<std::string> f;
+  std::vector<int32_t> pairs;
+  std::vector<size_t> line_of;      // trial -> index into names
+  std::vector<std::string> names;   // "key1 key2 " of every scored trial
+  long n_err = 0;
+  while (lr.Next(&line)) {
+    SplitFields(line, &f);
+    if (f.size() != 2)
+      throw xv::KioError("Bad line " + std::to_string(names.size() + n_err) + " in input (expected two fields: key1 key2): " + line);
+    auto i1 = train.row.find(f[0]);
+    if (i1 == train.row.end()) {
+      XWARN("Key " << f[0] << " not present in training iVectors.");
+      ++n_err;
+      continue;
+    }
+    auto i2 = test.row.find(f[1]);
+    if (i2 == test.row.end()) {
+      XWARN("Key " << f[1] << " not present in test iVectors.");
+      ++n_err;
+      continue;
+    }
+    pairs.push_back(i1->second);
+    pairs.push_back(i2->second);
+    names.push_back(f[0] + " " + f[1] + " ");
+  }
+  const int st = lr.Close();
+  if (st != 0) throw xv::KioError("the trials command of " + a.pos[3] + " exited with status " + std::to_string(st));
+  const long n_done = (long)names.size();
+  const Clock::time_point t1 = Clock::now();
+  std::vector<double> scores(n_done);
+  xv::PldaScore(dev, train.y.data(), train.num.data(), train.p.n(), test.y.data(), test.p.n(), dim, plda.psi.data(),
+                pairs.data(), n_done, scores.data());
+  const Clock::time_point t2 = Clock::now();
+  xv::Output out;
+  out.Open(a.pos[4]);
+  double sum = 0, sumsq = 0;
+  std::ostringstream o;
+  for (long i = 0; i < n_done; ++i) {
+    const float s = (float)scores[i];   // BaseFloat, printed with the stream's default 6 significant digits
+    sum += s;
+    sumsq += (double)s * s;
+    o << names[i] << s << '\n';
+    if (o.tellp() > (1 << 20) || i + 1 == n_done) {
+      out.Puts(o.str());
+      o.str("");
+    }
+  }
+  out.Close();
+  const Clock::time_point t3 = Clock::now();
+  if (n_done != 0) {
+    const float mean = (float)(sum / n_done), scatter = (float)(sumsq / n_done), var = scatter - mean * mean;
+    XLOG("Mean score was " << mean << ", standard deviation was " << sqrtf(var > 0 ? var : 0));
+  }
+  XLOG("Processed " << n_done << " trials, " << n_err << " had errors.");
+  XLOG("Timing: trials read in " << secs(t0, t1) << " s, scored on the device in " << secs(t1, t2) << " s, written in "
+                                 << secs(t2, t3) << " s");
+  return n_done != 0 ? 0 : 1;
+}
+
+int ComputeEer(const Args& a) {
+  if (a.pos.size() != 1) return -2;
+  LineReader lr(a.pos[0]);
+  std::string line;
+  std::vector<std::string> f;
+  std::vector<float> tgt, non;
+  while (lr.Next(&line)) {
+    SplitFields(line, &f);
+    if (f.size() != 2) throw xv::KioError("Invalid input line (must have two fields: score target|nontarget): " + line);
+    char* end = nullptr;
+    const float s = strtof(f[0].c_str(), &end);
+    if (end == f[0].c_str() || *end || !isfinite(s)) throw xv::KioError("Invalid input line (first field must be float): " + line);
+    if (f[1] == "target") tgt.push_back(s);
+    else if (f[1] == "nontarget") non.push_back(s);
+    else throw xv::KioError("Invalid input line (second field must be 'target' or 'nontarget'): " + line);
+  }
+  lr.Close();
+  if (tgt.empty() && non.empty()) throw xv::KioError("Empty input.");
+  if (tgt.empty()) throw xv::KioError("No target scores seen.");
+  if (non.empty()) throw xv::KioError("No non-target scores seen.");
+  std::sort(tgt.begin(), tgt.end());
+  std::sort(non.begin(), non.end());
+  size_t p = 0;
+  const size_t nt = tgt.size();
+  for (; p + 1 < nt; ++p) {
+    const long nn = (long)non.size();
+    long q = nn - 1 - (long)(nn * (double)p / (double)nt);
+    if (q < 0) q = 0;
+    if (non[q] < tgt[p]) break;
+  }
+  const float eer = (float)((double)p / (double)nt);
+  XLOG("Equal error rate is " << 100.0 * eer << "%, at threshold " << tgt[p]);
+  std::ostringstream o;
+  o.precision(4);
+  o << 100.0 * eer << '\n';
+  fputs(o.str().c_str(), stdout);
+  return 0;
+}
+
+const char* Usage(const std::string& prog) {
+  if (prog == "ivector-compute-lda")
+    return "Compute an LDA matrix for iVector system.  Reads in iVectors per utterance, and an utt2spk file which it uses to\n"
+           "help work out the within-speaker and between-speaker covariance matrices.  Outputs an LDA projection to a\n"
+           "specified dimension.  By default it will normalize so that the projected within-class covariance is unit.\n"
+           "Usage: ivector-compute-lda [options] <ivector-rspecifier> <utt2spk-rspecifier> <lda-matrix-out>\n"
+           "Options: --dim=100 --total-covariance-factor=0.0 --covariance-floor=1e-06 --binary=true\n";
+  if (prog == "ivector-compute-plda")
+    return "Computes a Plda object (for Probabilistic Linear Discriminant Analysis) from a set of iVectors.\n"
+           "Usage: ivector-compute-plda [options] <spk2utt-rspecifier> <ivector-rspecifier> <plda-out>\n"
+           "Options: --num-em-iters=10 --binary=true\n";
+  if (prog == "ivector-copy-plda")
+    return "Copy a PLDA object, possibly applying smoothing to the within-class covariance\n"
+           "Usage: ivector-copy-plda [--smoothing=0.0] [--binary=true] <plda-in> <plda-out>\n";
+  if (prog == "compute-eer")
+    return "Computes Equal Error Rate.  Input is a series of lines, each with two fields: the score and 'target' or\n"
+           "'nontarget'.  The EER is printed in percent on the standard output.\n"
+           "Usage: compute-eer <scores-in>\n"
+           "e.g.: compute-eer -\n";
+  return "Computes log-likelihood ratios for trials using PLDA model.  The trials file has lines 'key1 key2' (speaker,\n"
+         "utterance); the output has lines 'key1 key2 score'.\n"
+         "Usage: ivector-plda-scoring <plda> <train-ivector-rspecifier> <test-ivector-rspecifier>\n"
+         "                            <trials-rxfilename> <scores-wxfilename>\n"
+         "Options: --num-utts=<rspecifier> --normalize-length=true --simple-length-normalization=false\n";
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  xv::InstallMappedFileFaultHandler(strrchr(argv[0], '/') ? strrchr(argv[0], '/') + 1 : argv[0]);
+  const char* slash = strrchr(argv[0], '/');
+  g_prog = slash ? slash + 1 : argv[0];
+  Args a;
+  std::string cmdline = g_prog;
+  for (int i = 1; i < argc; ++i) {
+    std::string s = argv[i];
+    cmdline += " " + s;
+    if (s.compare(0, 2, "--") == 0 && s.size() > 2 && a.pos.empty()) {
+      size_t eq = s.find('=');
+      const std::string name = s.substr(2, eq == std::string::npos ? std::string::npos : eq - 2);
+      const std::string val = eq == std::string::npos ? "" : s.substr(eq + 1);
+      bool ok = true;
+      if (name == "help") {
+        fputs(Usage(g_prog), stderr);
+        return 0;
+      } else if (name == "binary") ok = ParseBool(val, &a.binary);
+      else if (name == "dim" && g_prog == "ivector-compute-lda") ok = ParseInt(val, &a.lda_dim);
+      else if (name == "total-covariance-factor" && g_prog == "ivector-compute-lda") ok = ParseDouble(val, &a.total_covariance_factor);
+      else if (name == "covariance-floor" && g_prog == "ivector-compute-lda") ok = ParseDouble(val, &a.covariance_floor);
+      else if (name == "num-em-iters" && g_prog == "ivector-compute-plda") ok = ParseInt(val, &a.num_em_iters) && a.num_em_iters >= 0;
+      else if (name == "smoothing" && g_prog == "ivector-copy-plda") ok = ParseDouble(val, &a.smoothing);
+      else if (name == "normalize-length" && g_prog == "ivector-plda-scoring") ok = ParseBool(val, &a.normalize_length);
+      else if (name == "simple-length-normalization" && g_prog == "ivector-plda-scoring") ok = ParseBool(val, &a.simple_length_norm);
+      else if (name == "num-utts" && g_prog == "ivector-plda-scoring") a.num_utts = val;
+      else if (name == "device") a.device = atoi(val.c_str());
+      else if (name == "verbose" || name == "print-args" || name == "config") ok = true;   // accepted, no effect
+      else {
+        fprintf(stderr, "ERROR (%s) Invalid option %s\n\n%s", g_prog.c_str(), s.c_str(), Usage(g_prog));
+        return 255;
+      }
+      if (!ok) {
+        fprintf(stderr, "ERROR (%s) Invalid value for option %s\n", g_prog.c_str(), s.c_str());
+        return 255;
+      }
+      continue;
+    }
+    a.pos.push_back(s);
+  }
+  fprintf(stderr, "%s \n", cmdline.c_str());
+  try {
+    int rc;
+    if (g_prog == "ivector-compute-lda") rc = ComputeLda(a);
+    else if (g_prog == "ivector-compute-plda") rc = ComputePlda(a);
+    else if (g_prog == "ivector-copy-plda") rc = CopyPlda(a);
+    else if (g_prog == "compute-eer") rc = ComputeEer(a);
+    else rc = PldaScoring(a);
+    if (rc == -2) {
+      fputs(Usage(g_prog), stderr);
+      return 1;
+    }
+    return rc;
+  } catch (const std::exception& e) {
+    fprintf(stderr, "ERROR (%s) %s\n", g_prog.c_str(), e.what());
+    return 255;
+  }
+}
