@@ -284,7 +284,8 @@ xv_status xv_backend_apply(int device, const float* x, int32_t n, int32_t dim, c
 xv_status xv_segment_mean(int device, const float* x, int32_t n, int32_t dim, const int32_t* seg_off, const int32_t* idx,
                           int32_t n_seg, int32_t acc64, float* out);
 
-/* ---- PLDA back-end (stage 7 of egs/sre/v2/run_sre10.sh: ivector-compute-lda, ivector-compute-plda, ivector-plda-scoring)
+/* ---- PLDA back-end (stage 7 of egs/sre/v2/run_sre10.sh: ivector-compute-lda, ivector-compute-plda, ivector-plda-scoring;
+ * stage 2 of v2/run_sre16.sh: ivector-adapt-plda)
  * Device kernels behind host buffers, fp64 arithmetic on fp32 vectors, deterministic (fixed reduction orders, no float
  * atomics).  device_ms (optional, may be NULL) receives the kernel time between two events around the launches.
  *   xv_scatter_stats   segment s = rows idx[seg_off[s] .. seg_off[s+1]) of x [n][dim] (seg_off[0] == 0, offsets do not
@@ -303,6 +304,12 @@ xv_status xv_segment_mean(int device, const float* x, int32_t n, int32_t dim, co
  *   xv_plda_estimate   host only: ivector-compute-plda's EM (num_em_iters iterations) from per-speaker sums / counts and
  *                      the scatter statistics of the same rows; mean[dim], transform[dim][dim], psi[dim] (descending);
  *                      n_floored (optional) = between-class eigenvalues floored at zero.
+ *   xv_plda_adapt      host only: ivector-adapt-plda (PldaUnsupervisedAdaptor::UpdatePlda) from the statistics of n >= 1
+ *                      unlabelled vectors, m[dim] = sum x and v[dim][dim] = sum x x^T (xv_scatter_stats with one segment
+ *                      that lists every row: sums and s_tot), the model (mean, transform, psi >= 0) and the three scales
+ *                      (Kaldi's defaults 1.0, 0.3, 0.7); mean_out[dim], transform_out[dim][dim], psi_out[dim] (descending);
+ *                      s_out (optional, [dim]) = eigenvalues of the adaptation covariance in the space where the model's
+ *                      total covariance is I, descending.
  * The device entries fail with XV_ERR_DEVICE when no gfx950 device is usable. */
 xv_status xv_scatter_stats(int device, const float* x, int32_t n, int32_t dim, const int32_t* seg_off, const int32_t* idx,
                            int32_t n_seg, double* s_tot, double* sums, double* s_bet, float* device_ms);
@@ -316,6 +323,9 @@ xv_status xv_lda_estimate(int32_t dim, int64_t n, const double* s_tot, const dou
 xv_status xv_plda_estimate(int32_t dim, int32_t n_spk, const double* sums, const int32_t* counts, const double* s_tot,
                            const double* s_bet, int32_t num_em_iters, double* mean, double* transform, double* psi,
                            int32_t* n_floored);
+xv_status xv_plda_adapt(int32_t dim, int64_t n, const double* m, const double* v, const double* mean, const double* transform,
+                        const double* psi, double mean_diff_scale, double within_covar_scale, double between_covar_scale,
+                        double* mean_out, double* transform_out, double* psi_out, double* s_out);
 
 /* ---- kernel-level entry (unit tests of the HIP GEMM against a plain fp32 reference) ------------------- */
 typedef struct {

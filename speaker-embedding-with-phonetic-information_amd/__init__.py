@@ -95,7 +95,7 @@ ABI_SYMBOLS = [
     "xv_ctx_set_calibration_file", "xv_calibration_file_read", "xv_calibration_file_publish", "xv_recognize_feature_pipeline", "xv_ctx_set_lite_layers", "xv_ctx_lite_layers",
     "xv_extract_table", "xv_frontend_cmvn_select", "xv_plan_chunks", "xv_ctx_create_broadcast", "xv_kernel_tdnn_gemm",
     "xv_backend_apply", "xv_segment_mean", "xv_scatter_stats", "xv_plda_transform", "xv_plda_score", "xv_lda_estimate",
-    "xv_plda_estimate", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
+    "xv_plda_estimate", "xv_plda_adapt", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
 ]
 
 _lib = None
@@ -669,6 +669,30 @@ def plda_estimate(sums, counts, s_tot, s_bet, num_em_iters=10):
     _check(L.xv_plda_estimate(dim, n_spk, sums.ctypes.data, counts.ctypes.data, s_tot.ctypes.data, s_bet.ctypes.data, num_em_iters,
                               mean.ctypes.data, transform.ctypes.data, psi.ctypes.data, ctypes.byref(fl)))
     return mean, transform, psi
+
+
+def plda_adapt(n, m, v, mean, transform, psi, mean_diff_scale=1.0, within_covar_scale=0.3, between_covar_scale=0.7):
+    """ivector-adapt-plda's update on the host (no GPU needed) from the statistics of n unlabelled vectors, m = sum x [dim]
+    and v = sum x x^T [dim, dim] (scatter_stats with one segment of every row: sums[0] and s_tot), and the model (mean,
+    transform, psi).  Returns (mean, transform, psi, s), float64; s: the eigenvalues of the adaptation covariance in the
+    space where the model's total covariance is I, descending."""
+    import numpy as np
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    transform = np.ascontiguousarray(transform, dtype=np.float64)
+    psi = np.ascontiguousarray(psi, dtype=np.float64)
+    dim = mean.shape[0]
+    if m.shape != (dim,) or v.shape != (dim, dim) or transform.shape != (dim, dim) or psi.shape != (dim,):
+        raise XvError(XV_ERR_ARG, "PLDA adaptation: statistics and model shapes do not agree on dimension %d" % dim)
+    mean_out = np.empty(dim); transform_out = np.empty((dim, dim)); psi_out = np.empty(dim); s = np.empty(dim)
+    L = lib()
+    L.xv_plda_adapt.argtypes = [ctypes.c_int32, ctypes.c_int64] + [ctypes.c_void_p] * 5 + [ctypes.c_double] * 3 + \
+        [ctypes.c_void_p] * 4
+    _check(L.xv_plda_adapt(dim, int(n), m.ctypes.data, v.ctypes.data, mean.ctypes.data, transform.ctypes.data, psi.ctypes.data,
+                           mean_diff_scale, within_covar_scale, between_covar_scale, mean_out.ctypes.data,
+                           transform_out.ctypes.data, psi_out.ctypes.data, s.ctypes.data))
+    return mean_out, transform_out, psi_out, s
 
 
 def kernel_tdnn_gemm(desc):

@@ -623,6 +623,27 @@ xv_status xv_plda_estimate(int32_t dim, int32_t n_spk, const double* sums, const
   });
 }
 
+xv_status xv_plda_adapt(int32_t dim, int64_t n, const double* m, const double* v, const double* mean, const double* transform,
+                        const double* psi, double mean_diff_scale, double within_covar_scale, double between_covar_scale,
+                        double* mean_out, double* transform_out, double* psi_out, double* s_out) {
+  if (dim < 1 || n < 1 || !m || !v || !mean || !transform || !psi || !mean_out || !transform_out || !psi_out)
+    return Fail(XV_ERR_ARG, "xv_plda_adapt: bad argument");
+  for (int d = 0; d < dim; ++d)
+    if (!(psi[d] >= 0.0)) return Fail(XV_ERR_ARG, "xv_plda_adapt: psi must not be negative");
+  return Guard([&] {
+    xv::Plda p;
+    p.dim = dim;
+    p.mean.assign(mean, mean + dim);
+    p.transform.assign(transform, transform + (size_t)dim * dim);
+    p.psi.assign(psi, psi + dim);
+    xv::AdaptPlda((long)n, m, v, mean_diff_scale, within_covar_scale, between_covar_scale, &p, s_out);
+    std::copy(p.mean.begin(), p.mean.end(), mean_out);
+    std::copy(p.transform.begin(), p.transform.end(), transform_out);
+    std::copy(p.psi.begin(), p.psi.end(), psi_out);
+    return XV_OK;
+  });
+}
+
 // One process, several GPUs: multi_gpu.cc (one ncclBroadcast of the packed image, bounded wait, contexts from the device copies).
 xv_status xv_ctx_create_broadcast(const xv_model* m, const int* devices, int n, int precision, xv_ctx** out) {
   if (!m || !devices || !out || n < 1) return Fail(XV_ERR_ARG, "xv_ctx_create_broadcast: bad argument");

@@ -450,6 +450,96 @@ int PldaFromStats(int dim, int n_spk, const double* sums, const int32_t* counts,
   return floored;
 }
 
+namespace {
+std::string VecText(const std::vector<double>& v) {   // Kaldi's Vector output: " [ a b c ]"
+  std::ostringstream o;
+  o << " [ ";
+  for (double x : v) o << x << " ";
+  o << "]";
+  return o.str();
+}
+}  // namespace
+
+void AdaptPlda(long n, const double* m, const double* v, double mean_diff_scale, double within_covar_scale,
+               double between_covar_scale, Plda* plda, double* s_out, std::vector<std::string>* log) {
+  if (n < 1) throw EngineError("PLDA adaptation: no vectors");
+  const int dim = plda->dim;
+  const size_t dd = (size_t)dim * dim;
+  for (int d = 0; d < dim; ++d)
+    if (!(plda->psi[d] >= 0.0)) throw EngineError("PLDA adaptation: the model's psi must not be negative");
+  // the adaptation data's mean and covariance; the covariance also takes mean_diff_scale of the mean shift
+  std::vector<double> mu(dim), diff(dim);
+  double diff_norm = 0.0;
+  for (int d = 0; d < dim; ++d) {
+    mu[d] = m[d] / (double)n;
+    diff[d] = mu[d] - plda->mean[d];
+    diff_norm += diff[d] * diff[d];
+  }
+  Mat var(dd);
+  for (int i = 0; i < dim; ++i)
+    for (int j = 0; j < dim; ++j)
+      var[(size_t)i * dim + j] = v[(size_t)i * dim + j] / (double)n - mu[i] * mu[j] + mean_diff_scale * diff[i] * diff[j];
+  // T' = diag(1/sqrt(1 + psi)) T: the space where the model's total covariance is I; there T' var T'^T = P diag(s) P^T
+  Mat tm(plda->transform);
+  for (int i = 0; i < dim; ++i) {
+    const double f = 1.0 / sqrt(1.0 + plda->psi[i]);
+    for (int j = 0; j < dim; ++j) tm[(size_t)i * dim + j] *= f;
+  }
+  Mat vp = Sandwich(dim, dim, tm, var);
+  std::vector<double> s(dim);
+  Mat p(dd);
+  SymmetricEig(dim, vp.data(), s.data(), p.data());
+  // W = diag(1/(1+psi)), B = diag(psi/(1+psi)) there; seen along P (W2 = P^T W P, B2 = P^T B P), each direction with
+  // s_i > 1 gets the scaled excess s_i - 1 on both diagonals
+  Mat pt(dd), w(dd, 0.0), b(dd, 0.0);
+  for (int i = 0; i < dim; ++i) {
+    w[(size_t)i * dim + i] = 1.0 / (1.0 + plda->psi[i]);
+    b[(size_t)i * dim + i] = plda->psi[i] / (1.0 + plda->psi[i]);
+    for (int j = 0; j < dim; ++j) pt[(size_t)i * dim + j] = p[(size_t)j * dim + i];
+  }
+  Mat w2 = Sandwich(dim, dim, pt, w), b2 = Sandwich(dim, dim, pt, b);
+  for (int i = 0; i < dim; ++i)
+    if (s[i] > 1.0) {
+      w2[(size_t)i * dim + i] += within_covar_scale * (s[i] - 1.0);
+      b2[(size_t)i * dim + i] += between_covar_scale * (s[i] - 1.0);
+    }
+  // back in the T' space: Wm = P W2 P^T = C C^T, C^-1 Bm C^-T = Q diag(psi') Q^T; the new transform is Q^T C^-1 T'
+  Mat wm = Sandwich(dim, dim, p, w2), bm = Sandwich(dim, dim, p, b2);
+  Mat c(dd), ci(dd);
+  if (!Cholesky(dim, wm.data(), c.data()))
+    throw EngineError("PLDA adaptation: the adapted within-class covariance is not positive definite");
+  InvertLower(dim, c.data(), ci.data());
+  Mat bp = Sandwich(dim, dim, ci, bm);
+  std::vector<double> psi(dim);
+  Mat q(dd);
+  SymmetricEig(dim, bp.data(), psi.data(), q.data());
+  Mat cit(dd, 0.0);   // C^-1 T' (C^-1 lower)
+  for (int i = 0; i < dim; ++i)
+    for (int k = 0; k <= i; ++k) {
+      const double x = ci[(size_t)i * dim + k];
+      for (int j = 0; j < dim; ++j) cit[(size_t)i * dim + j] += x * tm[(size_t)k * dim + j];
+    }
+  Mat t(dd, 0.0);
+  for (int i = 0; i < dim; ++i)
+    for (int k = 0; k < dim; ++k) {
+      const double x = q[(size_t)k * dim + i];
+      for (int j = 0; j < dim; ++j) t[(size_t)i * dim + j] += x * cit[(size_t)k * dim + j];
+    }
+  if (log) {
+    std::ostringstream o;
+    o << "Mean differs from old mean with norm " << sqrt(diff_norm);
+    log->push_back(o.str());
+    log->push_back("Eigenvalues of adaptation-data total-covariance in space where out-of-domain PLDA total-covariance is unit, are: " +
+                   VecText(s));
+    log->push_back("Old diagonal of between-class covar was: " + VecText(plda->psi) + ", new diagonal is " + VecText(psi));
+  }
+  if (s_out) std::copy(s.begin(), s.end(), s_out);
+  plda->mean = mu;
+  plda->transform = t;
+  plda->psi = psi;
+  plda->ComputeDerivedVars();
+}
+
 // ---------------------------------------------------------------------------------------------------- the model
 void Plda::ComputeDerivedVars() {
   offset.assign(dim, 0.0);

@@ -1,5 +1,5 @@
-// PLDA back-end (stage 7 of egs/sre/v2/run_sre10.sh:221-252, v5/run_sre10.sh:105-137, v2/run_sre16.sh:76-116):
-// LDA and two-covariance PLDA estimation, the PLDA model object, trial scoring.  Semantics are upstream Kaldi's
+// PLDA back-end (stage 7 of egs/sre/v2/run_sre10.sh:221-252, v5/run_sre10.sh:105-137, stage 2 of v2/run_sre16.sh:76-175):
+// LDA and two-covariance PLDA estimation, unsupervised PLDA adaptation, the PLDA model object, trial scoring.  Semantics are upstream Kaldi's
 // (ivector/plda.cc, ivector/ivector-extractor.cc's LDA helpers, ivectorbin/*.cc) [UPSTREAM, recalled]: not vendored in
 // the reference, restated here and in tests/plda_ref.py.
 // The statistics over the data and the per-trial work run on the device (plda_kernels.h); the host does the small dense
@@ -53,5 +53,12 @@ int LdaFromStats(int dim, long n, const double* s_tot, const double* s_bet, cons
 // of between-class eigenvalues floored at zero.  log (optional) receives one line per EM iteration.
 int PldaFromStats(int dim, int n_spk, const double* sums, const int32_t* counts, const double* s_tot, const double* s_bet,
                   int num_em_iters, Plda* out, std::vector<std::string>* log = nullptr);
+// ivector-adapt-plda (PldaUnsupervisedAdaptor::UpdatePlda [UPSTREAM, recalled]): adapts `plda` in place to n unlabelled
+// vectors with sum m [dim] and scatter v = sum x x^T [dim][dim].  The adaptation covariance (plus mean_diff_scale times the
+// outer product of the mean shift) is diagonalised in the space where the model's total covariance is I; its excess over 1
+// in each direction is added to the within- and between-class covariances with the two scales.  s (optional, [dim])
+// receives those eigenvalues, descending.  log (optional) receives the mean shift, the eigenvalues and the old / new psi.
+void AdaptPlda(long n, const double* m, const double* v, double mean_diff_scale, double within_covar_scale,
+               double between_covar_scale, Plda* plda, double* s = nullptr, std::vector<std::string>* log = nullptr);
 
 }  // namespace xv

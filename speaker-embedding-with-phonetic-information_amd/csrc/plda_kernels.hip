@@ -1,5 +1,6 @@
 // PLDA back-end kernels (plda_kernels.h): scatter statistics for LDA / PLDA estimation, Kaldi's TransformIvector, and
-// the per-trial log-likelihood ratio.  fp64 arithmetic with plain FMA, 256-thread workgroups, fixed reduction orders.
+// the per-trial log-likelihood ratio.  fp64 arithmetic with plain FMA, 256-thread workgroups (64 for the segment sums), fixed
+// reduction orders.
 #include "plda_kernels.h"
 
 namespace xv {
@@ -122,15 +123,28 @@ __global__ __launch_bounds__(256) void chunk_sum_kernel(const double* part, int 
   out[(size_t)j * dim + i] = s;
 }
 
-// sums[s] = rows of segment s added in list order (fp64).
-__global__ __launch_bounds__(256) void segment_sum64_kernel(const ScatterArgs a) {
+// sums[s] = rows of segment s added in list order (fp64).  One wave per (segment, 64 columns), a lane per column.  The
+// rows are loaded kSumAhead at a time before any of them is added, so the loads overlap while every column keeps one
+// add chain in list order (the same bits as one add per loaded row).  A segment of the whole table (ivector-adapt-plda)
+// thus runs on dim / 64 waves with kSumAhead loads in flight each, instead of one load at a time.
+constexpr int kSumAhead = 64;
+
+__global__ __launch_bounds__(64) void segment_sum64_kernel(const ScatterArgs a) {
   const int s = blockIdx.x;
+  const int k = blockIdx.y * 64 + threadIdx.x;
+  if (k >= a.dim) return;
   const int b = a.seg_off[s], e = a.seg_off[s + 1];
-  for (int k = threadIdx.x; k < a.dim; k += 256) {
-    double acc = 0.0;
-    for (int i = b; i < e; ++i) acc += (double)a.x[(long)a.idx[i] * a.ldx + k];
-    a.sums[(size_t)s * a.dim + k] = acc;
+  double acc = 0.0;
+  int i = b;
+  for (; i + kSumAhead <= e; i += kSumAhead) {
+    float v[kSumAhead];
+#pragma unroll
+    for (int u = 0; u < kSumAhead; ++u) v[u] = a.x[(long)a.idx[i + u] * a.ldx + k];
+#pragma unroll
+    for (int u = 0; u < kSumAhead; ++u) acc += (double)v[u];
   }
+  for (; i < e; ++i) acc += (double)a.x[(long)a.idx[i] * a.ldx + k];
+  a.sums[(size_t)s * a.dim + k] = acc;
 }
 
 hipError_t rank_k(const RankKArgs& r, double* out, hipStream_t s) {
@@ -159,7 +173,7 @@ size_t scatter_stats_workspace(int dim, int n_idx, int n_seg) {
 hipError_t launch_scatter_stats(const ScatterArgs& a, hipStream_t s) {
   if (a.dim < 1 || a.n_seg < 0 || a.n_idx < 0) return hipErrorInvalidValue;
   if (a.n_seg > 0) {
-    hipLaunchKernelGGL(segment_sum64_kernel, dim3(a.n_seg), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(segment_sum64_kernel, dim3(a.n_seg, (a.dim + 63) / 64), dim3(64), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

@@ -1,18 +1,20 @@
-// ivector-compute-lda / ivector-compute-plda / ivector-copy-plda / ivector-plda-scoring / compute-eer - drop-in command lines
-// for the back-end stage of the recipes (stage 7 of egs/sre/v2/run_sre10.sh:221-252; v5/run_sre10.sh:105-137,
-// v2/run_sre16.sh:76-116), one executable dispatching on its name:
+// ivector-compute-lda / ivector-compute-plda / ivector-copy-plda / ivector-adapt-plda / ivector-plda-scoring / compute-eer -
+// drop-in command lines for the back-end stage of the recipes (stage 7 of egs/sre/v2/run_sre10.sh:221-252;
+// v5/run_sre10.sh:105-137, stage 2 of v2/run_sre16.sh:76-175), one executable dispatching on its name:
 //   ivector-compute-lda [--dim=100 --total-covariance-factor=0.0 --covariance-floor=1e-6 --binary=true]
 //                       <ivector-rspecifier> <utt2spk-rspecifier> <lda-matrix-out>                      run_sre10.sh:229-231
 //   ivector-compute-plda [--num-em-iters=10 --binary=true] <spk2utt-rspecifier> <ivector-rspecifier> <plda-out>   :234-236
 //   ivector-copy-plda [--smoothing=0.0 --binary=true] <plda-in> <plda-out>                                       :243
+//   ivector-adapt-plda [--mean-diff-scale=1.0 --within-covar-scale=0.3 --between-covar-scale=0.7 --binary=true]
+//                      <plda-in> <ivectors-rspecifier> <plda-out>                       stage 2 of v2/run_sre16.sh:97-101
 //   ivector-plda-scoring [--normalize-length=true --simple-length-normalization=false --num-utts=<rspecifier>]
 //                        <plda> <train-ivector-rspecifier> <test-ivector-rspecifier> <trials-rxfilename> <scores-wxfilename>
 //                                                                                                           :240-246
 //   compute-eer <scores-rxfilename>    ("score target|nontarget" lines; the EER in percent on stdout)           :252
-// The statistics over the vectors, the PLDA transform of the vectors and the per-trial scores run on the HIP device
-// (plda.h); without a GPU these tools fail (exit 255).  compute-eer is host arithmetic only.  Semantics are upstream
-// Kaldi's [UPSTREAM, recalled] (ivectorbin/*.cc, ivector/plda.cc); log lines and exit codes follow the Kaldi idiom
-// (0 iff something was written, 1 if nothing was, 255 on an error).
+// The statistics over the vectors (for the adaptation: one segment that lists every vector), the PLDA transform of the
+// vectors and the per-trial scores run on the HIP device (plda.h); without a GPU these tools fail (exit 255).  compute-eer
+// is host arithmetic only.  Semantics are upstream Kaldi's [UPSTREAM, recalled] (ivectorbin/*.cc, ivector/plda.cc); log
+// lines and exit codes follow the Kaldi idiom (0 iff something was written, 1 if nothing was, 255 on an error).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -21,6 +23,7 @@
 #include <algorithm>
 #include <chrono>
 #include <map>
+#include <numeric>
 #include <sstream>
 #include <string>
 #include <unordered_map>
@@ -58,6 +61,9 @@ struct Args {
   double covariance_floor = 1e-6;
   int num_em_iters = 10;                // ivector-compute-plda
   double smoothing = 0.0;               // ivector-copy-plda
+  double mean_diff_scale = 1.0;         // ivector-adapt-plda
+  double within_covar_scale = 0.3;
+  double between_covar_scale = 0.7;
   bool normalize_length = true;         // ivector-plda-scoring
   bool simple_length_norm = false;
   std::string num_utts;
@@ -264,6 +270,33 @@ int CopyPlda(const Args& a) {
     XLOG("New value of Psi is " << VecText(plda.psi));
   }
   xv::WritePlda(a.pos[1], a.binary, plda);
+  return 0;
+}
+
+// PldaUnsupervisedAdaptor: the vectors' sum and scatter (fp64, on the device, xv::ScatterStats with one segment that
+// lists every row), then the update on the host (xv::AdaptPlda).
+int AdaptPlda(const Args& a) {
+  if (a.pos.size() != 3) return -2;
+  const int dev = PickDevice(a.device);
+  xv::Plda plda;
+  xv::ReadPlda(a.pos[0], &plda);
+  Packed p;
+  long n_err = 0;
+  ReadAll(a.pos[1], &p, &n_err);
+  XLOG("Accumulated stats from " << p.n() << " iVectors.");
+  if (p.n() == 0) throw xv::KioError("No iVectors read: there are no statistics to adapt the PLDA model with.");
+  if (p.dim != plda.dim)
+    throw xv::KioError("iVector dimension " + std::to_string(p.dim) + " does not match the PLDA dimension " + std::to_string(plda.dim));
+  const int dim = p.dim;
+  std::vector<int32_t> off = {0, p.n()}, idx(p.n());
+  std::iota(idx.begin(), idx.end(), 0);
+  std::vector<double> sum(dim), scatter((size_t)dim * dim);
+  xv::ScatterStats(dev, p.data.data(), p.n(), dim, off.data(), idx.data(), 1, scatter.data(), sum.data(), nullptr);
+  std::vector<std::string> log;
+  xv::AdaptPlda(p.n(), sum.data(), scatter.data(), a.mean_diff_scale, a.within_covar_scale, a.between_covar_scale, &plda, nullptr,
+                &log);
+  for (const std::string& l : log) XLOG(l);
+  xv::WritePlda(a.pos[2], a.binary, plda);
   return 0;
 }
 
@@ -491,6 +524,11 @@ const char* Usage(const std::string& prog) {
   if (prog == "ivector-copy-plda")
     return "Copy a PLDA object, possibly applying smoothing to the within-class covariance\n"
            "Usage: ivector-copy-plda [--smoothing=0.0] [--binary=true] <plda-in> <plda-out>\n";
+  if (prog == "ivector-adapt-plda")
+    return "Adapt a PLDA object using unsupervised adaptation-data iVectors from a different domain to the training data.\n"
+           "Usage: ivector-adapt-plda [options] <plda-in> <ivectors-rspecifier> <plda-out>\n"
+           "e.g.: ivector-adapt-plda plda ark:ivectors.ark plda.adapted\n"
+           "Options: --mean-diff-scale=1.0 --within-covar-scale=0.3 --between-covar-scale=0.7 --binary=true\n";
   if (prog == "compute-eer")
     return "Computes Equal Error Rate.  Input is a series of lines, each with two fields: the score and 'target' or\n"
            "'nontarget'.  The EER is printed in percent on the standard output.\n"
@@ -528,6 +566,9 @@ int main(int argc, char** argv) {
       else if (name == "covariance-floor" && g_prog == "ivector-compute-lda") ok = ParseDouble(val, &a.covariance_floor);
       else if (name == "num-em-iters" && g_prog == "ivector-compute-plda") ok = ParseInt(val, &a.num_em_iters) && a.num_em_iters >= 0;
       else if (name == "smoothing" && g_prog == "ivector-copy-plda") ok = ParseDouble(val, &a.smoothing);
+      else if (name == "mean-diff-scale" && g_prog == "ivector-adapt-plda") ok = ParseDouble(val, &a.mean_diff_scale);
+      else if (name == "within-covar-scale" && g_prog == "ivector-adapt-plda") ok = ParseDouble(val, &a.within_covar_scale);
+      else if (name == "between-covar-scale" && g_prog == "ivector-adapt-plda") ok = ParseDouble(val, &a.between_covar_scale);
       else if (name == "normalize-length" && g_prog == "ivector-plda-scoring") ok = ParseBool(val, &a.normalize_length);
       else if (name == "simple-length-normalization" && g_prog == "ivector-plda-scoring") ok = ParseBool(val, &a.simple_length_norm);
       else if (name == "num-utts" && g_prog == "ivector-plda-scoring") a.num_utts = val;
@@ -551,6 +592,7 @@ int main(int argc, char** argv) {
     if (g_prog == "ivector-compute-lda") rc = ComputeLda(a);
     else if (g_prog == "ivector-compute-plda") rc = ComputePlda(a);
     else if (g_prog == "ivector-copy-plda") rc = CopyPlda(a);
+    else if (g_prog == "ivector-adapt-plda") rc = AdaptPlda(a);
     else if (g_prog == "compute-eer") rc = ComputeEer(a);
     else rc = PldaScoring(a);
     if (rc == -2) {
