@@ -653,17 +653,7 @@ Engine::Engine(const uint8_t* blob, size_t n, int device, const void* device_ima
           throw EngineError("the pooled layer must feed only the statistics pooling");
   }
   nplanes_ = PrecWPlanes(info_.precision);   // residual planes exist for every split mode
-  // Kernel modes.  slow_prec_ runs everything that is not a frame-level GEMM of a "fast" chunk; fast chunks (only
-  // kPrecFp16x2 / kPrecAuto have them) are those that pool at least fast_min_pooled_ frames, see FillPlan.
-  const bool fast_family = info_.precision == kPrecFp16x2 || info_.precision == kPrecAuto || info_.precision == kPrecFp16Mx ||
-                           info_.precision == kPrecFp16Mx2;
-  slow_prec_ = fast_family ? (int)kPrecFp16x3 : info_.precision;
-  has_fast_ = !frame_mode_ && fast_family;
-  // fast chunks run kPrecFp16Mx on the layers that allow it (packed residual plane, sources with a group-max table)
-  // and kPrecFp16x2 on the others
-  fast_mx_ = has_fast_ && (info_.precision == kPrecAuto || info_.precision == kPrecFp16Mx || info_.precision == kPrecFp16Mx2);
-  fast_mx2_ = has_fast_ && info_.precision == kPrecFp16Mx2;
-  fast_min_pooled_ = 0;
+  fast_mode_ = info_.precision;   // the kernel modes (engine.h: slow_prec, has_fast, fast_mx, fast_mx2) follow from it
   if (info_.precision == kPrecAuto || info_.precision == kPrecFp16Mx2) {
     // kPrecFp16Mx2 corrects the activation rounding, but what is left still averages over the pooled frames: 3-4e-5 at
     // 386 pooled frames, 4.5e-5 at 123, 0.6-1.5e-4 at 11 - chunks below the threshold take the three-pass arithmetic
@@ -672,7 +662,6 @@ Engine::Engine(const uint8_t* blob, size_t n, int device, const void* device_ima
     mx2_min_pooled_ = (e && *e) ? atoi(e) : kDefaultFastMinPooledMx2;
     mx_min_pooled_ = (e && *e) ? atoi(e) : kDefaultFastMinPooled;
   }
-  fast_mode_ = info_.precision;
   Check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate");
   {
     const char* e = getenv("XVEC_LANES");
@@ -878,7 +867,7 @@ void Engine::EnsureCapacity(Lane& L, int rows, int b_pad, hipStream_t s) {
       }
     }
     // per layer: max |activation| of every 16-row group (what a kPrecFp16Mx consumer scales its 4-bit copy by)
-    if (fast_mx_ || can_switch_fast_mode()) Ensure(&L.gmax, layers_.size() * (size_t)(rows / kRowAlign) * 4, true, s);
+    if (fast_mx() || can_switch_fast_mode()) Ensure(&L.gmax, layers_.size() * (size_t)(rows / kRowAlign) * 4, true, s);
     L.gmax_stride = rows / kRowAlign;
     L.cap_rows = rows;
   }
@@ -942,7 +931,7 @@ void Engine::FillPlan(const int32_t* row_offsets, int B, Plan* plan, std::vector
     const int last = std::min(key[b] - 1 - pl.right, info_.pool_right);
     if (last < pool_first) throw EngineError("chunk has no frame inside the pooling window");
     cnt[b] = last - pool_first + 1;
-    fast[b] = has_fast_ && cnt[b] >= fast_min_pooled_;
+    fast[b] = has_fast() && cnt[b] >= fast_min_pooled_;
   }
   long off = 0;
   for (int pass = 0; pass < 2; ++pass) {
@@ -954,7 +943,7 @@ void Engine::FillPlan(const int32_t* row_offsets, int B, Plan* plan, std::vector
     }
     // the 256-row GEMM variant needs an even number of 128-row tiles; the region of the two-pass kernels is cut into
     // 512-row tiles by the stream-K variant
-    off = RoundUp((int)off, (pass == 0 && has_fast_) ? 4 * kBM : 2 * kBM);
+    off = RoundUp((int)off, (pass == 0 && has_fast()) ? 4 * kBM : 2 * kBM);
     if (pass == 0) plan->rows_fast = (int)off;
   }
   plan->rows = (int)off;
@@ -990,7 +979,7 @@ void Engine::FillPlan(const int32_t* row_offsets, int B, Plan* plan, std::vector
   // per layer: the rows of every 16-row group that are computable frames of that layer (kPrecFp16Mx group maxima)
   const int nlay = (int)info_.layers.size();
   std::vector<int8_t> act_range;
-  if (fast_mx_ && !frame_mode_) {
+  if (fast_mx() && !frame_mode_) {
     act_range.assign((size_t)nlay * ngrp * 2, 0);
     for (int i = 0; i < nlay; ++i) {
       const BlobLayerInfo& li = info_.layers[i];
@@ -1086,20 +1075,233 @@ void Engine::Forward(const Plan& plan, const float* feats_dev, float* out_dev, i
                 out_ld, stream);
 }
 
-void Engine::ForwardOnLane(size_t lane, const Plan& plan, const float* feats_dev, float* out_dev, int out_ld,
-                           hipStream_t stream) {
-  Check(hipSetDevice(device_), "hipSetDevice");
-  Lane& L = lanes_[lane % lanes_.size()];
-  hipStream_t s = stream ? stream : L.stream;
-  if (stream && stream != stream_ && std::find(ext_streams_.begin(), ext_streams_.end(), stream) == ext_streams_.end()) {
-    bool own = false;
-    for (const Lane& l : lanes_) own = own || l.stream == stream;
-    if (!own) ext_streams_.push_back(stream);
+// Layer i's arguments over all rows of the plan; returns its epilogue.  mx_pass: the fast rows read the group maxima of the
+// sources and record those of the output planes (LaunchPrec drops both for the other rows).  direct_out: the output layer
+// writes into out_dev itself.
+int Engine::LayerArgs(Lane& L, const Plan& plan, size_t i, bool mx_pass, float* out_dev, int out_ld, bool direct_out,
+                      GemmArgs* args) {
+  const BlobLayerInfo& li = info_.layers[i];
+  const DevLayer& dl = layers_[i];
+  auto gmax_of = [&](int layer) { return (unsigned*)L.gmax.p + (size_t)layer * L.gmax_stride; };
+  GemmArgs& ga = *args;
+  memset(&ga, 0, sizeof ga);
+  ga.nseg = (int)li.src.size();
+  int ksteps = 0;
+  for (int j = 0; j < ga.nseg; ++j) {
+    const LayerSource& src = li.src[j];
+    Seg& sg = ga.seg[j];
+    if (src.layer == kSrcInput) {
+      sg.hi = ActBase(L.in_hi, in_ld_);
+      sg.lo = ActBase(L.in_lo, in_ld_);
+      sg.ld = in_ld_;
+    } else if (src.layer == kSrcPooled) {
+      sg.hi = (const uint16_t*)L.stats_hi.p;
+      sg.lo = (const uint16_t*)L.stats_lo.p;
+      sg.ld = stats_ld_;
+    } else {
+      const BlobLayerInfo& pi = info_.layers[src.layer];
+      if (pi.segment_level) {
+        sg.hi = (const uint16_t*)L.act[src.layer].act_hi.p;
+        sg.lo = (const uint16_t*)L.act[src.layer].act_lo.p;
+      } else {
+        sg.hi = ActBase(L.act[src.layer].act_hi, pi.n_pad);
+        sg.lo = ActBase(L.act[src.layer].act_lo, pi.n_pad);
+      }
+      sg.ld = pi.n_pad;
+    }
+    sg.row_shift = li.segment_level ? 0 : src.offset;
+    sg.ksteps = SrcKPad(src.dim, src.layer, li.segment_level, info_.precision) / kBK;
+    const bool frame_src = !li.segment_level && src.layer >= 0 && !info_.layers[src.layer].segment_level;
+    sg.gmax = (mx_pass && frame_src) ? gmax_of(src.layer) : nullptr;
+    if (fast_mx2() && frame_src) {
+      const int pn = info_.layers[src.layer].n_pad;
+      sg.lo4 = (const uint8_t*)L.act[src.layer].act_lo4.p + (size_t)kHalo * (pn / 2);
+      sg.lo4s = (const uint8_t*)L.act[src.layer].act_lo4s.p + (size_t)kHalo * Lo4ScalePitch(pn);
+    }
+    ksteps += sg.ksteps;
   }
-  if (L.busy) Check(hipStreamWaitEvent(s, L.done, 0), "hipStreamWaitEvent(lane)");
-  EnsureCapacity(L, plan.rows, plan.b_pad, s);
-  const int prec = slow_prec_;
+  ga.total_ksteps = ksteps;
+  ga.w_hi = dl.w_hi;
+  ga.w_lo = dl.w_lo;
+  ga.ldw = li.k_pad;
+  ga.w4 = dl.w4;
+  ga.w4_scale = dl.w4_scale;
+  ga.ldw4 = dl.ldw4;
+  ga.w4b = dl.w4b;
+  ga.w4b_scale = dl.w4b_scale;
+  ga.ldw4b = dl.ldw4b;
+  ga.n_tiles = li.n_pad / kBN;
+  ga.relu = li.relu;
+  ga.bn = li.bn;
+  ga.bias = dl.bias;
+  ga.scale = dl.scale;
+  ga.offset = dl.offset;
+  int epi;
+  if (!li.segment_level) {
+    ga.m_tiles = plan.rows / kBM;
+    if ((int)i == info_.pooled_layer) {
+      epi = kEpiStats;
+      ga.partial = (float*)L.partial.p;
+      ga.ldp = li.n_pad;
+      ga.grp_range = plan.d_grp_range;
+    } else if (frame_mode_ && (int)i == info_.output_layer && logits16()) {
+      epi = kEpiAct;   // the head's logits as an fp16 plane (no halo rows: nothing splices them)
+      ga.out_hi = (uint16_t*)L.frame_f32.p;
+      ga.out_lo = nullptr;
+      ga.ldo = li.n_pad;
+    } else if (frame_mode_ && (int)i == info_.output_layer) {
+      epi = kEpiF32;
+      ga.out_f32 = (float*)L.frame_f32.p;
+      ga.ldf = li.n_pad;
+      ga.m_valid = plan.rows;
+    } else {
+      epi = kEpiAct;
+      ga.out_hi = ActBase(L.act[i].act_hi, li.n_pad);
+      ga.out_lo = ActBase(L.act[i].act_lo, li.n_pad);
+      ga.ldo = li.n_pad;
+      if (fast_mx2()) {
+        ga.out_lo4 = (uint8_t*)L.act[i].act_lo4.p + (size_t)kHalo * (li.n_pad / 2);
+        ga.out_lo4s = (uint8_t*)L.act[i].act_lo4s.p + (size_t)kHalo * Lo4ScalePitch(li.n_pad);
+      }
+      if (mx_pass) {   // (the fast rows start at row 0: the tables need no offset)
+        ga.gmax_out = gmax_of((int)i);
+        ga.out_range = plan.d_act_range + (size_t)i * plan.ngrp * 2;
+      }
+    }
+  } else {
+    ga.m_tiles = plan.b_pad / kBM;
+    // few rows, long K (3000 for the embedding layer): K is split over up to 24 slices of at least 4 steps - a rule that does
+    // not depend on the batch, so an utterance's sums are formed in the same order whatever it is batched with.  Measured
+    // on the 256-chunk embedding layer (94 steps, 2 x 4 tiles), GEMM + reduction: 12 steps x 8 slices 23.3 us, 8 x 12 20.4,
+    // 6 x 16 19.4, 4 x 24 18.8, 3 x 32 19.3, 2 x 47 25.2 (with the workgroups spread over all XCDs, kernels.hip; while they
+    // all sat on two of them more slices only queued: 25.9 / 31.6 / 36.8 us for 8 / 12 / 24 slices)
+    const int per = std::max(4, (ksteps + 23) / 24);
+    ga.ksteps_per_slice = per;
+    ga.ksplit = (ksteps + per - 1) / per;
+    if (ga.ksplit > 1) {
+      Ensure(&L.splitk_ws, (size_t)ga.ksplit * plan.b_pad * li.n_pad * 4, false);
+      ga.splitk_ws = (float*)L.splitk_ws.p;
+    }
+    if ((int)i == info_.output_layer) {
+      epi = kEpiF32;
+      ga.out_f32 = direct_out ? out_dev : (float*)L.out_f32.p;
+      ga.ldf = direct_out ? out_ld : li.n_pad;
+      ga.m_valid = plan.B;
+    } else {
+      epi = kEpiAct;
+      ga.out_hi = (uint16_t*)L.act[i].act_hi.p;
+      ga.out_lo = (uint16_t*)L.act[i].act_lo.p;
+      ga.ldo = li.n_pad;
+    }
+  }
+  // scales of the residual plane in the tile order of this epilogue's operand orientation (TileMxScales)
+  if (ga.w4_scale && epi == kEpiStats) ga.w4_scale += (size_t)li.n_pad * (li.k_pad / kBK);
+  if (ga.w4b_scale && epi == kEpiStats) ga.w4b_scale += (size_t)li.n_pad * (li.k_pad / kBK);
+  return epi;
+}
 
+// tdnn_first_kernel over device rows [r0, r1): reads the caller's fp32 rows through the plan's tables (absolute device rows:
+// no pointer shifts)
+FirstArgs Engine::FirstLayerArgs(const Plan& plan, size_t i, const GemmArgs& ga, const float* feats_dev, int r0, int r1) const {
+  const BlobLayerInfo& li = info_.layers[i];
+  FirstArgs fa;
+  memset(&fa, 0, sizeof fa);
+  fa.g = ga;
+  fa.feats = feats_dev;
+  fa.feats_valid_idx = (long)plan.src_off[0] * info_.input_dim;
+  fa.grp_src = (const int4*)plan.d_grp_src;
+  fa.rows = plan.rows;
+  fa.dim = info_.input_dim;
+  fa.noff = (int)li.src.size();
+  for (int j = 0; j < fa.noff; ++j) fa.off[j] = li.src[j].offset;
+  fa.wc_hi = layers_[i].wc_hi;
+  fa.wc_lo = layers_[i].wc_lo;
+  fa.row0 = r0;
+  fa.nrows = r1 - r0;
+  return fa;
+}
+
+// The arguments of a launch over all rows restricted to rows [r0, r1) (r0: a multiple of kBM)
+static GemmArgs SliceRows(GemmArgs g, long r0, long r1) {
+  g.m_tiles = (int)((r1 - r0) / kBM);
+  g.m_valid = (int)(r1 - r0);
+  for (int j = 0; j < g.nseg; ++j) {
+    Seg& sg = g.seg[j];
+    sg.hi += r0 * sg.ld;
+    if (sg.lo) sg.lo += r0 * sg.ld;
+    if (sg.lo4) sg.lo4 += r0 * (sg.ld / 2);
+    if (sg.lo4s) sg.lo4s += r0 * Lo4ScalePitch(sg.ld);
+  }
+  if (g.out_hi) g.out_hi += r0 * g.ldo;
+  if (g.out_lo) g.out_lo += r0 * g.ldo;
+  if (g.out_lo4) g.out_lo4 += r0 * (g.ldo / 2);
+  if (g.out_lo4s) g.out_lo4s += r0 * Lo4ScalePitch(g.ldo);
+  if (g.out_f32) g.out_f32 += r0 * g.ldf;
+  if (g.partial) g.partial += (r0 / kRowAlign) * 2 * g.ldp;
+  if (g.grp_range) g.grp_range += (r0 / kRowAlign) * 2;
+  return g;
+}
+
+// Which arithmetic and which kernel one launch of layer i runs - over the fast rows (`fast`: the pass has fast rows, so its
+// mx_pass is fast_mx()) or the others - is decided here and nowhere else.  g: the launch's arguments; the slow rows drop
+// the group-max tables, a lite layer that emits no residual plane drops that output, and a launch that runs
+// tdnn_gemm_kernel_p8 gets that kernel's weight images.
+int Engine::LaunchPrec(size_t i, int epi, bool fast, GemmArgs* g) const {
+  const BlobLayerInfo& li = info_.layers[i];
+  const DevLayer& dl = layers_[i];
+  int p = slow_prec();
+  if (!fast) {
+    g->gmax_out = nullptr;
+    g->out_range = nullptr;
+    for (int j = 0; j < g->nseg; ++j) g->seg[j].gmax = nullptr;
+    // single-pass fp16: the layers tdnn_gemm_kernel_p8 can run, run it - for every launch (see below)
+    if (dl.first || p != kPrecFp16 || li.segment_level) return p;
+  } else if (dl.first) {
+    // tdnn_first_kernel: the planes epilogue of the fast arithmetic (mixed mode: a first layer whose consumers are all lite
+    // writes the fp16 plane only)
+    return (fast_mx2() && (!lite_mask_ || lite_emits_[i])) ? (int)kPrecFp16x3E : (int)kPrecFp16x2;
+  } else if (fast_mx2() && lite_mask_ && lite_[i] && gemm_mx_applicable(*g)) {
+    // a lite layer of the mixed mode (SetLiteMask): the 1.25-pass product, with the planes epilogue that writes the residual
+    // plane of its output where a consumer needs it
+    p = (lite_emits_[i] && epi == kEpiAct) ? (int)kPrecFp16MxE : (int)kPrecFp16Mx;
+    if (p == kPrecFp16Mx) {
+      g->out_lo4 = nullptr;
+      g->out_lo4s = nullptr;
+    }
+  } else if (fast_mx2()) {
+    // every layer emits the 4-bit residual of its fp16 plane; a layer that cannot run the second walk reads the
+    // network input only (PackModel checked it) and runs the three-pass arithmetic on the planes of prep_input
+    p = gemm_mx2_applicable(*g) ? (int)kPrecFp16Mx2 : (int)kPrecFp16x3E;
+    if (p == kPrecFp16x3E && epi != kEpiAct) throw EngineError("fp16mx2: layer " + li.name + " cannot run the mode");
+    if (p == kPrecFp16x3E) return p;
+  } else {
+    p = (fast_mx() && gemm_mx_applicable(*g)) ? (int)kPrecFp16Mx : (int)kPrecFp16x2;
+    if (p == kPrecFp16x2) return p;
+  }
+  // tdnn_gemm_kernel_p8 runs all of a layer's launches in the mode that it can, whatever their size (its sums are formed in
+  // another order than the 32-column kernels', and a chunk's embedding must not depend on its batch).  It needs the weight
+  // images of the mode in its walk order: none for fp16, the residual plane for fp16mx(-E), also the 4-bit weights for fp16mx2.
+  const bool mx = p != kPrecFp16, mx2 = p == kPrecFp16Mx2;
+  if (!use_p8_ || (epi != kEpiAct && epi != kEpiStats) || (mx && !dl.w4p) || (mx2 && !dl.w4bp)) return p;
+  const size_t so = epi == kEpiStats ? (size_t)li.n_pad * (li.k_pad / kBK) : 0;   // scales in the statistics tile order
+  GemmArgs g8 = *g;
+  g8.p8 = 1;
+  g8.p8_whole = p8_whole_;
+  if (mx) {
+    g8.w4 = dl.w4p;
+    g8.w4_scale = dl.w4p_scale + so;
+  }
+  if (mx2) {
+    g8.w4b = dl.w4bp;
+    g8.ldw4b = li.k_pad * 2;
+    g8.w4b_scale = dl.w4bp_scale + so;
+  }
+  if (gemm_p8_applicable(g8, p)) *g = g8;
+  return p;
+}
+
+// prep_input: the input planes of the batch; with fast rows it also clears the group-max tables of the pass
+PrepArgs Engine::PrepInputArgs(const Lane& L, const Plan& plan, const float* feats_dev, bool mx_pass) const {
   PrepArgs pa;
   pa.feats = feats_dev;
   pa.src_off = plan.d_src_off;
@@ -1112,10 +1314,57 @@ void Engine::ForwardOnLane(size_t lane, const Plan& plan, const float* feats_dev
   pa.out_lo = ActBase(L.in_lo, in_ld_);
   pa.pad_left = pad_left_;
   pa.pad_right = pad_right_;
-  const bool mx_pass = fast_mx_ && plan.rows_fast > 0;
   pa.zero_words = mx_pass ? (unsigned*)L.gmax.p : nullptr;
   pa.n_zero_words = mx_pass ? (int)(layers_.size() * (size_t)L.gmax_stride) : 0;
-  auto gmax_of = [&](int layer) { return (unsigned*)L.gmax.p + (size_t)layer * L.gmax_stride; };
+  return pa;
+}
+
+PoolArgs Engine::PoolingArgs(const Lane& L, const Plan& plan) const {
+  PoolArgs po;
+  po.partial = (const float*)L.partial.p;
+  po.ldp = info_.layers[info_.pooled_layer].n_pad;
+  po.utt_grp0 = plan.d_utt_grp0;
+  po.utt_grp1 = plan.d_utt_grp1;
+  po.utt_count = plan.d_utt_count;
+  po.B = plan.B;
+  po.dim = info_.pool_dim;
+  po.var_floor = info_.variance_floor;
+  po.out_hi = (uint16_t*)L.stats_hi.p;
+  po.out_lo = (uint16_t*)L.stats_lo.p;
+  po.ld = stats_ld_;
+  return po;
+}
+
+// frame_output: one row per input frame, or a pooled output taken after a LogSoftmaxComponent (e.g. the speaker posteriors
+// of the unedited x-vector net)
+FrameOutArgs Engine::OutputArgs(const Lane& L, const Plan& plan, float* out_dev, int out_ld) const {
+  const BlobLayerInfo& ol = info_.layers[info_.output_layer];
+  FrameOutArgs fo;
+  fo.src = logits16() ? nullptr : (const float*)(frame_mode_ ? L.frame_f32.p : L.out_f32.p);
+  fo.src16 = logits16() ? (const uint16_t*)L.frame_f32.p : nullptr;
+  fo.ld = ol.n_pad;
+  fo.out_row = frame_mode_ ? plan.d_out_row : nullptr;
+  fo.n_out = frame_mode_ ? plan.n_out : plan.B;
+  fo.dim = info_.output_dim;
+  fo.log_softmax = ol.log_softmax;
+  fo.out = out_dev;
+  fo.out_ld = out_ld;
+  return fo;
+}
+
+void Engine::ForwardOnLane(size_t lane, const Plan& plan, const float* feats_dev, float* out_dev, int out_ld,
+                           hipStream_t stream) {
+  Check(hipSetDevice(device_), "hipSetDevice");
+  Lane& L = lanes_[lane % lanes_.size()];
+  hipStream_t s = stream ? stream : L.stream;
+  if (stream && stream != stream_ && std::find(ext_streams_.begin(), ext_streams_.end(), stream) == ext_streams_.end()) {
+    bool own = false;
+    for (const Lane& l : lanes_) own = own || l.stream == stream;
+    if (!own) ext_streams_.push_back(stream);
+  }
+  if (L.busy) Check(hipStreamWaitEvent(s, L.done, 0), "hipStreamWaitEvent(lane)");
+  EnsureCapacity(L, plan.rows, plan.b_pad, s);
+  const bool mx_pass = fast_mx() && plan.rows_fast > 0;
   // profiling: every launch_* call below is bracketed by its own (start, stop) event pair, stamped by the dispatch
   // itself (kernels.hip: set_launch_events) - no extra packets between the kernels of the timed region
   std::vector<hipEvent_t> prof_run;
@@ -1133,314 +1382,58 @@ void Engine::ForwardOnLane(size_t lane, const Plan& plan, const float* feats_dev
   auto disarm = [&]() {
     if (prof_on_) set_launch_events(nullptr, nullptr);
   };
+  const PrepArgs pa = PrepInputArgs(L, plan, feats_dev, mx_pass);
   if (need_prep_) {
     arm("prep_input");
-    Check(launch_prep_input(pa, prec, s), "prep_input launch");
+    Check(launch_prep_input(pa, slow_prec(), s), "prep_input launch");
     disarm();
   } else if (pa.n_zero_words > 0) {
     // the group-max tables of this pass, otherwise cleared by prep_input
     Check(hipMemsetAsync(pa.zero_words, 0, (size_t)pa.n_zero_words * 4, s), "hipMemsetAsync(group maxima)");
   }
 
-  bool direct_out = false;   // the output layer wrote into out_dev itself
+  // the embedding goes straight into the caller's buffer when its rows can take the 16-byte stores of all n_pad columns (no
+  // padding columns, aligned); otherwise through out_f32 and a strided copy
+  const BlobLayerInfo& ol = info_.layers[info_.output_layer];
+  const bool direct_out = ol.segment_level && !ol.log_softmax && ol.n_pad == info_.output_dim && (out_ld & 3) == 0 &&
+                          out_ld >= ol.n_pad && ((uintptr_t)out_dev & 15) == 0;
   for (size_t i = 0; i < layers_.size(); ++i) {
     const BlobLayerInfo& li = info_.layers[i];
-    DevLayer& dl = layers_[i];
     GemmArgs ga;
-    memset(&ga, 0, sizeof ga);
-    ga.nseg = (int)li.src.size();
-    int ksteps = 0;
-    for (int j = 0; j < ga.nseg; ++j) {
-      const LayerSource& src = li.src[j];
-      Seg& sg = ga.seg[j];
-      if (src.layer == kSrcInput) {
-        sg.hi = ActBase(L.in_hi, in_ld_);
-        sg.lo = ActBase(L.in_lo, in_ld_);
-        sg.ld = in_ld_;
-      } else if (src.layer == kSrcPooled) {
-        sg.hi = (const uint16_t*)L.stats_hi.p;
-        sg.lo = (const uint16_t*)L.stats_lo.p;
-        sg.ld = stats_ld_;
-      } else {
-        const BlobLayerInfo& pi = info_.layers[src.layer];
-        if (pi.segment_level) {
-          sg.hi = (const uint16_t*)L.act[src.layer].act_hi.p;
-          sg.lo = (const uint16_t*)L.act[src.layer].act_lo.p;
-        } else {
-          sg.hi = ActBase(L.act[src.layer].act_hi, pi.n_pad);
-          sg.lo = ActBase(L.act[src.layer].act_lo, pi.n_pad);
-        }
-        sg.ld = pi.n_pad;
-      }
-      sg.row_shift = li.segment_level ? 0 : src.offset;
-      sg.ksteps = SrcKPad(src.dim, src.layer, li.segment_level, info_.precision) / kBK;
-      sg.gmax = (mx_pass && !li.segment_level && src.layer >= 0 && !info_.layers[src.layer].segment_level) ? gmax_of(src.layer)
-                                                                                                      : nullptr;
-      if (fast_mx2_ && !li.segment_level && src.layer >= 0 && !info_.layers[src.layer].segment_level) {
-        const int pn = info_.layers[src.layer].n_pad;
-        sg.lo4 = (const uint8_t*)L.act[src.layer].act_lo4.p + (size_t)kHalo * (pn / 2);
-        sg.lo4s = (const uint8_t*)L.act[src.layer].act_lo4s.p + (size_t)kHalo * Lo4ScalePitch(pn);
-      }
-      ksteps += sg.ksteps;
-    }
-    ga.total_ksteps = ksteps;
-    ga.w_hi = dl.w_hi;
-    ga.w_lo = dl.w_lo;
-    ga.ldw = li.k_pad;
-    ga.w4 = dl.w4;
-    ga.w4_scale = dl.w4_scale;
-    ga.ldw4 = dl.ldw4;
-    ga.w4b = dl.w4b;
-    ga.w4b_scale = dl.w4b_scale;
-    ga.ldw4b = dl.ldw4b;
-    ga.n_tiles = li.n_pad / kBN;
-    ga.relu = li.relu;
-    ga.bn = li.bn;
-    ga.bias = dl.bias;
-    ga.scale = dl.scale;
-    ga.offset = dl.offset;
-    int epi;
-    if (!li.segment_level) {
-      ga.m_tiles = plan.rows / kBM;
-      if ((int)i == info_.pooled_layer) {
-        epi = kEpiStats;
-        ga.partial = (float*)L.partial.p;
-        ga.ldp = li.n_pad;
-        ga.grp_range = plan.d_grp_range;
-      } else if (frame_mode_ && (int)i == info_.output_layer && logits16()) {
-        epi = kEpiAct;   // the head's logits as an fp16 plane (no halo rows: nothing splices them)
-        ga.out_hi = (uint16_t*)L.frame_f32.p;
-        ga.out_lo = nullptr;
-        ga.ldo = li.n_pad;
-      } else if (frame_mode_ && (int)i == info_.output_layer) {
-        epi = kEpiF32;
-        ga.out_f32 = (float*)L.frame_f32.p;
-        ga.ldf = li.n_pad;
-        ga.m_valid = plan.rows;
-      } else {
-        epi = kEpiAct;
-        ga.out_hi = ActBase(L.act[i].act_hi, li.n_pad);
-        ga.out_lo = ActBase(L.act[i].act_lo, li.n_pad);
-        ga.ldo = li.n_pad;
-        if (fast_mx2_) {
-          ga.out_lo4 = (uint8_t*)L.act[i].act_lo4.p + (size_t)kHalo * (li.n_pad / 2);
-          ga.out_lo4s = (uint8_t*)L.act[i].act_lo4s.p + (size_t)kHalo * Lo4ScalePitch(li.n_pad);
-        }
-      }
-    } else {
-      ga.m_tiles = plan.b_pad / kBM;
-      // few rows, long K (3000 for the embedding layer): K is split over up to 24 slices of at least 4 steps - a rule that does
-      // not depend on the batch, so an utterance's sums are formed in the same order whatever it is batched with.  Measured
-      // on the 256-chunk embedding layer (94 steps, 2 x 4 tiles), GEMM + reduction: 12 steps x 8 slices 23.3 us, 8 x 12 20.4,
-      // 6 x 16 19.4, 4 x 24 18.8, 3 x 32 19.3, 2 x 47 25.2 (with the workgroups spread over all XCDs, kernels.hip; while they
-      // all sat on two of them more slices only queued: 25.9 / 31.6 / 36.8 us for 8 / 12 / 24 slices)
-      const int per = std::max(4, (ksteps + 23) / 24);
-      ga.ksteps_per_slice = per;
-      ga.ksplit = (ksteps + per - 1) / per;
-      if (ga.ksplit > 1) {
-        Ensure(&L.splitk_ws, (size_t)ga.ksplit * plan.b_pad * li.n_pad * 4, false);
-        ga.splitk_ws = (float*)L.splitk_ws.p;
-      }
-      if ((int)i == info_.output_layer) {
-        epi = kEpiF32;
-        // the embedding goes straight into the caller's buffer when its rows can take the 16-byte stores of all n_pad
-        // columns (no padding columns, aligned); otherwise through out_f32 and a strided copy
-        direct_out = !li.log_softmax && li.n_pad == info_.output_dim && (out_ld & 3) == 0 && out_ld >= li.n_pad &&
-                     ((uintptr_t)out_dev & 15) == 0;
-        ga.out_f32 = direct_out ? out_dev : (float*)L.out_f32.p;
-        ga.ldf = direct_out ? out_ld : li.n_pad;
-        ga.m_valid = plan.B;
-      } else {
-        epi = kEpiAct;
-        ga.out_hi = (uint16_t*)L.act[i].act_hi.p;
-        ga.out_lo = (uint16_t*)L.act[i].act_lo.p;
-        ga.ldo = li.n_pad;
-      }
-    }
-    // scales of the residual plane in the tile order of this epilogue's operand orientation (TileMxScales)
-    if (ga.w4_scale && epi == kEpiStats) ga.w4_scale += (size_t)li.n_pad * (li.k_pad / kBK);
-    if (ga.w4b_scale && epi == kEpiStats) ga.w4b_scale += (size_t)li.n_pad * (li.k_pad / kBK);
+    const int epi = LayerArgs(L, plan, i, mx_pass, out_dev, out_ld, direct_out, &ga);
     arm(std::string("tdnn_gemm<") + (epi == kEpiAct ? "act" : epi == kEpiF32 ? "f32" : "stats") + ">:" + li.name);
-    if (dl.first) {
-      // reads the caller's fp32 rows through the plan's tables; one launch per row region, the planes epilogue of the
-      // region's arithmetic (absolute device rows: no pointer shifts)
-      FirstArgs fa;
-      memset(&fa, 0, sizeof fa);
-      fa.g = ga;
-      fa.feats = feats_dev;
-      fa.feats_valid_idx = (long)plan.src_off[0] * info_.input_dim;
-      fa.grp_src = (const int4*)plan.d_grp_src;
-      fa.rows = plan.rows;
-      fa.dim = info_.input_dim;
-      fa.noff = (int)li.src.size();
-      for (int j = 0; j < fa.noff; ++j) fa.off[j] = li.src[j].offset;
-      fa.wc_hi = dl.wc_hi;
-      fa.wc_lo = dl.wc_lo;
-      for (int region = 0; region < 2; ++region) {
-        fa.row0 = region == 0 ? 0 : plan.rows_fast;
-        fa.nrows = (region == 0 ? plan.rows_fast : plan.rows) - fa.row0;
-        if (fa.nrows <= 0) continue;
-        int eprec = prec;   // slow region: both planes of the three-pass arithmetic
-        fa.g.gmax_out = nullptr;
-        fa.g.out_range = nullptr;
-        if (region == 0) {
-          // (mixed mode: a first layer whose consumers are all lite writes the fp16 plane only)
-          eprec = (fast_mx2_ && (!lite_mask_ || lite_emits_[i])) ? (int)kPrecFp16x3E : (int)kPrecFp16x2;
-          if (mx_pass) {
-            fa.g.gmax_out = gmax_of((int)i);
-            fa.g.out_range = plan.d_act_range + (size_t)i * plan.ngrp * 2;
-          }
-        }
-        Check(launch_tdnn_first(fa, eprec, s), "tdnn_first launch");
-        if (first_prof) prof_labels_.back() += std::string(" ") + last_gemm_kernel();
-      }
-    } else if (li.segment_level || plan.rows_fast == 0) {
-      if (prec == kPrecFp16 && use_p8_ && !li.segment_level && (epi == kEpiAct || epi == kEpiStats)) {
-        // single-pass fp16: the layers tdnn_gemm_kernel_p8 can run, run it - for every launch (see the fast region below)
-        GemmArgs g8 = ga;
-        g8.p8 = 1;
-        g8.p8_whole = p8_whole_;
-        if (gemm_p8_applicable(g8, kPrecFp16)) ga = g8;
-      }
-      Check(launch_tdnn_gemm(ga, prec, epi, s), "tdnn_gemm launch");
+    if (!layers_[i].first && (li.segment_level || plan.rows_fast == 0)) {
+      const int p = LaunchPrec(i, epi, false, &ga);
+      Check(launch_tdnn_gemm(ga, p, epi, s), "tdnn_gemm launch");
       if (first_prof) prof_labels_.back() += std::string(" ") + last_gemm_kernel();
     } else {
-      // rows [0, rows_fast): two-pass kernels; the rest: slow_prec_.  Same arguments, row base moved.
+      // one launch per row region: [0, rows_fast) in the fast arithmetic, the rest in slow_prec()
       for (int region = 0; region < 2; ++region) {
-        const long r0 = region == 0 ? 0 : plan.rows_fast;
-        const long r1 = region == 0 ? plan.rows_fast : plan.rows;
+        const int r0 = region == 0 ? 0 : plan.rows_fast, r1 = region == 0 ? plan.rows_fast : plan.rows;
         if (r1 <= r0) continue;
-        GemmArgs gr = ga;
-        gr.m_tiles = (int)((r1 - r0) / kBM);
-        for (int j = 0; j < gr.nseg; ++j) {
-          gr.seg[j].hi += r0 * gr.seg[j].ld;
-          if (gr.seg[j].lo) gr.seg[j].lo += r0 * gr.seg[j].ld;
-          if (gr.seg[j].lo4) gr.seg[j].lo4 += r0 * (gr.seg[j].ld / 2);
-          if (gr.seg[j].lo4s) gr.seg[j].lo4s += r0 * Lo4ScalePitch(gr.seg[j].ld);
+        if (layers_[i].first) {
+          FirstArgs fa = FirstLayerArgs(plan, i, ga, feats_dev, r0, r1);
+          const int p = LaunchPrec(i, epi, region == 0, &fa.g);
+          Check(launch_tdnn_first(fa, p, s), "tdnn_first launch");
+        } else {
+          GemmArgs gr = SliceRows(ga, r0, r1);
+          const int p = LaunchPrec(i, epi, region == 0, &gr);
+          Check(launch_tdnn_gemm(gr, p, epi, s), "tdnn_gemm launch");
         }
-        if (gr.out_hi) gr.out_hi += r0 * gr.ldo;
-        if (gr.out_lo) gr.out_lo += r0 * gr.ldo;
-        if (gr.out_lo4) gr.out_lo4 += r0 * (gr.ldo / 2);
-        if (gr.out_lo4s) gr.out_lo4s += r0 * Lo4ScalePitch(gr.ldo);
-        // the fast region records the group maxima of the planes it writes and, where the layer allows, runs the
-        // 1.25-pass mode on them (region 0 starts at row 0: the tables need no offset)
-        if (region == 0 && mx_pass && epi == kEpiAct) {
-          gr.gmax_out = gmax_of((int)i);
-          gr.out_range = plan.d_act_range + (size_t)i * plan.ngrp * 2;
-        }
-        if (region != 0)
-          for (int j = 0; j < gr.nseg; ++j) gr.seg[j].gmax = nullptr;
-        if (gr.out_f32) gr.out_f32 += r0 * gr.ldf;
-        if (gr.partial) gr.partial += (r0 / kRowAlign) * 2 * gr.ldp;
-        if (gr.grp_range) gr.grp_range += (r0 / kRowAlign) * 2;
-        gr.m_valid = (int)(r1 - r0);
-        int rprec = prec;
-        if (region == 0) {
-          if (fast_mx2_ && lite_mask_ && lite_[i] && mx_pass && gemm_mx_applicable(gr)) {
-            // a lite layer of the mixed mode (SetLiteMask): the 1.25-pass product, on the 256 x 256 kernel where no consumer
-            // needs the residual plane of its output, else with the planes epilogue that writes it
-            if (lite_emits_[i] && epi == kEpiAct) {
-              rprec = kPrecFp16MxE;
-            } else {
-              rprec = kPrecFp16Mx;
-              gr.out_lo4 = nullptr;
-              gr.out_lo4s = nullptr;
-            }
-            // (both on the 256 x 256 kernel where the layer's shape allows: the same K walk, so the fp16 plane of a lite layer
-            // has the same bits whether or not it also writes its residual plane)
-            if (use_p8_ && dl.w4p && (epi == kEpiAct || epi == kEpiStats)) {
-              GemmArgs g8 = gr;
-              g8.p8 = 1;
-              g8.p8_whole = p8_whole_;
-              g8.w4 = dl.w4p;
-              g8.w4_scale = dl.w4p_scale + (epi == kEpiStats ? (size_t)li.n_pad * (li.k_pad / kBK) : 0);
-              if (gemm_p8_applicable(g8, rprec)) gr = g8;
-            }
-          } else if (fast_mx2_) {
-            // every layer emits the 4-bit residual of its fp16 plane; a layer that cannot run the second walk reads the
-            // network input only (PackModel checked it) and runs the three-pass arithmetic on the planes of prep_input
-            rprec = gemm_mx2_applicable(gr) ? (int)kPrecFp16Mx2 : (int)kPrecFp16x3E;
-            if (rprec == kPrecFp16x3E && epi != kEpiAct) throw EngineError("fp16mx2: layer " + li.name + " cannot run the mode");
-            if (rprec == kPrecFp16Mx2 && use_p8_ && dl.w4p && dl.w4bp && (epi == kEpiAct || epi == kEpiStats)) {
-              // the 1.5-pass launches of the layers tdnn_gemm_kernel_p8 can run: both 4-bit images in its walk orders
-              const size_t so = epi == kEpiStats ? (size_t)li.n_pad * (li.k_pad / kBK) : 0;
-              GemmArgs g8 = gr;
-              g8.p8 = 1;
-              g8.p8_whole = p8_whole_;
-              g8.w4 = dl.w4p;
-              g8.w4_scale = dl.w4p_scale + so;
-              g8.w4b = dl.w4bp;
-              g8.ldw4b = li.k_pad * 2;
-              g8.w4b_scale = dl.w4bp_scale + so;
-              if (gemm_p8_applicable(g8, kPrecFp16Mx2)) gr = g8;
-            }
-          } else {
-            rprec = (mx_pass && gemm_mx_applicable(gr)) ? (int)kPrecFp16Mx : (int)kPrecFp16x2;
-            if (rprec == kPrecFp16Mx && use_p8_ && dl.w4p && (epi == kEpiAct || epi == kEpiStats)) {
-              // the layer's 1.25-pass launches run the 256 x 256 x 64 kernel - all of them, whatever their size: its sums are
-              // formed in another order than the 32-column kernels', and a chunk's embedding must not depend on its batch
-              GemmArgs g8 = gr;
-              g8.p8 = 1;
-              g8.p8_whole = p8_whole_;
-              g8.w4 = dl.w4p;
-              g8.w4_scale = dl.w4p_scale + (epi == kEpiStats ? (size_t)li.n_pad * (li.k_pad / kBK) : 0);
-              if (gemm_p8_applicable(g8, kPrecFp16Mx)) gr = g8;
-            }
-          }
-        }
-        Check(launch_tdnn_gemm(gr, rprec, epi, s), "tdnn_gemm launch");
         if (first_prof) prof_labels_.back() += std::string(" ") + last_gemm_kernel();
       }
     }
     disarm();
 
     if ((int)i == info_.pooled_layer) {
-      PoolArgs po;
-      po.partial = (const float*)L.partial.p;
-      po.ldp = li.n_pad;
-      po.utt_grp0 = plan.d_utt_grp0;
-      po.utt_grp1 = plan.d_utt_grp1;
-      po.utt_count = plan.d_utt_count;
-      po.B = plan.B;
-      po.dim = info_.pool_dim;
-      po.var_floor = info_.variance_floor;
-      po.out_hi = (uint16_t*)L.stats_hi.p;
-      po.out_lo = (uint16_t*)L.stats_lo.p;
-      po.ld = stats_ld_;
       arm("pool_finalise");
-      Check(launch_pool_finalise(po, prec, s), "pool_finalise launch");
+      Check(launch_pool_finalise(PoolingArgs(L, plan), slow_prec(), s), "pool_finalise launch");
       disarm();
     }
   }
-  const BlobLayerInfo& ol = info_.layers[info_.output_layer];
-  if (frame_mode_) {
-    FrameOutArgs fo;
-    fo.src = logits16() ? nullptr : (const float*)L.frame_f32.p;
-    fo.src16 = logits16() ? (const uint16_t*)L.frame_f32.p : nullptr;
-    fo.ld = ol.n_pad;
-    fo.out_row = plan.d_out_row;
-    fo.n_out = plan.n_out;
-    fo.dim = info_.output_dim;
-    fo.log_softmax = ol.log_softmax;
-    fo.out = out_dev;
-    fo.out_ld = out_ld;
+  if (frame_mode_ || ol.log_softmax) {
     arm("frame_output");
-    Check(launch_frame_output(fo, s), "frame_output launch");
-    disarm();
-  } else if (ol.log_softmax) {
-    // pooled output taken after a LogSoftmaxComponent (e.g. the speaker posteriors of the unedited x-vector net)
-    FrameOutArgs fo;
-    fo.src = (const float*)L.out_f32.p;
-    fo.src16 = nullptr;
-    fo.ld = ol.n_pad;
-    fo.out_row = nullptr;
-    fo.n_out = plan.B;
-    fo.dim = info_.output_dim;
-    fo.log_softmax = 1;
-    fo.out = out_dev;
-    fo.out_ld = out_ld;
-    arm("frame_output");
-    Check(launch_frame_output(fo, s), "frame_output launch");
+    Check(launch_frame_output(OutputArgs(L, plan, out_dev, out_ld), s), "frame_output launch");
     disarm();
   } else if (!direct_out) {
     Check(hipMemcpy2DAsync(out_dev, (size_t)out_ld * 4, L.out_f32.p, (size_t)ol.n_pad * 4, (size_t)info_.output_dim * 4,
@@ -1461,9 +1454,6 @@ void Engine::SetFastMode(int mode) {
   for (const HostSlot& S : host_slots_)
     if (S.pending) throw EngineError("SetFastMode with a batch in flight");
   fast_mode_ = mode;
-  fast_mx2_ = mode == kPrecFp16Mx2;
-  fast_mx_ = mode != kPrecFp16x3;
-  has_fast_ = mode != kPrecFp16x3;
   fast_min_pooled_ = mode == kPrecFp16Mx2 ? mx2_min_pooled_ : mx_min_pooled_;
   lite_mask_ = 0;
   lite_.assign(layers_.size(), 0);

@@ -252,6 +252,13 @@ class Engine {
   void FillPlan(const int32_t* row_offsets, int B, Plan* plan, std::vector<uint8_t>* tables) const;
   static void BindPlan(Plan* plan, const void* device_tables);
   void ForwardOnLane(size_t lane, const Plan& plan, const float* feats_dev, float* out_dev, int out_ld, hipStream_t stream);
+  // the steps of ForwardOnLane (engine.cc)
+  int LayerArgs(Lane& L, const Plan& plan, size_t i, bool mx_pass, float* out_dev, int out_ld, bool direct_out, GemmArgs* args);
+  FirstArgs FirstLayerArgs(const Plan& plan, size_t i, const GemmArgs& ga, const float* feats_dev, int r0, int r1) const;
+  int LaunchPrec(size_t i, int epi, bool fast, GemmArgs* g) const;
+  PrepArgs PrepInputArgs(const Lane& L, const Plan& plan, const float* feats_dev, bool mx_pass) const;
+  PoolArgs PoolingArgs(const Lane& L, const Plan& plan) const;
+  FrameOutArgs OutputArgs(const Lane& L, const Plan& plan, float* out_dev, int out_ld) const;
   void Check(hipError_t e, const char* what) const;
  public:
   // throws when a kernel of this process reported a fault the HIP API cannot see (called after synchronising)
@@ -271,15 +278,17 @@ class Engine {
   bool frame_mode_ = false;   // output is one row per input frame (nnet3-compute semantics), no pooling
   int pad_left_ = 0, pad_right_ = 0;
   int nplanes_ = 1;
-  // precision policy (engine.cc, constructor): kernel mode of everything but the frame-level GEMMs of "fast" chunks,
-  // whether fast chunks exist at all, and the number of pooled frames that makes a chunk fast
+  // Kernel modes, functions of the packed precision and fast_mode_ (each launch's: LaunchPrec).  slow_prec() runs all but the
+  // frame-level GEMMs of "fast" chunks (FillPlan), which the fast families alone have: kPrecFp16Mx where a layer allows it and
+  // kPrecFp16x2 elsewhere (fast_mx), or kPrecFp16Mx2 on every frame-level layer, kPrecFp16x3E on the input (fast_mx2).
   static constexpr int kDefaultFastMinPooled = 300;
-  int slow_prec_ = 0;
-  bool has_fast_ = false;
-  bool fast_mx_ = false;
+  static bool fast_family(int p) { return p == kPrecFp16x2 || p == kPrecAuto || p == kPrecFp16Mx || p == kPrecFp16Mx2; }
+  int slow_prec() const { return fast_family(info_.precision) ? (int)kPrecFp16x3 : info_.precision; }
+  bool has_fast() const { return !frame_mode_ && fast_family(fast_mode_); }
+  bool fast_mx() const { return has_fast() && fast_mode_ != kPrecFp16x2; }
+  bool fast_mx2() const { return has_fast() && fast_mode_ == kPrecFp16Mx2; }
   int p8_whole_ = 0;   // XVEC_DEBUG=p8_whole: partition policy of tdnn_gemm_kernel_p8 (engine.cc)
   bool use_p8_ = true;      // tdnn_gemm_kernel_p8 for the layers and modes it can run (XVEC_DEBUG=p8=0: never)
-  bool fast_mx2_ = false;   // kPrecFp16Mx2: every frame-level layer of a fast chunk runs it (or kPrecFp16x3E on the input)
   // Frame-level log-posteriors in the single-pass fp16 mode: the head's logits stay a 16-bit plane like every other layer's
   // output of that mode (2 instead of 4 bytes per logit written by the head GEMM and read by the LogSoftmax pass: the two
   // were store- and bandwidth-bound on 1.6 GB each way); the log-posteriors themselves are fp32.  Every other mode keeps
