@@ -327,6 +327,59 @@ xv_status xv_plda_adapt(int32_t dim, int64_t n, const double* m, const double* v
                         const double* psi, double mean_diff_scale, double within_covar_scale, double between_covar_scale,
                         double* mean_out, double* transform_out, double* psi_out, double* s_out);
 
+/* ---- feature stage (stage 1 of egs/sre/v2/run_sre10.sh:78-90: compute-mfcc-feats, compute-vad) -------------------
+ * Waveform to MFCC and MFCC to energy-VAD decisions on the device, behind host buffers.  Semantics are Kaldi's
+ * (option names and defaults of compute-mfcc-feats / compute-vad); fp32 arithmetic.  A result depends on the utterance
+ * and the options, never on the batch: an utterance computed alone and inside any batch gives the same bytes.
+ * window_type: 0 povey, 1 hamming, 2 hanning, 3 rectangular, 4 blackman.  Not built (XV_ERR_ARG): VTLN, HTK
+ * compatibility, round_to_power_of_two == 0, resampling.
+ *   xv_mfcc_options_default  Kaldi's defaults (16 kHz, 25/10 ms, povey, dither 1.0, 23 mel bins, 13 ceps, lifter 22).
+ *   xv_mfcc_num_frames       host only: frames Kaldi extracts from n_samples samples (snip_edges true: 1 + (n - L)/S for
+ *                            n >= L, else 0; false: (n + S/2)/S); -1 with xv_last_error() for unusable options.
+ *   xv_mfcc_utt_seed         host only: the 64-bit hash of an utterance key that keys the dither generator.
+ *   xv_mfcc_compute          samples: fp32 in Kaldi's unscaled range (+-32768), utterance u = samples[sample_offsets[u] ..
+ *                            sample_offsets[u+1]); utt_seeds [n_utts] may be NULL when dither == 0 (else XV_ERR_ARG).
+ *                            out_row_offsets [n_utts + 1] is written (frame offsets); out receives
+ *                            out_row_offsets[n_utts] * num_ceps floats - size it with xv_mfcc_num_frames.  Dither is drawn
+ *                            from a counter-based generator keyed by (seed, frame, sample): reproducible, and the same in
+ *                            any job, shard or batch; it matches Kaldi's rand()-driven dither in distribution only.
+ *   xv_mfcc_compute_i16      the same for 16-bit PCM (converted on the device; the same bytes out).
+ *   xv_vad_energy            Kaldi's ComputeVadEnergy on feats [row_offsets[n_utts]][dim] (column 0 = log energy):
+ *                            out[row] = 1.0 / 0.0 per frame.  The utterance mean is summed in a fixed order in fp64.
+ *   xv_wave_read             host only: reads a RIFF/WAVE (16-bit PCM) from an rxfilename (file or "cmd |"), picks a channel
+ *                            as compute-mfcc-feats --channel does (-1: mono as is, else channel 0); *samples is malloc'ed
+ *                            [*n] int16, released with xv_wave_free.
+ *   xv_mfcc_kernel_time      for tools/bench_mfcc.py: runs the int16 batch reps times on one set of device buffers and returns the
+ *                            shortest kernel time between two events (ms), copies excluded.
+ * The device entries fail with XV_ERR_DEVICE when no gfx950 device is usable. */
+typedef struct {
+  float sample_frequency, frame_length_ms, frame_shift_ms, dither, preemphasis_coefficient, blackman_coeff;
+  int32_t remove_dc_offset, window_type, round_to_power_of_two, snip_edges;
+  int32_t num_mel_bins;
+  float low_freq, high_freq;
+  int32_t num_ceps;
+  float cepstral_lifter;
+  int32_t use_energy, raw_energy;
+  float energy_floor;
+} xv_mfcc_options;
+typedef struct {
+  float vad_energy_threshold, vad_energy_mean_scale, vad_proportion_threshold;
+  int32_t vad_frames_context;
+} xv_vad_options;
+void xv_mfcc_options_default(xv_mfcc_options* opts);
+int64_t xv_mfcc_num_frames(const xv_mfcc_options* opts, int64_t n_samples);
+uint64_t xv_mfcc_utt_seed(const char* key);
+xv_status xv_mfcc_compute(int device, const xv_mfcc_options* opts, const float* samples, const int64_t* sample_offsets,
+                          int32_t n_utts, const uint64_t* utt_seeds, float* out, int32_t* out_row_offsets);
+xv_status xv_mfcc_compute_i16(int device, const xv_mfcc_options* opts, const int16_t* samples, const int64_t* sample_offsets,
+                              int32_t n_utts, const uint64_t* utt_seeds, float* out, int32_t* out_row_offsets);
+xv_status xv_mfcc_kernel_time(int device, const xv_mfcc_options* opts, const int16_t* samples, const int64_t* sample_offsets,
+                              int32_t n_utts, int32_t reps, float* kernel_ms);
+xv_status xv_vad_energy(int device, const xv_vad_options* vad_opts, const float* feats, const int32_t* row_offsets,
+                        int32_t n_utts, int32_t dim, float* out);
+xv_status xv_wave_read(const char* rxfilename, int32_t channel, int32_t* rate, int16_t** samples, int64_t* n);
+void xv_wave_free(int16_t* samples);
+
 /* ---- kernel-level entry (unit tests of the HIP GEMM against a plain fp32 reference) ------------------- */
 typedef struct {
   const void* hi;   /* device plane (bf16 / fp16) at logical row 0 */

@@ -95,7 +95,9 @@ ABI_SYMBOLS = [
     "xv_ctx_set_calibration_file", "xv_calibration_file_read", "xv_calibration_file_publish", "xv_recognize_feature_pipeline", "xv_ctx_set_lite_layers", "xv_ctx_lite_layers",
     "xv_extract_table", "xv_frontend_cmvn_select", "xv_plan_chunks", "xv_ctx_create_broadcast", "xv_kernel_tdnn_gemm",
     "xv_backend_apply", "xv_segment_mean", "xv_scatter_stats", "xv_plda_transform", "xv_plda_score", "xv_lda_estimate",
-    "xv_plda_estimate", "xv_plda_adapt", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
+    "xv_plda_estimate", "xv_plda_adapt",
+    "xv_mfcc_options_default", "xv_mfcc_num_frames", "xv_mfcc_utt_seed", "xv_mfcc_compute", "xv_mfcc_compute_i16", "xv_mfcc_kernel_time", "xv_vad_energy",
+    "xv_wave_read", "xv_wave_free", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
 ]
 
 _lib = None
@@ -693,6 +695,138 @@ def plda_adapt(n, m, v, mean, transform, psi, mean_diff_scale=1.0, within_covar_
                            mean_diff_scale, within_covar_scale, between_covar_scale, mean_out.ctypes.data,
                            transform_out.ctypes.data, psi_out.ctypes.data, s.ctypes.data))
     return mean_out, transform_out, psi_out, s
+
+
+class MfccOptions(ctypes.Structure):
+    """xv_mfcc_options; mfcc_options() gives Kaldi's defaults with keyword overrides."""
+    _fields_ = [(n, ctypes.c_float) for n in ("sample_frequency", "frame_length_ms", "frame_shift_ms", "dither",
+                                              "preemphasis_coefficient", "blackman_coeff")] + \
+               [(n, ctypes.c_int32) for n in ("remove_dc_offset", "window_type", "round_to_power_of_two", "snip_edges", "num_mel_bins")] + \
+               [("low_freq", ctypes.c_float), ("high_freq", ctypes.c_float), ("num_ceps", ctypes.c_int32),
+                ("cepstral_lifter", ctypes.c_float), ("use_energy", ctypes.c_int32), ("raw_energy", ctypes.c_int32),
+                ("energy_floor", ctypes.c_float)]
+
+
+class VadOptions(ctypes.Structure):
+    _fields_ = [("vad_energy_threshold", ctypes.c_float), ("vad_energy_mean_scale", ctypes.c_float),
+                ("vad_proportion_threshold", ctypes.c_float), ("vad_frames_context", ctypes.c_int32)]
+
+
+WINDOW_TYPES = {"povey": 0, "hamming": 1, "hanning": 2, "rectangular": 3, "blackman": 4}
+_MFCC_ALIASES = {"frame_length": "frame_length_ms", "frame_shift": "frame_shift_ms"}
+
+
+def mfcc_options(**opts):
+    """Kaldi's compute-mfcc-feats defaults (xv_mfcc_options_default) with overrides named like the command-line options
+    (underscores for dashes): sample_frequency, frame_length, frame_shift, dither, preemphasis_coefficient, remove_dc_offset,
+    window_type (a name), blackman_coeff, round_to_power_of_two, snip_edges, num_mel_bins, low_freq, high_freq, num_ceps,
+    cepstral_lifter, use_energy, raw_energy, energy_floor."""
+    L = lib()
+    L.xv_mfcc_options_default.argtypes = [ctypes.POINTER(MfccOptions)]
+    L.xv_mfcc_options_default.restype = None
+    o = MfccOptions()
+    L.xv_mfcc_options_default(ctypes.byref(o))
+    names = {n for n, _ in MfccOptions._fields_}
+    for k, v in opts.items():
+        k = _MFCC_ALIASES.get(k, k)
+        if k not in names:
+            raise XvError(XV_ERR_ARG, "unknown MFCC option %r" % k)
+        if k == "window_type" and isinstance(v, str):
+            if v not in WINDOW_TYPES:
+                raise XvError(XV_ERR_ARG, "Invalid window type %s" % v)
+            v = WINDOW_TYPES[v]
+        setattr(o, k, v)
+    return o
+
+
+def mfcc_num_frames(n_samples, **opts):
+    """Frames Kaldi extracts from n_samples samples under these options (host only)."""
+    L = lib()
+    L.xv_mfcc_num_frames.argtypes = [ctypes.POINTER(MfccOptions), ctypes.c_int64]
+    L.xv_mfcc_num_frames.restype = ctypes.c_int64
+    o = opts["options"] if "options" in opts else mfcc_options(**opts)
+    n = L.xv_mfcc_num_frames(ctypes.byref(o), int(n_samples))
+    if n < 0:
+        raise XvError(XV_ERR_ARG, L.xv_last_error().decode(errors="replace"))
+    return int(n)
+
+
+def utt_seed(key):
+    """The 64-bit hash of an utterance key that keys the dither generator (xv_mfcc_utt_seed)."""
+    L = lib()
+    L.xv_mfcc_utt_seed.argtypes = [ctypes.c_char_p]
+    L.xv_mfcc_utt_seed.restype = ctypes.c_uint64
+    return int(L.xv_mfcc_utt_seed(key.encode()))
+
+
+def mfcc(waves, keys=None, device=0, **opts):
+    """MFCCs of a list of waveforms on the device (compute-mfcc-feats): waves are 1-d arrays in Kaldi's unscaled range, all
+    int16 (converted on the device) or anything else (taken as float32).  keys name the utterances for the dither generator
+    (default "0", "1", ...; unused with dither=0).  Returns a list of float32 [frames, num_ceps] arrays."""
+    import numpy as np
+    L = lib()
+    o = opts.pop("options") if "options" in opts else mfcc_options(**opts)
+    i16 = len(waves) > 0 and all(np.asarray(w).dtype == np.int16 for w in waves)
+    dt = np.int16 if i16 else np.float32
+    ws = [np.ascontiguousarray(w, dtype=dt).reshape(-1) for w in waves]
+    off = np.zeros(len(ws) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(w) for w in ws])
+    samples = np.concatenate(ws) if ws else np.zeros(0, dt)
+    if samples.size == 0:
+        samples = np.zeros(1, dt)
+    if keys is None:
+        keys = [str(i) for i in range(len(ws))]
+    seeds = np.array([utt_seed(k) for k in keys], dtype=np.uint64)
+    frames = [mfcc_num_frames(len(w), options=o) for w in ws]
+    out = np.empty((max(1, sum(frames)), o.num_ceps), dtype=np.float32)
+    row_off = np.zeros(len(ws) + 1, dtype=np.int32)
+    fn = L.xv_mfcc_compute_i16 if i16 else L.xv_mfcc_compute
+    fn.argtypes = [ctypes.c_int, ctypes.POINTER(MfccOptions), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                   ctypes.c_void_p, ctypes.c_void_p]
+    _check(fn(device, ctypes.byref(o), samples.ctypes.data, off.ctypes.data, len(ws), seeds.ctypes.data if len(ws) else None,
+              out.ctypes.data, row_off.ctypes.data))
+    assert list(np.diff(row_off)) == frames
+    return [out[row_off[i]:row_off[i + 1]].copy() for i in range(len(ws))]
+
+
+def vad(feats, device=0, vad_energy_threshold=5.0, vad_energy_mean_scale=0.5, vad_proportion_threshold=0.6, vad_frames_context=0):
+    """Kaldi's energy VAD (compute-vad) on the device for a list of float32 [frames, dim] feature matrices (column 0 = log
+    energy).  Returns a list of float32 [frames] arrays of 1.0 / 0.0."""
+    import numpy as np
+    L = lib()
+    fs = [np.ascontiguousarray(f, dtype=np.float32) for f in feats]
+    dim = fs[0].shape[1] if fs else 1
+    if any(f.ndim != 2 or f.shape[1] != dim for f in fs):
+        raise XvError(XV_ERR_ARG, "vad: every feature matrix must be [frames, %d]" % dim)
+    off = np.zeros(len(fs) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([f.shape[0] for f in fs])
+    packed = np.concatenate(fs, axis=0) if fs else np.zeros((0, dim), np.float32)
+    out = np.empty(max(1, int(off[-1])), dtype=np.float32)
+    o = VadOptions(vad_energy_threshold, vad_energy_mean_scale, vad_proportion_threshold, vad_frames_context)
+    L.xv_vad_energy.argtypes = [ctypes.c_int, ctypes.POINTER(VadOptions), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                ctypes.c_int32, ctypes.c_void_p]
+    _check(L.xv_vad_energy(device, ctypes.byref(o), packed.ctypes.data if packed.size else None, off.ctypes.data, len(fs), dim,
+                           out.ctypes.data))
+    return [out[off[i]:off[i + 1]].copy() for i in range(len(fs))]
+
+
+def read_wave(rxfilename, channel=-1):
+    """Reads a 16-bit PCM RIFF/WAVE from a file or a "cmd |" pipe the way compute-mfcc-feats does (xv_wave_read; host only).
+    Returns (rate, int16 array of the chosen channel)."""
+    import numpy as np
+    L = lib()
+    L.xv_wave_read.argtypes = [ctypes.c_char_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                               ctypes.POINTER(ctypes.POINTER(ctypes.c_int16)), ctypes.POINTER(ctypes.c_int64)]
+    L.xv_wave_free.argtypes = [ctypes.POINTER(ctypes.c_int16)]
+    L.xv_wave_free.restype = None
+    rate, n = ctypes.c_int32(0), ctypes.c_int64(0)
+    p = ctypes.POINTER(ctypes.c_int16)()
+    _check(L.xv_wave_read(os.fsencode(rxfilename), channel, ctypes.byref(rate), ctypes.byref(p), ctypes.byref(n)))
+    try:
+        x = np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.int16)
+    finally:
+        L.xv_wave_free(p)
+    return rate.value, x
 
 
 def kernel_tdnn_gemm(desc):

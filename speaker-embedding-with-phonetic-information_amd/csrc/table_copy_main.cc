@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -18,9 +19,13 @@ int main(int argc, char** argv) {
   const bool vectors = strstr(prog, "vector") != nullptr;
   try {
     std::vector<std::string> pos;
+    std::string num_frames_wspecifier;   // copy-feats --write-num-frames=<int32 wspecifier> (steps/make_mfcc.sh:88: utt2num_frames)
     for (int i = 1; i < argc; ++i) {
       std::string a = argv[i];
-      if (a.compare(0, 2, "--") == 0 && pos.empty()) continue;  // ark,t: / ark: in the wspecifier decides the form
+      if (a.compare(0, 2, "--") == 0 && pos.empty()) {
+        if (!vectors && a.compare(0, 19, "--write-num-frames=") == 0) num_frames_wspecifier = a.substr(19);
+        continue;  // the others: ark,t: / ark: in the wspecifier decides the form
+      }
       pos.push_back(a);
     }
     if (pos.size() != 2) {
@@ -29,6 +34,8 @@ int main(int argc, char** argv) {
     }
     xv::TableWriter w(pos[1]);
     long n = 0, bad = 0;
+    std::unique_ptr<xv::TableWriter> wn;
+    if (!num_frames_wspecifier.empty()) wn.reset(new xv::TableWriter(num_frames_wspecifier));
     if (!vectors) {
       xv::SequentialMatrixReader r(pos[0]);
       std::string key, err;
@@ -40,6 +47,7 @@ int main(int argc, char** argv) {
           continue;
         }
         w.WriteMat(key, m);
+        if (wn) wn->WriteInt32(key, m.rows);
         ++n;
       }
     } else {
@@ -84,6 +92,7 @@ int main(int argc, char** argv) {
       }
     }
     w.Close();
+    if (wn) wn->Close();
     fprintf(stderr, "LOG (%s) Copied %ld %s%s\n", prog, n, vectors ? "vectors" : "feature matrices",
             bad ? " (some entries failed)" : "");
     return n > 0 ? 0 : 1;
