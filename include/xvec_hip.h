@@ -380,6 +380,55 @@ xv_status xv_vad_energy(int device, const xv_vad_options* vad_opts, const float*
 xv_status xv_wave_read(const char* rxfilename, int32_t channel, int32_t* rate, int16_t** samples, int64_t* n);
 void xv_wave_free(int16_t* samples);
 
+/* ---- augmentation stage (stage 2 of egs/sre/v2/run_sre10.sh:92-159: wav-reverberate) -------------------------------
+ * Convolution with a room impulse response, additive noises at given SNRs and start times, normalisation, shift, trim or
+ * repetition and the conversion to 16-bit samples, on the device for a ragged batch.  Semantics are Kaldi's wav-reverberate for
+ * one output channel (csrc/reverb.h restates them); fp32 signals, fp64 power sums in a fixed order.  An utterance's output
+ * depends on the utterance alone, never on the batch.
+ *   xv_reverb_options_default  Kaldi's defaults: shift_output 1, normalize_output 1, duration 0, volume 0, channels 0.
+ *   xv_reverb_output_length    host only: samples written for an input of n samples and a RIR of rir_len taps (0: none).
+ *   xv_wav_reverberate         samples: int16 (samples_are_i16 != 0) or fp32 in the 16-bit range, utterance u =
+ *                              [sample_offsets[u], sample_offsets[u+1]), all at sample_rate.  rirs / noises: fp32 as read from
+ *                              their files (not scaled), ragged by rir_offsets [n_rirs + 1] / noise_offsets [n_noises + 1].
+ *                              utt_rir [n_utts]: index of the utterance's RIR or -1 (NULL: none anywhere; utterances that name
+ *                              the same index share its spectra).  The additive signals of utterance u are entries
+ *                              [utt_add_offsets[u], utt_add_offsets[u+1]) of add_noise (index into the noises), add_snr (dB)
+ *                              and add_start (seconds); utt_add_offsets NULL: none.  out_offsets [n_utts + 1] is written;
+ *                              out_f32 receives out_offsets[n_utts] floats, the signal before quantisation - size it with
+ *                              xv_reverb_output_length; out_i16 (may be NULL) the samples as a wave file holds them (truncated
+ *                              toward zero, saturated) and clipped (may be NULL) [n_utts] how many were saturated.  The
+ *                              channel fields of the options are for the readers of files and are not looked at here.
+ *   xv_reverb_kernel_time      for tools/bench_reverb.py: the same call reps times, returns the shortest sum of the kernels'
+ *                              times between events (ms), copies excluded.
+ *   xv_recognize_wav_pipeline  host only: whether a wav.scp entry is a pipe that compute-mfcc-feats takes over instead of running
+ *                              it (last stage wav-reverberate with only its own options, reading "-" or one file, writing
+ *                              "-"; one level of nesting inside the additive signals; csrc/fuse_wav.h); *found = 0 / 1 and,
+ *                              when found, description receives "name=value" lines: source, impulse-response, the options
+ *                              and additive[i].snr / .start / .rx or the nested element's fields.
+ *   xv_wave_write              host only: writes one channel as RIFF/WAVE, 16-bit PCM, to a wxfilename (file, "-" or "| cmd"),
+ *                              fp32 samples truncated toward zero and saturated as above; *clipped (may be NULL) the count. */
+typedef struct {
+  int32_t shift_output, normalize_output;
+  float duration, volume;
+  int32_t input_wave_channel, rir_channel, noise_channel;
+} xv_reverb_options;
+void xv_reverb_options_default(xv_reverb_options* opts);
+int64_t xv_reverb_output_length(const xv_reverb_options* opts, float sample_rate, int64_t n_samples, int64_t rir_len);
+xv_status xv_wav_reverberate(int device, const xv_reverb_options* opts, float sample_rate, const void* samples,
+                             int32_t samples_are_i16, const int64_t* sample_offsets, int32_t n_utts, const float* rirs,
+                             const int64_t* rir_offsets, int32_t n_rirs, const int32_t* utt_rir, const float* noises,
+                             const int64_t* noise_offsets, int32_t n_noises, const int32_t* utt_add_offsets,
+                             const int32_t* add_noise, const float* add_snr, const float* add_start, int64_t* out_offsets,
+                             float* out_f32, int16_t* out_i16, int64_t* clipped);
+xv_status xv_reverb_kernel_time(int device, const xv_reverb_options* opts, float sample_rate, const void* samples,
+                                int32_t samples_are_i16, const int64_t* sample_offsets, int32_t n_utts, const float* rirs,
+                                const int64_t* rir_offsets, int32_t n_rirs, const int32_t* utt_rir, const float* noises,
+                                const int64_t* noise_offsets, int32_t n_noises, const int32_t* utt_add_offsets,
+                                const int32_t* add_noise, const float* add_snr, const float* add_start, int32_t reps,
+                                float* kernel_ms);
+xv_status xv_recognize_wav_pipeline(const char* rxfilename, int32_t* found, char* description, size_t description_cap);
+xv_status xv_wave_write(const char* wxfilename, int32_t rate, const float* samples, int64_t n, int64_t* clipped);
+
 /* ---- kernel-level entry (unit tests of the HIP GEMM against a plain fp32 reference) ------------------- */
 typedef struct {
   const void* hi;   /* device plane (bf16 / fp16) at logical row 0 */

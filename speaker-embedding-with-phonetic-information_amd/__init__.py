@@ -97,6 +97,7 @@ ABI_SYMBOLS = [
     "xv_backend_apply", "xv_segment_mean", "xv_scatter_stats", "xv_plda_transform", "xv_plda_score", "xv_lda_estimate",
     "xv_plda_estimate", "xv_plda_adapt",
     "xv_mfcc_options_default", "xv_mfcc_num_frames", "xv_mfcc_utt_seed", "xv_mfcc_compute", "xv_mfcc_compute_i16", "xv_mfcc_kernel_time", "xv_vad_energy",
+    "xv_reverb_options_default", "xv_reverb_output_length", "xv_wav_reverberate", "xv_reverb_kernel_time", "xv_wave_write", "xv_recognize_wav_pipeline",
     "xv_wave_read", "xv_wave_free", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
 ]
 
@@ -827,6 +828,149 @@ def read_wave(rxfilename, channel=-1):
     finally:
         L.xv_wave_free(p)
     return rate.value, x
+
+
+def write_wave(wxfilename, samples, rate):
+    """Writes a 1-d array as one channel of 16-bit PCM RIFF/WAVE to a file, "-" or "| cmd" (xv_wave_write; host only): values
+    are truncated toward zero and saturated to the 16-bit range.  Returns how many were saturated."""
+    import numpy as np
+    L = lib()
+    L.xv_wave_write.argtypes = [ctypes.c_char_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    x = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+    clipped = ctypes.c_int64(0)
+    _check(L.xv_wave_write(os.fsencode(wxfilename), int(rate), x.ctypes.data if x.size else None, x.size, ctypes.byref(clipped)))
+    return clipped.value
+
+
+def recognize_wav_pipeline(rxfilename):
+    """None, or the fields of the wav-reverberate line compute-mfcc-feats would take over instead of running it
+    (xv_recognize_wav_pipeline; host only): a dict of the "name=value" lines, e.g. "source", "impulse-response", "duration",
+    "additive[0].rx", "additive[1].source"."""
+    L = lib()
+    L.xv_recognize_wav_pipeline.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_size_t]
+    found = ctypes.c_int32(0)
+    buf = ctypes.create_string_buffer(1 << 16)
+    _check(L.xv_recognize_wav_pipeline(rxfilename.encode(), ctypes.byref(found), buf, len(buf)))
+    if not found.value:
+        return None
+    return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
+
+
+class ReverbOptions(ctypes.Structure):
+    """xv_reverb_options; reverb_options() gives Kaldi's defaults with keyword overrides."""
+    _fields_ = [("shift_output", ctypes.c_int32), ("normalize_output", ctypes.c_int32), ("duration", ctypes.c_float),
+                ("volume", ctypes.c_float), ("input_wave_channel", ctypes.c_int32), ("rir_channel", ctypes.c_int32),
+                ("noise_channel", ctypes.c_int32)]
+
+
+def reverb_options(**opts):
+    """wav-reverberate's defaults (xv_reverb_options_default) with overrides named like the command-line options (underscores
+    for dashes): shift_output, normalize_output, duration, volume, input_wave_channel, rir_channel, noise_channel."""
+    L = lib()
+    L.xv_reverb_options_default.argtypes = [ctypes.POINTER(ReverbOptions)]
+    L.xv_reverb_options_default.restype = None
+    o = ReverbOptions()
+    L.xv_reverb_options_default(ctypes.byref(o))
+    names = {n for n, _ in ReverbOptions._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise XvError(XV_ERR_ARG, "unknown wav-reverberate option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+def reverb_output_length(n_samples, rir_len=0, rate=8000.0, **opts):
+    """Samples wav-reverberate writes for an input of n_samples and a RIR of rir_len taps (0: none); host only."""
+    L = lib()
+    L.xv_reverb_output_length.argtypes = [ctypes.POINTER(ReverbOptions), ctypes.c_float, ctypes.c_int64, ctypes.c_int64]
+    L.xv_reverb_output_length.restype = ctypes.c_int64
+    o = opts["options"] if "options" in opts else reverb_options(**opts)
+    return int(L.xv_reverb_output_length(ctypes.byref(o), float(rate), int(n_samples), int(rir_len)))
+
+
+_REVERB_ARGTYPES = [ctypes.c_int, ctypes.POINTER(ReverbOptions), ctypes.c_float, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                    ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                    ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+
+
+def _ragged(arrays, dtype):
+    import numpy as np
+    xs = [np.ascontiguousarray(a, dtype=dtype).reshape(-1) for a in arrays]
+    off = np.zeros(len(xs) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(x) for x in xs])
+    flat = np.concatenate(xs) if xs else np.zeros(0, dtype)
+    if flat.size == 0:
+        flat = np.zeros(1, dtype)
+    return flat, off
+
+
+def reverberate(waves, rirs=None, additive=None, rate=8000.0, device=0, return_int16=False, kernel_time_reps=0, **opts):
+    """wav-reverberate on the device for a list of waveforms (1-d arrays in the 16-bit range, all int16 or taken as float32).
+    rirs: None, or one entry per waveform: None, an array (the impulse response as read from its file, not scaled), or an int
+    index into `rir_list=` given among the options (utterances naming the same index share its spectra).  additive: None, or
+    per waveform a list of (noise array, snr dB, start seconds).  Options are named like the command line's (shift_output,
+    normalize_output, duration, volume).  Returns a list of float32 arrays (the signal before quantisation); with
+    return_int16 a list of (float32, int16, clipped count).  kernel_time_reps > 0: returns the kernels' time in ms instead
+    (xv_reverb_kernel_time)."""
+    import numpy as np
+    L = lib()
+    rir_list = list(opts.pop("rir_list", []))
+    o = opts.pop("options") if "options" in opts else reverb_options(**opts)
+    i16 = len(waves) > 0 and all(np.asarray(w).dtype == np.int16 for w in waves)
+    samples, off = _ragged(waves, np.int16 if i16 else np.float32)
+    n = len(waves)
+    utt_rir = np.full(max(1, n), -1, dtype=np.int32)
+    if rirs is not None:
+        if len(rirs) != n:
+            raise XvError(XV_ERR_ARG, "reverberate: one RIR entry per waveform")
+        for u, r in enumerate(rirs):
+            if r is None:
+                continue
+            if isinstance(r, (int, np.integer)):
+                utt_rir[u] = int(r)
+            else:
+                rir_list.append(r)
+                utt_rir[u] = len(rir_list) - 1
+    rir_flat, rir_off = _ragged(rir_list, np.float32)
+    noise_list, add_noise, add_snr, add_start = [], [], [], []
+    add_off = np.zeros(n + 1, dtype=np.int32)
+    if additive is not None:
+        if len(additive) != n:
+            raise XvError(XV_ERR_ARG, "reverberate: one list of additive signals per waveform")
+        for u, lst in enumerate(additive):
+            for (x, snr, start) in (lst or []):
+                noise_list.append(x)
+                add_noise.append(len(noise_list) - 1)
+                add_snr.append(snr)
+                add_start.append(start)
+            add_off[u + 1] = len(add_noise)
+    noise_flat, noise_off = _ragged(noise_list, np.float32)
+    add_noise = np.array(add_noise + [0], dtype=np.int32)
+    add_snr = np.array(add_snr + [0], dtype=np.float32)
+    add_start = np.array(add_start + [0], dtype=np.float32)
+    lens = [reverb_output_length(off[u + 1] - off[u], rir_off[utt_rir[u] + 1] - rir_off[utt_rir[u]] if utt_rir[u] >= 0 else 0,
+                                 rate, options=o) for u in range(n)]
+    total = max(1, sum(max(0, x) for x in lens))
+    common = (device, ctypes.byref(o), float(rate), samples.ctypes.data, 1 if i16 else 0, off.ctypes.data, n,
+              rir_flat.ctypes.data, rir_off.ctypes.data, len(rir_list), utt_rir.ctypes.data,
+              noise_flat.ctypes.data, noise_off.ctypes.data, len(noise_list), add_off.ctypes.data if additive is not None else None,
+              add_noise.ctypes.data, add_snr.ctypes.data, add_start.ctypes.data)
+    if kernel_time_reps > 0:
+        L.xv_reverb_kernel_time.argtypes = _REVERB_ARGTYPES + [ctypes.c_int32, ctypes.POINTER(ctypes.c_float)]
+        ms = ctypes.c_float(0)
+        _check(L.xv_reverb_kernel_time(*common, int(kernel_time_reps), ctypes.byref(ms)))
+        return ms.value
+    out = np.empty(total, dtype=np.float32)
+    out16 = np.empty(total, dtype=np.int16) if return_int16 else None
+    clipped = np.zeros(max(1, n), dtype=np.int64)
+    out_off = np.zeros(n + 1, dtype=np.int64)
+    L.xv_wav_reverberate.argtypes = _REVERB_ARGTYPES + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _check(L.xv_wav_reverberate(*common, out_off.ctypes.data, out.ctypes.data, out16.ctypes.data if return_int16 else None,
+                                clipped.ctypes.data))
+    assert list(np.diff(out_off)) == [max(0, x) for x in lens]
+    if return_int16:
+        return [(out[out_off[u]:out_off[u + 1]].copy(), out16[out_off[u]:out_off[u + 1]].copy(), int(clipped[u])) for u in range(n)]
+    return [out[out_off[u]:out_off[u + 1]].copy() for u in range(n)]
 
 
 def kernel_tdnn_gemm(desc):

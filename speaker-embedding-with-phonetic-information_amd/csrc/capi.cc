@@ -3,6 +3,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <memory>
 #include <string>
 #include <vector>
@@ -12,10 +13,12 @@
 #include "engine.h"
 #include "extractor.h"
 #include "feat.h"
+#include "reverb.h"
 #include "wave.h"
 #include "kernels.h"
 #include "calib_file.h"
 #include "fuse_pipe.h"
+#include "fuse_wav.h"
 #include "multi_gpu.h"
 #include "nnet3_raw.h"
 #include "plda.h"
@@ -759,6 +762,118 @@ xv_status xv_wave_read(const char* rxfilename, int32_t channel, int32_t* rate, i
 }
 
 void xv_wave_free(int16_t* samples) { free(samples); }
+
+xv_status xv_wave_write(const char* wxfilename, int32_t rate, const float* samples, int64_t n, int64_t* clipped) {
+  if (!wxfilename || n < 0 || (n > 0 && !samples)) return Fail(XV_ERR_ARG, "xv_wave_write: bad argument");
+  return Guard([&] {
+    const int64_t c = xv::WriteWave(wxfilename, rate, samples, n);
+    if (clipped) *clipped = c;
+    return XV_OK;
+  });
+}
+
+xv_status xv_recognize_wav_pipeline(const char* rxfilename, int32_t* found, char* description, size_t description_cap) {
+  if (!rxfilename || !found) return Fail(XV_ERR_ARG, "xv_recognize_wav_pipeline: null argument");
+  return Guard([&] {
+    xv::FusedWav p;
+    *found = xv::RecognizeWavPipeline(rxfilename, &p) ? 1 : 0;
+    if (*found && description) {
+      const std::string d = xv::DescribeFusedWav(p);
+      if (d.size() + 1 > description_cap) return Fail(XV_ERR_ARG, "xv_recognize_wav_pipeline: output buffer too small");
+      memcpy(description, d.c_str(), d.size() + 1);
+    }
+    return XV_OK;
+  });
+}
+
+void xv_reverb_options_default(xv_reverb_options* opts) {
+  if (opts) *opts = xv::ReverbDefaults();
+}
+
+int64_t xv_reverb_output_length(const xv_reverb_options* opts, float sample_rate, int64_t n_samples, int64_t rir_len) {
+  if (!opts) {
+    Fail(XV_ERR_ARG, "xv_reverb_output_length: null options");
+    return -1;
+  }
+  return xv::ReverbOutputLength(*opts, sample_rate, n_samples, rir_len);
+}
+
+namespace {
+void FillReverbBatch(xv::ReverbBatch* out, float sample_rate, const void* samples, int32_t samples_are_i16, const int64_t* sample_offsets,
+                              int32_t n_utts, const float* rirs, const int64_t* rir_offsets, int32_t n_rirs, const int32_t* utt_rir,
+                              const float* noises, const int64_t* noise_offsets, int32_t n_noises, const int32_t* utt_add_offsets,
+                              const int32_t* add_noise, const float* add_snr, const float* add_start) {
+  xv::ReverbBatch b;
+  b.rate = sample_rate;
+  b.samples = samples;
+  b.is_i16 = samples_are_i16 != 0;
+  b.sample_off = sample_offsets;
+  b.n_utts = n_utts;
+  b.rirs = rirs;
+  b.rir_off = rir_offsets;
+  b.n_rirs = n_rirs;
+  b.utt_rir = n_rirs > 0 ? utt_rir : nullptr;
+  b.noises = noises;
+  b.noise_off = noise_offsets;
+  b.n_noises = n_noises;
+  b.utt_add_off = utt_add_offsets;
+  b.add_noise = add_noise;
+  b.add_snr = add_snr;
+  b.add_start = add_start;
+  *out = b;
+}
+}  // namespace
+
+xv_status xv_wav_reverberate(int device, const xv_reverb_options* opts, float sample_rate, const void* samples,
+                             int32_t samples_are_i16, const int64_t* sample_offsets, int32_t n_utts, const float* rirs,
+                             const int64_t* rir_offsets, int32_t n_rirs, const int32_t* utt_rir, const float* noises,
+                             const int64_t* noise_offsets, int32_t n_noises, const int32_t* utt_add_offsets,
+                             const int32_t* add_noise, const float* add_snr, const float* add_start, int64_t* out_offsets,
+                             float* out_f32, int16_t* out_i16, int64_t* clipped) {
+  if (!opts || !sample_offsets || !out_offsets || n_utts < 0) return Fail(XV_ERR_ARG, "xv_wav_reverberate: bad argument");
+  if (utt_add_offsets && n_utts > 0 && utt_add_offsets[n_utts] > utt_add_offsets[0] && (!add_noise || !add_snr || !add_start))
+    return Fail(XV_ERR_ARG, "xv_wav_reverberate: additive signals without their index, SNR or start time");
+  return Guard([&] {
+    xv::ReverbBatch b;
+    FillReverbBatch(&b, sample_rate, samples, samples_are_i16, sample_offsets, n_utts, rirs, rir_offsets, n_rirs,
+                                            utt_rir, noises, noise_offsets, n_noises, utt_add_offsets, add_noise, add_snr, add_start);
+    xv::Reverberate(device, *opts, b, out_offsets, out_f32, out_i16, clipped);
+    return XV_OK;
+  });
+}
+
+xv_status xv_reverb_kernel_time(int device, const xv_reverb_options* opts, float sample_rate, const void* samples,
+                                int32_t samples_are_i16, const int64_t* sample_offsets, int32_t n_utts, const float* rirs,
+                                const int64_t* rir_offsets, int32_t n_rirs, const int32_t* utt_rir, const float* noises,
+                                const int64_t* noise_offsets, int32_t n_noises, const int32_t* utt_add_offsets,
+                                const int32_t* add_noise, const float* add_snr, const float* add_start, int32_t reps,
+                                float* kernel_ms) {
+  if (!opts || !sample_offsets || !kernel_ms || n_utts < 1 || reps < 1) return Fail(XV_ERR_ARG, "xv_reverb_kernel_time: bad argument");
+  return Guard([&] {
+    xv::ReverbBatch b;
+    FillReverbBatch(&b, sample_rate, samples, samples_are_i16, sample_offsets, n_utts, rirs, rir_offsets, n_rirs,
+                                            utt_rir, noises, noise_offsets, n_noises, utt_add_offsets, add_noise, add_snr, add_start);
+    std::vector<int64_t> off(n_utts + 1);
+    std::vector<float> out;
+    float best = 0.f;
+    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
+      if (r == 0) {
+        int64_t total = 0;
+        for (int u = 0; u < n_utts; ++u) {
+          const int ri = b.utt_rir ? b.utt_rir[u] : -1;
+          const int64_t rl = ri >= 0 && ri < n_rirs ? rir_offsets[ri + 1] - rir_offsets[ri] : 0;
+          total += std::max<int64_t>(0, xv::ReverbOutputLength(*opts, sample_rate, sample_offsets[u + 1] - sample_offsets[u], rl));
+        }
+        out.resize((size_t)total + 1);
+      }
+      float ms = 0.f;
+      xv::Reverberate(device, *opts, b, off.data(), out.data(), nullptr, nullptr, &ms);
+      if (r == 1 || (r > 1 && ms < best)) best = ms;
+    }
+    *kernel_ms = best;
+    return XV_OK;
+  });
+}
 
 // One process, several GPUs: multi_gpu.cc (one ncclBroadcast of the packed image, bounded wait, contexts from the device copies).
 xv_status xv_ctx_create_broadcast(const xv_model* m, const int* devices, int n, int precision, xv_ctx** out) {

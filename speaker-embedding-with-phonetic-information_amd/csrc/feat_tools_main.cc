@@ -16,7 +16,9 @@
 #include <vector>
 
 #include "feat.h"
+#include "fuse_wav.h"
 #include "kio.h"
+#include "knobs.h"
 #include "wave.h"
 
 namespace {
@@ -66,18 +68,54 @@ constexpr int64_t kBatchSamples = 16 << 20;   // samples per device call (32 MiB
 constexpr int64_t kBatchFloats = 16 << 20;    // feature values per device call of compute-vad
 
 int ComputeMfcc(const xv::MfccToolOptions& t, const std::vector<std::string>& pos) {
-  xv::MfccComputer mc(PickDevice(t.device), t.mfcc);
+  xv::MfccComputer mc(PickDevice(t.device), t.mfcc);   // the same device as `device` below
   xv::SequentialWaveReader reader(pos[0]);
   xv::TableWriter writer(pos[1]);
-  long num_utts = 0, num_success = 0;
+  long num_utts = 0, num_success = 0, num_fused = 0;
   std::vector<std::string> keys;
+  std::vector<std::vector<int16_t>> waves;               // per utterance; empty while its job waits for the device
+  std::vector<std::unique_ptr<xv::WavJob>> jobs;         // per utterance; null for a plain entry
+  int64_t pending = 0;
   std::vector<int16_t> samples;
   std::vector<int64_t> off = {0};
   std::vector<uint64_t> seeds;
   std::vector<float> feats;
   std::vector<int32_t> row_off;
+  const int device = PickDevice(t.device);
+  // wav-reverberate lines (fuse_wav.h): read here, reverberated on the device with the batch
+  const bool fuse = xv::DebugKnobInt("fuse_wav", 1) != 0;
+  std::unique_ptr<xv::WavJob> taken;
+  if (fuse)
+    reader.SetEntryHook([&](const std::string& rx, xv::WaveData* w, std::string* error) {
+      xv::FusedWav p;
+      if (!xv::RecognizeWavPipeline(rx, &p)) return false;
+      taken.reset(new xv::WavJob);
+      try {
+        xv::LoadWavJob(p, taken.get());
+        w->rate = taken->rate;
+        w->channels = 1;
+        w->samples.clear();
+      } catch (const xv::KioError& e) {
+        *error = e.what();
+        taken.reset();
+      }
+      return true;
+    });
   auto flush = [&] {
     if (keys.empty()) return;
+    std::vector<xv::WavJob*> run;
+    for (auto& j : jobs)
+      if (j) run.push_back(j.get());
+    xv::RunWavJobs(device, run);
+    for (size_t u = 0; u < keys.size(); ++u) {
+      if (jobs[u]) {
+        if (jobs[u]->clipped > 0) XWARN("clipped " << jobs[u]->clipped << " samples out of total " << jobs[u]->out.size() << " of utterance " << keys[u]);
+        waves[u].swap(jobs[u]->out);
+        jobs[u].reset();
+      }
+      samples.insert(samples.end(), waves[u].begin(), waves[u].end());
+      off.push_back((int64_t)samples.size());
+    }
     row_off.assign(keys.size() + 1, 0);
     mc.Compute(samples.data(), true, off.data(), (int)keys.size(), seeds.data(), &feats, row_off.data());
     const int nc = t.mfcc.num_ceps;
@@ -100,6 +138,9 @@ int ComputeMfcc(const xv::MfccToolOptions& t, const std::vector<std::string>& po
       ++num_success;
     }
     keys.clear();
+    waves.clear();
+    jobs.clear();
+    pending = 0;
     samples.clear();
     off.assign(1, 0);
     seeds.clear();
@@ -107,14 +148,16 @@ int ComputeMfcc(const xv::MfccToolOptions& t, const std::vector<std::string>& po
   std::string key, err, warn;
   xv::WaveData w;
   std::vector<int16_t> one;
-  while (reader.Next(&key, &w, &err)) {
+  for (;;) {
+    taken.reset();
+    if (!reader.Next(&key, &w, &err)) break;
     ++num_utts;
     if (!err.empty()) {
       if (!reader.permissive()) throw xv::KioError("Failed to read wave data for key " + key + ": " + err);
       XWARN("Skipping utterance " << key << ": " << err);
       continue;
     }
-    const double duration = w.rate > 0 ? (double)w.frames() / w.rate : 0.0;
+    const double duration = w.rate > 0 ? (double)(taken ? (size_t)taken->out_len : w.frames()) / w.rate : 0.0;
     if (duration < t.min_duration) {
       XWARN("File: " << key << " is too short (" << duration << " sec): producing no output.");
       continue;
@@ -133,13 +176,20 @@ int ComputeMfcc(const xv::MfccToolOptions& t, const std::vector<std::string>& po
     }
     if (!warn.empty()) XWARN(warn << " (utterance " << key << ")");
     keys.push_back(key);
-    samples.insert(samples.end(), one.begin(), one.end());
-    off.push_back((int64_t)samples.size());
+    pending += taken ? taken->out_len : (int64_t)one.size();
+    if (taken) {
+      ++num_fused;
+      waves.emplace_back();
+    } else {
+      waves.push_back(one);
+    }
+    jobs.push_back(std::move(taken));
     seeds.push_back(xv::UttSeed(key.c_str()));
-    if ((int64_t)samples.size() >= kBatchSamples) flush();
+    if (pending >= kBatchSamples) flush();
   }
   flush();
   writer.Close();
+  XLOG("Took over " << num_fused << " wav-reverberate entries of the wave table" << (fuse ? "" : " (fuse_wav=0)"));
   XLOG(" Done " << num_success << " out of " << num_utts << " utterances.");
   return num_success != 0 ? 0 : 1;
 }

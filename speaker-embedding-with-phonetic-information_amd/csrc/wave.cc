@@ -103,6 +103,53 @@ void SelectChannel(const WaveData& w, int channel, std::vector<int16_t>* out, st
   for (size_t i = 0; i < n; ++i) (*out)[i] = w.samples[i * (size_t)w.channels + (size_t)c];
 }
 
+void WriteWaveI16(const std::string& wxfilename, int rate, const int16_t* samples, int64_t n) {
+  if (n < 0 || rate < 1) throw KioError("WAVE: bad arguments for writing " + wxfilename);
+  if ((uint64_t)n * 2 + 36 > 0xFFFFFFFFull) throw KioError("WAVE: too many samples for a RIFF file: " + wxfilename);
+  unsigned char h[44];
+  auto put32 = [&](int at, uint32_t v) { for (int i = 0; i < 4; ++i) h[at + i] = (unsigned char)(v >> (8 * i)); };
+  auto put16 = [&](int at, uint32_t v) { h[at] = (unsigned char)v; h[at + 1] = (unsigned char)(v >> 8); };
+  memcpy(h, "RIFF", 4);
+  put32(4, (uint32_t)(36 + n * 2));
+  memcpy(h + 8, "WAVEfmt ", 8);
+  put32(16, 16);
+  put16(20, 1);
+  put16(22, 1);
+  put32(24, (uint32_t)rate);
+  put32(28, (uint32_t)rate * 2);
+  put16(32, 2);
+  put16(34, 16);
+  memcpy(h + 36, "data", 4);
+  put32(40, (uint32_t)(n * 2));
+  Output out;
+  out.Open(wxfilename);
+  out.Write(h, sizeof h);
+  if (n) out.Write(samples, (size_t)n * 2);   // the hosts this builds for are little-endian
+  const int st = out.Close();
+  if (st != 0) throw KioError("WAVE: writing " + wxfilename + " failed (status " + std::to_string(st) + ")");
+}
+
+int64_t WriteWave(const std::string& wxfilename, int rate, const float* samples, int64_t n) {
+  std::vector<int16_t> q((size_t)(n > 0 ? n : 0));
+  int64_t clipped = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const float v = samples[i];
+    if (v >= 32768.f) {
+      q[i] = 32767;
+      ++clipped;
+    } else if (v <= -32769.f) {
+      q[i] = -32768;
+      ++clipped;
+    } else if (v != v) {
+      q[i] = 0;
+    } else {
+      q[i] = (int16_t)(int)v;
+    }
+  }
+  WriteWaveI16(wxfilename, rate, q.data(), n);
+  return clipped;
+}
+
 SequentialWaveReader::SequentialWaveReader(const std::string& rspecifier) {
   opts_ = ParseRspecifier(rspecifier);
   in_.Open(opts_.rxfilename);
@@ -132,6 +179,7 @@ bool SequentialWaveReader::Next(std::string* key, WaveData* w, std::string* erro
     }
     std::string rx = line.substr(sp + 1);
     while (!rx.empty() && (rx.back() == ' ' || rx.back() == '\t' || rx.back() == '\r')) rx.pop_back();
+    if (hook_ && hook_(rx, w, error)) return true;
     try {
       Input data;
       data.Open(rx);
