@@ -165,14 +165,16 @@ MfccTables BuildMfccTables(const xv_mfcc_options& o) {
         w.push_back((float)v);
       }
     }
+    // Kaldi asserts here; an empty bin would read log(FLT_EPSILON) for ever.  Bins b and b + 2 do not overlap, so with no
+    // empty bin num-mel-bins is at most 2 * P/2 = P: the kernel keeps the log mel energies in an LDS plane of P floats.
+    if (first < 0)
+      throw KioError("MFCC options: mel bin " + std::to_string(b) + " of " + std::to_string(nb) + " contains no FFT bin (" +
+                     std::to_string(nfft) + " bins of " + std::to_string(bin_width) + " Hz): You may have set --num-mel-bins too large.");
     t.mel_woff[b] = (int32_t)t.mel_w.size();
-    if (first >= 0) {
-      t.mel_first[b] = first;
-      t.mel_len[b] = last - first + 1;
-      t.mel_w.insert(t.mel_w.end(), w.begin(), w.end());
-    }
+    t.mel_first[b] = first;
+    t.mel_len[b] = last - first + 1;
+    t.mel_w.insert(t.mel_w.end(), w.begin(), w.end());
   }
-  if (t.mel_w.empty()) t.mel_w.push_back(0.f);
   // DCT-II, orthonormal (Kaldi's ComputeDctMatrix), first num_ceps rows, stored transposed
   const int nc = o.num_ceps;
   t.dct_t.resize((size_t)nb * nc);

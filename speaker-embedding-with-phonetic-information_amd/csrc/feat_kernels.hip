@@ -190,6 +190,8 @@ hipError_t launch_mfcc(const MfccArgs& a, hipStream_t s) {
   if (a.total_frames <= 0) return hipSuccess;
   if (a.padded < 2 || a.padded > kMfccMaxPadded || (1 << a.log2_padded) != a.padded || a.frame_len > a.padded || a.frame_len < 1)
     return hipErrorInvalidValue;
+  // the log mel energies live in re[0 .. num_bins) (one LDS plane of `padded` floats), the DCT reads num_ceps <= num_bins of them
+  if (a.num_bins < 1 || a.num_bins > a.padded || a.num_ceps < 1 || a.num_ceps > a.num_bins) return hipErrorInvalidValue;
   hipLaunchKernelGGL(mfcc_kernel<T>, dim3(a.total_frames), dim3(kWave), mfcc_lds_bytes(a.padded), s, a);
   return hipGetLastError();
 }

@@ -232,10 +232,10 @@ def vad(feats, v, dtype=np.float64):
     T = len(c0)
     thr = vad_threshold(c0, v, dtype)
     ctx = int(v["vad_frames_context"])
-    out = np.zeros(T, np.float32)
-    for t in range(T):
-        lo, hi = max(0, t - ctx), min(T - 1, t + ctx)
-        den = hi - lo + 1
-        num = int((c0[lo:hi + 1] > thr).sum())
-        out[t] = 1.0 if dtype(num) >= dtype(den) * dtype(v["vad_proportion_threshold"]) else 0.0
-    return out
+    # frame t looks at frames lo .. hi: num of them are above the threshold (exact integer counts through a running sum)
+    t = np.arange(T)
+    lo, hi = np.maximum(0, t - ctx), np.minimum(T - 1, t + ctx)
+    above = np.concatenate([[0], np.cumsum(c0 > thr)])
+    num = above[hi + 1] - above[lo]
+    den = hi - lo + 1
+    return (num.astype(dtype) >= den.astype(dtype) * dtype(v["vad_proportion_threshold"])).astype(np.float32)

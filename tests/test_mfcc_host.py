@@ -44,6 +44,27 @@ def test_num_frames_hand_worked():
     assert P.utt_seed("utt1") == P.utt_seed("utt1") != P.utt_seed("utt2")
 
 
+def test_a_mel_bank_with_an_empty_bin_is_refused_before_any_device(tmp_path):
+    """8 kHz, L = 200 in a 256-point FFT: 128 FFT bins of 31.25 Hz; the low mel bins of a 200-bin bank are narrower than that.
+    Kaldi asserts ("You may have set --num-mel-bins too large"); the option error comes before the device is looked for."""
+    P = H.pkg()
+    wave = [np.zeros(4000, np.int16)]
+    for kw in (dict(num_mel_bins=200), dict(num_mel_bins=200, num_ceps=150), dict(num_mel_bins=100000, num_ceps=1),
+               dict(num_mel_bins=60, low_freq=3000.0, high_freq=3100.0)):
+        with pytest.raises(P.XvError, match="You may have set --num-mel-bins too large") as e:
+            P.mfcc(wave, dither=0.0, **dict(CONF, **kw))
+        assert e.value.status == P.XV_ERR_ARG and "no HIP device" not in str(e.value), kw
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="")
+    r = _run([os.path.join(BIN, "compute-mfcc-feats"), "--sample-frequency=8000", "--num-mel-bins=200", "scp:x", "ark:y"], env=env)
+    assert r.returncode == 255 and b"You may have set --num-mel-bins too large" in r.stderr, r.stderr.decode()[-400:]
+    # the largest banks the issue's sweep uses are accepted: the refusal is of empty bins, not of large banks
+    for kw in (dict(num_mel_bins=40, num_ceps=40), dict(sample_frequency=16000.0, num_mel_bins=80, num_ceps=70, high_freq=0.0)):
+        assert P.mfcc_num_frames(8000, **dict(CONF, **kw)) > 0
+        r = _run([os.path.join(BIN, "compute-mfcc-feats"), "--sample-frequency=%g" % dict(CONF, **kw)["sample_frequency"],
+                  "--num-mel-bins=%d" % kw["num_mel_bins"], "--num-ceps=%d" % kw["num_ceps"]], env=env)
+        assert r.returncode == 1 and b"Usage" in r.stderr, r.stderr.decode()[-400:]
+
+
 def test_wave_read(tmp_path):
     P = H.pkg()
     rng = np.random.default_rng(0)
