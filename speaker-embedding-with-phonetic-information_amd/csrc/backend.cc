@@ -4,6 +4,7 @@
 
 #include <string>
 
+#include "cli.h"
 #include "engine.h"
 #include "kernels.h"
 
@@ -88,6 +89,29 @@ void SegmentMean(int device, const float* x, int n, int dim, const int32_t* seg_
   a.out = (float*)dout.p;
   Check(launch_segment_mean(a, nullptr), "segment mean kernel launch");
   Check(hipMemcpy(out, dout.p, (size_t)n_seg * dim * 4, hipMemcpyDeviceToHost), "copy result");
+}
+
+// The warning carries the caller's file and line (the defaults in backend.h), not this file's: the tools' log lines name the
+// tool's own source file, and that part of a log line is kept as it was when each tool had its own copy of this loop.
+// p->dim is kept between calls, so every batch of one table must have the dimension of the first.
+bool ReadBatch(SequentialVectorReader& r, int cap, Packed* p, long* n_err, const char* caller_file, int caller_line) {
+  p->keys.clear();
+  p->data.clear();
+  std::string key, err;
+  std::vector<float> v;
+  while ((cap < 0 || p->n() < cap) && r.Next(&key, &v, &err)) {
+    if (!err.empty()) {
+      LogLine("WARNING", caller_file, caller_line, "Failed to read vector for key " + key + ": " + err);
+      ++*n_err;
+      continue;
+    }
+    if (p->dim == 0) p->dim = (int)v.size();
+    if ((int)v.size() != p->dim || p->dim == 0)
+      throw KioError("vector " + key + " has dimension " + std::to_string(v.size()) + ", expected " + std::to_string(p->dim));
+    p->keys.push_back(key);
+    p->data.insert(p->data.end(), v.begin(), v.end());
+  }
+  return p->n() > 0;
 }
 
 }  // namespace xv

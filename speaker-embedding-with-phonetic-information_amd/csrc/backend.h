@@ -6,7 +6,10 @@
 #pragma once
 #include <stdint.h>
 
+#include <string>
 #include <vector>
+
+#include "kio.h"
 
 namespace xv {
 
@@ -24,5 +27,18 @@ void BackendApply(int device, const float* x, int n, int dim, const BackendOptio
 // out[s] = mean of rows idx[seg_off[s] .. seg_off[s+1]) of x ([n][dim]); fp32 or fp64 accumulation in list order.
 void SegmentMean(int device, const float* x, int n, int dim, const int32_t* seg_off, const int32_t* idx, int n_seg,
                  bool acc64, float* out);
+
+// Vectors of a table, packed for the calls above; every vector must have the dimension of the first one.
+struct Packed {
+  std::vector<std::string> keys;
+  std::vector<float> data;
+  int dim = 0;
+  int n() const { return (int)keys.size(); }
+};
+
+// Reads up to `cap` vectors (cap < 0: all) into *p, replacing what it held.  Returns false when the table is exhausted and
+// nothing was read.  An entry that cannot be read is counted in *n_err and warned about in the caller's name (cli.h LogLine).
+bool ReadBatch(SequentialVectorReader& r, int cap, Packed* p, long* n_err, const char* caller_file = __builtin_FILE(),
+               int caller_line = __builtin_LINE());
 
 }  // namespace xv

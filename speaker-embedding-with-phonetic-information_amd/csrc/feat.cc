@@ -7,6 +7,7 @@
 
 #include <limits>
 
+#include "cli.h"
 #include "engine.h"
 #include "feat_kernels.h"
 #include "kio.h"
@@ -338,49 +339,8 @@ void VadEnergy(int device, const xv_vad_options& o, const float* feats, const in
 }
 
 // ---------------------------------------------------------------------------------------------- options
-std::vector<std::pair<std::string, std::string>> ReadConfigFile(const std::string& path) {
-  Input in;
-  in.Open(path);
-  std::vector<std::pair<std::string, std::string>> out;
-  std::string line;
-  int c = 0;
-  while (c >= 0) {
-    line.clear();
-    while ((c = in.Get()) >= 0 && c != '\n') line.push_back((char)c);
-    const size_t hash = line.find('#');
-    if (hash != std::string::npos) line.resize(hash);
-    const size_t b = line.find_first_not_of(" \t\r");
-    if (b == std::string::npos) continue;
-    const size_t e = line.find_last_not_of(" \t\r");
-    line = line.substr(b, e - b + 1);
-    if (line.compare(0, 2, "--") != 0)
-      throw KioError("Reading config file " + path + ": line '" + line + "' does not look like a line from a Kaldi command-line program's config file: should be of the form --x=y");
-    const size_t eq = line.find('=');
-    out.emplace_back(line.substr(2, eq == std::string::npos ? std::string::npos : eq - 2),
-                     eq == std::string::npos ? std::string() : line.substr(eq + 1));
-  }
-  return out;
-}
-
 namespace {
 
-bool ToBool(const std::string& name, const std::string& v) {
-  if (v == "true" || v == "t" || v == "1" || v.empty()) return true;
-  if (v == "false" || v == "f" || v == "0") return false;
-  throw KioError("Invalid format for boolean argument --" + name + "=" + v);
-}
-float ToFloat(const std::string& name, const std::string& v) {
-  char* end = nullptr;
-  const double d = strtod(v.c_str(), &end);
-  if (v.empty() || !end || *end) throw KioError("Invalid floating-point option --" + name + "=" + v);
-  return (float)d;
-}
-int ToInt(const std::string& name, const std::string& v) {
-  char* end = nullptr;
-  const long d = strtol(v.c_str(), &end, 10);
-  if (v.empty() || !end || *end) throw KioError("Invalid integer option --" + name + "=" + v);
-  return (int)d;
-}
 [[noreturn]] void Refuse(const std::string& name, const std::string& v, const char* why) {
   throw KioError("--" + name + "=" + v + " is not supported: " + why);
 }

@@ -1,12 +1,11 @@
-// Host layer of the feature stage (compute-mfcc-feats, compute-vad): options, Kaldi-style --config files, the window / mel /
-// DCT tables the MFCC kernel reads, and the device calls.  Semantics are upstream Kaldi's (feat/feature-window.cc,
-// feat/mel-computations.cc, feat/feature-mfcc.cc, ivector/voice-activity-detection.cc) [UPSTREAM, recalled], restated in
-// tests/mfcc_ref.py; parity with Kaldi is unpinned.  No CPU path: the device entries throw EngineError without a GPU.
+// Host layer of the feature stage (compute-mfcc-feats, compute-vad): options, the window / mel / DCT tables the MFCC kernel
+// reads, and the device calls.  Semantics are upstream Kaldi's (feat/feature-window.cc, feat/mel-computations.cc,
+// feat/feature-mfcc.cc, ivector/voice-activity-detection.cc) [UPSTREAM, recalled], restated in tests/mfcc_ref.py; parity with
+// Kaldi is unpinned.  No CPU path: the device entries throw EngineError without a GPU.
 #pragma once
 #include <stdint.h>
 
 #include <string>
-#include <utility>
 #include <vector>
 
 #include "../../include/xvec_hip.h"
@@ -58,9 +57,7 @@ class MfccComputer {
 // Kaldi's ComputeVadEnergy on a ragged batch (feats [row_off[n_utts]][dim], out [row_off[n_utts]]).
 void VadEnergy(int device, const xv_vad_options& o, const float* feats, const int32_t* row_off, int n_utts, int dim, float* out);
 
-// ---- command-line options (the tools and the tests' --config cases)
-// "--name=value" lines of a Kaldi config file ('#' starts a comment, blank lines allowed); KioError on anything else.
-std::vector<std::pair<std::string, std::string>> ReadConfigFile(const std::string& path);
+// ---- command-line options (the tools; --config files are read by cli.h)
 // Applies one option; returns false for a name this option set does not know; throws KioError for a bad value and for
 // options that are refused (they would change the numbers and are not built).
 struct MfccToolOptions {

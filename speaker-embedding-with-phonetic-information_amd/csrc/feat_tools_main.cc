@@ -11,10 +11,10 @@
 #include <string.h>
 
 #include <memory>
-#include <sstream>
 #include <string>
 #include <vector>
 
+#include "cli.h"
 #include "feat.h"
 #include "fuse_wav.h"
 #include "kio.h"
@@ -22,24 +22,6 @@
 #include "wave.h"
 
 namespace {
-
-std::string g_prog = "compute-mfcc-feats";
-
-void LogLine(const char* level, int line, const std::string& msg) {
-  fprintf(stderr, "%s (%s[xvec-hip-0.1]:main():feat_tools_main.cc:%d) %s\n", level, g_prog.c_str(), line, msg.c_str());
-}
-#define XLOG(msg)                       \
-  do {                                  \
-    std::ostringstream _o;              \
-    _o << msg;                          \
-    LogLine("LOG", __LINE__, _o.str()); \
-  } while (0)
-#define XWARN(msg)                          \
-  do {                                      \
-    std::ostringstream _o;                  \
-    _o << msg;                              \
-    LogLine("WARNING", __LINE__, _o.str()); \
-  } while (0)
 
 const char* Usage(bool vad) {
   if (vad)
@@ -58,17 +40,12 @@ const char* Usage(bool vad) {
          "Not built (refused): --vtln-map, --vtln-warp != 1, --htk-compat=true, --output-format=htk, resampling.\n";
 }
 
-int PickDevice(int requested) {
-  if (requested >= 0) return requested;
-  const char* e = getenv("XVEC_DEVICE");
-  return (e && *e) ? atoi(e) : 0;
-}
-
 constexpr int64_t kBatchSamples = 16 << 20;   // samples per device call (32 MiB of 16-bit PCM)
 constexpr int64_t kBatchFloats = 16 << 20;    // feature values per device call of compute-vad
 
 int ComputeMfcc(const xv::MfccToolOptions& t, const std::vector<std::string>& pos) {
-  xv::MfccComputer mc(PickDevice(t.device), t.mfcc);   // the same device as `device` below
+  const int device = xv::PickDevice(t.device);
+  xv::MfccComputer mc(device, t.mfcc);
   xv::SequentialWaveReader reader(pos[0]);
   xv::TableWriter writer(pos[1]);
   long num_utts = 0, num_success = 0, num_fused = 0;
@@ -81,7 +58,6 @@ int ComputeMfcc(const xv::MfccToolOptions& t, const std::vector<std::string>& po
   std::vector<uint64_t> seeds;
   std::vector<float> feats;
   std::vector<int32_t> row_off;
-  const int device = PickDevice(t.device);
   // wav-reverberate lines (fuse_wav.h): read here, reverberated on the device with the batch
   const bool fuse = xv::DebugKnobInt("fuse_wav", 1) != 0;
   std::unique_ptr<xv::WavJob> taken;
@@ -195,7 +171,7 @@ int ComputeMfcc(const xv::MfccToolOptions& t, const std::vector<std::string>& po
 }
 
 int ComputeVad(const xv_vad_options& o, int device, const std::vector<std::string>& pos) {
-  const int dev = PickDevice(device);
+  const int dev = xv::PickDevice(device);
   xv::SequentialMatrixReader reader(pos[0]);
   xv::TableWriter writer(pos[1]);
   long num_done = 0, num_err = 0, num_unvoiced = 0;
@@ -258,63 +234,28 @@ int ComputeVad(const xv_vad_options& o, int device, const std::vector<std::strin
 }  // namespace
 
 int main(int argc, char** argv) {
-  const char* slash = strrchr(argv[0], '/');
-  g_prog = slash ? slash + 1 : argv[0];
-  xv::InstallMappedFileFaultHandler(g_prog.c_str());
-  const bool vad = g_prog.find("vad") != std::string::npos;
+  const bool vad = xv::ProgramName(argv[0]).find("vad") != std::string::npos;
   xv::MfccToolOptions t;
   t.mfcc = xv::MfccDefaults();
   xv_vad_options vo = xv::VadDefaults();
   int vad_device = -1;
-  std::vector<std::string> pos;
-  std::vector<std::pair<std::string, std::string>> cli;
-  std::string config, cmdline = g_prog;
-  for (int i = 1; i < argc; ++i) {
-    std::string s = argv[i];
-    cmdline += " " + s;
-    if (s.compare(0, 2, "--") == 0 && pos.empty()) {
-      const size_t eq = s.find('=');
-      const std::string name = s.substr(2, eq == std::string::npos ? std::string::npos : eq - 2);
-      const std::string val = eq == std::string::npos ? "" : s.substr(eq + 1);
-      if (name == "help") {
-        fputs(Usage(vad), stderr);
-        return 0;
-      }
-      if (name == "config") config = val;
-      else cli.emplace_back(name, val);
-      continue;
+  xv::CliTool tool;
+  tool.usage = Usage(vad);
+  tool.config_file = true;
+  tool.set = [&](const std::string& n, const std::string& v) {
+    bool known;
+    if (!vad) {
+      known = xv::SetMfccOption(n, v, &t);
+    } else {
+      known = xv::SetVadOption(n, v, &vo) || n == "device" || n == "verbose" || n == "print-args";
+      if (n == "device") vad_device = atoi(v.c_str());
     }
-    pos.push_back(s);
-  }
-  fprintf(stderr, "%s \n", cmdline.c_str());
-  try {
-    // the config file first, then the command line (which wins)
-    std::vector<std::pair<std::string, std::string>> all;
-    if (!config.empty()) all = xv::ReadConfigFile(config);
-    all.insert(all.end(), cli.begin(), cli.end());
-    for (const auto& nv : all) {
-      bool known;
-      if (vad) {
-        known = xv::SetVadOption(nv.first, nv.second, &vo);
-        if (!known && nv.first == "device") { vad_device = atoi(nv.second.c_str()); known = true; }
-        if (!known && (nv.first == "verbose" || nv.first == "print-args")) known = true;
-      } else {
-        known = xv::SetMfccOption(nv.first, nv.second, &t);
-      }
-      if (!known) {
-        fprintf(stderr, "ERROR (%s) Invalid option --%s%s%s\n\n%s", g_prog.c_str(), nv.first.c_str(), nv.second.empty() ? "" : "=",
-                nv.second.c_str(), Usage(vad));
-        return 255;
-      }
-    }
-    if (!vad) (void)xv::BuildMfccTables(t.mfcc);   // option errors before any device is touched
-    if (pos.size() != 2) {
-      fputs(Usage(vad), stderr);
-      return 1;
-    }
+    return known ? xv::OptionResult::kOk : xv::OptionResult::kUnknown;
+  };
+  tool.run = [&](const std::vector<std::string>& pos) {
+    if (!vad) (void)xv::BuildMfccTables(t.mfcc);   // option errors before the argument count and before any device is touched
+    if (pos.size() != 2) return xv::kUsageError;
     return vad ? ComputeVad(vo, vad_device, pos) : ComputeMfcc(t, pos);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "ERROR (%s) %s\n", g_prog.c_str(), e.what());
-    return 255;
-  }
+  };
+  return xv::CliMain(argc, argv, tool);
 }

@@ -15,84 +15,24 @@
 #include <string.h>
 
 #include <memory>
-#include <sstream>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "backend.h"
+#include "cli.h"
 #include "kio.h"
 
 namespace {
 
-std::string g_prog = "ivector-mean";
-
-void LogLine(const char* level, int line, const std::string& msg) {
-  fprintf(stderr, "%s (%s[xvec-hip-0.1]:main():ivector_tools_main.cc:%d) %s\n", level, g_prog.c_str(), line, msg.c_str());
-}
-#define XLOG(msg)                       \
-  do {                                  \
-    std::ostringstream _o;              \
-    _o << msg;                          \
-    LogLine("LOG", __LINE__, _o.str()); \
-  } while (0)
-#define XWARN(msg)                          \
-  do {                                      \
-    std::ostringstream _o;                  \
-    _o << msg;                              \
-    LogLine("WARNING", __LINE__, _o.str()); \
-  } while (0)
-
 struct Args {
-  std::vector<std::string> pos;
+  std::vector<std::string> pos;   // set by main() for the tool that runs
   bool binary = true;          // --binary (ivector-mean's mean file)
   bool normalize = true;       // ivector-normalize-length
   bool scaleup = true;
   bool subtract_mean = true;   // ivector-subtract-global-mean
   int device = -1;
 };
-
-bool ParseBool(const std::string& v, bool* out) {
-  if (v == "true" || v == "t" || v == "1" || v.empty()) *out = true;
-  else if (v == "false" || v == "f" || v == "0") *out = false;
-  else return false;
-  return true;
-}
-
-int PickDevice(int requested) {
-  if (requested >= 0) return requested;
-  const char* e = getenv("XVEC_DEVICE");
-  return (e && *e) ? atoi(e) : 0;
-}
-
-// All vectors of a table, packed; every vector must have the dimension of the first one.
-struct Packed {
-  std::vector<std::string> keys;
-  std::vector<float> data;
-  int dim = 0;
-  int n() const { return (int)keys.size(); }
-};
-
-// Reads up to `cap` vectors (cap < 0: all).  Returns false when the table is exhausted and nothing was read.
-bool ReadBatch(xv::SequentialVectorReader& r, int cap, Packed* p, long* n_err) {
-  p->keys.clear();
-  p->data.clear();
-  std::string key, err;
-  std::vector<float> v;
-  while ((cap < 0 || p->n() < cap) && r.Next(&key, &v, &err)) {
-    if (!err.empty()) {
-      XWARN("Failed to read vector for key " << key << ": " << err);
-      ++*n_err;
-      continue;
-    }
-    if (p->dim == 0) p->dim = (int)v.size();
-    if ((int)v.size() != p->dim || p->dim == 0)
-      throw xv::KioError("vector " + key + " has dimension " + std::to_string(v.size()) + ", expected " + std::to_string(p->dim));
-    p->keys.push_back(key);
-    p->data.insert(p->data.end(), v.begin(), v.end());
-  }
-  return p->n() > 0;
-}
 
 double Norm(const float* v, int n) {
   double s = 0;
@@ -103,17 +43,14 @@ double Norm(const float* v, int n) {
 constexpr int kBatch = 65536;   // vectors per device call of the streaming tools
 
 int IvectorMean(const Args& a) {
-  const int dev = PickDevice(a.device);
+  const int dev = xv::PickDevice(a.device);
   if (a.pos.size() == 2) {
     // global mean -> Kaldi vector object
     xv::SequentialVectorReader r(a.pos[0]);
-    Packed p;
+    xv::Packed p;
     long n_err = 0;
-    ReadBatch(r, -1, &p, &n_err);
-    if (p.n() == 0) {
-      fprintf(stderr, "ERROR (%s) No iVectors read\n", g_prog.c_str());
-      return 255;
-    }
+    xv::ReadBatch(r, -1, &p, &n_err);
+    if (p.n() == 0) throw xv::KioError("No iVectors read");
     std::vector<int32_t> off = {0, p.n()}, idx(p.n());
     for (int i = 0; i < p.n(); ++i) idx[i] = i;
     std::vector<float> mean(p.dim);
@@ -122,13 +59,13 @@ int IvectorMean(const Args& a) {
     xv::WriteVectorObject(a.pos[1], a.binary, mean.data(), p.dim);
     return 0;
   }
-  if (a.pos.size() != 3 && a.pos.size() != 4) return -2;
+  if (a.pos.size() != 3 && a.pos.size() != 4) return xv::kUsageError;
   std::vector<xv::TokenList> spk2utt = xv::ReadTokenVectorTable(a.pos[0]);
   // the vector table is accessed by utterance key, as Kaldi's RandomAccessBaseFloatVectorReader
   xv::SequentialVectorReader r(a.pos[1]);
-  Packed p;
+  xv::Packed p;
   long n_read_err = 0;
-  ReadBatch(r, -1, &p, &n_read_err);
+  xv::ReadBatch(r, -1, &p, &n_read_err);
   std::unordered_map<std::string, int> row;
   for (int i = 0; i < p.n(); ++i) row.emplace(p.keys[i], i);
   xv::TableWriter w(a.pos[2]);
@@ -139,10 +76,7 @@ int IvectorMean(const Args& a) {
   long num_spk_err = 0, num_utt_done = 0, num_utt_err = 0;
   for (size_t s = 0; s < spk2utt.size(); ++s) {
     const xv::TokenList& e = spk2utt[s];
-    if (e.tokens.empty()) {
-      fprintf(stderr, "ERROR (%s) Speaker with no utterances.\n", g_prog.c_str());
-      return 255;
-    }
+    if (e.tokens.empty()) throw xv::KioError("Speaker with no utterances.");
     int count = 0;
     for (const std::string& utt : e.tokens) {
       auto it = row.find(utt);
@@ -192,13 +126,13 @@ int IvectorMean(const Args& a) {
 }
 
 int SubtractGlobalMean(const Args& a) {
-  const int dev = PickDevice(a.device);
+  const int dev = xv::PickDevice(a.device);
   if (a.pos.size() == 2) {
     // the mean of the input itself
     xv::SequentialVectorReader r(a.pos[0]);
-    Packed p;
+    xv::Packed p;
     long n_err = 0;
-    ReadBatch(r, -1, &p, &n_err);
+    xv::ReadBatch(r, -1, &p, &n_err);
     XLOG("Read " << p.n() << " iVectors.");
     xv::TableWriter w(a.pos[1]);
     if (p.n() != 0) {
@@ -216,15 +150,15 @@ int SubtractGlobalMean(const Args& a) {
     XLOG("Wrote " << p.n() << " mean-subtracted iVectors");
     return p.n() != 0 ? 0 : 1;
   }
-  if (a.pos.size() != 3) return -2;
+  if (a.pos.size() != 3) return xv::kUsageError;
   std::vector<float> mean;
   xv::ReadVectorObject(a.pos[0], &mean);
   xv::SequentialVectorReader r(a.pos[1]);
   xv::TableWriter w(a.pos[2]);
-  Packed p;
+  xv::Packed p;
   long n_err = 0, n_done = 0;
   std::vector<float> out;
-  while (ReadBatch(r, kBatch, &p, &n_err)) {
+  while (xv::ReadBatch(r, kBatch, &p, &n_err)) {
     if (p.dim != (int)mean.size())
       throw xv::KioError("iVector dimension " + std::to_string(p.dim) + " does not match the mean's " + std::to_string(mean.size()));
     out.resize(p.data.size());
@@ -240,16 +174,16 @@ int SubtractGlobalMean(const Args& a) {
 }
 
 int TransformVec(const Args& a) {
-  if (a.pos.size() != 3) return -2;
-  const int dev = PickDevice(a.device);
+  if (a.pos.size() != 3) return xv::kUsageError;
+  const int dev = xv::PickDevice(a.device);
   xv::Matrix t;
   xv::ReadMatrixObject(a.pos[0], &t);
   xv::SequentialVectorReader r(a.pos[1]);
   xv::TableWriter w(a.pos[2]);
-  Packed p;
+  xv::Packed p;
   long n_err = 0, n_done = 0;
   std::vector<float> out;
-  while (ReadBatch(r, kBatch, &p, &n_err)) {
+  while (xv::ReadBatch(r, kBatch, &p, &n_err)) {
     if (t.cols != p.dim && t.cols != p.dim + 1)
       throw xv::KioError("Dimension mismatch: input vector has dimension " + std::to_string(p.dim) + " and transform has " +
                          std::to_string(t.cols) + " columns.");
@@ -268,15 +202,15 @@ int TransformVec(const Args& a) {
 }
 
 int NormalizeLength(const Args& a) {
-  if (a.pos.size() != 2) return -2;
-  const int dev = PickDevice(a.device);
+  if (a.pos.size() != 2) return xv::kUsageError;
+  const int dev = xv::PickDevice(a.device);
   xv::SequentialVectorReader r(a.pos[0]);
   xv::TableWriter w(a.pos[1]);
-  Packed p;
+  xv::Packed p;
   long n_err = 0, n_done = 0;
   double tot_ratio = 0, tot_ratio2 = 0;
   std::vector<float> out, ratio;
-  while (ReadBatch(r, kBatch, &p, &n_err)) {
+  while (xv::ReadBatch(r, kBatch, &p, &n_err)) {
     out.resize(p.data.size());
     ratio.resize(p.n());
     xv::BackendOptions o;
@@ -318,57 +252,33 @@ const char* Usage(const std::string& prog) {
          " or:   ivector-mean [--binary=true] <ivector-rspecifier> <mean-wxfilename>\n";
 }
 
+// All four tools know all of these; --config, --verbose and --print-args are accepted and have no effect.
+xv::OptionResult SetOption(const std::string& name, const std::string& val, Args* a) {
+  bool ok = true;
+  if (name == "binary") ok = xv::ParseBool(val, &a->binary);
+  else if (name == "normalize") ok = xv::ParseBool(val, &a->normalize);
+  else if (name == "scaleup") ok = xv::ParseBool(val, &a->scaleup);
+  else if (name == "subtract-mean") ok = xv::ParseBool(val, &a->subtract_mean);
+  else if (name == "device") a->device = atoi(val.c_str());
+  else if (name != "verbose" && name != "print-args" && name != "config") return xv::OptionResult::kUnknown;
+  return ok ? xv::OptionResult::kOk : xv::OptionResult::kBadValue;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-  xv::InstallMappedFileFaultHandler(strrchr(argv[0], '/') ? strrchr(argv[0], '/') + 1 : argv[0]);
-  const char* slash = strrchr(argv[0], '/');
-  g_prog = slash ? slash + 1 : argv[0];
+  const std::string prog = xv::ProgramName(argv[0]);
   Args a;
-  std::string cmdline = g_prog;
-  for (int i = 1; i < argc; ++i) {
-    std::string s = argv[i];
-    cmdline += " " + s;
-    if (s.compare(0, 2, "--") == 0 && a.pos.empty()) {
-      size_t eq = s.find('=');
-      const std::string name = s.substr(2, eq == std::string::npos ? std::string::npos : eq - 2);
-      const std::string val = eq == std::string::npos ? "" : s.substr(eq + 1);
-      bool ok = true;
-      if (name == "help") {
-        fputs(Usage(g_prog), stderr);
-        return 0;
-      } else if (name == "binary") ok = ParseBool(val, &a.binary);
-      else if (name == "normalize") ok = ParseBool(val, &a.normalize);
-      else if (name == "scaleup") ok = ParseBool(val, &a.scaleup);
-      else if (name == "subtract-mean") ok = ParseBool(val, &a.subtract_mean);
-      else if (name == "device") a.device = atoi(val.c_str());
-      else if (name == "verbose" || name == "print-args" || name == "config") ok = true;   // accepted, no effect
-      else {
-        fprintf(stderr, "ERROR (%s) Invalid option %s\n\n%s", g_prog.c_str(), s.c_str(), Usage(g_prog));
-        return 255;
-      }
-      if (!ok) {
-        fprintf(stderr, "ERROR (%s) Invalid value for option %s\n", g_prog.c_str(), s.c_str());
-        return 255;
-      }
-      continue;
-    }
-    a.pos.push_back(s);
-  }
-  fprintf(stderr, "%s \n", cmdline.c_str());
-  try {
-    int rc;
-    if (g_prog == "ivector-subtract-global-mean") rc = SubtractGlobalMean(a);
-    else if (g_prog == "transform-vec") rc = TransformVec(a);
-    else if (g_prog == "ivector-normalize-length") rc = NormalizeLength(a);
-    else rc = IvectorMean(a);
-    if (rc == -2) {
-      fputs(Usage(g_prog), stderr);
-      return 1;
-    }
-    return rc;
-  } catch (const std::exception& e) {
-    fprintf(stderr, "ERROR (%s) %s\n", g_prog.c_str(), e.what());
-    return 255;
-  }
+  xv::CliTool tool;
+  tool.usage = Usage(prog);
+  tool.config_file = false;
+  tool.set = [&](const std::string& name, const std::string& val) { return SetOption(name, val, &a); };
+  tool.run = [&](const std::vector<std::string>& pos) {
+    a.pos = pos;
+    if (prog == "ivector-subtract-global-mean") return SubtractGlobalMean(a);
+    if (prog == "transform-vec") return TransformVec(a);
+    if (prog == "ivector-normalize-length") return NormalizeLength(a);
+    return IvectorMean(a);
+  };
+  return xv::CliMain(argc, argv, tool);
 }

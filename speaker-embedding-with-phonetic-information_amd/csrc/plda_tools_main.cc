@@ -30,31 +30,14 @@
 #include <vector>
 
 #include "backend.h"
+#include "cli.h"
 #include "kio.h"
 #include "plda.h"
 
 namespace {
 
-std::string g_prog = "ivector-plda-scoring";
-
-void LogLine(const char* level, int line, const std::string& msg) {
-  fprintf(stderr, "%s (%s[xvec-hip-0.1]:main():plda_tools_main.cc:%d) %s\n", level, g_prog.c_str(), line, msg.c_str());
-}
-#define XLOG(msg)                       \
-  do {                                  \
-    std::ostringstream _o;              \
-    _o << msg;                          \
-    LogLine("LOG", __LINE__, _o.str()); \
-  } while (0)
-#define XWARN(msg)                          \
-  do {                                      \
-    std::ostringstream _o;                  \
-    _o << msg;                              \
-    LogLine("WARNING", __LINE__, _o.str()); \
-  } while (0)
-
 struct Args {
-  std::vector<std::string> pos;
+  std::vector<std::string> pos;         // set by main() for the tool that runs
   bool binary = true;
   int lda_dim = 100;                    // ivector-compute-lda --dim
   double total_covariance_factor = 0.0;
@@ -70,56 +53,10 @@ struct Args {
   int device = -1;
 };
 
-bool ParseBool(const std::string& v, bool* out) {
-  if (v == "true" || v == "t" || v == "1" || v.empty()) *out = true;
-  else if (v == "false" || v == "f" || v == "0") *out = false;
-  else return false;
-  return true;
-}
-
-bool ParseDouble(const std::string& v, double* out) {
-  char* end = nullptr;
-  *out = strtod(v.c_str(), &end);
-  return !v.empty() && end && *end == 0;
-}
-
-bool ParseInt(const std::string& v, int* out) {
-  char* end = nullptr;
-  const long l = strtol(v.c_str(), &end, 10);
-  *out = (int)l;
-  return !v.empty() && end && *end == 0;
-}
-
-int PickDevice(int requested) {
-  if (requested >= 0) return requested;
-  const char* e = getenv("XVEC_DEVICE");
-  return (e && *e) ? atoi(e) : 0;
-}
-
-// A whole vector table, packed; every vector must have the dimension of the first one.
-struct Packed {
-  std::vector<std::string> keys;
-  std::vector<float> data;
-  int dim = 0;
-  int n() const { return (int)keys.size(); }
-};
-
-void ReadAll(const std::string& rspecifier, Packed* p, long* n_err) {
+// A whole vector table; a failed input pipe is an error.
+void ReadAll(const std::string& rspecifier, xv::Packed* p, long* n_err) {
   xv::SequentialVectorReader r(rspecifier);
-  std::string key, err;
-  std::vector<float> v;
-  while (r.Next(&key, &v, &err)) {
-    if (!err.empty()) {
-      XWARN("Failed to read vector for key " << key << ": " << err);
-      ++*n_err;
-      continue;
-    }
-    if (p->dim == 0) p->dim = (int)v.size();
-    if ((int)v.size() != p->dim || p->dim == 0)
-      throw xv::KioError("vector " + key + " has dimension " + std::to_string(v.size()) + ", expected " + std::to_string(p->dim));
-    p->keys.push_back(key);
-    p->data.insert(p->data.end(), v.begin(), v.end());
-  }
+  xv::ReadBatch(r, -1, p, n_err);
   const int st = r.Close();
   if (st != 0) throw xv::KioError("the input pipe of " + rspecifier + " exited with status " + std::to_string(st));
 }
@@ -147,9 +84,9 @@ void WriteFloatMatrixObject(const std::string& wx, bool binary, int rows, int co
 }
 
 int ComputeLda(const Args& a) {
-  if (a.pos.size() != 3) return -2;
-  const int dev = PickDevice(a.device);
-  Packed p;
+  if (a.pos.size() != 3) return xv::kUsageError;
+  const int dev = xv::PickDevice(a.device);
+  xv::Packed p;
   long n_err = 0;
   ReadAll(a.pos[0], &p, &n_err);
   const std::unordered_map<std::string, std::string> utt2spk = xv::ReadTokenTable(a.pos[1]);
@@ -201,10 +138,10 @@ int ComputeLda(const Args& a) {
 }
 
 int ComputePlda(const Args& a) {
-  if (a.pos.size() != 3) return -2;
-  const int dev = PickDevice(a.device);
+  if (a.pos.size() != 3) return xv::kUsageError;
+  const int dev = xv::PickDevice(a.device);
   const std::vector<xv::TokenList> spk2utt = xv::ReadTokenVectorTable(a.pos[0]);
-  Packed p;
+  xv::Packed p;
   long n_read_err = 0;
   ReadAll(a.pos[1], &p, &n_read_err);
   std::unordered_map<std::string, int> row;
@@ -260,7 +197,7 @@ std::string VecText(const std::vector<double>& v) {
 }
 
 int CopyPlda(const Args& a) {
-  if (a.pos.size() != 2) return -2;
+  if (a.pos.size() != 2) return xv::kUsageError;
   xv::Plda plda;
   xv::ReadPlda(a.pos[0], &plda);
   if (a.smoothing != 0.0) {
@@ -276,11 +213,11 @@ int CopyPlda(const Args& a) {
 // PldaUnsupervisedAdaptor: the vectors' sum and scatter (fp64, on the device, xv::ScatterStats with one segment that
 // lists every row), then the update on the host (xv::AdaptPlda).
 int AdaptPlda(const Args& a) {
-  if (a.pos.size() != 3) return -2;
-  const int dev = PickDevice(a.device);
+  if (a.pos.size() != 3) return xv::kUsageError;
+  const int dev = xv::PickDevice(a.device);
   xv::Plda plda;
   xv::ReadPlda(a.pos[0], &plda);
-  Packed p;
+  xv::Packed p;
   long n_err = 0;
   ReadAll(a.pos[1], &p, &n_err);
   XLOG("Accumulated stats from " << p.n() << " iVectors.");
@@ -344,8 +281,8 @@ class LineReader {
 };
 
 int PldaScoring(const Args& a) {
-  if (a.pos.size() != 5) return -2;
-  const int dev = PickDevice(a.device);
+  if (a.pos.size() != 5) return xv::kUsageError;
+  const int dev = xv::PickDevice(a.device);
   xv::Plda plda;
   xv::ReadPlda(a.pos[0], &plda);
   const int dim = plda.dim;
@@ -354,13 +291,13 @@ int PldaScoring(const Args& a) {
 
   // one table -> transformed vectors on the device
   struct Side {
-    Packed p;
+    xv::Packed p;
     std::vector<double> num;
     std::vector<float> y;
     std::unordered_map<std::string, int> row;
   } train, test;
   auto load = [&](const std::string& rspec, bool is_train, Side* s, long* n_err) {
-    Packed raw;
+    xv::Packed raw;
     long read_err = 0;
     ReadAll(rspec, &raw, &read_err);
     if (raw.n() > 0 && raw.dim != dim)
@@ -472,7 +409,7 @@ int PldaScoring(const Args& a) {
 }
 
 int ComputeEer(const Args& a) {
-  if (a.pos.size() != 1) return -2;
+  if (a.pos.size() != 1) return xv::kUsageError;
   LineReader lr(a.pos[0]);
   std::string line;
   std::vector<std::string> f;
@@ -541,67 +478,44 @@ const char* Usage(const std::string& prog) {
          "Options: --num-utts=<rspecifier> --normalize-length=true --simple-length-normalization=false\n";
 }
 
+// Every tool knows --binary and its own options only: a sibling's option is an unknown one.  --config, --verbose and
+// --print-args are accepted and have no effect.
+xv::OptionResult SetOption(const std::string& prog, const std::string& name, const std::string& val, Args* a) {
+  bool ok = true;
+  if (name == "binary") ok = xv::ParseBool(val, &a->binary);
+  else if (name == "dim" && prog == "ivector-compute-lda") ok = xv::ParseInt(val, &a->lda_dim);
+  else if (name == "total-covariance-factor" && prog == "ivector-compute-lda") ok = xv::ParseDouble(val, &a->total_covariance_factor);
+  else if (name == "covariance-floor" && prog == "ivector-compute-lda") ok = xv::ParseDouble(val, &a->covariance_floor);
+  else if (name == "num-em-iters" && prog == "ivector-compute-plda") ok = xv::ParseInt(val, &a->num_em_iters) && a->num_em_iters >= 0;
+  else if (name == "smoothing" && prog == "ivector-copy-plda") ok = xv::ParseDouble(val, &a->smoothing);
+  else if (name == "mean-diff-scale" && prog == "ivector-adapt-plda") ok = xv::ParseDouble(val, &a->mean_diff_scale);
+  else if (name == "within-covar-scale" && prog == "ivector-adapt-plda") ok = xv::ParseDouble(val, &a->within_covar_scale);
+  else if (name == "between-covar-scale" && prog == "ivector-adapt-plda") ok = xv::ParseDouble(val, &a->between_covar_scale);
+  else if (name == "normalize-length" && prog == "ivector-plda-scoring") ok = xv::ParseBool(val, &a->normalize_length);
+  else if (name == "simple-length-normalization" && prog == "ivector-plda-scoring") ok = xv::ParseBool(val, &a->simple_length_norm);
+  else if (name == "num-utts" && prog == "ivector-plda-scoring") a->num_utts = val;
+  else if (name == "device") a->device = atoi(val.c_str());
+  else if (name != "verbose" && name != "print-args" && name != "config") return xv::OptionResult::kUnknown;
+  return ok ? xv::OptionResult::kOk : xv::OptionResult::kBadValue;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-  xv::InstallMappedFileFaultHandler(strrchr(argv[0], '/') ? strrchr(argv[0], '/') + 1 : argv[0]);
-  const char* slash = strrchr(argv[0], '/');
-  g_prog = slash ? slash + 1 : argv[0];
+  const std::string prog = xv::ProgramName(argv[0]);
   Args a;
-  std::string cmdline = g_prog;
-  for (int i = 1; i < argc; ++i) {
-    std::string s = argv[i];
-    cmdline += " " + s;
-    if (s.compare(0, 2, "--") == 0 && s.size() > 2 && a.pos.empty()) {
-      size_t eq = s.find('=');
-      const std::string name = s.substr(2, eq == std::string::npos ? std::string::npos : eq - 2);
-      const std::string val = eq == std::string::npos ? "" : s.substr(eq + 1);
-      bool ok = true;
-      if (name == "help") {
-        fputs(Usage(g_prog), stderr);
-        return 0;
-      } else if (name == "binary") ok = ParseBool(val, &a.binary);
-      else if (name == "dim" && g_prog == "ivector-compute-lda") ok = ParseInt(val, &a.lda_dim);
-      else if (name == "total-covariance-factor" && g_prog == "ivector-compute-lda") ok = ParseDouble(val, &a.total_covariance_factor);
-      else if (name == "covariance-floor" && g_prog == "ivector-compute-lda") ok = ParseDouble(val, &a.covariance_floor);
-      else if (name == "num-em-iters" && g_prog == "ivector-compute-plda") ok = ParseInt(val, &a.num_em_iters) && a.num_em_iters >= 0;
-      else if (name == "smoothing" && g_prog == "ivector-copy-plda") ok = ParseDouble(val, &a.smoothing);
-      else if (name == "mean-diff-scale" && g_prog == "ivector-adapt-plda") ok = ParseDouble(val, &a.mean_diff_scale);
-      else if (name == "within-covar-scale" && g_prog == "ivector-adapt-plda") ok = ParseDouble(val, &a.within_covar_scale);
-      else if (name == "between-covar-scale" && g_prog == "ivector-adapt-plda") ok = ParseDouble(val, &a.between_covar_scale);
-      else if (name == "normalize-length" && g_prog == "ivector-plda-scoring") ok = ParseBool(val, &a.normalize_length);
-      else if (name == "simple-length-normalization" && g_prog == "ivector-plda-scoring") ok = ParseBool(val, &a.simple_length_norm);
-      else if (name == "num-utts" && g_prog == "ivector-plda-scoring") a.num_utts = val;
-      else if (name == "device") a.device = atoi(val.c_str());
-      else if (name == "verbose" || name == "print-args" || name == "config") ok = true;   // accepted, no effect
-      else {
-        fprintf(stderr, "ERROR (%s) Invalid option %s\n\n%s", g_prog.c_str(), s.c_str(), Usage(g_prog));
-        return 255;
-      }
-      if (!ok) {
-        fprintf(stderr, "ERROR (%s) Invalid value for option %s\n", g_prog.c_str(), s.c_str());
-        return 255;
-      }
-      continue;
-    }
-    a.pos.push_back(s);
-  }
-  fprintf(stderr, "%s \n", cmdline.c_str());
-  try {
-    int rc;
-    if (g_prog == "ivector-compute-lda") rc = ComputeLda(a);
-    else if (g_prog == "ivector-compute-plda") rc = ComputePlda(a);
-    else if (g_prog == "ivector-copy-plda") rc = CopyPlda(a);
-    else if (g_prog == "ivector-adapt-plda") rc = AdaptPlda(a);
-    else if (g_prog == "compute-eer") rc = ComputeEer(a);
-    else rc = PldaScoring(a);
-    if (rc == -2) {
-      fputs(Usage(g_prog), stderr);
-      return 1;
-    }
-    return rc;
-  } catch (const std::exception& e) {
-    fprintf(stderr, "ERROR (%s) %s\n", g_prog.c_str(), e.what());
-    return 255;
-  }
+  xv::CliTool tool;
+  tool.usage = Usage(prog);
+  tool.config_file = false;
+  tool.set = [&](const std::string& name, const std::string& val) { return SetOption(prog, name, val, &a); };
+  tool.run = [&](const std::vector<std::string>& pos) {
+    a.pos = pos;
+    if (prog == "ivector-compute-lda") return ComputeLda(a);
+    if (prog == "ivector-compute-plda") return ComputePlda(a);
+    if (prog == "ivector-copy-plda") return CopyPlda(a);
+    if (prog == "ivector-adapt-plda") return AdaptPlda(a);
+    if (prog == "compute-eer") return ComputeEer(a);
+    return PldaScoring(a);
+  };
+  return xv::CliMain(argc, argv, tool);
 }

@@ -9,34 +9,15 @@
 #include <string.h>
 
 #include <algorithm>
-#include <sstream>
 #include <string>
 #include <vector>
 
-#include "feat.h"
+#include "cli.h"
 #include "kio.h"
 #include "reverb.h"
 #include "wave.h"
 
 namespace {
-
-std::string g_prog = "wav-reverberate";
-
-void LogLine(const char* level, int line, const std::string& msg) {
-  fprintf(stderr, "%s (%s[xvec-hip-0.1]:main():wav_reverberate_main.cc:%d) %s\n", level, g_prog.c_str(), line, msg.c_str());
-}
-#define XLOG(msg)                       \
-  do {                                  \
-    std::ostringstream _o;              \
-    _o << msg;                          \
-    LogLine("LOG", __LINE__, _o.str()); \
-  } while (0)
-#define XWARN(msg)                          \
-  do {                                      \
-    std::ostringstream _o;                  \
-    _o << msg;                              \
-    LogLine("WARNING", __LINE__, _o.str()); \
-  } while (0)
 
 const char* kUsage =
     "Corrupts the wave files supplied via input pipe with the specified\n"
@@ -50,24 +31,6 @@ const char* kUsage =
     "         --shift-output (true) --normalize-output (true) --duration (0) --volume (0) --input-wave-channel (0)\n"
     "         --rir-channel (0) --noise-channel (0) --config=<file> --verbose --device=<gpu>\n"
     "Not built (refused): --multi-channel-output=true.\n";
-
-bool ToBool(const std::string& name, const std::string& v) {
-  if (v == "true" || v == "t" || v == "1" || v.empty()) return true;
-  if (v == "false" || v == "f" || v == "0") return false;
-  throw xv::KioError("Invalid format for boolean argument --" + name + "=" + v);
-}
-float ToFloat(const std::string& name, const std::string& v) {
-  char* end = nullptr;
-  const double d = strtod(v.c_str(), &end);
-  if (v.empty() || !end || *end) throw xv::KioError("Invalid floating-point option --" + name + "=" + v);
-  return (float)d;
-}
-int ToInt(const std::string& name, const std::string& v) {
-  char* end = nullptr;
-  const long d = strtol(v.c_str(), &end, 10);
-  if (v.empty() || !end || *end) throw xv::KioError("Invalid integer option --" + name + "=" + v);
-  return (int)d;
-}
 
 std::vector<std::string> SplitCommas(const std::string& s) {
   std::vector<std::string> out;
@@ -96,18 +59,18 @@ bool SetOption(const std::string& n, const std::string& v, Tool* t) {
   else if (n == "additive-signals") t->additive_signals = v;
   else if (n == "snrs") t->snrs = v;
   else if (n == "start-times") t->start_times = v;
-  else if (n == "shift-output") t->o.shift_output = ToBool(n, v);
-  else if (n == "normalize-output") t->o.normalize_output = ToBool(n, v);
-  else if (n == "duration") t->o.duration = ToFloat(n, v);
-  else if (n == "volume") t->o.volume = ToFloat(n, v);
-  else if (n == "input-wave-channel") t->o.input_wave_channel = ToInt(n, v);
-  else if (n == "rir-channel") t->o.rir_channel = ToInt(n, v);
-  else if (n == "noise-channel") t->o.noise_channel = ToInt(n, v);
+  else if (n == "shift-output") t->o.shift_output = xv::ToBool(n, v);
+  else if (n == "normalize-output") t->o.normalize_output = xv::ToBool(n, v);
+  else if (n == "duration") t->o.duration = xv::ToFloat(n, v);
+  else if (n == "volume") t->o.volume = xv::ToFloat(n, v);
+  else if (n == "input-wave-channel") t->o.input_wave_channel = xv::ToInt(n, v);
+  else if (n == "rir-channel") t->o.rir_channel = xv::ToInt(n, v);
+  else if (n == "noise-channel") t->o.noise_channel = xv::ToInt(n, v);
   else if (n == "multi-channel-output") {
-    if (ToBool(n, v)) throw xv::KioError("--" + n + "=" + v + " is not supported: one output channel is written");
-  } else if (n == "verbose") t->verbose = ToInt(n, v);
-  else if (n == "device") t->device = ToInt(n, v);
-  else if (n == "print-args") (void)ToBool(n, v);
+    if (xv::ToBool(n, v)) throw xv::KioError("--" + n + "=" + v + " is not supported: one output channel is written");
+  } else if (n == "verbose") t->verbose = xv::ToInt(n, v);
+  else if (n == "device") t->device = xv::ToInt(n, v);
+  else if (n == "print-args") (void)xv::ToBool(n, v);
   else return false;
   return true;
 }
@@ -159,13 +122,8 @@ int Run(const Tool& t, const std::vector<std::string>& pos) {
     noises.insert(noises.end(), one.begin(), one.end());
     noise_off.push_back((int64_t)noises.size());
     add_noise.push_back((int32_t)i);
-    snrs.push_back(ToFloat("snrs", snr_s[i]));
-    starts.push_back(ToFloat("start-times", start_s[i]));
-  }
-  int device = t.device;
-  if (device < 0) {
-    const char* e = getenv("XVEC_DEVICE");
-    device = (e && *e) ? atoi(e) : 0;
+    snrs.push_back(xv::ToFloat("snrs", snr_s[i]));
+    starts.push_back(xv::ToFloat("start-times", start_s[i]));
   }
   xv::ReverbBatch b;
   b.rate = (float)rate;
@@ -195,7 +153,7 @@ int Run(const Tool& t, const std::vector<std::string>& pos) {
   std::vector<float> out_f((size_t)n_out + 1);
   std::vector<int16_t> out_q((size_t)n_out + 1);
   int64_t out_off[2] = {0, 0}, clipped = 0;
-  xv::Reverberate(device, t.o, b, out_off, out_f.data(), out_q.data(), &clipped);
+  xv::Reverberate(xv::PickDevice(t.device), t.o, b, out_off, out_f.data(), out_q.data(), &clipped);
   if (clipped > 0) XWARN("clipped " << clipped << " samples out of total " << n_out << "; reduce volume?");
   xv::WriteWaveI16(pos[1], rate, out_q.data(), n_out);
   if (t.verbose >= 1) XLOG("Wrote " << n_out << " samples at " << rate << " Hz to " << pos[1]);
@@ -205,48 +163,13 @@ int Run(const Tool& t, const std::vector<std::string>& pos) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  const char* slash = strrchr(argv[0], '/');
-  g_prog = slash ? slash + 1 : argv[0];
   Tool t;
-  std::vector<std::string> pos;
-  std::vector<std::pair<std::string, std::string>> cli;
-  std::string config, cmdline = g_prog;
-  for (int i = 1; i < argc; ++i) {
-    std::string s = argv[i];
-    cmdline += " " + s;
-    if (s.compare(0, 2, "--") == 0 && pos.empty()) {
-      const size_t eq = s.find('=');
-      const std::string name = s.substr(2, eq == std::string::npos ? std::string::npos : eq - 2);
-      const std::string val = eq == std::string::npos ? "" : s.substr(eq + 1);
-      if (name == "help") {
-        fputs(kUsage, stderr);
-        return 0;
-      }
-      if (name == "config") config = val;
-      else cli.emplace_back(name, val);
-      continue;
-    }
-    pos.push_back(s);
-  }
-  fprintf(stderr, "%s \n", cmdline.c_str());
-  try {
-    std::vector<std::pair<std::string, std::string>> all;
-    if (!config.empty()) all = xv::ReadConfigFile(config);
-    all.insert(all.end(), cli.begin(), cli.end());
-    for (const auto& nv : all) {
-      if (!SetOption(nv.first, nv.second, &t)) {
-        fprintf(stderr, "ERROR (%s) Invalid option --%s%s%s\n\n%s", g_prog.c_str(), nv.first.c_str(), nv.second.empty() ? "" : "=",
-                nv.second.c_str(), kUsage);
-        return 255;
-      }
-    }
-    if (pos.size() != 2) {
-      fputs(kUsage, stderr);
-      return 1;
-    }
-    return Run(t, pos);
-  } catch (const std::exception& e) {
-    fprintf(stderr, "ERROR (%s) %s\n", g_prog.c_str(), e.what());
-    return 255;
-  }
+  xv::CliTool tool;
+  tool.usage = kUsage;
+  tool.config_file = true;
+  tool.set = [&](const std::string& n, const std::string& v) {
+    return SetOption(n, v, &t) ? xv::OptionResult::kOk : xv::OptionResult::kUnknown;
+  };
+  tool.run = [&](const std::vector<std::string>& pos) { return pos.size() == 2 ? Run(t, pos) : xv::kUsageError; };
+  return xv::CliMain(argc, argv, tool);
 }

@@ -223,3 +223,31 @@ def test_transform_vec_reads_the_text_matrix_the_reference_helpers_write(tmp_pat
     y = dict(kio.read_ark(str(tmp_path / "y.ark"), "vector"))
     for k, v in vecs:
         assert np.allclose(y[k], M @ v, rtol=1e-6), k
+
+
+def test_small_tools_pick_the_same_device_three_ways(tmp_path):
+    """--device=0, XVEC_DEVICE=0 and neither (the default ordinal is 0) name the same device: one tool of each of the four
+    executables that share PickDevice writes the same bytes all three ways."""
+    d = tmp_path
+    rng = np.random.default_rng(5)
+    kio.write_ark_vectors(str(d / "v8.ark"), [("v%d" % i, rng.standard_normal(8).astype(np.float32)) for i in range(4)])
+    kio.write_ark_vectors(str(d / "v4.ark"), [("s%d-u%d" % (i // 2, i % 2), (rng.standard_normal(4) + i // 2).astype(np.float32))
+                                               for i in range(6)])
+    (d / "utt2spk").write_text("".join("s%d-u%d s%d\n" % (i // 2, i % 2, i // 2) for i in range(6)))
+    kio.write_ark_matrices(str(d / "feats.ark"), [("utt", (rng.standard_normal((30, 5)) * 3 + 4).astype(np.float32))])
+    assert H.pkg().write_wave(str(d / "in.wav"), (rng.standard_normal(4000) * 3000).astype(np.int16), 8000) == 0
+    tools = [
+        (["ivector-normalize-length"], ["ark:%s/v8.ark" % d], "ark:%s"),
+        (["ivector-compute-lda", "--dim=2"], ["ark:%s/v4.ark" % d, "ark:%s/utt2spk" % d], "%s"),
+        (["compute-vad"], ["ark:%s/feats.ark" % d], "ark:%s"),
+        (["wav-reverberate", "--volume=0.5"], ["%s/in.wav" % d], "%s"),
+    ]
+    base = {k: v for k, v in os.environ.items() if k != "XVEC_DEVICE"}
+    for head, inputs, out_form in tools:
+        outs = []
+        for way, (opt, env) in enumerate(((["--device=0"], base), ([], dict(base, XVEC_DEVICE="0")), ([], base))):
+            out = d / ("%s.%d" % (head[0], way))
+            r = _run([os.path.join(BIN, head[0])] + head[1:] + opt + inputs + [out_form % out], env=env, timeout=120)
+            assert r.returncode == 0, (head, way, r.stderr.decode())
+            outs.append(out.read_bytes())
+        assert len(outs[0]) > 0 and outs[0] == outs[1] == outs[2], head
