@@ -468,6 +468,13 @@ typedef struct {
    * come from xv_pack_mx_residual64 (and, XV_PREC_FP16MX2, w4b / w4b_scale from xv_pack_mx_weights64 with ldw4b = 2 * ldw).  A layer runs this kernel for every launch of a mode or for none (its sums are formed in
    * another order than the 32-column kernels'). */
   int32_t p8;
+  /* epilogue 0 with gmax_out: device int8 [rows/16][2], first / last (exclusive) row of every 16-row group that counts for its
+   * maximum (NULL: every row) */
+  const int8_t* out_range;
+  /* > 1: split-K (XV_PREC_BF16X3 .. XV_PREC_FP16X3, epilogues 0 and 1, not p8): the K steps are divided over slices by the
+   * engine's rule (at least 4 steps per slice, at most 24 slices), whose raw sums a second kernel adds in slice order.  The value
+   * must be the number of slices that rule gives for this K (XV_ERR_ARG otherwise); the entry owns the workspace.  0 / 1: off */
+  int32_t ksplit;
 } xv_gemm_desc;
 /* Host helper for the test above: packs the e2m1 residual plane of one weight matrix exactly like xv_model_pack does
  * (w, w_hi_f16: [n_pad][k_len] row-major, k_len = sum of the segments' k_len; seg_src[j] equal = same source plane).
@@ -492,6 +499,73 @@ xv_status xv_pack_mx_weights64(const float* w, int32_t n_pad, int32_t nseg, cons
  * epilogue (xv_gemm_desc.epilogue): n_pad * (k_len / 32) bytes.  n_pad must be a multiple of 128. */
 xv_status xv_tile_mx_scales(const uint8_t* natural, int32_t n_pad, int32_t k_len, int32_t epilogue, uint8_t* tiled);
 xv_status xv_kernel_tdnn_gemm(const xv_gemm_desc* d);
+
+/* ---- kernel-level entries of the frame-level and small kernels (unit tests; same conventions: device pointers from the caller
+ * unless stated, an optional stream, XV_ERR_ARG with a reason for geometry a kernel cannot run, no engine or context) ---------- */
+/* tdnn_first_kernel: the layer(s) that read the network input.  Chunk b holds rows [row_offsets[b], row_offsets[b + 1]) of feats
+ * (row_offsets[0] may be > 0) and starts at device row dev_off[b]; device frame t of a chunk is its source frame
+ * clamp(t - pad_left, 0, len - 1) for t < len + pad_left + pad_right; device rows outside every chunk read as zero.  The entry
+ * builds the kernel's group table with the engine's own function, compacts both weight planes and launches rows
+ * [row0, row0 + nrows).  Output pointers are indexed by absolute device row. */
+typedef struct {
+  const float* feats;            /* device fp32 [.. row_offsets[B]][dim] */
+  const int32_t* row_offsets;    /* HOST [B + 1] */
+  const int32_t* dev_off;        /* HOST [B], multiples of 16, chunks in increasing, non-overlapping order of device rows */
+  int32_t B;
+  int32_t rows;                  /* device rows, multiple of 64 */
+  int32_t pad_left, pad_right;
+  int32_t dim, noff;
+  int32_t off[8];                /* time offsets in Append() order, each within +-15 */
+  const void* w_hi; const void* w_lo;   /* 16-bit planes [n_pad][ldw] in the generic walk layout: segment j at column j * seg_pad */
+  int32_t ldw, seg_pad;
+  int32_t n_pad;                 /* multiple of 128 */
+  int32_t epi_prec;              /* what the planes epilogue writes: XV_PREC_BF16X3 / XV_PREC_FP16X3 (hi + lo), XV_PREC_FP16X2 (fp16
+                                  * plane only), XV_PREC_FP16X3E (fp16 plane + 4-bit residual); the products are three-pass */
+  const float* bias; const float* scale; const float* offset;
+  int32_t relu, bn;
+  void* out_hi; void* out_lo; int32_t ldo;
+  void* out_lo4; void* out_lo4_scale;
+  void* gmax_out; const int8_t* out_range;   /* as in xv_gemm_desc */
+  int32_t row0, nrows;           /* multiples of 64 */
+  int32_t max_wgs;               /* > 0: at most this many workgroups per group of 512 columns (0: the launcher's rule) */
+  void* hip_stream;
+} xv_first_layer_desc;
+xv_status xv_kernel_first_layer(const xv_first_layer_desc* d);
+/* prep_input_kernel: fp32 rows -> 16-bit planes [rows][ld] (precision XV_PREC_BF16X3 .. XV_PREC_FP16X3; out_lo only for the split
+ * ones), all tables on the device; zero_words (may be NULL): n_zero_words 32-bit words cleared by the same launch */
+typedef struct {
+  int32_t precision;
+  const float* feats; const int32_t* src_off; const int32_t* dev_off; const int32_t* grp_utt;
+  int32_t rows;                  /* multiple of 128 */
+  int32_t dim, ld;               /* ld: multiple of 32, >= dim */
+  void* out_hi; void* out_lo;
+  int32_t pad_left, pad_right;
+  void* zero_words; int32_t n_zero_words;
+  void* hip_stream;
+} xv_prep_input_desc;
+xv_status xv_kernel_prep_input(const xv_prep_input_desc* d);
+/* pool_finalise_kernel: per chunk b and column, the partials of groups [utt_grp0[b], utt_grp1[b]) -> mean | stddev as planes
+ * [B][ld] (ld >= 2 dim) */
+typedef struct {
+  int32_t precision;             /* XV_PREC_BF16X3 .. XV_PREC_FP16X3 */
+  const float* partial; int32_t ldp;   /* [groups][2][ldp] */
+  const int32_t* utt_grp0; const int32_t* utt_grp1; const int32_t* utt_count;
+  int32_t B, dim;
+  float var_floor;
+  void* out_hi; void* out_lo; int32_t ld;
+  void* hip_stream;
+} xv_pool_finalise_desc;
+xv_status xv_kernel_pool_finalise(const xv_pool_finalise_desc* d);
+/* frame_output kernels: out[o][0 .. dim) = (log-softmax of) row out_row[o] (o when out_row is NULL) of src [..][ld]; src16: the
+ * logits as fp16 instead (log_softmax only, dim <= 16384) */
+typedef struct {
+  const float* src; const void* src16; int32_t ld;
+  const int32_t* out_row; int32_t n_out;
+  int32_t dim, log_softmax;
+  float* out; int32_t out_ld;
+  void* hip_stream;
+} xv_frame_output_desc;
+xv_status xv_kernel_frame_output(const xv_frame_output_desc* d);
 
 #ifdef __cplusplus
 }

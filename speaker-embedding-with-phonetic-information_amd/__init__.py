@@ -61,7 +61,44 @@ class GemmDesc(ctypes.Structure):
                 ("gmax_out", ctypes.c_void_p),
                 ("w4b", ctypes.c_void_p), ("ldw4b", ctypes.c_int32), ("w4b_scale", ctypes.c_void_p),
                 ("out_lo4", ctypes.c_void_p), ("out_lo4_scale", ctypes.c_void_p),
-                ("p8", ctypes.c_int32)]
+                ("p8", ctypes.c_int32),
+                ("out_range", ctypes.c_void_p), ("ksplit", ctypes.c_int32)]
+
+
+class FirstLayerDesc(ctypes.Structure):
+    """xv_first_layer_desc (row_offsets / dev_off are HOST arrays: keep the numpy arrays alive over the call)"""
+    _fields_ = [("feats", ctypes.c_void_p), ("row_offsets", ctypes.c_void_p), ("dev_off", ctypes.c_void_p), ("B", ctypes.c_int32),
+                ("rows", ctypes.c_int32), ("pad_left", ctypes.c_int32), ("pad_right", ctypes.c_int32),
+                ("dim", ctypes.c_int32), ("noff", ctypes.c_int32), ("off", ctypes.c_int32 * 8),
+                ("w_hi", ctypes.c_void_p), ("w_lo", ctypes.c_void_p), ("ldw", ctypes.c_int32), ("seg_pad", ctypes.c_int32),
+                ("n_pad", ctypes.c_int32), ("epi_prec", ctypes.c_int32),
+                ("bias", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("offset", ctypes.c_void_p),
+                ("relu", ctypes.c_int32), ("bn", ctypes.c_int32),
+                ("out_hi", ctypes.c_void_p), ("out_lo", ctypes.c_void_p), ("ldo", ctypes.c_int32),
+                ("out_lo4", ctypes.c_void_p), ("out_lo4_scale", ctypes.c_void_p),
+                ("gmax_out", ctypes.c_void_p), ("out_range", ctypes.c_void_p),
+                ("row0", ctypes.c_int32), ("nrows", ctypes.c_int32), ("max_wgs", ctypes.c_int32),
+                ("hip_stream", ctypes.c_void_p)]
+
+
+class PrepInputDesc(ctypes.Structure):
+    _fields_ = [("precision", ctypes.c_int32), ("feats", ctypes.c_void_p), ("src_off", ctypes.c_void_p), ("dev_off", ctypes.c_void_p),
+                ("grp_utt", ctypes.c_void_p), ("rows", ctypes.c_int32), ("dim", ctypes.c_int32), ("ld", ctypes.c_int32),
+                ("out_hi", ctypes.c_void_p), ("out_lo", ctypes.c_void_p), ("pad_left", ctypes.c_int32), ("pad_right", ctypes.c_int32),
+                ("zero_words", ctypes.c_void_p), ("n_zero_words", ctypes.c_int32), ("hip_stream", ctypes.c_void_p)]
+
+
+class PoolFinaliseDesc(ctypes.Structure):
+    _fields_ = [("precision", ctypes.c_int32), ("partial", ctypes.c_void_p), ("ldp", ctypes.c_int32),
+                ("utt_grp0", ctypes.c_void_p), ("utt_grp1", ctypes.c_void_p), ("utt_count", ctypes.c_void_p),
+                ("B", ctypes.c_int32), ("dim", ctypes.c_int32), ("var_floor", ctypes.c_float),
+                ("out_hi", ctypes.c_void_p), ("out_lo", ctypes.c_void_p), ("ld", ctypes.c_int32), ("hip_stream", ctypes.c_void_p)]
+
+
+class FrameOutputDesc(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("src16", ctypes.c_void_p), ("ld", ctypes.c_int32),
+                ("out_row", ctypes.c_void_p), ("n_out", ctypes.c_int32), ("dim", ctypes.c_int32), ("log_softmax", ctypes.c_int32),
+                ("out", ctypes.c_void_p), ("out_ld", ctypes.c_int32), ("hip_stream", ctypes.c_void_p)]
 
 
 class Calibration(ctypes.Structure):
@@ -98,6 +135,7 @@ ABI_SYMBOLS = [
     "xv_plda_estimate", "xv_plda_adapt",
     "xv_mfcc_options_default", "xv_mfcc_num_frames", "xv_mfcc_utt_seed", "xv_mfcc_compute", "xv_mfcc_compute_i16", "xv_mfcc_kernel_time", "xv_vad_energy",
     "xv_reverb_options_default", "xv_reverb_output_length", "xv_wav_reverberate", "xv_reverb_kernel_time", "xv_wave_write", "xv_recognize_wav_pipeline",
+    "xv_kernel_first_layer", "xv_kernel_prep_input", "xv_kernel_pool_finalise", "xv_kernel_frame_output",
     "xv_wave_read", "xv_wave_free", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
 ]
 
@@ -174,6 +212,10 @@ def lib():
     L.xv_ctx_create_broadcast.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int,
                                           ctypes.POINTER(ctypes.c_void_p)]
     L.xv_kernel_tdnn_gemm.argtypes = [ctypes.POINTER(GemmDesc)]
+    L.xv_kernel_first_layer.argtypes = [ctypes.POINTER(FirstLayerDesc)]
+    L.xv_kernel_prep_input.argtypes = [ctypes.POINTER(PrepInputDesc)]
+    L.xv_kernel_pool_finalise.argtypes = [ctypes.POINTER(PoolFinaliseDesc)]
+    L.xv_kernel_frame_output.argtypes = [ctypes.POINTER(FrameOutputDesc)]
     L.xv_ctx_calibrate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_float,
                                    ctypes.POINTER(Calibration)]
     L.xv_ctx_set_fast_mode.argtypes = [ctypes.c_void_p, ctypes.c_int32]
@@ -975,6 +1017,22 @@ def reverberate(waves, rirs=None, additive=None, rate=8000.0, device=0, return_i
 
 def kernel_tdnn_gemm(desc):
     _check(lib().xv_kernel_tdnn_gemm(ctypes.byref(desc)))
+
+
+def kernel_first_layer(desc):
+    _check(lib().xv_kernel_first_layer(ctypes.byref(desc)))
+
+
+def kernel_prep_input(desc):
+    _check(lib().xv_kernel_prep_input(ctypes.byref(desc)))
+
+
+def kernel_pool_finalise(desc):
+    _check(lib().xv_kernel_pool_finalise(ctypes.byref(desc)))
+
+
+def kernel_frame_output(desc):
+    _check(lib().xv_kernel_frame_output(ctypes.byref(desc)))
 
 
 def pack_mx_residual(w, w_hi_f16, segs, walk64=False):

@@ -939,6 +939,27 @@ xv_status xv_kernel_tdnn_gemm(const xv_gemm_desc* d) {
     a.out_lo4 = (uint8_t*)d->out_lo4;
     a.out_lo4s = (uint8_t*)d->out_lo4_scale;
     a.p8 = d->p8;
+    a.out_range = d->out_range;
+    if (d->ksplit > 1) {
+      if (d->precision < xv::kPrecBf16x3 || d->precision > xv::kPrecFp16x3 || a.p8 ||
+          (d->epilogue != xv::kEpiAct && d->epilogue != xv::kEpiF32))
+        return Fail(XV_ERR_ARG, "xv_kernel_tdnn_gemm: split-K needs XV_PREC_BF16X3 .. XV_PREC_FP16X3, epilogue 0 or 1 and no p8");
+      a.ksteps_per_slice = xv::SplitKStepsPerSlice(a.total_ksteps);
+      a.ksplit = (a.total_ksteps + a.ksteps_per_slice - 1) / a.ksteps_per_slice;
+      if (a.ksplit != d->ksplit)
+        return Fail(XV_ERR_ARG, "xv_kernel_tdnn_gemm: " + std::to_string(a.total_ksteps) + " K steps are split over " +
+                                    std::to_string(a.ksplit) + " slices, not " + std::to_string(d->ksplit));
+      void* ws = nullptr;
+      hipError_t e = hipMalloc(&ws, (size_t)a.ksplit * d->rows * d->n_pad * 4);
+      if (e != hipSuccess) return Fail(XV_ERR_DEVICE, std::string("hipMalloc(split-K workspace): ") + hipGetErrorString(e));
+      a.splitk_ws = (float*)ws;
+      e = xv::launch_tdnn_gemm(a, d->precision, d->epilogue, (hipStream_t)d->hip_stream);
+      const hipError_t e2 = hipStreamSynchronize((hipStream_t)d->hip_stream);
+      (void)hipFree(ws);
+      if (e != hipSuccess || e2 != hipSuccess)
+        return Fail(XV_ERR_DEVICE, std::string("tdnn_gemm split-K launch: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+      return XV_OK;
+    }
     if (a.p8) {
       if (!xv::gemm_p8_applicable(a, d->precision) || (d->epilogue != xv::kEpiAct && d->epilogue != xv::kEpiStats))
         return Fail(XV_ERR_ARG, "xv_kernel_tdnn_gemm: p8 needs XV_PREC_FP16, XV_PREC_FP16MX or XV_PREC_FP16MX2, epilogue 0 or 2, rows and n_pad "
@@ -952,6 +973,189 @@ xv_status xv_kernel_tdnn_gemm(const xv_gemm_desc* d) {
                               "K groups of whole 128-column blocks and an even number of 128-row tiles");
     hipError_t e = xv::launch_tdnn_gemm(a, d->precision, d->epilogue, (hipStream_t)d->hip_stream);
     if (e != hipSuccess) return Fail(XV_ERR_DEVICE, std::string("tdnn_gemm launch: ") + hipGetErrorString(e));
+    return XV_OK;
+  });
+}
+
+namespace {
+// device memory of one test entry: freed when the entry returns
+struct DevMem {
+  void* p = nullptr;
+  ~DevMem() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t Alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
+};
+}  // namespace
+
+xv_status xv_kernel_first_layer(const xv_first_layer_desc* d) {
+  if (!d) return Fail(XV_ERR_ARG, "xv_kernel_first_layer: null descriptor");
+  return Guard([&] {
+    const char* who = "xv_kernel_first_layer: ";
+    if (!d->feats || !d->row_offsets || !d->dev_off || !d->w_hi || !d->w_lo || !d->bias || !d->out_hi || (d->bn && (!d->scale || !d->offset)))
+      return Fail(XV_ERR_ARG, std::string(who) + "a required pointer is null");
+    const int p = d->epi_prec;
+    if (p != xv::kPrecBf16x3 && p != xv::kPrecFp16x3 && p != xv::kPrecFp16x2 && p != xv::kPrecFp16x3E)
+      return Fail(XV_ERR_ARG, std::string(who) + "epi_prec must be XV_PREC_BF16X3, XV_PREC_FP16X3, XV_PREC_FP16X2 or XV_PREC_FP16X3E");
+    if ((p == xv::kPrecBf16x3 || p == xv::kPrecFp16x3) && !d->out_lo) return Fail(XV_ERR_ARG, std::string(who) + "the split planes need out_lo");
+    if (p == xv::kPrecFp16x3E && (!d->out_lo4 || !d->out_lo4_scale))
+      return Fail(XV_ERR_ARG, std::string(who) + "XV_PREC_FP16X3E needs out_lo4 and out_lo4_scale");
+    if (d->B < 1 || d->rows < xv::kFirstRows || d->rows % xv::kFirstRows || d->n_pad < xv::kBN || d->n_pad % xv::kBN ||
+        d->ldo < d->n_pad || d->ldo % 64 || d->pad_left < 0 || d->pad_right < 0)
+      return Fail(XV_ERR_ARG, std::string(who) + "bad geometry (rows: multiple of 64, n_pad: multiple of 128, ldo: multiple of 64, >= n_pad)");
+    if (d->nrows < xv::kFirstRows || d->nrows % xv::kFirstRows || d->row0 < 0 || d->row0 % xv::kFirstRows || d->row0 + (long)d->nrows > d->rows)
+      return Fail(XV_ERR_ARG, std::string(who) + "row0 and nrows must be multiples of 64 inside [0, rows]");
+    if (d->dim < 1 || d->noff < 1 || d->noff > 8) return Fail(XV_ERR_ARG, std::string(who) + "dim >= 1 and 1 .. 8 offsets");
+    int off[8];
+    for (int j = 0; j < d->noff; ++j) {
+      off[j] = d->off[j];
+      if (off[j] < -15 || off[j] > 15) return Fail(XV_ERR_ARG, std::string(who) + "time offsets beyond +-15 frames");
+    }
+    if (!xv::FirstLayerApplicable(d->dim, d->noff, off))
+      return Fail(XV_ERR_ARG, std::string(who) + "tdnn_first_kernel cannot run this shape (dim rounded up to 8 must be <= 24, noff x that <= 128, "
+                                                 "and (64 + offset span) x that <= 2048)");
+    if (d->seg_pad < d->dim || (long)(d->noff - 1) * d->seg_pad + d->dim > d->ldw)
+      return Fail(XV_ERR_ARG, std::string(who) + "the weight planes do not hold noff segments of dim columns");
+    // 16-row groups of the chunks
+    const int ngrp = d->rows / xv::kRowAlign;
+    std::vector<int32_t> grp_utt(ngrp, -1);
+    long next_free = 0;
+    if (d->row_offsets[0] < 0) return Fail(XV_ERR_ARG, std::string(who) + "negative row offset");
+    for (int b = 0; b < d->B; ++b) {
+      const long len = (long)d->row_offsets[b + 1] - d->row_offsets[b];
+      const long span = (len + d->pad_left + d->pad_right + xv::kRowAlign - 1) / xv::kRowAlign * xv::kRowAlign;
+      if (len < 1 || d->dev_off[b] % xv::kRowAlign || d->dev_off[b] < next_free || d->dev_off[b] + span > d->rows)
+        return Fail(XV_ERR_ARG, std::string(who) + "chunk " + std::to_string(b) + ": empty, not on a 16-row boundary, overlapping or beyond rows");
+      next_free = d->dev_off[b] + span;
+      for (long g = d->dev_off[b] / xv::kRowAlign; g < next_free / xv::kRowAlign; ++g) grp_utt[g] = b;
+    }
+    std::vector<int32_t> grp_src((size_t)ngrp * 4);
+    xv::FillFirstGroupSources(ngrp, grp_utt.data(), d->dev_off, d->row_offsets, d->pad_left, d->pad_right, grp_src.data());
+    hipStream_t s = (hipStream_t)d->hip_stream;
+    DevMem tab, wch, wcl;
+    const size_t wc_bytes = (size_t)d->n_pad * xv::kFirstK * 2;
+    hipError_t e = tab.Alloc(grp_src.size() * 4);
+    if (e == hipSuccess) e = wch.Alloc(wc_bytes);
+    if (e == hipSuccess) e = wcl.Alloc(wc_bytes);
+    if (e == hipSuccess) e = hipMemcpy(tab.p, grp_src.data(), grp_src.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return Fail(XV_ERR_DEVICE, std::string("first_layer tables: ") + hipGetErrorString(e));
+    xv::FirstArgs fa;
+    memset(&fa, 0, sizeof fa);
+    fa.g.n_tiles = d->n_pad / xv::kBN;
+    fa.g.m_tiles = d->rows / xv::kBM;
+    fa.g.relu = d->relu;
+    fa.g.bn = d->bn;
+    fa.g.bias = d->bias;
+    fa.g.scale = d->scale;
+    fa.g.offset = d->offset;
+    fa.g.out_hi = (uint16_t*)d->out_hi;
+    fa.g.out_lo = (uint16_t*)d->out_lo;
+    fa.g.ldo = d->ldo;
+    fa.g.out_lo4 = (uint8_t*)d->out_lo4;
+    fa.g.out_lo4s = (uint8_t*)d->out_lo4_scale;
+    fa.g.gmax_out = (unsigned*)d->gmax_out;
+    fa.g.out_range = d->out_range;
+    fa.feats = d->feats;
+    fa.feats_valid_idx = (long)d->row_offsets[0] * d->dim;
+    fa.grp_src = (const int4*)tab.p;
+    fa.rows = d->rows;
+    fa.dim = d->dim;
+    fa.row0 = d->row0;
+    fa.nrows = d->nrows;
+    fa.noff = d->noff;
+    for (int j = 0; j < d->noff; ++j) fa.off[j] = off[j];
+    fa.wc_hi = (const uint16_t*)wch.p;
+    fa.wc_lo = (const uint16_t*)wcl.p;
+    fa.max_wgs = d->max_wgs > 0 ? d->max_wgs : 0;
+    e = xv::launch_compact_first((const uint16_t*)d->w_hi, d->ldw, d->seg_pad, d->n_pad, d->noff, d->dim, (uint16_t*)wch.p, s);
+    if (e == hipSuccess) e = xv::launch_compact_first((const uint16_t*)d->w_lo, d->ldw, d->seg_pad, d->n_pad, d->noff, d->dim, (uint16_t*)wcl.p, s);
+    if (e == hipSuccess) e = xv::launch_tdnn_first(fa, p, s);
+    const hipError_t e2 = hipStreamSynchronize(s);   // the tables above are freed on return
+    if (e != hipSuccess || e2 != hipSuccess)
+      return Fail(XV_ERR_DEVICE, std::string("tdnn_first launch: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+    return XV_OK;
+  });
+}
+
+xv_status xv_kernel_prep_input(const xv_prep_input_desc* d) {
+  if (!d) return Fail(XV_ERR_ARG, "xv_kernel_prep_input: null descriptor");
+  return Guard([&] {
+    if (d->precision < xv::kPrecBf16x3 || d->precision > xv::kPrecFp16x3) return Fail(XV_ERR_ARG, "xv_kernel_prep_input: precision must be 0 .. 3");
+    const bool split = xv::PrecXPlanes(d->precision) == 2;
+    if (!d->feats || !d->src_off || !d->dev_off || !d->grp_utt || !d->out_hi || (split && !d->out_lo))
+      return Fail(XV_ERR_ARG, "xv_kernel_prep_input: a required pointer is null");
+    if (d->rows < xv::kBM || d->rows % xv::kBM || d->ld < xv::kBK || d->ld % xv::kBK || d->dim < 1 || d->dim > d->ld || d->pad_left < 0 ||
+        d->pad_right < 0 || d->n_zero_words < 0 || (d->n_zero_words > 0 && !d->zero_words))
+      return Fail(XV_ERR_ARG, "xv_kernel_prep_input: bad geometry (rows: multiple of 128, ld: multiple of 32, >= dim)");
+    xv::PrepArgs a;
+    memset(&a, 0, sizeof a);
+    a.feats = d->feats;
+    a.src_off = d->src_off;
+    a.dev_off = d->dev_off;
+    a.grp_utt = d->grp_utt;
+    a.rows = d->rows;
+    a.dim = d->dim;
+    a.ld = d->ld;
+    a.out_hi = (uint16_t*)d->out_hi;
+    a.out_lo = (uint16_t*)d->out_lo;
+    a.pad_left = d->pad_left;
+    a.pad_right = d->pad_right;
+    a.zero_words = (unsigned*)d->zero_words;
+    a.n_zero_words = d->n_zero_words;
+    const hipError_t e = xv::launch_prep_input(a, d->precision, (hipStream_t)d->hip_stream);
+    if (e != hipSuccess) return Fail(XV_ERR_DEVICE, std::string("prep_input launch: ") + hipGetErrorString(e));
+    return XV_OK;
+  });
+}
+
+xv_status xv_kernel_pool_finalise(const xv_pool_finalise_desc* d) {
+  if (!d) return Fail(XV_ERR_ARG, "xv_kernel_pool_finalise: null descriptor");
+  return Guard([&] {
+    if (d->precision < xv::kPrecBf16x3 || d->precision > xv::kPrecFp16x3) return Fail(XV_ERR_ARG, "xv_kernel_pool_finalise: precision must be 0 .. 3");
+    const bool split = xv::PrecXPlanes(d->precision) == 2;
+    if (!d->partial || !d->utt_grp0 || !d->utt_grp1 || !d->utt_count || !d->out_hi || (split && !d->out_lo))
+      return Fail(XV_ERR_ARG, "xv_kernel_pool_finalise: a required pointer is null");
+    if (d->B < 1 || d->dim < 1 || d->ldp < d->dim || d->ld < 2 * d->dim)
+      return Fail(XV_ERR_ARG, "xv_kernel_pool_finalise: bad geometry (ldp >= dim, ld >= 2 dim)");
+    xv::PoolArgs a;
+    memset(&a, 0, sizeof a);
+    a.partial = d->partial;
+    a.ldp = d->ldp;
+    a.utt_grp0 = d->utt_grp0;
+    a.utt_grp1 = d->utt_grp1;
+    a.utt_count = d->utt_count;
+    a.B = d->B;
+    a.dim = d->dim;
+    a.var_floor = d->var_floor;
+    a.out_hi = (uint16_t*)d->out_hi;
+    a.out_lo = (uint16_t*)d->out_lo;
+    a.ld = d->ld;
+    const hipError_t e = xv::launch_pool_finalise(a, d->precision, (hipStream_t)d->hip_stream);
+    if (e != hipSuccess) return Fail(XV_ERR_DEVICE, std::string("pool_finalise launch: ") + hipGetErrorString(e));
+    return XV_OK;
+  });
+}
+
+xv_status xv_kernel_frame_output(const xv_frame_output_desc* d) {
+  if (!d) return Fail(XV_ERR_ARG, "xv_kernel_frame_output: null descriptor");
+  return Guard([&] {
+    if ((!d->src && !d->src16) || !d->out) return Fail(XV_ERR_ARG, "xv_kernel_frame_output: a required pointer is null");
+    if (d->n_out < 1 || d->dim < 1 || d->ld < d->dim || d->out_ld < d->dim) return Fail(XV_ERR_ARG, "xv_kernel_frame_output: bad geometry");
+    if (d->src16 && (!d->log_softmax || d->dim > 256 * 64))
+      return Fail(XV_ERR_ARG, "xv_kernel_frame_output: fp16 logits are read by the log-softmax kernels only, rows of up to 16384 columns");
+    xv::FrameOutArgs a;
+    memset(&a, 0, sizeof a);
+    a.src = d->src;
+    a.src16 = (const uint16_t*)d->src16;
+    a.ld = d->ld;
+    a.out_row = d->out_row;
+    a.n_out = d->n_out;
+    a.dim = d->dim;
+    a.log_softmax = d->log_softmax;
+    a.out = d->out;
+    a.out_ld = d->out_ld;
+    const hipError_t e = xv::launch_frame_output(a, (hipStream_t)d->hip_stream);
+    if (e != hipSuccess) return Fail(XV_ERR_DEVICE, std::string("frame_output launch: ") + hipGetErrorString(e));
     return XV_OK;
   });
 }

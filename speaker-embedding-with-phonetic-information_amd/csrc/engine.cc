@@ -1009,16 +1009,7 @@ void Engine::FillPlan(const int32_t* row_offsets, int B, Plan* plan, std::vector
   plan->o_gs = Align256(plan->o_ar + act_range.size());
   // source of every 16-row group for the first-layer kernel (kernels.h, FirstArgs::grp_src)
   std::vector<int32_t> grp_src((size_t)ngrp * 4, 0);
-  for (int g = 0; g < ngrp; ++g) {
-    const int b = grp_utt[g];
-    if (b < 0) continue;
-    const int t0 = g * kRowAlign - dev_off[b];
-    const int s0 = row_offsets[b], len = key[b];
-    grp_src[4 * g] = s0 + t0 - pad_left_;
-    grp_src[4 * g + 1] = len + pad_left_ + pad_right_ - t0;
-    grp_src[4 * g + 2] = s0;
-    grp_src[4 * g + 3] = s0 + len - 1;
-  }
+  FillFirstGroupSources(ngrp, grp_utt.data(), dev_off.data(), row_offsets, pad_left_, pad_right_, grp_src.data());
   const size_t total = Align256(plan->o_gs + grp_src.size() * 4);
   std::vector<uint8_t>& host = *tables;
   host.assign(total, 0);
@@ -1170,12 +1161,8 @@ int Engine::LayerArgs(Lane& L, const Plan& plan, size_t i, bool mx_pass, float* 
     }
   } else {
     ga.m_tiles = plan.b_pad / kBM;
-    // few rows, long K (3000 for the embedding layer): K is split over up to 24 slices of at least 4 steps - a rule that does
-    // not depend on the batch, so an utterance's sums are formed in the same order whatever it is batched with.  Measured
-    // on the 256-chunk embedding layer (94 steps, 2 x 4 tiles), GEMM + reduction: 12 steps x 8 slices 23.3 us, 8 x 12 20.4,
-    // 6 x 16 19.4, 4 x 24 18.8, 3 x 32 19.3, 2 x 47 25.2 (with the workgroups spread over all XCDs, kernels.hip; while they
-    // all sat on two of them more slices only queued: 25.9 / 31.6 / 36.8 us for 8 / 12 / 24 slices)
-    const int per = std::max(4, (ksteps + 23) / 24);
+    // few rows, long K: split over K slices by a rule that does not depend on the batch (kernels.h)
+    const int per = SplitKStepsPerSlice(ksteps);
     ga.ksteps_per_slice = per;
     ga.ksplit = (ksteps + per - 1) / per;
     if (ga.ksplit > 1) {

@@ -257,7 +257,7 @@ struct GemmArgs {
   // split-K (small-M layers after the pooling): ksplit > 1 -> K steps are divided over gridDim.y slices whose raw
   // accumulators go to splitk_ws[slice][rows][n_pad]; a second kernel adds them in slice order and applies the epilogue
   int ksplit;
-  int ksteps_per_slice;
+  int ksteps_per_slice;   // SplitKStepsPerSlice
   float* splitk_ws;
   // start stagger of the 256x128 variant (set by the launcher): the first stagger_wgs workgroups sleep up to
   // stagger_units x 2048 cycles, see the kernel
@@ -280,6 +280,17 @@ struct GemmArgs {
   int p8_ktiles_lo;      // kPrecFp16Mx2: tiles of the second walk (256 4-bit columns each); w4b / w4b_scale are then in ITS order
                          // (PlanWalkLoSteps64)
 };
+
+// Split-K of the segment-level layers (few rows, long K: 3000 for the embedding layer): K is split over up to 24 slices of at least
+// 4 steps - a rule that does not depend on the batch, so an utterance's sums are formed in the same order whatever it is batched
+// with.  Measured on the 256-chunk embedding layer (94 steps, 2 x 4 tiles), GEMM + reduction: 12 steps x 8 slices 23.3 us, 8 x 12
+// 20.4, 6 x 16 19.4, 4 x 24 18.8, 3 x 32 19.3, 2 x 47 25.2 (with the workgroups spread over all XCDs, kernels.hip; while they all sat
+// on two of them more slices only queued: 25.9 / 31.6 / 36.8 us for 8 / 12 / 24 slices).  The number of slices is
+// ceil(ksteps / SplitKStepsPerSlice(ksteps)).
+inline int SplitKStepsPerSlice(int ksteps) {
+  const int per = (ksteps + 23) / 24;
+  return per < 4 ? 4 : per;
+}
 
 // Arms a (start, stop) event pair for the kernels of the NEXT launch_* call of this thread (profiling; see kernels.hip).
 // Pass (nullptr, nullptr) to disarm.
@@ -349,7 +360,27 @@ struct FirstArgs {
   int off[8];               // time offsets in Append() order
   const uint16_t* wc_hi;    // compact weight planes [n_pad][kFirstK] (launch_compact_first)
   const uint16_t* wc_lo;
+  int max_wgs;              // > 0: at most this many workgroups per column group (0: one per CU, at most one per row block).  The
+                            // kernel-level test entry sets it to walk a workgroup past its table window with few rows; the engine
+                            // leaves it 0
 };
+// FirstArgs::grp_src for a batch: chunk b holds source rows [row_offsets[b], row_offsets[b + 1]) and starts at device row
+// dev_off[b]; grp_utt[g] = chunk of 16-row group g or -1.  grp_src receives ngrp x 4 words.
+inline void FillFirstGroupSources(int ngrp, const int32_t* grp_utt, const int32_t* dev_off, const int32_t* row_offsets, int pad_left,
+                                  int pad_right, int32_t* grp_src) {
+  for (int g = 0; g < ngrp; ++g) {
+    int32_t* e = grp_src + 4 * (size_t)g;
+    e[0] = e[1] = e[2] = e[3] = 0;
+    const int b = grp_utt[g];
+    if (b < 0) continue;
+    const int t0 = g * kRowAlign - dev_off[b];
+    const int s0 = row_offsets[b], len = row_offsets[b + 1] - row_offsets[b];
+    e[0] = s0 + t0 - pad_left;
+    e[1] = len + pad_left + pad_right - t0;
+    e[2] = s0;
+    e[3] = s0 + len - 1;
+  }
+}
 // epi_prec selects what the planes epilogue writes: kPrecFp16x3 / kPrecBf16x3 (hi + lo planes), kPrecFp16x3E (fp16 plane +
 // 4-bit residual), kPrecFp16x2 (fp16 plane only); the products are three-pass in every case
 hipError_t launch_tdnn_first(const FirstArgs& a, int epi_prec, hipStream_t s);

@@ -3855,7 +3855,9 @@ hipError_t launch_tdnn_first(const FirstArgs& a, int epi_prec, hipStream_t s) {
     attr_done.fetch_or(1ull << (attr_dev & 63), std::memory_order_release);
   }
   const int ncg = (a.g.n_tiles * kBN + 511) / 512;
-  const int grid = std::max(1, std::min(device_cu_count() / ncg, a.nrows / kFirstRows)) * ncg;
+  int wgs = std::min(device_cu_count() / ncg, a.nrows / kFirstRows);
+  if (a.max_wgs > 0) wgs = std::min(wgs, a.max_wgs);
+  const int grid = std::max(1, wgs) * ncg;
   const char* what;
   switch (epi_prec) {
     case kPrecFp16x3:
@@ -4272,7 +4274,9 @@ __global__ __launch_bounds__(256) void pool_finalise_kernel(const PoolArgs a) {
   asm volatile("" : "+v"(m2));  // keep the product separately rounded: hipcc would contract it into an FMA
   float var = ex2 - m2;
   var = fmaxf(var, a.var_floor);
-  const float sd = __fsqrt_rn(var);
+  // sqrtf is the correctly rounded square root (hipcc's default for fp32); __fsqrt_rn is not: without OCML's rounded operations
+  // the HIP headers define it as the native v_sqrt_f32, one ulp off for one value in nine
+  const float sd = sqrtf(var);
   const long base = (long)b * a.ld;
   const uint16_t mh = to16<F16>(mu), sh = to16<F16>(sd);
   a.out_hi[base + col] = mh;

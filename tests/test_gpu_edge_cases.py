@@ -215,7 +215,7 @@ def test_compressed_feature_archive_through_the_cli(tmp_path, v2):
     (16, (-15, 0, 15), 64),           # the same span with 16-float rows fits
 ])
 def test_first_layer_shapes(feat_dim, offsets, w1):
-    """The layers that read the network input run tdnn_first_kernel where its layout allows (feature rows of <= 32 floats,
+    """The layers that read the network input run tdnn_first_kernel where its layout allows (feature rows of <= 24 floats,
     noff x roundup(dim, 8) <= 128 compact K columns, at most four staged floats per thread and unit) and prep_input + the generic kernel elsewhere:
     every shape against the oracle in the three-pass arithmetic and in the default (fp16mx2 planes + 4-bit residual, or the
     hi-only planes of fp16mx), with chunks in both row regions, and the profile report says which kernel ran."""
@@ -239,7 +239,7 @@ def test_first_layer_shapes(feat_dim, offsets, w1):
     ref = np.stack([ev.compute(u)[0] for u in utts])
     dp = (feat_dim + 7) // 8 * 8
     span = max(offsets) - min(offsets)
-    fits = dp <= 32 and len(offsets) * dp <= 128 and span <= 30 and (64 + span) * dp <= 4 * 512   # kernels.h FirstLayerApplicable
+    fits = dp <= 24 and len(offsets) * dp <= 128 and span <= 30 and (64 + span) * dp <= 4 * 512   # kernels.h FirstLayerApplicable
     for prec, tol in (("fp16x3", 2e-5), ("default", 1e-4)):
         ctx = P.Context(model, precision=P.PRECISIONS[prec])
         out = ctx.forward_batch(feats, offs)

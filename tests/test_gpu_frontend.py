@@ -43,6 +43,33 @@ def test_sliding_cmn_and_vad_selection(ctx, center):
     assert np.array_equal(out2, raw) and np.array_equal(off2, offs)
 
 
+@pytest.mark.parametrize("center", [True, False])
+@pytest.mark.parametrize("feat_dim", [32, 33, 40, 64])
+def test_sliding_cmn_and_vad_selection_of_wide_features(feat_dim, center):
+    """cmn_prefix_kernel cuts the time axis into 1024 / dp segments, dp = 32 for features of up to 32 dimensions and 64 beyond (16
+    segments): both widths at their limits, utterances shorter than, as long as and one longer than the number of segments.  Same
+    oracle and bar as above."""
+    P = H.pkg()
+    net = H.nm.synthesize(H.tiny_config(feat_dim=feat_dim), seed=5)
+    ctx = P.Context(P.Model(raw=net.to_bytes(True), nnet_config="output-node name=output input=tdnn6.affine"))
+    lens = [1, 5, 31, 32, 33, 700]
+    utts = [H.features(80 + i, T, feat_dim) + 3.0 for i, T in enumerate(lens)]
+    vads = [fe.synthetic_vad(i, T) for i, T in enumerate(lens)]
+    vads[0][:] = 1.0
+    raw, offs = H.pack(utts)
+    out, out_off = ctx.frontend(raw, offs, np.concatenate(vads), cmn_window=300, center=center)
+    for i, (u, v) in enumerate(zip(utts, vads)):
+        ref = fe.select_voiced(fe.sliding_cmn(u, 300, center), v)
+        got = out[out_off[i]:out_off[i + 1]]
+        if ref is None:
+            assert got.shape[0] == 0
+            continue
+        assert got.shape == ref.shape, i
+        assert np.abs(got - ref).max() <= 2e-6 * max(1.0, np.abs(u).max()), (i, np.abs(got - ref).max())
+    out2, off2 = ctx.frontend(raw, offs, None, cmn_window=0)
+    assert np.array_equal(out2, raw) and np.array_equal(off2, offs)
+
+
 @pytest.mark.parametrize("chunk", [10000, 150])   # 150: utterances are cut into chunks -> the host round-trip path
 def test_cli_with_fused_front_end(tmp_path, chunk):
     net, line = H.synth_model("v2_xvector")

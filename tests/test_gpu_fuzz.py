@@ -45,10 +45,12 @@ def test_forward_passes_of_the_fuzz_build_are_bit_identical():
 def test_kernel_launch_tests_pass_on_the_fuzz_build():
     """tests/test_gpu_kernels.py - single launches against the bit-exact emulations - on the fuzz build: the 47 launches of the
     256 x 256 kernel (every shape of the 1.5-pass arithmetic among them, whose round-4 race this method finds in 12 of them when
-    it is put back: make fuzz-inject).  All 142 launch tests on the fuzz build: tools/fuzz_schedule.py (48 s; they ran inside the
+    it is put back: make fuzz-inject) and the launches of tdnn_first_kernel (tests/test_gpu_frame_kernels.py: its two wave groups run
+    half a unit apart around one barrier per unit).  All 142 launch tests on the fuzz build: tools/fuzz_schedule.py (48 s; they ran inside the
     suite in round 5, which the driver's time does not leave room for)."""
     _need_fuzz_build()
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(H.ROOT, "tests", "test_gpu_kernels.py"), "-m", "gpu", "-q", "-x",
-                        "-k", "p8 and not bit_stable", "-p", "no:cacheprovider"], env=dict(os.environ, XVEC_LIB=FUZZ_LIB), stdout=subprocess.PIPE,
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(H.ROOT, "tests", "test_gpu_kernels.py"),
+                        os.path.join(H.ROOT, "tests", "test_gpu_frame_kernels.py"), "-m", "gpu", "-q", "-x",
+                        "-k", "(p8 and not bit_stable) or test_first_layer", "-p", "no:cacheprovider"], env=dict(os.environ, XVEC_LIB=FUZZ_LIB), stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:]

@@ -46,8 +46,9 @@ def _planes_value(hi, lo):
     return hi.float() + (lo.float() if lo is not None else 0)
 
 
-def _run_case(prec, epi, rows, n_pad, segs, relu, bn, seed=0, m_valid=None, p8=0):
-    """segs: list of (source index, ld, row_shift, k_len).  Returns (kernel output, reference output)."""
+def _run_case(prec, epi, rows, n_pad, segs, relu, bn, seed=0, m_valid=None, p8=0, ksplit=0):
+    """segs: list of (source index, ld, row_shift, k_len).  Returns (kernel output, reference output).
+    ksplit > 1: split-K over that many slices (the number the engine's rule gives for this K)."""
     torch = _torch()
     P = _pkg()
     g = torch.Generator(device="cpu").manual_seed(seed)
@@ -82,6 +83,7 @@ def _run_case(prec, epi, rows, n_pad, segs, relu, bn, seed=0, m_valid=None, p8=0
     d.relu, d.bn = int(relu), int(bn)
     d.hip_stream = None
     d.p8 = p8
+    d.ksplit = ksplit
 
     # reference on the values the kernel actually sees (quantised planes), accumulated in fp32/fp64
     Xq = [_planes_value(*p).double() for p in Xp]
@@ -280,7 +282,9 @@ def _gmax_bits(plane_abs_max, torch):
     return plane_abs_max.float().view(torch.int32)
 
 
-def _run_mx_case(epi, rows, n_pad, segs, seed=0, variant_rows=None, prec=6, p8=0):
+def _run_mx_case(epi, rows, n_pad, segs, seed=0, variant_rows=None, prec=6, p8=0, out_range=False, ksplit=0):
+    """out_range (epilogue 0): the launch gets a table of the rows of every 16-row group that count for its recorded maximum,
+    drawn like grp_range below (some groups empty), and the expected maxima are those of the rows inside it."""
     torch = _torch()
     P = _pkg()
     g = torch.Generator(device="cpu").manual_seed(seed)
@@ -338,6 +342,7 @@ def _run_mx_case(epi, rows, n_pad, segs, seed=0, variant_rows=None, prec=6, p8=0
     d.relu, d.bn = 1, 1
     d.hip_stream = None
     d.p8 = p8
+    d.ksplit = ksplit
 
     # ---- reference: fp16 x . fp16 w_hi + q4(x / sx) sx . q4((w - w_hi) / sw) sw, in fp64
     Whd = Wh.double()
@@ -386,6 +391,17 @@ def _run_mx_case(epi, rows, n_pad, segs, seed=0, variant_rows=None, prec=6, p8=0
         gm_out = torch.zeros(rows // 16, dtype=torch.int32, device=dev)
         d.out_hi, d.out_lo, d.ldo = oh.data_ptr(), None, n_pad
         d.gmax_out = gm_out.data_ptr()
+        counted = torch.ones(rows // 16, 16, dtype=torch.bool, device=dev)
+        if out_range:
+            rng = np.random.default_rng(seed)
+            first = rng.integers(0, 10, rows // 16).astype(np.int8)
+            last = np.minimum(16, first + rng.integers(0, 17, rows // 16)).astype(np.int8)
+            first[1], last[1] = 5, 5        # nothing counts
+            first[2], last[2] = 0, 16       # everything does
+            rt = torch.from_numpy(np.stack([first, last], 1).copy()).to(dev)
+            d.out_range = rt.data_ptr()
+            r16 = torch.arange(16, device=dev)[None, :]
+            counted = (r16 >= rt[:, :1]) & (r16 < rt[:, 1:])
         if prec in (7, 9):
             o4 = torch.zeros(rows, n_pad // 2, dtype=torch.uint8, device=dev)
             o4s = torch.zeros(rows, (n_pad // 64 + 3) // 4 * 4, dtype=torch.uint8, device=dev)
@@ -393,9 +409,12 @@ def _run_mx_case(epi, rows, n_pad, segs, seed=0, variant_rows=None, prec=6, p8=0
         P.kernel_tdnn_gemm(d)
         torch.cuda.synchronize()
         # the recorded group maxima are those of the fp32 results before the fp16 rounding of the plane
-        want = z.float().abs().reshape(rows // 16, 16, -1).amax(dim=(1, 2))[:run_rows // 16]
+        want = (z.float().abs().reshape(rows // 16, 16, -1) * counted[:, :, None]).amax(dim=(1, 2))[:run_rows // 16]
         got = gm_out.view(torch.float32)[:run_rows // 16]
         assert torch.allclose(got, want, rtol=1e-4, atol=0), (got[:4], want[:4])
+        if out_range:   # a group without a counted row records nothing at all
+            empty = ~counted.any(dim=1)[:run_rows // 16]
+            assert torch.all(gm_out[:run_rows // 16][empty] == 0)
         if prec in (7, 9):   # the output plane with its own 4-bit residual: two to three bits better than fp16 alone
             if prec == 9:
                 return oh.double().cpu().numpy() + _decode_lo4(o4, o4s, n_pad), z.cpu().numpy(), oh.cpu().numpy()
