@@ -500,6 +500,26 @@ xv_status xv_pack_mx_weights64(const float* w, int32_t n_pad, int32_t nseg, cons
 xv_status xv_tile_mx_scales(const uint8_t* natural, int32_t n_pad, int32_t k_len, int32_t epilogue, uint8_t* tiled);
 xv_status xv_kernel_tdnn_gemm(const xv_gemm_desc* d);
 
+/* ---- compressed feature matrices (copy-feats --compress=true) and stage 3 of the recipes, without a model context ------------
+ * Kaldi's CompressedMatrix as csrc/compress.h restates it.  method: 1 automatic ("CM" when rows > 8, else "CM2"), 2 "CM", 3 "CM2",
+ * 5 "CM3"; the fixed-range methods 4, 6 and 7 are XV_ERR_ARG.  An object is what follows the "CM " / "CM2 " / "CM3 " token. */
+/* host only: the size of the object of a rows x cols matrix and its token (a static string) */
+xv_status xv_compressed_size(int32_t rows, int32_t cols, int32_t method, size_t* nbytes, const char** format);
+/* host buffers, blocking: the n matrices feats[row_off[u] .. row_off[u + 1])[cols] (row-major, packed) are compressed on the device;
+ * object u is written to out_bytes + out_off[u], out_off[n + 1] is filled by the call (objects follow each other without gaps;
+ * size the buffer with xv_compressed_size).  nonfinite_flags[u] != 0 (may be NULL): the matrix holds a NaN or an infinity, or
+ * its range is not finite, and its object means nothing - write the floats instead.  A matrix's bytes depend on the matrix and
+ * the method only. */
+xv_status xv_compress_matrices(int device, const float* feats, const int32_t* row_off, int32_t n, int32_t cols, int32_t method,
+                               uint8_t* out_bytes, int64_t* out_off, int32_t* nonfinite_flags);
+/* the kernels' time of one such call in ms: the best of reps runs after one that warms up */
+xv_status xv_compress_kernel_time(int device, const float* feats, const int32_t* row_off, int32_t n, int32_t cols, int32_t method,
+                                  int32_t reps, float* kernel_ms);
+/* apply-cmvn-sliding --norm-vars=false: the kernels of xv_frontend_cmvn_select with every frame kept (cols <= 64); out has the
+ * shape of raw.  raw_off[0] must be 0. */
+xv_status xv_cmvn_sliding(int device, const float* raw, const int32_t* raw_off, int32_t n, int32_t cols, int32_t cmn_window,
+                          int32_t min_cmn_window, int32_t center, float* out);
+
 /* ---- kernel-level entries of the frame-level and small kernels (unit tests; same conventions: device pointers from the caller
  * unless stated, an optional stream, XV_ERR_ARG with a reason for geometry a kernel cannot run, no engine or context) ---------- */
 /* tdnn_first_kernel: the layer(s) that read the network input.  Chunk b holds rows [row_offsets[b], row_offsets[b + 1]) of feats

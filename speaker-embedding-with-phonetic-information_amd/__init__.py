@@ -135,6 +135,7 @@ ABI_SYMBOLS = [
     "xv_plda_estimate", "xv_plda_adapt",
     "xv_mfcc_options_default", "xv_mfcc_num_frames", "xv_mfcc_utt_seed", "xv_mfcc_compute", "xv_mfcc_compute_i16", "xv_mfcc_kernel_time", "xv_vad_energy",
     "xv_reverb_options_default", "xv_reverb_output_length", "xv_wav_reverberate", "xv_reverb_kernel_time", "xv_wave_write", "xv_recognize_wav_pipeline",
+    "xv_compressed_size", "xv_compress_matrices", "xv_compress_kernel_time", "xv_cmvn_sliding",
     "xv_kernel_first_layer", "xv_kernel_prep_input", "xv_kernel_pool_finalise", "xv_kernel_frame_output",
     "xv_wave_read", "xv_wave_free", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
 ]
@@ -1013,6 +1014,74 @@ def reverberate(waves, rirs=None, additive=None, rate=8000.0, device=0, return_i
     if return_int16:
         return [(out[out_off[u]:out_off[u + 1]].copy(), out16[out_off[u]:out_off[u + 1]].copy(), int(clipped[u])) for u in range(n)]
     return [out[out_off[u]:out_off[u + 1]].copy() for u in range(n)]
+
+
+def _pack_matrices(mats, what):
+    import numpy as np
+    ms = [np.ascontiguousarray(m, dtype=np.float32) for m in mats]
+    if any(m.ndim != 2 for m in ms):
+        raise XvError(XV_ERR_ARG, "%s: every matrix must be two-dimensional" % what)
+    widths = {m.shape[1] for m in ms if m.shape[0] > 0}
+    if len(widths) > 1:
+        raise XvError(XV_ERR_ARG, "%s: the matrices of one call share their column count" % what)
+    cols = widths.pop() if widths else 0
+    off = np.zeros(len(ms) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([m.shape[0] if cols else 0 for m in ms])
+    rows = [m for m in ms if m.shape[0] > 0 and cols]
+    packed = np.concatenate(rows, axis=0) if rows else np.zeros((0, max(cols, 1)), np.float32)
+    return np.ascontiguousarray(packed), off, cols
+
+
+def compressed_size(rows, cols, method=1):
+    """(bytes of the object that follows the token, "CM" / "CM2" / "CM3") of a rows x cols matrix: host only."""
+    L = lib()
+    n, fmt = ctypes.c_size_t(0), ctypes.c_char_p()
+    L.xv_compressed_size.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t),
+                                     ctypes.POINTER(ctypes.c_char_p)]
+    _check(L.xv_compressed_size(rows, cols, method, ctypes.byref(n), ctypes.byref(fmt)))
+    return int(n.value), fmt.value.decode()
+
+
+def compress(mats, method=1, device=0, return_flags=False, kernel_time_reps=0):
+    """Kaldi's compressed matrices (copy-feats --compress=true) of a list of float32 matrices that share their column count, on
+    the device.  Returns a list of `bytes`, each what follows the "CM " / "CM2 " / "CM3 " token (compressed_size names the
+    token); with return_flags also the list of flags that mark the matrices holding a value that is not finite, whose bytes
+    mean nothing.  kernel_time_reps > 0: returns the kernels' time in ms instead (xv_compress_kernel_time)."""
+    import numpy as np
+    L = lib()
+    packed, off, cols = _pack_matrices(mats, "compress")
+    n = len(off) - 1
+    common = [device, packed.ctypes.data if packed.size else None, off.ctypes.data, n, cols, method]
+    types = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+    if kernel_time_reps > 0:
+        ms = ctypes.c_float(0)
+        L.xv_compress_kernel_time.argtypes = types + [ctypes.c_int32, ctypes.POINTER(ctypes.c_float)]
+        _check(L.xv_compress_kernel_time(*common, int(kernel_time_reps), ctypes.byref(ms)))
+        return ms.value
+    total = sum(compressed_size(int(off[u + 1] - off[u]), cols, method)[0] for u in range(n))
+    out = np.zeros(max(1, total), dtype=np.uint8)
+    out_off = np.zeros(n + 1, dtype=np.int64)
+    flags = np.zeros(max(1, n), dtype=np.int32)
+    L.xv_compress_matrices.argtypes = types + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _check(L.xv_compress_matrices(*common, out.ctypes.data, out_off.ctypes.data, flags.ctypes.data))
+    assert int(out_off[n]) == total
+    objs = [out[out_off[u]:out_off[u + 1]].tobytes() for u in range(n)]
+    return (objs, [bool(f) for f in flags[:n]]) if return_flags else objs
+
+
+def cmvn_sliding(mats, cmn_window=600, min_cmn_window=100, center=False, device=0):
+    """apply-cmvn-sliding --norm-vars=false on the device, without a model: a list of float32 [frames, dim] matrices in, the
+    same shapes out (the kernels of Context.frontend with every frame kept)."""
+    import numpy as np
+    L = lib()
+    packed, off, cols = _pack_matrices(mats, "cmvn_sliding")
+    n = len(off) - 1
+    out = np.empty_like(packed)
+    L.xv_cmvn_sliding.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                  ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
+    _check(L.xv_cmvn_sliding(device, packed.ctypes.data if packed.size else None, off.ctypes.data, n, max(cols, 1), cmn_window,
+                             min_cmn_window, 1 if center else 0, out.ctypes.data if out.size else None))
+    return [out[off[u]:off[u + 1]].copy() for u in range(n)]
 
 
 def kernel_tdnn_gemm(desc):

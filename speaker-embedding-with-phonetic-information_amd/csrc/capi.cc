@@ -10,6 +10,7 @@
 
 #include "../../include/xvec_hip.h"
 #include "backend.h"
+#include "compress.h"
 #include "engine.h"
 #include "extractor.h"
 #include "feat.h"
@@ -871,6 +872,57 @@ xv_status xv_reverb_kernel_time(int device, const xv_reverb_options* opts, float
       if (r == 1 || (r > 1 && ms < best)) best = ms;
     }
     *kernel_ms = best;
+    return XV_OK;
+  });
+}
+
+// Compressed feature matrices and the model-free sliding CMN: compress.cc.
+xv_status xv_compressed_size(int32_t rows, int32_t cols, int32_t method, size_t* nbytes, const char** format) {
+  if (rows < 0 || cols < 0) return Fail(XV_ERR_ARG, "xv_compressed_size: bad argument");
+  if (!xv::CompressedSize(rows, cols, method, nbytes, format)) return Fail(XV_ERR_ARG, xv::CompressionMethodError(method));
+  g_err.clear();
+  return XV_OK;
+}
+
+xv_status xv_compress_matrices(int device, const float* feats, const int32_t* row_off, int32_t n, int32_t cols, int32_t method,
+                               uint8_t* out_bytes, int64_t* out_off, int32_t* nonfinite_flags) {
+  if (n < 0 || cols < 0 || !row_off || !out_off) return Fail(XV_ERR_ARG, "xv_compress_matrices: bad argument");
+  if (!xv::CompressionMethodError(method).empty()) return Fail(XV_ERR_ARG, xv::CompressionMethodError(method));
+  return Guard([&] {
+    xv::CompressMatrices(device, feats, row_off, n, cols, method, out_bytes, out_off, nonfinite_flags);
+    return XV_OK;
+  });
+}
+
+xv_status xv_compress_kernel_time(int device, const float* feats, const int32_t* row_off, int32_t n, int32_t cols, int32_t method,
+                                  int32_t reps, float* kernel_ms) {
+  if (!feats || !row_off || !kernel_ms || n < 1 || cols < 1 || reps < 1) return Fail(XV_ERR_ARG, "xv_compress_kernel_time: bad argument");
+  if (!xv::CompressionMethodError(method).empty()) return Fail(XV_ERR_ARG, xv::CompressionMethodError(method));
+  return Guard([&] {
+    std::vector<int64_t> off(n + 1);
+    size_t total = 0;
+    for (int u = 0; u < n; ++u) {
+      size_t nb = 0;
+      xv::CompressedSize(row_off[u + 1] - row_off[u], cols, method, &nb, nullptr);
+      total += nb;
+    }
+    std::vector<uint8_t> out(total + 1);
+    float best = 0.f;
+    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
+      float ms = 0.f;
+      xv::CompressMatrices(device, feats, row_off, n, cols, method, out.data(), off.data(), nullptr, &ms);
+      if (r == 1 || (r > 1 && ms < best)) best = ms;
+    }
+    *kernel_ms = best;
+    return XV_OK;
+  });
+}
+
+xv_status xv_cmvn_sliding(int device, const float* raw, const int32_t* raw_off, int32_t n, int32_t cols, int32_t cmn_window,
+                          int32_t min_cmn_window, int32_t center, float* out) {
+  if (n < 0 || cols < 1 || !raw_off) return Fail(XV_ERR_ARG, "xv_cmvn_sliding: bad argument");
+  return Guard([&] {
+    xv::CmvnSliding(device, raw, raw_off, n, cols, cmn_window, min_cmn_window, center != 0, out);
     return XV_OK;
   });
 }

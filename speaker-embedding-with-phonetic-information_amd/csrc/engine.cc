@@ -1748,41 +1748,61 @@ std::string Engine::ProfileReport() {
   return o.str();
 }
 
+FrontEndBytes FrontEndSizes(long raw_rows, int n_utts, int n_out, int dim) {
+  FrontEndBytes z;
+  z.raw = (size_t)raw_rows * dim * 4;
+  z.prefix = (size_t)(raw_rows + n_utts) * dim * 8;
+  z.out = (size_t)n_out * dim * 4;
+  z.tab = Align256(Align256(Align256((size_t)(n_utts + 1) * 4) + (size_t)n_out * 4) + (size_t)n_out * 4);
+  return z;
+}
+
+void FrontEndRun(hipStream_t s, const FrontEndBuffers& b, int dim, const float* raw, const int32_t* raw_off, int n_utts,
+                 const int32_t* sel_row, const int32_t* sel_utt, int n_out, int cmn_window, bool center, int min_window, float* out) {
+  auto check = [](hipError_t e, const char* what) {
+    if (e != hipSuccess) throw EngineError(std::string(what) + ": " + hipGetErrorString(e));
+  };
+  const int D = dim;
+  const long raw_rows = raw_off[n_utts];
+  const size_t o_off = 0, o_row = Align256((size_t)(n_utts + 1) * 4), o_utt = Align256(o_row + (size_t)n_out * 4);
+  const size_t tab = Align256(o_utt + (size_t)n_out * 4);
+  std::vector<uint8_t> host(tab, 0);
+  memcpy(host.data() + o_off, raw_off, (size_t)(n_utts + 1) * 4);
+  memcpy(host.data() + o_row, sel_row, (size_t)n_out * 4);
+  memcpy(host.data() + o_utt, sel_utt, (size_t)n_out * 4);
+  check(hipMemcpyAsync(b.tab, host.data(), tab, hipMemcpyHostToDevice, s), "hipMemcpyAsync(front-end tables)");
+  check(hipMemcpyAsync(b.raw, raw, (size_t)raw_rows * D * 4, hipMemcpyHostToDevice, s), "hipMemcpyAsync(raw feats)");
+  FrontEndArgs fa;
+  fa.raw = (const float*)b.raw;
+  fa.raw_off = (const int32_t*)((const uint8_t*)b.tab + o_off);
+  fa.prefix = (double*)b.prefix;
+  fa.n_utts = n_utts;
+  fa.dim = D;
+  fa.sel_row = (const int32_t*)((const uint8_t*)b.tab + o_row);
+  fa.sel_utt = (const int32_t*)((const uint8_t*)b.tab + o_utt);
+  fa.n_out = n_out;
+  fa.cmn_window = cmn_window;
+  fa.center = center ? 1 : 0;
+  fa.min_window = min_window;
+  fa.out = (float*)b.out;
+  check(launch_frontend(fa, s), "front-end launch");
+  check(hipMemcpyAsync(out, b.out, (size_t)n_out * D * 4, hipMemcpyDeviceToHost, s), "hipMemcpyAsync(front-end out)");
+  check(hipStreamSynchronize(s), "hipStreamSynchronize");
+}
+
 void Engine::FrontEndHost(const float* raw, const int32_t* raw_off, int n_utts, const int32_t* sel_row,
                           const int32_t* sel_utt, int n_out, int cmn_window, bool center, int min_window, float* out) {
   Check(hipSetDevice(device_), "hipSetDevice");
   if (n_out <= 0) return;
   const int D = info_.input_dim;
-  const long raw_rows = raw_off[n_utts];
   Check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-  Ensure(&fe_raw_, (size_t)raw_rows * D * 4, false);
-  Ensure(&fe_prefix_, (size_t)(raw_rows + n_utts) * D * 8, false);
-  Ensure(&fe_out_, (size_t)n_out * D * 4, false);
-  const size_t o_off = 0, o_row = Align256((size_t)(n_utts + 1) * 4), o_utt = Align256(o_row + (size_t)n_out * 4);
-  const size_t tab = Align256(o_utt + (size_t)n_out * 4);
-  Ensure(&fe_tab_, tab, false);
-  std::vector<uint8_t> host(tab, 0);
-  memcpy(host.data() + o_off, raw_off, (size_t)(n_utts + 1) * 4);
-  memcpy(host.data() + o_row, sel_row, (size_t)n_out * 4);
-  memcpy(host.data() + o_utt, sel_utt, (size_t)n_out * 4);
-  Check(hipMemcpyAsync(fe_tab_.p, host.data(), tab, hipMemcpyHostToDevice, stream_), "hipMemcpyAsync(front-end tables)");
-  Check(hipMemcpyAsync(fe_raw_.p, raw, (size_t)raw_rows * D * 4, hipMemcpyHostToDevice, stream_), "hipMemcpyAsync(raw feats)");
-  FrontEndArgs fa;
-  fa.raw = (const float*)fe_raw_.p;
-  fa.raw_off = (const int32_t*)((const uint8_t*)fe_tab_.p + o_off);
-  fa.prefix = (double*)fe_prefix_.p;
-  fa.n_utts = n_utts;
-  fa.dim = D;
-  fa.sel_row = (const int32_t*)((const uint8_t*)fe_tab_.p + o_row);
-  fa.sel_utt = (const int32_t*)((const uint8_t*)fe_tab_.p + o_utt);
-  fa.n_out = n_out;
-  fa.cmn_window = cmn_window;
-  fa.center = center ? 1 : 0;
-  fa.min_window = min_window;
-  fa.out = (float*)fe_out_.p;
-  Check(launch_frontend(fa, stream_), "front-end launch");
-  Check(hipMemcpyAsync(out, fe_out_.p, (size_t)n_out * D * 4, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(front-end out)");
-  Check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+  const FrontEndBytes z = FrontEndSizes(raw_off[n_utts], n_utts, n_out, D);
+  Ensure(&fe_raw_, z.raw, false);
+  Ensure(&fe_prefix_, z.prefix, false);
+  Ensure(&fe_out_, z.out, false);
+  Ensure(&fe_tab_, z.tab, false);
+  const FrontEndBuffers b = {fe_raw_.p, fe_prefix_.p, fe_out_.p, fe_tab_.p};
+  FrontEndRun(stream_, b, D, raw, raw_off, n_utts, sel_row, sel_utt, n_out, cmn_window, center, min_window, out);
 }
 
 void Engine::EnsurePinned(void** p, size_t* have, size_t bytes) {

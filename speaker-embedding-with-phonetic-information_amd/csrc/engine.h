@@ -342,4 +342,19 @@ struct Engine::Plan {
   ~Plan();
 };
 
+// The blocking front-end on device buffers the caller owns, shared by Engine::FrontEndHost and the model-free CmvnSliding
+// (compress.h): uploads the tables and the raw rows, launches the front-end kernels on `s`, downloads the result and waits.
+struct FrontEndBuffers {
+  void* raw;      // FrontEndBytes::raw
+  void* prefix;
+  void* out;
+  void* tab;
+};
+struct FrontEndBytes {
+  size_t raw, prefix, out, tab;
+};
+FrontEndBytes FrontEndSizes(long raw_rows, int n_utts, int n_out, int dim);
+void FrontEndRun(hipStream_t s, const FrontEndBuffers& b, int dim, const float* raw, const int32_t* raw_off, int n_utts,
+                 const int32_t* sel_row, const int32_t* sel_utt, int n_out, int cmn_window, bool center, int min_window, float* out);
+
 }  // namespace xv

@@ -1468,6 +1468,15 @@ void TableWriter::WriteMat(const std::string& key, const Matrix& m) {
   End();
 }
 
+void TableWriter::WriteCompressed(const std::string& key, const char* format, const void* bytes, size_t n) {
+  if (!opts_.binary) throw KioError("a compressed matrix cannot be written to a text table");
+  Begin(key);
+  ark_.Puts(format);
+  ark_.Put(' ');
+  ark_.Write(bytes, n);
+  End();
+}
+
 void TableWriter::WriteInt32(const std::string& key, int32_t v) {
   Begin(key);
   xv::WriteInt32(ark_, opts_.binary, v);

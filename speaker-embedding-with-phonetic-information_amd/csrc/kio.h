@@ -293,6 +293,10 @@ class TableWriter {
   ~TableWriter();
   void WriteVec(const std::string& key, const float* v, int n);
   void WriteMat(const std::string& key, const Matrix& m);
+  // A compressed matrix (compress.h): "key \0B<format> <object>", format "CM", "CM2" or "CM3" and the n bytes that follow the
+  // token.  Binary tables only; the scp line points at the "\0B" like WriteMat's.
+  void WriteCompressed(const std::string& key, const char* format, const void* bytes, size_t n);
+  bool binary() const { return opts_.binary; }
   void WriteInt32(const std::string& key, int32_t v);   // Int32Writer (num_utts.ark)
   void Close();
 
