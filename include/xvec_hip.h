@@ -520,6 +520,27 @@ xv_status xv_compress_kernel_time(int device, const float* feats, const int32_t*
 xv_status xv_cmvn_sliding(int device, const float* raw, const int32_t* raw_off, int32_t n, int32_t cols, int32_t cmn_window,
                           int32_t min_cmn_window, int32_t center, float* out);
 
+/* ---- per-speaker cepstral mean and variance normalisation (compute-cmvn-stats / apply-cmvn), without a model context ----------
+ * Kaldi's transform/cmvn.cc as csrc/cmvn.h restates it. */
+/* host buffers, blocking: Kaldi's statistics of the n_utts matrices feats[row_off[u] .. row_off[u + 1])[cols] (row-major, packed;
+ * row_off[0] = 0), summed on the device in fp64: stats[u] = double[2][cols + 1], row 0 the column sums and the frame count, row 1
+ * the sums of squares and 0.  The order of every sum depends on the matrix's shape only: a matrix's statistics are the same bits
+ * in whatever batch it is.  device_ms (may be NULL): the kernels' time. */
+xv_status xv_cmvn_stats(int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t cols, double* stats,
+                        float* device_ms);
+/* host only: one statistics matrix -> float norm[2][cols], row 0 the offset and row 1 the scale of out = x * scale + offset.
+ * Computed in fp64, stored as float.  A count below 1 is XV_ERR_IO ("Insufficient stats ..."); norm_vars without norm_means is
+ * XV_ERR_ARG.  skip_dims [n_skip]: columns left as they are.  num_floored (may be NULL): variances floored at 1e-20. */
+xv_status xv_cmvn_norm(const double* stats, int32_t cols, int32_t norm_means, int32_t norm_vars, int32_t reverse,
+                       const int32_t* skip_dims, int32_t n_skip, float* norm, int32_t* num_floored);
+/* host buffers, blocking: out[r][d] = feats[r][d] * scale + offset on the device, in fp32 with the product and the sum each rounded
+ * on their own; matrix u takes norm utt_norm[u] (>= 0) of norms[..][2][cols].  out has the shape of feats. */
+xv_status xv_cmvn_apply(int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t cols, const float* norms,
+                        const int32_t* utt_norm, float* out);
+/* the kernels' times of one statistics call and one application in ms: the best of reps runs after one that warms up */
+xv_status xv_cmvn_kernel_time(int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t cols, int32_t reps,
+                              float* stats_ms, float* apply_ms);
+
 /* ---- kernel-level entries of the frame-level and small kernels (unit tests; same conventions: device pointers from the caller
  * unless stated, an optional stream, XV_ERR_ARG with a reason for geometry a kernel cannot run, no engine or context) ---------- */
 /* tdnn_first_kernel: the layer(s) that read the network input.  Chunk b holds rows [row_offsets[b], row_offsets[b + 1]) of feats

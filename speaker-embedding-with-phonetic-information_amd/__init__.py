@@ -136,6 +136,7 @@ ABI_SYMBOLS = [
     "xv_mfcc_options_default", "xv_mfcc_num_frames", "xv_mfcc_utt_seed", "xv_mfcc_compute", "xv_mfcc_compute_i16", "xv_mfcc_kernel_time", "xv_vad_energy",
     "xv_reverb_options_default", "xv_reverb_output_length", "xv_wav_reverberate", "xv_reverb_kernel_time", "xv_wave_write", "xv_recognize_wav_pipeline",
     "xv_compressed_size", "xv_compress_matrices", "xv_compress_kernel_time", "xv_cmvn_sliding",
+    "xv_cmvn_stats", "xv_cmvn_norm", "xv_cmvn_apply", "xv_cmvn_kernel_time",
     "xv_kernel_first_layer", "xv_kernel_prep_input", "xv_kernel_pool_finalise", "xv_kernel_frame_output",
     "xv_wave_read", "xv_wave_free", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
 ]
@@ -1081,6 +1082,68 @@ def cmvn_sliding(mats, cmn_window=600, min_cmn_window=100, center=False, device=
                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
     _check(L.xv_cmvn_sliding(device, packed.ctypes.data if packed.size else None, off.ctypes.data, n, max(cols, 1), cmn_window,
                              min_cmn_window, 1 if center else 0, out.ctypes.data if out.size else None))
+    return [out[off[u]:off[u + 1]].copy() for u in range(n)]
+
+
+def cmvn_stats(feats_list, device=0, kernel_time_reps=0):
+    """Kaldi's CMVN statistics (compute-cmvn-stats) of a list of float32 [frames, cols] matrices that share their column count, summed
+    on the device in fp64: a float64 array [n][2][cols + 1] - row 0 the column sums and the frame count, row 1 the sums of squares and
+    0.  A matrix's statistics do not depend on the batch it is in.  kernel_time_reps > 0: (stats_ms, apply_ms) of xv_cmvn_kernel_time."""
+    import numpy as np
+    L = lib()
+    packed, off, cols = _pack_matrices(feats_list, "cmvn_stats")
+    n = len(off) - 1
+    if cols < 1:
+        raise XvError(XV_ERR_ARG, "cmvn_stats: no matrix with rows and columns")
+    if kernel_time_reps > 0:
+        a, b = ctypes.c_float(0), ctypes.c_float(0)
+        L.xv_cmvn_kernel_time.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+        _check(L.xv_cmvn_kernel_time(device, packed.ctypes.data, off.ctypes.data, n, cols, int(kernel_time_reps), ctypes.byref(a),
+                                     ctypes.byref(b)))
+        return a.value, b.value
+    stats = np.zeros((n, 2, cols + 1), dtype=np.float64)
+    L.xv_cmvn_stats.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                ctypes.c_void_p]
+    _check(L.xv_cmvn_stats(device, packed.ctypes.data if packed.size else None, off.ctypes.data, n, cols, stats.ctypes.data, None))
+    return stats
+
+
+def cmvn_norm(stats, norm_means=True, norm_vars=False, reverse=False, skip_dims=(), return_floored=False):
+    """One [2][cols + 1] statistics matrix -> float32 [2][cols]: row 0 the offset, row 1 the scale of out = x * scale + offset
+    (xv_cmvn_norm: fp64 arithmetic, host only)."""
+    import numpy as np
+    L = lib()
+    st = np.ascontiguousarray(stats, dtype=np.float64)
+    if st.ndim != 2 or st.shape[0] != 2 or st.shape[1] < 2:
+        raise XvError(XV_ERR_ARG, "cmvn_norm: the statistics are a [2][cols + 1] matrix")
+    cols = st.shape[1] - 1
+    skip = np.ascontiguousarray(list(skip_dims), dtype=np.int32)
+    norm = np.zeros((2, cols), dtype=np.float32)
+    floored = ctypes.c_int32(0)
+    L.xv_cmvn_norm.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                               ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
+    _check(L.xv_cmvn_norm(st.ctypes.data, cols, int(bool(norm_means)), int(bool(norm_vars)), int(bool(reverse)),
+                          skip.ctypes.data if skip.size else None, int(skip.size), norm.ctypes.data, ctypes.byref(floored)))
+    return (norm, int(floored.value)) if return_floored else norm
+
+
+def apply_cmvn(feats_list, norms, utt_norm, device=0):
+    """out = x * scale + offset on the device (apply-cmvn): matrix u of feats_list takes norms[utt_norm[u]] ([2][cols] each, as cmvn_norm
+    returns them).  fp32, the product and the sum each rounded on their own.  Returns the list of normalised matrices."""
+    import numpy as np
+    L = lib()
+    packed, off, cols = _pack_matrices(feats_list, "apply_cmvn")
+    n = len(off) - 1
+    nm = np.ascontiguousarray(norms, dtype=np.float32)
+    un = np.ascontiguousarray(utt_norm, dtype=np.int32)
+    if un.shape != (n,) or nm.ndim != 3 or nm.shape[1:] != (2, max(cols, 1)) or (n and (un.min() < 0 or un.max() >= nm.shape[0])):
+        raise XvError(XV_ERR_ARG, "apply_cmvn: norms are [n_norms][2][cols] and utt_norm names one of them per matrix")
+    out = np.empty_like(packed)
+    L.xv_cmvn_apply.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                ctypes.c_void_p, ctypes.c_void_p]
+    _check(L.xv_cmvn_apply(device, packed.ctypes.data if packed.size else None, off.ctypes.data, n, max(cols, 1), nm.ctypes.data,
+                           un.ctypes.data, out.ctypes.data if out.size else None))
     return [out[off[u]:off[u + 1]].copy() for u in range(n)]
 
 

@@ -10,6 +10,7 @@
 
 #include "../../include/xvec_hip.h"
 #include "backend.h"
+#include "cmvn.h"
 #include "compress.h"
 #include "engine.h"
 #include "extractor.h"
@@ -923,6 +924,69 @@ xv_status xv_cmvn_sliding(int device, const float* raw, const int32_t* raw_off, 
   if (n < 0 || cols < 1 || !raw_off) return Fail(XV_ERR_ARG, "xv_cmvn_sliding: bad argument");
   return Guard([&] {
     xv::CmvnSliding(device, raw, raw_off, n, cols, cmn_window, min_cmn_window, center != 0, out);
+    return XV_OK;
+  });
+}
+
+xv_status xv_cmvn_stats(int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t cols, double* stats,
+                        float* device_ms) {
+  if (n_utts < 0 || cols < 1 || !row_off || (n_utts > 0 && !stats)) return Fail(XV_ERR_ARG, "xv_cmvn_stats: bad argument");
+  return Guard([&] {
+    xv::CmvnStats(device, feats, row_off, n_utts, cols, stats, device_ms);
+    return XV_OK;
+  });
+}
+
+xv_status xv_cmvn_norm(const double* stats, int32_t cols, int32_t norm_means, int32_t norm_vars, int32_t reverse,
+                       const int32_t* skip_dims, int32_t n_skip, float* norm, int32_t* num_floored) {
+  return Guard([&] {
+    try {
+      const int floored = xv::CmvnNorm(stats, cols, norm_means != 0, norm_vars != 0, reverse != 0, skip_dims, n_skip, norm);
+      if (num_floored) *num_floored = floored;
+    } catch (const xv::CmvnArgError& e) {
+      return Fail(XV_ERR_ARG, e.what());
+    }
+    return XV_OK;
+  });
+}
+
+xv_status xv_cmvn_apply(int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t cols, const float* norms,
+                        const int32_t* utt_norm, float* out) {
+  if (n_utts < 0 || cols < 1 || !row_off || (n_utts > 0 && (!utt_norm || !norms))) return Fail(XV_ERR_ARG, "xv_cmvn_apply: bad argument");
+  int n_norms = 0;
+  for (int u = 0; u < n_utts; ++u) {
+    if (utt_norm[u] < 0) return Fail(XV_ERR_ARG, "xv_cmvn_apply: negative norm index");
+    n_norms = utt_norm[u] + 1 > n_norms ? utt_norm[u] + 1 : n_norms;
+  }
+  return Guard([&] {
+    xv::CmvnApply(device, feats, row_off, n_utts, cols, norms, n_norms, utt_norm, out);
+    return XV_OK;
+  });
+}
+
+xv_status xv_cmvn_kernel_time(int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t cols, int32_t reps,
+                              float* stats_ms, float* apply_ms) {
+  if (!feats || !row_off || !stats_ms || !apply_ms || n_utts < 1 || cols < 1 || reps < 1)
+    return Fail(XV_ERR_ARG, "xv_cmvn_kernel_time: bad argument");
+  return Guard([&] {
+    std::vector<double> stats((size_t)n_utts * 2 * (cols + 1));
+    std::vector<float> norms((size_t)n_utts * 2 * cols), out((size_t)row_off[n_utts] * cols);
+    std::vector<int32_t> utt_norm(n_utts);
+    float best_s = 0.f, best_a = 0.f;
+    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
+      float ms = 0.f;
+      xv::CmvnStats(device, feats, row_off, n_utts, cols, stats.data(), &ms);
+      if (r == 1 || (r > 1 && ms < best_s)) best_s = ms;
+      if (r == 0)
+        for (int u = 0; u < n_utts; ++u) {
+          utt_norm[u] = u;
+          xv::CmvnNorm(stats.data() + (size_t)u * 2 * (cols + 1), cols, true, true, false, nullptr, 0, norms.data() + (size_t)u * 2 * cols);
+        }
+      xv::CmvnApply(device, feats, row_off, n_utts, cols, norms.data(), n_utts, utt_norm.data(), out.data(), &ms);
+      if (r == 1 || (r > 1 && ms < best_a)) best_a = ms;
+    }
+    *stats_ms = best_s;
+    *apply_ms = best_a;
     return XV_OK;
   });
 }

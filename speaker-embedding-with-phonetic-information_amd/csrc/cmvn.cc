@@ -1,0 +1,368 @@
+#include "cmvn.h"
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "cmvn_kernels.h"
+#include "engine.h"
+#include "kernels.h"
+
+// CmvnNorm is compared with tests/cmvn_ref.py for equality: var = s / n - mean * mean in two roundings, not a fused one
+#pragma clang fp contract(off)
+
+namespace xv {
+namespace {
+
+void Check(hipError_t e, const char* what) {
+  if (e != hipSuccess) throw EngineError(std::string(what) + ": " + hipGetErrorString(e));
+}
+
+struct DevBuf {
+  void* p = nullptr;
+  DevBuf() = default;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  void Alloc(size_t n) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    Check(hipMalloc(&p, n ? n : 8), "hipMalloc");
+  }
+  void Upload(const void* src, size_t n, const char* what) {
+    Alloc(n);
+    if (n) Check(hipMemcpy(p, src, n, hipMemcpyHostToDevice), what);
+  }
+  template <typename T>
+  void Upload(const std::vector<T>& v, const char* what) { Upload(v.data(), v.size() * sizeof(T), what); }
+  template <typename T> T* as() const { return (T*)p; }
+};
+
+struct Events {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  explicit Events(bool on) {
+    if (!on) return;
+    Check(hipEventCreate(&e0), "hipEventCreate");
+    Check(hipEventCreate(&e1), "hipEventCreate");
+  }
+  ~Events() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  void Start() { if (e0) Check(hipEventRecord(e0, nullptr), "hipEventRecord"); }
+  void Stop(float* ms) {
+    if (!e1) return;
+    Check(hipEventRecord(e1, nullptr), "hipEventRecord");
+    Check(hipEventSynchronize(e1), "hipEventSynchronize");
+    Check(hipEventElapsedTime(ms, e0, e1), "hipEventElapsedTime");
+  }
+};
+
+void UseDevice(int device) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
+    throw EngineError("no HIP device available: the CMVN kernels need a gfx950 GPU (there is no CPU path)");
+  if (device < 0 || device >= n) throw EngineError("device index out of range");
+  Check(hipSetDevice(device), "hipSetDevice");
+}
+
+// The batch on the device: row offsets, the float rows (uploaded, or expanded from the stored objects) and the work items of
+// the matrices that take part (keep == nullptr: all of them).
+struct DeviceBatch {
+  DevBuf feats, row_off, item_mat, item_blk, mat_item0, cm, cm_off;
+  std::vector<int32_t> h_item0;
+  int n_items = 0;
+  CmvnArgs args;
+  DeviceBatch(const char* who, const float* host_feats, const int32_t* off, int n, int cols, const CmvnCompressed* c,
+              const int32_t* keep) {
+    if (off[0] != 0) throw KioError(std::string(who) + ": row offsets must start at 0");
+    std::vector<int32_t> mat, blk;
+    h_item0.assign(1, 0);
+    int max_rows = 0;
+    for (int u = 0; u < n; ++u) {
+      const int rows = off[u + 1] - off[u];
+      if (rows < 0) throw KioError(std::string(who) + ": row offsets must not decrease");
+      max_rows = rows > max_rows ? rows : max_rows;
+      if (!keep || keep[u] >= 0)
+        for (int b = 0; b < (rows + kCmvnRowBlock - 1) / kCmvnRowBlock; ++b) {
+          mat.push_back(u);
+          blk.push_back(b);
+        }
+      h_item0.push_back((int32_t)mat.size());
+    }
+    n_items = (int)mat.size();
+    const size_t total = (size_t)off[n] * cols;
+    memset(&args, 0, sizeof args);
+    row_off.Upload(off, (size_t)(n + 1) * 4, "copy row offsets");
+    if (c && total) {
+      if (cols > 64) throw KioError(std::string(who) + ": compressed input with more than 64 columns (the device expansion's limit)");
+      if (!c->bytes || !c->off) throw KioError(std::string(who) + ": null compressed input");
+      for (int u = 0; u < n; ++u) {
+        const int rows = off[u + 1] - off[u];
+        const size_t need = 16 + (size_t)cols * 8 + (size_t)rows * cols;
+        int32_t rc[2];
+        if (c->off[u] < 0 || (size_t)c->off[u] + need > c->nbytes) throw KioError(std::string(who) + ": compressed object out of bounds");
+        memcpy(rc, c->bytes + c->off[u] + 8, 8);
+        if (rc[0] != rows || rc[1] != cols) throw KioError(std::string(who) + ": compressed object does not have the shape of its matrix");
+      }
+      feats.Alloc(total * 4);
+      cm.Upload(c->bytes, c->nbytes, "copy compressed features");
+      cm_off.Upload(c->off, (size_t)n * 8, "copy object offsets");
+      CmExpandArgs ca;
+      ca.cm = cm.as<uint8_t>();
+      ca.cm_off = cm_off.as<int64_t>();
+      ca.raw_off = row_off.as<int32_t>();
+      ca.n_utts = n;
+      ca.dim = cols;
+      ca.max_rows = max_rows;
+      ca.out = feats.as<float>();
+      Check(launch_cm_expand(ca, nullptr), "cm_expand launch");
+    } else {
+      if (total && !host_feats) throw KioError(std::string(who) + ": null input");
+      feats.Upload(host_feats, total * 4, "copy features");
+    }
+    item_mat.Upload(mat, "copy work items");
+    item_blk.Upload(blk, "copy work items");
+    mat_item0.Upload(h_item0, "copy work items");
+    args.feats = feats.as<float>();
+    args.row_off = row_off.as<int32_t>();
+    args.n = n;
+    args.cols = cols;
+    args.item_mat = item_mat.as<int32_t>();
+    args.item_blk = item_blk.as<int32_t>();
+    args.n_items = n_items;
+    args.mat_item0 = mat_item0.as<int32_t>();
+  }
+};
+
+}  // namespace
+
+bool ParseSkipDims(const std::string& value, std::vector<int>* dims) {
+  dims->clear();
+  if (value.empty()) return true;
+  size_t a = 0;
+  for (;;) {
+    const size_t b = value.find(':', a);
+    const std::string t = value.substr(a, b == std::string::npos ? std::string::npos : b - a);
+    if (t.empty() || t.size() > 6 || t.find_first_not_of("0123456789") != std::string::npos) return false;
+    dims->push_back(atoi(t.c_str()));
+    if (b == std::string::npos) return true;
+    a = b + 1;
+  }
+}
+
+int CmvnNorm(const double* stats, int cols, bool norm_means, bool norm_vars, bool reverse, const int* skip_dims, int n_skip,
+             float* norm) {
+  if (!stats || !norm || cols < 1 || n_skip < 0 || (n_skip && !skip_dims)) throw CmvnArgError("cmvn-norm: bad argument");
+  if (norm_vars && !norm_means) throw CmvnArgError("You cannot normalize the variance but not the mean.");
+  const double count = stats[cols];
+  if (!(count >= 1.0)) {
+    char buf[128];
+    snprintf(buf, sizeof buf, "Insufficient stats for cepstral mean and variance normalization: count = %g", count);
+    throw KioError(buf);
+  }
+  std::vector<char> skip((size_t)cols, 0);
+  for (int i = 0; i < n_skip; ++i) {
+    if (skip_dims[i] < 0 || skip_dims[i] >= cols)
+      throw CmvnArgError("skip-dims: dimension " + std::to_string(skip_dims[i]) + " is out of range for " + std::to_string(cols) + " columns");
+    skip[skip_dims[i]] = 1;
+  }
+  int floored = 0;
+  for (int d = 0; d < cols; ++d) {
+    if (!norm_means) {
+      norm[d] = 0.f;
+      norm[cols + d] = 1.f;
+      continue;
+    }
+    const double s0 = skip[d] ? 0.0 : stats[d], s1 = skip[d] ? count : stats[cols + 1 + d];
+    const double mean = s0 / count;
+    double scale = 1.0, offset = reverse ? mean : -mean;
+    if (norm_vars) {
+      const double sq = s1 / count;
+      const double m2 = mean * mean;
+      double var = sq - m2;
+      if (var < 1.0e-20) {
+        var = 1.0e-20;
+        ++floored;
+      }
+      if (reverse) {
+        scale = sqrt(var);
+      } else {
+        scale = 1.0 / sqrt(var);
+        const double ms = mean * scale;
+        offset = -ms;
+      }
+    }
+    norm[d] = (float)offset;
+    norm[cols + d] = (float)scale;
+  }
+  return floored;
+}
+
+void CmvnStats(int device, const float* feats, const int32_t* row_off, int n, int cols, double* stats, float* device_ms,
+               const CmvnCompressed* cm) {
+  if (device_ms) *device_ms = 0.f;
+  if (n < 0 || cols < 1 || !row_off || (n > 0 && !stats)) throw KioError("cmvn-stats: bad argument");
+  if (n == 0) return;
+  UseDevice(device);
+  DeviceBatch b("cmvn-stats", feats, row_off, n, cols, cm, nullptr);
+  DevBuf partial, d_stats;
+  partial.Alloc((size_t)b.n_items * 2 * cols * 8);
+  const size_t sbytes = (size_t)n * 2 * (cols + 1) * 8;
+  d_stats.Alloc(sbytes);
+  b.args.partial = partial.as<double>();
+  b.args.stats = d_stats.as<double>();
+  Events ev(device_ms != nullptr);
+  ev.Start();
+  Check(launch_cmvn_stats(b.args, nullptr), "cmvn_stats launch");
+  ev.Stop(device_ms);
+  Check(hipMemcpy(stats, d_stats.p, sbytes, hipMemcpyDeviceToHost), "copy statistics");
+}
+
+void CmvnApply(int device, const float* feats, const int32_t* row_off, int n, int cols, const float* norms, int n_norms,
+               const int32_t* utt_norm, float* out, float* device_ms, const CmvnCompressed* cm) {
+  if (device_ms) *device_ms = 0.f;
+  if (n < 0 || cols < 1 || !row_off || n_norms < 0 || (n > 0 && !utt_norm)) throw KioError("cmvn-apply: bad argument");
+  if (n == 0 || row_off[n] == 0) return;
+  if (!out) throw KioError("cmvn-apply: null output");
+  for (int u = 0; u < n; ++u)
+    if (utt_norm[u] < -1 || utt_norm[u] >= n_norms) throw KioError("cmvn-apply: a matrix names a norm that is not in the table");
+  if (n_norms > 0 && !norms) throw KioError("cmvn-apply: null norm table");
+  UseDevice(device);
+  DeviceBatch b("cmvn-apply", feats, row_off, n, cols, cm, utt_norm);
+  if (b.n_items == 0) return;
+  const size_t bytes = (size_t)row_off[n] * cols * 4;
+  DevBuf d_norms, d_utt_norm, d_out;
+  d_norms.Upload(norms, (size_t)n_norms * 2 * cols * 4, "copy norms");
+  d_utt_norm.Upload(utt_norm, (size_t)n * 4, "copy norm indices");
+  d_out.Alloc(bytes);
+  b.args.norms = d_norms.as<float>();
+  b.args.utt_norm = d_utt_norm.as<int32_t>();
+  b.args.out = d_out.as<float>();
+  Events ev(device_ms != nullptr);
+  ev.Start();
+  Check(launch_cmvn_apply(b.args, nullptr), "cmvn_apply launch");
+  ev.Stop(device_ms);
+  // rows of the matrices that were left out hold nothing: only the others are copied back
+  Check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+  for (int u = 0; u < n; ++u) {
+    if (utt_norm[u] < 0 || row_off[u + 1] == row_off[u]) continue;
+    int v = u;
+    while (v + 1 < n && utt_norm[v + 1] >= 0) ++v;   // one copy per run of kept matrices
+    const size_t o = (size_t)row_off[u] * cols, e = (size_t)row_off[v + 1] * cols;
+    Check(hipMemcpy(out + o, d_out.as<float>() + o, (e - o) * 4, hipMemcpyDeviceToHost), "copy normalised features");
+    u = v;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct FeatBatchReader::Impl {
+  int64_t max_frames;
+  bool allow_cm;
+  std::unique_ptr<MatrixTableIndexer> indexer;
+  std::unique_ptr<SequentialMatrixReader> seq;
+  FileMapper mapper;
+  Input in;
+  std::string in_path;
+  // the matrix that did not fit the batch before
+  bool held = false;
+  std::string held_key;
+  Matrix held_m;
+  bool done = false;
+
+  // the next readable matrix with rows; false at the end
+  bool Read(std::string* key, Matrix* m, std::vector<Problem>* problems) {
+    for (;;) {
+      std::string err;
+      if (indexer) {
+        MatrixTableIndexer::Entry e;
+        if (!indexer->Next(&e)) return false;
+        *key = e.key;
+        if (!e.error.empty()) {
+          err = e.error;
+        } else {
+          try {
+            *m = Matrix();
+            if (!mapper.View(e, m, allow_cm)) ReadIndexedMatrix(e, &in, &in_path, m);
+          } catch (const std::exception& ex) {
+            err = ex.what();
+          }
+        }
+      } else {
+        *m = Matrix();
+        if (!seq->Next(key, m, &err)) return false;
+      }
+      if (!err.empty()) {
+        problems->push_back(Problem{*key, err});
+        continue;
+      }
+      if (m->rows == 0 || m->cols == 0) {
+        problems->push_back(Problem{*key, ""});
+        continue;
+      }
+      if (m->cm && m->cols > 64) {   // wider than the device expansion takes: the floats are made here
+        Matrix full;
+        ExpandCompressedView(*m, &full);
+        *m = std::move(full);
+      }
+      return true;
+    }
+  }
+};
+
+FeatBatchReader::FeatBatchReader(const std::string& rspecifier, int64_t max_frames, bool allow_compressed) : impl_(new Impl) {
+  impl_->max_frames = max_frames;
+  impl_->allow_cm = allow_compressed;
+  impl_->indexer.reset(new MatrixTableIndexer(rspecifier));
+  if (!impl_->indexer->usable()) {
+    impl_->indexer.reset();
+    impl_->seq.reset(new SequentialMatrixReader(rspecifier));
+  }
+}
+
+FeatBatchReader::~FeatBatchReader() {}
+
+bool FeatBatchReader::Next(Batch* b, std::vector<Problem>* problems) {
+  Impl& I = *impl_;
+  *b = Batch();
+  b->row_off.assign(1, 0);
+  if (I.done) return false;
+  for (;;) {
+    std::string key;
+    Matrix m;
+    if (I.held) {
+      key = std::move(I.held_key);
+      m = std::move(I.held_m);
+      I.held = false;
+    } else if (!I.Read(&key, &m, problems)) {
+      I.done = true;
+      break;
+    }
+    const bool cm = m.cm != nullptr;
+    if (!b->keys.empty() && (m.cols != b->cols || cm != b->compressed)) {   // a batch has one width and one kind
+      I.held = true;
+      I.held_key = std::move(key);
+      I.held_m = std::move(m);
+      break;
+    }
+    b->cols = m.cols;
+    b->compressed = cm;
+    b->keys.push_back(std::move(key));
+    if (cm) {
+      b->cm_off.push_back((int64_t)b->cm.size());
+      b->cm.insert(b->cm.end(), m.cm, m.cm + m.cm_bytes);
+    } else {
+      const size_t at = b->feats.size(), count = (size_t)m.rows * m.cols;
+      b->feats.resize(at + count);
+      memcpy(b->feats.data() + at, m.Data(), count * 4);   // (a view of a mapped archive has the archive's alignment)
+    }
+    b->max_rows = m.rows > b->max_rows ? m.rows : b->max_rows;
+    b->row_off.push_back(b->row_off.back() + m.rows);
+    if (b->row_off.back() >= I.max_frames) break;
+  }
+  return !b->keys.empty();
+}
+
+}  // namespace xv

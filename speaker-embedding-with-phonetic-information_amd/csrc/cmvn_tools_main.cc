@@ -1,18 +1,31 @@
 // apply-cmvn-sliding / select-voiced-frames - drop-in command lines for stage 3 of the recipes (egs/sre/v2/run_sre10.sh:161-166
 // through local/nnet3/xvector/prepare_feats_for_egs.sh:66-71; v3-v5: sid/nnet3_cvector/cvector/prepare_feats.sh:88-92 and
-// :132-137); one executable, dispatching on its name:
+// :132-137) - and compute-cmvn-stats / apply-cmvn, the per-speaker normalisation in front of the acoustic-model path
+// (steps/compute_cmvn_stats.sh:104; sid/nnet3_cvector/am/extract_bn.sh:59).  One executable, dispatching on its name:
 //   apply-cmvn-sliding [--norm-vars=false --center --cmn-window --min-cmn-window] <feats-rspecifier> <feats-wspecifier>
 //   select-voiced-frames <feats-rspecifier> <vad-rspecifier> <feats-wspecifier>
+//   compute-cmvn-stats [--spk2utt=<rspecifier>] [--binary=true] <feats-rspecifier> (<stats-wspecifier>|<stats-wxfilename>)
+//   apply-cmvn [--utt2spk=<rspecifier>] [--norm-means=true] [--norm-vars=false] [--skip-dims=a:b:c] [--reverse=false]
+//              (<stats-rspecifier>|<stats-rxfilename>) <feats-rspecifier> <feats-wspecifier>
+// compute-cmvn-stats sums on the device (cmvn.h: fp64, an order that depends on the matrix alone) and adds the utterances of a
+// speaker on the host in spk2utt order; apply-cmvn computes the norms on the host and runs the affine map on the device.  Both
+// read the features ahead in batches, stored "CM" objects going up as they are, and fail without a GPU (exit 255); only
+// apply-cmvn --norm-means=false, which copies the features through, opens no device.
 // apply-cmvn-sliding runs the device front-end's sliding-CMN kernels (compress.h CmvnSliding: the same launch path as the
 // extractor's fused pipeline, fuse_pipe.h) and takes the options that pipeline recognises; without a GPU it fails (exit 255).
 // select-voiced-frames is a row gather on the host and opens no device; its warnings are the fused front-end's
 // (table_extract.cc), so that the two paths say the same.
 #include <stdlib.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
+#include <map>
+#include <unordered_map>
+
 #include "cli.h"
+#include "cmvn.h"
 #include "compress.h"
 #include "kio.h"
 
@@ -126,10 +139,274 @@ int SelectVoicedFrames(const std::vector<std::string>& pos) {
   return num_done != 0 ? 0 : 1;
 }
 
+
+constexpr int64_t kBatchFrames = 1 << 18;   // frames read ahead per device call of the two per-speaker tools
+
+// "ark:..." / "scp,p:..." is a table; anything else a file (Kaldi's ClassifyWspecifier / ClassifyRspecifier, as far as needed)
+bool IsTable(const std::string& spec) {
+  const size_t colon = spec.find(':');
+  if (colon == std::string::npos) return false;
+  const std::string kind = spec.substr(0, spec.find_first_of(",:"));
+  return kind == "ark" || kind == "scp";
+}
+
+void ReportProblems(const std::vector<xv::FeatBatchReader::Problem>& problems, long* num_err) {
+  for (const auto& p : problems) {
+    if (p.what.empty()) XWARN("Empty feature matrix for utterance " << p.key);
+    else XWARN("Failed to read features for key " << p.key << ": " << p.what);
+    ++*num_err;
+  }
+}
+
+struct StatsOptions {
+  std::string spk2utt;
+  bool binary = true;
+  int device = -1;
+};
+
+int ComputeCmvnStats(const StatsOptions& o, const std::vector<std::string>& pos) {
+  const int dev = xv::PickDevice(o.device);
+  const bool table = IsTable(pos[1]);
+  if (!o.spk2utt.empty() && !table) throw xv::KioError("--spk2utt option not compatible with wxfilename as output (did you forget ark:?)");
+  std::vector<xv::TokenList> spk2utt;
+  if (!o.spk2utt.empty()) spk2utt = xv::ReadTokenVectorTable(o.spk2utt);
+  std::unique_ptr<xv::TableWriter> writer;
+  if (table) writer.reset(new xv::TableWriter(pos[1]));
+  xv::FeatBatchReader reader(pos[0], kBatchFrames, true);
+  long num_done = 0, num_err = 0;
+  std::unordered_map<std::string, std::vector<double>> utt_stats;   // --spk2utt: looked up by key afterwards
+  std::vector<double> global;
+  xv::FeatBatchReader::Batch b;
+  std::vector<xv::FeatBatchReader::Problem> problems;
+  std::vector<double> stats;
+  for (bool more = true; more;) {
+    problems.clear();
+    more = reader.Next(&b, &problems);
+    ReportProblems(problems, &num_err);
+    if (!more) break;
+    const int n = (int)b.keys.size(), w = b.cols + 1;
+    stats.assign((size_t)n * 2 * w, 0.0);
+    const xv::CmvnCompressed cm = b.View();
+    xv::CmvnStats(dev, b.feats.data(), b.row_off.data(), n, b.cols, stats.data(), nullptr, b.compressed ? &cm : nullptr);
+    for (int u = 0; u < n; ++u) {
+      const double* st = stats.data() + (size_t)u * 2 * w;
+      if (!spk2utt.empty()) {
+        utt_stats.emplace(b.keys[u], std::vector<double>(st, st + 2 * w));   // the first entry of a key wins
+      } else if (table) {
+        writer->WriteMatDouble(b.keys[u], st, 2, w);
+        ++num_done;
+      } else {
+        if (global.empty()) global.assign(2 * (size_t)w, 0.0);
+        if (global.size() != 2 * (size_t)w) throw xv::KioError("Dimension mismatch: utterance " + b.keys[u] + " has " + std::to_string(b.cols) + " columns");
+        for (int i = 0; i < 2 * w; ++i) global[i] += st[i];
+        ++num_done;
+      }
+    }
+  }
+  if (!spk2utt.empty()) {
+    for (const xv::TokenList& spk : spk2utt) {
+      std::vector<double> acc;
+      for (const std::string& utt : spk.tokens) {
+        auto it = utt_stats.find(utt);
+        if (it == utt_stats.end()) {
+          XWARN("Did not find features for utterance " << utt);
+          ++num_err;
+          continue;
+        }
+        if (acc.empty()) acc.assign(it->second.size(), 0.0);
+        if (acc.size() != it->second.size()) throw xv::KioError("Dimension mismatch among the utterances of speaker " + spk.key);
+        for (size_t i = 0; i < acc.size(); ++i) acc[i] += it->second[i];   // spk2utt list order, fp64
+        ++num_done;
+      }
+      if (acc.empty()) {
+        XWARN("No stats accumulated for speaker " << spk.key);
+        continue;
+      }
+      writer->WriteMatDouble(spk.key, acc.data(), 2, (int)(acc.size() / 2));
+    }
+  } else if (!table && !global.empty()) {
+    xv::Output out;
+    out.Open(pos[1]);
+    if (o.binary) out.Write("\0B", 2);
+    xv::WriteMatrixDouble(out, o.binary, global.data(), 2, (int)(global.size() / 2));
+    if (out.Close() != 0) throw xv::KioError("error closing output " + pos[1]);
+    XLOG("Wrote global CMVN stats to " << pos[1]);
+  }
+  if (writer) writer->Close();
+  XLOG("Done accumulating CMVN stats for " << num_done << " utterances; " << num_err << " had errors.");
+  return num_done != 0 ? 0 : 1;
+}
+
+struct ApplyOptions {
+  std::string utt2spk;
+  bool norm_means = true, norm_vars = false, reverse = false;
+  std::vector<int> skip_dims;
+  int device = -1;
+};
+
+int ApplyCmvn(const ApplyOptions& o, const std::vector<std::string>& pos) {
+  if (o.norm_vars && !o.norm_means) throw xv::KioError("You cannot normalize the variance but not the mean.");
+  const bool per_key = IsTable(pos[0]);
+  std::unordered_map<std::string, std::string> utt2spk;
+  if (!o.utt2spk.empty()) utt2spk = xv::ReadTokenTable(o.utt2spk);
+  std::unique_ptr<xv::RandomAccessDoubleMatrixReader> table;
+  xv::RandomAccessDoubleMatrixReader::Value global;
+  if (per_key) {
+    table.reset(new xv::RandomAccessDoubleMatrixReader(pos[0]));
+  } else {
+    xv::Input in;
+    in.Open(pos[0]);
+    const bool binary = xv::ReadBinaryHeader(in);
+    xv::ReadMatrixDouble(in, binary, &global.rows, &global.cols, &global.data);
+  }
+  const int dev = o.norm_means ? xv::PickDevice(o.device) : -1;
+  xv::TableWriter writer(pos[2]);
+  // --norm-means=false copies the features through: floats from the host readers, no device
+  xv::FeatBatchReader reader(pos[1], kBatchFrames, o.norm_means);
+  long num_done = 0, num_err = 0;
+  xv::FeatBatchReader::Batch b;
+  std::vector<xv::FeatBatchReader::Problem> problems;
+  std::vector<float> norms, out;
+  std::vector<int32_t> utt_norm;
+  // A speaker's (or the global) norm is computed once, and its flooring warning given once, however many batches its utterances
+  // are spread over.  Per-utterance statistics are met once each and are not kept.
+  const bool keep = !per_key || !o.utt2spk.empty();
+  std::map<std::string, std::vector<float>> kept_norm;
+  for (bool more = true; more;) {
+    problems.clear();
+    more = reader.Next(&b, &problems);
+    ReportProblems(problems, &num_err);
+    if (!more) break;
+    const int n = (int)b.keys.size();
+    norms.clear();
+    utt_norm.assign(n, -1);
+    std::map<std::string, int> norm_of;   // statistics key -> its norm in this batch
+    for (int u = 0; u < n && o.norm_means; ++u) {
+      std::string skey = b.keys[u];
+      if (per_key && !o.utt2spk.empty()) {
+        auto it = utt2spk.find(skey);
+        if (it == utt2spk.end()) {   // a key the map does not have finds no statistics
+          XWARN("No normalization statistics available for key " << b.keys[u] << ", producing no output for this utterance");
+          ++num_err;
+          continue;
+        }
+        skey = it->second;
+      }
+      if (!per_key) skey.clear();
+      auto known = norm_of.find(skey);
+      if (known != norm_of.end()) {
+        utt_norm[u] = known->second;
+        continue;
+      }
+      if (per_key && !table->HasKey(skey)) {
+        XWARN("No normalization statistics available for key " << b.keys[u] << ", producing no output for this utterance");
+        ++num_err;
+        continue;
+      }
+      const xv::RandomAccessDoubleMatrixReader::Value& st = per_key ? table->Get(skey) : global;
+      if (st.rows != 2 || st.cols != b.cols + 1) {
+        std::ostringstream m;
+        m << "Dimension mismatch: cmvn stats have dimension " << st.rows << "x" << st.cols << ", feats have dimension " << b.cols
+          << " (utterance " << b.keys[u] << ")";
+        throw xv::KioError(m.str());
+      }
+      const int k = (int)(norms.size() / (2 * (size_t)b.cols));
+      norms.resize(norms.size() + 2 * (size_t)b.cols);
+      float* norm = norms.data() + (size_t)k * 2 * b.cols;
+      auto seen = keep ? kept_norm.find(skey) : kept_norm.end();
+      if (seen != kept_norm.end()) {   // same statistics, same column count (checked above): same norm
+        std::copy(seen->second.begin(), seen->second.end(), norm);
+      } else {
+        const int floored = xv::CmvnNorm(st.data.data(), b.cols, o.norm_means, o.norm_vars, o.reverse, o.skip_dims.data(),
+                                         (int)o.skip_dims.size(), norm);
+        if (floored) XWARN("Flooring cepstral variance from a value below 1.0e-20 to 1.0e-20 in " << floored << " dimension(s) (statistics of " << (skey.empty() ? pos[0] : skey) << ")");
+        if (keep) kept_norm.emplace(skey, std::vector<float>(norm, norm + 2 * (size_t)b.cols));
+      }
+      norm_of.emplace(skey, k);
+      utt_norm[u] = k;
+    }
+    const float* result = b.feats.data();
+    if (o.norm_means) {
+      out.resize((size_t)b.row_off[n] * b.cols);
+      const xv::CmvnCompressed cm = b.View();
+      xv::CmvnApply(dev, b.feats.data(), b.row_off.data(), n, b.cols, norms.data(), (int)(norms.size() / (2 * (size_t)b.cols)),
+                    utt_norm.data(), out.data(), nullptr, b.compressed ? &cm : nullptr);
+      result = out.data();
+    }
+    for (int u = 0; u < n; ++u) {
+      if (o.norm_means && utt_norm[u] < 0) continue;
+      xv::Matrix m;
+      m.rows = b.row_off[u + 1] - b.row_off[u];
+      m.cols = b.cols;
+      m.data.assign(result + (size_t)b.row_off[u] * b.cols, result + (size_t)b.row_off[u + 1] * b.cols);
+      writer.WriteMat(b.keys[u], m);
+      ++num_done;
+    }
+  }
+  writer.Close();
+  XLOG("Applied cepstral mean " << (o.norm_vars ? "and variance " : "") << "normalization to " << num_done << " utterances, errors on "
+                                << num_err);
+  return num_done != 0 ? 0 : 1;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-  const bool select = xv::ProgramName(argv[0]).find("select") != std::string::npos;
+  const std::string prog = xv::ProgramName(argv[0]);
+  const bool select = prog.find("select") != std::string::npos;
+  const bool stats = prog.find("compute-cmvn-stats") != std::string::npos;
+  const bool apply = !stats && !select && prog.find("sliding") == std::string::npos && prog.find("apply-cmvn") != std::string::npos;
+  auto dashes = [](std::string n) {
+    for (char& c : n)
+      if (c == '_') c = '-';
+    return n;
+  };
+  if (stats) {
+    StatsOptions so;
+    xv::CliTool t;
+    t.usage = "Compute cepstral mean and variance normalization statistics, per utterance or, with --spk2utt, per speaker;\n"
+              "with a file instead of a table as the output, one global matrix.\n"
+              "Usage: compute-cmvn-stats [options] <feats-rspecifier> (<stats-wspecifier>|<stats-wxfilename>)\n"
+              "Options: --spk2utt=<rspecifier> --binary (true) --device=<gpu>\n"
+              "Not built (refused): --weights.\n";
+    t.config_file = false;
+    t.set = [&](const std::string& name, const std::string& val) {
+      const std::string n = dashes(name);
+      if (n == "verbose" || n == "print-args" || n == "config") return xv::OptionResult::kOk;
+      if (n == "spk2utt") so.spk2utt = val;
+      else if (n == "binary") so.binary = xv::ToBool(n, val);
+      else if (n == "device") so.device = xv::ToInt(n, val);
+      else if (n == "weights") throw xv::KioError("--weights is not built: no script of the recipes passes it");
+      else return xv::OptionResult::kUnknown;
+      return xv::OptionResult::kOk;
+    };
+    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : ComputeCmvnStats(so, pos); };
+    return xv::CliMain(argc, argv, t);
+  }
+  if (apply) {
+    ApplyOptions ao;
+    xv::CliTool t;
+    t.usage = "Apply cepstral mean and (optionally) variance normalization, per utterance or per speaker (--utt2spk), or with\n"
+              "one global statistics matrix.\n"
+              "Usage: apply-cmvn [options] (<cmvn-stats-rspecifier>|<cmvn-stats-rxfilename>) <feats-rspecifier> <feats-wspecifier>\n"
+              "Options: --utt2spk=<rspecifier> --norm-means (true) --norm-vars (false) --skip-dims=a:b:c --reverse (false) --device=<gpu>\n";
+    t.config_file = false;
+    t.set = [&](const std::string& name, const std::string& val) {
+      const std::string n = dashes(name);
+      if (n == "verbose" || n == "print-args" || n == "config") return xv::OptionResult::kOk;
+      if (n == "utt2spk") ao.utt2spk = val;
+      else if (n == "norm-means") ao.norm_means = xv::ToBool(n, val);
+      else if (n == "norm-vars") ao.norm_vars = xv::ToBool(n, val);
+      else if (n == "reverse") ao.reverse = xv::ToBool(n, val);
+      else if (n == "device") ao.device = xv::ToInt(n, val);
+      else if (n == "skip-dims") {
+        if (!xv::ParseSkipDims(val, &ao.skip_dims)) throw xv::KioError("Bad --skip-dims option (should be colon-separated list of integers)");
+      } else return xv::OptionResult::kUnknown;
+      return xv::OptionResult::kOk;
+    };
+    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : ApplyCmvn(ao, pos); };
+    return xv::CliMain(argc, argv, t);
+  }
   CmvnOptions o;
   xv::CliTool tool;
   tool.usage = select ? "Select a subset of frames of the input files, based on the output of\n"

@@ -1410,6 +1410,54 @@ const std::vector<float>& RandomAccessVectorReader::Value(const std::string& key
   return e.v;
 }
 
+RandomAccessDoubleMatrixReader::RandomAccessDoubleMatrixReader(const std::string& rspecifier) {
+  RspecifierOptions o = ParseRspecifier(rspecifier);
+  Input in;
+  in.Open(o.rxfilename);
+  std::string key;
+  while (ReadKey(in, &key)) {
+    Entry e;
+    if (o.is_scp) {
+      std::string rx;
+      int c;
+      while ((c = in.Get()) >= 0 && c != '\n') rx.push_back((char)c);
+      e.rx = Trim(rx);
+    } else {
+      const bool binary = ReadBinaryHeader(in);
+      ReadMatrixDouble(in, binary, &e.v.rows, &e.v.cols, &e.v.data);
+      e.loaded = true;
+    }
+    index_.emplace(key, (int)entries_.size());   // the first entry of a key wins
+    entries_.push_back(std::move(e));
+  }
+}
+
+const RandomAccessDoubleMatrixReader::Value& RandomAccessDoubleMatrixReader::Get(const std::string& key) {
+  auto it = index_.find(key);
+  if (it == index_.end()) throw KioError("key not found in table: " + key);
+  Entry& e = entries_[it->second];
+  if (!e.loaded) {
+    std::string path;
+    const long off = SplitOffset(e.rx, &path);
+    if (off >= 0) {
+      if (!(data_in_.IsOpen() && data_path_ == path)) {
+        data_in_.Open(path);
+        data_path_ = path;
+      }
+      data_in_.Seek(off);
+      const bool binary = ReadBinaryHeader(data_in_);
+      ReadMatrixDouble(data_in_, binary, &e.v.rows, &e.v.cols, &e.v.data);
+    } else {
+      Input in;
+      in.Open(e.rx);
+      const bool binary = ReadBinaryHeader(in);
+      ReadMatrixDouble(in, binary, &e.v.rows, &e.v.cols, &e.v.data);
+    }
+    e.loaded = true;
+  }
+  return e.v;
+}
+
 void RandomAccessVectorReader::Forget(const std::string& key) {
   const int i = Find(key);
   if (i < 0) return;
@@ -1465,6 +1513,12 @@ void TableWriter::WriteVec(const std::string& key, const float* v, int n) {
 void TableWriter::WriteMat(const std::string& key, const Matrix& m) {
   Begin(key);
   WriteMatrix(ark_, opts_.binary, m);
+  End();
+}
+
+void TableWriter::WriteMatDouble(const std::string& key, const double* m, int rows, int cols) {
+  Begin(key);
+  WriteMatrixDouble(ark_, opts_.binary, m, rows, cols);
   End();
 }
 

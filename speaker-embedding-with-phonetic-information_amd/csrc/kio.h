@@ -270,6 +270,26 @@ class RandomAccessVectorReader {
   std::string data_path_;
 };
 
+// Random-access reader of a table of double-precision matrices (cmvn.scp, "scp:$sdata/JOB/cmvn.scp"; FM / DM / text objects).
+// An archive is loaded as a whole; the values of a script file are read when they are first asked for and kept (one per speaker).
+class RandomAccessDoubleMatrixReader {
+ public:
+  struct Value {
+    int rows = 0, cols = 0;
+    std::vector<double> data;
+  };
+  explicit RandomAccessDoubleMatrixReader(const std::string& rspecifier);
+  bool HasKey(const std::string& key) { return index_.count(key) != 0; }
+  const Value& Get(const std::string& key);
+
+ private:
+  struct Entry { std::string rx; Value v; bool loaded = false; };
+  std::vector<Entry> entries_;
+  std::unordered_map<std::string, int> index_;
+  Input data_in_;
+  std::string data_path_;
+};
+
 // A text table of token lists, "key tok1 tok2 ...\n" per entry (spk2utt, "ark:$data/spk2utt").
 struct TokenList {
   std::string key;
@@ -293,6 +313,8 @@ class TableWriter {
   ~TableWriter();
   void WriteVec(const std::string& key, const float* v, int n);
   void WriteMat(const std::string& key, const Matrix& m);
+  // A double-precision matrix ("DM"; text: 17 significant digits): the CMVN statistics compute-cmvn-stats writes.
+  void WriteMatDouble(const std::string& key, const double* m, int rows, int cols);
   // A compressed matrix (compress.h): "key \0B<format> <object>", format "CM", "CM2" or "CM3" and the n bytes that follow the
   // token.  Binary tables only; the scp line points at the "\0B" like WriteMat's.
   void WriteCompressed(const std::string& key, const char* format, const void* bytes, size_t n);

@@ -259,7 +259,27 @@ void RawNnet::Read(const std::string& bytes) {
   ExpectToken(in, binary, "</Nnet3>");
 }
 
-void RawNnet::ReadFrom(const std::string& rxfilename) {
+static std::string Slurp(const std::string& rxfilename);
+
+void RawNnet::ReadFrom(const std::string& rxfilename) { Read(Slurp(rxfilename)); }
+
+void RawNnet::ReadAcousticModelFrom(const std::string& rxfilename) {
+  const std::string bytes = Slurp(rxfilename);
+  const bool bin = bytes.size() >= 2 && bytes[0] == 0 && bytes[1] == 'B';
+  size_t at = bin ? 2 : 0;
+  while (!bin && at < bytes.size() && isspace((unsigned char)bytes[at])) ++at;
+  static const char kOpen[] = "<TransitionModel>", kClose[] = "</TransitionModel>";
+  if (bytes.compare(at, sizeof kOpen - 1, kOpen) != 0)
+    throw KioError("expected <TransitionModel> at the start of the acoustic model " + rxfilename);
+  const size_t close = bytes.find(kClose, at);
+  if (close == std::string::npos) throw KioError("no </TransitionModel> in the acoustic model " + rxfilename);
+  size_t rest = close + sizeof kClose - 1;
+  if (rest < bytes.size() && bin && bytes[rest] == ' ') ++rest;   // a binary token is followed by one space
+  while (!bin && rest < bytes.size() && isspace((unsigned char)bytes[rest])) ++rest;
+  Read((bin ? std::string("\0B", 2) : std::string()) + bytes.substr(rest));
+}
+
+static std::string Slurp(const std::string& rxfilename) {
   Input in;
   in.Open(rxfilename);
   std::string bytes;
@@ -275,7 +295,7 @@ void RawNnet::ReadFrom(const std::string& rxfilename) {
   int status = in.Close();
   if (bytes.empty()) throw KioError("no model data read from '" + rxfilename + "'" +
                                     (status ? " (input command exited with status " + std::to_string(status) + ")" : ""));
-  Read(bytes);
+  return bytes;
 }
 
 void RawNnet::ApplyNnetConfig(const std::string& text) {

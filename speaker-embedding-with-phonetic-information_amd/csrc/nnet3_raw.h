@@ -60,6 +60,10 @@ class RawNnet {
   void Read(const std::string& bytes);
   // Reads the object found at an rxfilename (file, file:offset, -, "cmd |").
   void ReadFrom(const std::string& rxfilename);
+  // The network of an acoustic model (final.mdl = <TransitionModel> ... </TransitionModel> <Nnet3> ... </Nnet3> <LeftContext> ...
+  // <Priors> ...; nnet3-am-copy --raw=true): the transition model is skipped up to its closing token, not parsed - its
+  // topology encoding differs between Kaldi versions - and what follows the network is ignored.  Binary and text.
+  void ReadAcousticModelFrom(const std::string& rxfilename);
   // `nnet3-copy --nnet-config=<text>` for node lines: same-kind same-name nodes are replaced, new ones
   // appended (what extract.config "output-node name=output input=tdnn6.affine" needs).
   void ApplyNnetConfig(const std::string& config_text);

@@ -1,0 +1,24 @@
+"""hipcc's resource remarks for the CMVN kernels (cross-compiled, no GPU): no scratch, no spills."""
+import os
+import re
+import shutil
+import subprocess
+
+import helpers as H
+
+SRC = os.path.join(H.ROOT, H.PKG_NAME, "csrc", "cmvn_kernels.hip")
+
+
+def test_cmvn_kernels_use_no_scratch_and_spill_nothing():
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    assert os.path.exists(hipcc), "hipcc is what builds the library; without it nothing here is checked"
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-c", SRC, "-o", os.devnull,
+                        "-Rpass-analysis=kernel-resource-usage"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:]
+    names = re.findall(r"Function Name: (\S+)", r.stdout)
+    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stdout)]
+    sspill = [int(x) for x in re.findall(r"SGPRs Spill: (\d+)", r.stdout)]
+    vspill = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", r.stdout)]
+    # statistics (block partials, their reduction) and application
+    assert len(names) == 3 and len(scratch) == len(sspill) == len(vspill) == 3, r.stdout[-2000:]
+    assert not any(scratch) and not any(sspill) and not any(vspill), list(zip(names, scratch, sspill, vspill))
