@@ -541,6 +541,43 @@ xv_status xv_cmvn_apply(int device, const float* feats, const int32_t* row_off, 
 xv_status xv_cmvn_kernel_time(int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t cols, int32_t reps,
                               float* stats_ms, float* apply_ms);
 
+/* ---- the GMM-UBM stage of the i-vector baseline (add-deltas, gmm-gselect, fgmm-global-gselect-to-post), without a model context
+ * Semantics: csrc/ubm.h.  Everything on the device is fp32 with a summation order that depends on the frame and the model alone: a
+ * frame's results are the same bits in whatever batch it is.  Limits: n <= 64 selected Gaussians, dimension <= 96. */
+typedef struct xv_ubm xv_ubm;
+/* host buffers, blocking: out[r] = the (order + 1) blocks of D = (truncate > 0 ? truncate : cols) columns, utterance by utterance
+ * (row_off[0] = 0).  fp32, every product and every sum rounded on its own.  device_ms may be NULL. */
+xv_status xv_add_deltas(int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t cols, int32_t order,
+                        int32_t window, int32_t truncate, float* out, float* device_ms);
+/* A model is uploaded once per process and device and used through its handle.  Host arrays: gconsts [G]; diagonal:
+ * means_invvars and inv_vars [G][D]; full: means_invcovars [G][D] and inv_covars [G][D (D + 1) / 2], the packed lower triangles. */
+xv_status xv_ubm_diag_create(int device, int32_t num_gauss, int32_t dim, const float* gconsts, const float* means_invvars,
+                             const float* inv_vars, xv_ubm** out);
+xv_status xv_ubm_full_create(int device, int32_t num_gauss, int32_t dim, const float* gconsts, const float* means_invcovars,
+                             const float* inv_covars, xv_ubm** out);
+void xv_ubm_destroy(xv_ubm* m);
+/* the n best Gaussians of a diagonal model per frame, best first: idx [rows][n]; loglikes (may be NULL) the same shape.
+ * n above 64 or above the model's size is XV_ERR_IO and names the limit. */
+xv_status xv_ubm_gselect(const xv_ubm* diag, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t n, int32_t* idx,
+                         float* loglikes, float* device_ms);
+/* posteriors of a full model over the selected Gaussians gselect [rows][n]: count [rows]; idx and post [rows][n], of which the
+ * first count[t] entries of frame t are set (selection order, zeros dropped) and the rest are -1 / 0.  loglikes ([rows][n], before
+ * the softmax) and logsum ([rows]) may be NULL.  device_ms3 (may be NULL): the times of the sort, the scores and the softmax. */
+xv_status xv_ubm_post(const xv_ubm* full, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* gselect, int32_t n,
+                      float min_post, int32_t* count, int32_t* idx, float* post, float* loglikes, float* logsum, float* device_ms3);
+/* host only (fp64): a full model to its diagonal image; gconsts_out [G], means_invvars_out and inv_vars_out [G][D] */
+xv_status xv_fgmm_to_gmm(int32_t num_gauss, int32_t dim, const float* weights, const float* means_invcovars, const float* inv_covars,
+                         float* gconsts_out, float* means_invvars_out, float* inv_vars_out);
+/* host only (fp64, stored as float): the gconsts the tools recompute after they read a full model (csrc/ubm.h); a component
+ * whose inverse covariance is not positive definite gets -infinity.  num_bad (may be NULL): how many those are. */
+xv_status xv_fgmm_gconsts(int32_t num_gauss, int32_t dim, const float* weights, const float* means_invcovars, const float* inv_covars,
+                          float* gconsts_out, int32_t* num_bad);
+/* the kernels' times in ms, the best of reps runs after one that warms up: ms5 = {deltas (order 2, window 3 on the first dim / 3
+ * columns; 0 if dim is no multiple of 3), selection, sort, full-covariance scores, softmax}.  The two models share their
+ * dimension, which is the features'; 1 <= n <= 64. */
+xv_status xv_ubm_kernel_time(const xv_ubm* diag, const xv_ubm* full, const float* feats, const int32_t* row_off, int32_t n_utts,
+                             int32_t n, float min_post, int32_t reps, float* ms5);
+
 /* ---- kernel-level entries of the frame-level and small kernels (unit tests; same conventions: device pointers from the caller
  * unless stated, an optional stream, XV_ERR_ARG with a reason for geometry a kernel cannot run, no engine or context) ---------- */
 /* tdnn_first_kernel: the layer(s) that read the network input.  Chunk b holds rows [row_offsets[b], row_offsets[b + 1]) of feats

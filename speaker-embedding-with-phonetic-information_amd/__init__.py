@@ -137,6 +137,8 @@ ABI_SYMBOLS = [
     "xv_reverb_options_default", "xv_reverb_output_length", "xv_wav_reverberate", "xv_reverb_kernel_time", "xv_wave_write", "xv_recognize_wav_pipeline",
     "xv_compressed_size", "xv_compress_matrices", "xv_compress_kernel_time", "xv_cmvn_sliding",
     "xv_cmvn_stats", "xv_cmvn_norm", "xv_cmvn_apply", "xv_cmvn_kernel_time",
+    "xv_add_deltas", "xv_ubm_diag_create", "xv_ubm_full_create", "xv_ubm_destroy", "xv_ubm_gselect", "xv_ubm_post",
+    "xv_fgmm_to_gmm", "xv_fgmm_gconsts", "xv_ubm_kernel_time",
     "xv_kernel_first_layer", "xv_kernel_prep_input", "xv_kernel_pool_finalise", "xv_kernel_frame_output",
     "xv_wave_read", "xv_wave_free", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
 ]
@@ -1145,6 +1147,161 @@ def apply_cmvn(feats_list, norms, utt_norm, device=0):
     _check(L.xv_cmvn_apply(device, packed.ctypes.data if packed.size else None, off.ctypes.data, n, max(cols, 1), nm.ctypes.data,
                            un.ctypes.data, out.ctypes.data if out.size else None))
     return [out[off[u]:off[u + 1]].copy() for u in range(n)]
+
+
+def add_deltas(feats_list, order=2, window=2, truncate=0, device=0):
+    """add-deltas on the device: a list of float32 [frames, cols] matrices that share their column count in, the matrices of
+    (order + 1) * (truncate or cols) columns out.  fp32, every product and every sum rounded on its own (csrc/ubm.h)."""
+    import numpy as np
+    L = lib()
+    packed, off, cols = _pack_matrices(feats_list, "add_deltas")
+    n = len(off) - 1
+    if cols < 1:
+        raise XvError(XV_ERR_ARG, "add_deltas: no matrix with rows and columns")
+    oc = (order + 1) * (truncate if truncate > 0 else cols)
+    out = np.zeros((packed.shape[0], max(oc, 1)), dtype=np.float32)
+    L.xv_add_deltas.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    _check(L.xv_add_deltas(device, packed.ctypes.data, off.ctypes.data, n, cols, order, window, truncate, out.ctypes.data, None))
+    return [out[off[u]:off[u + 1]].copy() for u in range(n)]
+
+
+def fgmm_to_gmm(weights, means_invcovars, inv_covars):
+    """fgmm-global-to-gmm on the host in fp64: weights [G], means_invcovars [G][D], inv_covars [G][D (D + 1) / 2] (packed lower
+    triangles) -> (gconsts [G], means_invvars [G][D], inv_vars [G][D]) of the diagonal image."""
+    import numpy as np
+    L = lib()
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    b = np.ascontiguousarray(means_invcovars, dtype=np.float32)
+    ic = np.ascontiguousarray(inv_covars, dtype=np.float32)
+    if b.ndim != 2 or w.shape != (b.shape[0],) or ic.shape != (b.shape[0], b.shape[1] * (b.shape[1] + 1) // 2):
+        raise XvError(XV_ERR_ARG, "fgmm_to_gmm: weights [G], means_invcovars [G][D], inv_covars [G][D (D + 1) / 2]")
+    g, d = b.shape
+    gc, mi, iv = np.zeros(g, np.float32), np.zeros((g, d), np.float32), np.zeros((g, d), np.float32)
+    L.xv_fgmm_to_gmm.argtypes = [ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 6
+    _check(L.xv_fgmm_to_gmm(g, d, w.ctypes.data, b.ctypes.data, ic.ctypes.data, gc.ctypes.data, mi.ctypes.data, iv.ctypes.data))
+    return gc, mi, iv
+
+
+def fgmm_gconsts(weights, means_invcovars, inv_covars):
+    """The gconsts the tools recompute after they read a full model (xv_fgmm_gconsts: fp64 on the host, stored as float32)."""
+    import numpy as np
+    L = lib()
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    b = np.ascontiguousarray(means_invcovars, dtype=np.float32)
+    ic = np.ascontiguousarray(inv_covars, dtype=np.float32)
+    if b.ndim != 2 or w.shape != (b.shape[0],) or ic.shape != (b.shape[0], b.shape[1] * (b.shape[1] + 1) // 2):
+        raise XvError(XV_ERR_ARG, "fgmm_gconsts: weights [G], means_invcovars [G][D], inv_covars [G][D (D + 1) / 2]")
+    gc = np.zeros(b.shape[0], np.float32)
+    L.xv_fgmm_gconsts.argtypes = [ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 5
+    _check(L.xv_fgmm_gconsts(b.shape[0], b.shape[1], w.ctypes.data, b.ctypes.data, ic.ctypes.data, gc.ctypes.data, None))
+    return gc
+
+
+class Ubm:
+    """A GMM on one device, uploaded once (xv_ubm_diag_create / xv_ubm_full_create).  Ubm.diag(gconsts, means_invvars, inv_vars)
+    selects Gaussians; Ubm.full(gconsts, means_invcovars, inv_covars_packed) turns a selection into posteriors."""
+
+    def __init__(self, handle, num_gauss, dim, full):
+        self._h, self.num_gauss, self.dim, self.is_full = handle, num_gauss, dim, full
+
+    @classmethod
+    def _create(cls, fn_name, device, gconsts, a, b, full):
+        import numpy as np
+        L = lib()
+        gc = np.ascontiguousarray(gconsts, dtype=np.float32)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        if a.ndim != 2 or gc.shape != (a.shape[0],):
+            raise XvError(XV_ERR_ARG, "Ubm: gconsts [G] and a [G][D] matrix")
+        g, d = a.shape
+        if b.shape != ((g, d * (d + 1) // 2) if full else (g, d)):
+            raise XvError(XV_ERR_ARG, "Ubm: the second matrix does not have the model's shape")
+        fn = getattr(L, fn_name)
+        fn.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.POINTER(ctypes.c_void_p)]
+        h = ctypes.c_void_p()
+        _check(fn(device, g, d, gc.ctypes.data, a.ctypes.data, b.ctypes.data, ctypes.byref(h)))
+        return cls(h, g, d, full)
+
+    @classmethod
+    def diag(cls, gconsts, means_invvars, inv_vars, device=0):
+        return cls._create("xv_ubm_diag_create", device, gconsts, means_invvars, inv_vars, False)
+
+    @classmethod
+    def full(cls, gconsts, means_invcovars, inv_covars, device=0):
+        return cls._create("xv_ubm_full_create", device, gconsts, means_invcovars, inv_covars, True)
+
+    def close(self):
+        if self._h:
+            L = lib()
+            L.xv_ubm_destroy.argtypes = [ctypes.c_void_p]
+            L.xv_ubm_destroy.restype = None
+            L.xv_ubm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def gselect(self, feats_list, n, return_loglikes=False):
+        """The n best Gaussians per frame, best first: a list of int32 [frames, n] (and of float32 log-likelihoods)."""
+        import numpy as np
+        L = lib()
+        packed, off, cols = _pack_matrices(feats_list, "gselect")
+        if cols != self.dim:
+            raise XvError(XV_ERR_ARG, "gselect: the features have %d columns, the model %d" % (cols, self.dim))
+        nu, rows = len(off) - 1, packed.shape[0]
+        idx = np.zeros((rows, max(n, 1)), dtype=np.int32)
+        ll = np.zeros((rows, max(n, 1)), dtype=np.float32)
+        L.xv_ubm_gselect.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        _check(L.xv_ubm_gselect(self._h, packed.ctypes.data, off.ctypes.data, nu, n, idx.ctypes.data,
+                                ll.ctypes.data if return_loglikes else None, None))
+        sel = [idx[off[u]:off[u + 1]].copy() for u in range(nu)]
+        return (sel, [ll[off[u]:off[u + 1]].copy() for u in range(nu)]) if return_loglikes else sel
+
+    def post(self, feats_list, gselect_list, min_post=0.0, return_details=False):
+        """Posteriors over the selected Gaussians: per utterance a list (one entry per frame) of (int32 indices, float32
+        posteriors).  return_details: also the lists of log-likelihoods [frames, n] and of per-frame log-sums [frames]."""
+        import numpy as np
+        L = lib()
+        packed, off, cols = _pack_matrices(feats_list, "post")
+        if cols != self.dim:
+            raise XvError(XV_ERR_ARG, "post: the features have %d columns, the model %d" % (cols, self.dim))
+        gs = [np.ascontiguousarray(g, dtype=np.int32) for g in gselect_list]
+        nu, rows = len(off) - 1, packed.shape[0]
+        if nu == 0 or len(gs) != nu or any(g.ndim != 2 or g.shape[0] != off[u + 1] - off[u] or g.shape[1] != gs[0].shape[1] for u, g in enumerate(gs)):
+            raise XvError(XV_ERR_ARG, "post: one [frames, n] selection per utterance, all of one n")
+        n = gs[0].shape[1]
+        sel = np.ascontiguousarray(np.concatenate(gs, axis=0))
+        count = np.zeros(rows, dtype=np.int32)
+        idx = np.zeros((rows, n), dtype=np.int32)
+        post = np.zeros((rows, n), dtype=np.float32)
+        ll = np.zeros((rows, n), dtype=np.float32)
+        logsum = np.zeros(rows, dtype=np.float32)
+        L.xv_ubm_post.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                  ctypes.c_float] + [ctypes.c_void_p] * 6
+        _check(L.xv_ubm_post(self._h, packed.ctypes.data, off.ctypes.data, nu, sel.ctypes.data, n, float(min_post), count.ctypes.data,
+                             idx.ctypes.data, post.ctypes.data, ll.ctypes.data, logsum.ctypes.data, None))
+        out = [[(idx[t, :count[t]].copy(), post[t, :count[t]].copy()) for t in range(off[u], off[u + 1])] for u in range(nu)]
+        if not return_details:
+            return out
+        return out, [ll[off[u]:off[u + 1]].copy() for u in range(nu)], [logsum[off[u]:off[u + 1]].copy() for u in range(nu)]
+
+
+def ubm_kernel_time(diag, full, feats_list, n=20, min_post=0.025, reps=5):
+    """{deltas, gselect, sort, full, softmax} kernel times in ms of one batch (xv_ubm_kernel_time: the best of reps)."""
+    import numpy as np
+    L = lib()
+    packed, off, cols = _pack_matrices(feats_list, "ubm_kernel_time")
+    ms = (ctypes.c_float * 5)()
+    L.xv_ubm_kernel_time.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                     ctypes.c_float, ctypes.c_int32, ctypes.c_void_p]
+    _check(L.xv_ubm_kernel_time(diag._h, full._h, packed.ctypes.data, off.ctypes.data, len(off) - 1, n, float(min_post), reps, ms))
+    return dict(zip(("deltas", "gselect", "sort", "full", "softmax"), [float(x) for x in ms]))
 
 
 def kernel_tdnn_gemm(desc):

@@ -27,6 +27,7 @@
 #include "plda_kernels.h"
 #include "program.h"
 #include "table_extract.h"
+#include "ubm.h"
 
 struct xv_model {
   xv::TdnnProgram prog;
@@ -987,6 +988,122 @@ xv_status xv_cmvn_kernel_time(int device, const float* feats, const int32_t* row
     }
     *stats_ms = best_s;
     *apply_ms = best_a;
+    return XV_OK;
+  });
+}
+
+struct xv_ubm {
+  std::unique_ptr<xv::UbmModel> m;
+};
+
+xv_status xv_add_deltas(int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t cols, int32_t order,
+                        int32_t window, int32_t truncate, float* out, float* device_ms) {
+  if (n_utts < 0 || cols < 1 || !row_off) return Fail(XV_ERR_ARG, "xv_add_deltas: bad argument");
+  return Guard([&] {
+    xv::AddDeltas(device, feats, row_off, n_utts, cols, order, window, truncate, out, device_ms);
+    return XV_OK;
+  });
+}
+
+xv_status xv_ubm_diag_create(int device, int32_t num_gauss, int32_t dim, const float* gconsts, const float* means_invvars,
+                             const float* inv_vars, xv_ubm** out) {
+  if (!out) return Fail(XV_ERR_ARG, "xv_ubm_diag_create: bad argument");
+  return Guard([&] {
+    std::unique_ptr<xv_ubm> h(new xv_ubm);
+    h->m.reset(xv::UbmDiagCreate(device, num_gauss, dim, gconsts, means_invvars, inv_vars));
+    *out = h.release();
+    return XV_OK;
+  });
+}
+
+xv_status xv_ubm_full_create(int device, int32_t num_gauss, int32_t dim, const float* gconsts, const float* means_invcovars,
+                             const float* inv_covars, xv_ubm** out) {
+  if (!out) return Fail(XV_ERR_ARG, "xv_ubm_full_create: bad argument");
+  return Guard([&] {
+    std::unique_ptr<xv_ubm> h(new xv_ubm);
+    h->m.reset(xv::UbmFullCreate(device, num_gauss, dim, gconsts, means_invcovars, inv_covars));
+    *out = h.release();
+    return XV_OK;
+  });
+}
+
+void xv_ubm_destroy(xv_ubm* m) { delete m; }
+
+xv_status xv_ubm_gselect(const xv_ubm* diag, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t n, int32_t* idx,
+                         float* loglikes, float* device_ms) {
+  if (!diag || !row_off || n_utts < 0) return Fail(XV_ERR_ARG, "xv_ubm_gselect: bad argument");
+  return Guard([&] {
+    xv::UbmGselect(*diag->m, feats, row_off, n_utts, n, idx, loglikes, device_ms);
+    return XV_OK;
+  });
+}
+
+xv_status xv_ubm_post(const xv_ubm* full, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* gselect, int32_t n,
+                      float min_post, int32_t* count, int32_t* idx, float* post, float* loglikes, float* logsum, float* device_ms3) {
+  if (!full || !row_off || n_utts < 0) return Fail(XV_ERR_ARG, "xv_ubm_post: bad argument");
+  return Guard([&] {
+    xv::UbmPost(*full->m, feats, row_off, n_utts, gselect, n, min_post, count, idx, post, loglikes, logsum, device_ms3);
+    return XV_OK;
+  });
+}
+
+xv_status xv_fgmm_to_gmm(int32_t num_gauss, int32_t dim, const float* weights, const float* means_invcovars, const float* inv_covars,
+                         float* gconsts_out, float* means_invvars_out, float* inv_vars_out) {
+  if (num_gauss < 1 || dim < 1 || !weights || !means_invcovars || !inv_covars || !gconsts_out || !means_invvars_out || !inv_vars_out)
+    return Fail(XV_ERR_ARG, "xv_fgmm_to_gmm: bad argument");
+  return Guard([&] {
+    xv::FullGmmData f;
+    f.num_gauss = num_gauss;
+    f.dim = dim;
+    f.weights.assign(weights, weights + num_gauss);
+    f.means_invcovars.assign(means_invcovars, means_invcovars + (size_t)num_gauss * dim);
+    f.inv_covars.assign(inv_covars, inv_covars + (size_t)num_gauss * ((size_t)dim * (dim + 1) / 2));
+    xv::DiagGmmData d;
+    xv::FullGmmToDiag(f, &d);
+    std::copy(d.gconsts.begin(), d.gconsts.end(), gconsts_out);
+    std::copy(d.means_invvars.begin(), d.means_invvars.end(), means_invvars_out);
+    std::copy(d.inv_vars.begin(), d.inv_vars.end(), inv_vars_out);
+    return XV_OK;
+  });
+}
+
+xv_status xv_fgmm_gconsts(int32_t num_gauss, int32_t dim, const float* weights, const float* means_invcovars, const float* inv_covars,
+                          float* gconsts_out, int32_t* num_bad) {
+  if (num_gauss < 1 || dim < 1 || !weights || !means_invcovars || !inv_covars || !gconsts_out) return Fail(XV_ERR_ARG, "xv_fgmm_gconsts: bad argument");
+  return Guard([&] {
+    xv::FullGmmData f;
+    f.num_gauss = num_gauss;
+    f.dim = dim;
+    f.weights.assign(weights, weights + num_gauss);
+    f.means_invcovars.assign(means_invcovars, means_invcovars + (size_t)num_gauss * dim);
+    f.inv_covars.assign(inv_covars, inv_covars + (size_t)num_gauss * ((size_t)dim * (dim + 1) / 2));
+    const int bad = xv::ComputeGconsts(&f);
+    if (num_bad) *num_bad = bad;
+    std::copy(f.gconsts.begin(), f.gconsts.end(), gconsts_out);
+    return XV_OK;
+  });
+}
+
+xv_status xv_ubm_kernel_time(const xv_ubm* diag, const xv_ubm* full, const float* feats, const int32_t* row_off, int32_t n_utts,
+                             int32_t n, float min_post, int32_t reps, float* ms5) {
+  if (!diag || !full || !feats || !row_off || n_utts < 1 || reps < 1 || !ms5) return Fail(XV_ERR_ARG, "xv_ubm_kernel_time: bad argument");
+  if (diag->m->full() || !full->m->full() || diag->m->dim() != full->m->dim() || diag->m->device() != full->m->device())
+    return Fail(XV_ERR_ARG, "xv_ubm_kernel_time: a diagonal and a full model of one dimension on one device");
+  if (n < 1 || n > 64 || n > diag->m->num_gauss() || row_off[0] != 0 || row_off[n_utts] < 1)
+    return Fail(XV_ERR_ARG, "xv_ubm_kernel_time: 1 <= n <= min(64, the model's size) and at least one frame");
+  return Guard([&] {
+    const size_t rows = (size_t)row_off[n_utts];
+    const int dim = diag->m->dim();
+    std::vector<int32_t> gs(rows * n), count(rows), idx(rows * n);
+    std::vector<float> post(rows * n), deltas(dim % 3 == 0 ? rows * dim : 0);
+    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
+      float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+      if (dim % 3 == 0) xv::AddDeltas(diag->m->device(), feats, row_off, n_utts, dim, 2, 3, dim / 3, deltas.data(), &ms[0]);
+      xv::UbmGselect(*diag->m, feats, row_off, n_utts, n, gs.data(), nullptr, &ms[1]);
+      xv::UbmPost(*full->m, feats, row_off, n_utts, gs.data(), n, min_post, count.data(), idx.data(), post.data(), nullptr, nullptr, &ms[2]);
+      for (int i = 0; i < 5; ++i)
+        if (r == 1 || (r > 1 && ms[i] < ms5[i])) ms5[i] = ms[i];
+    }
     return XV_OK;
   });
 }

@@ -1543,4 +1543,399 @@ void TableWriter::Close() {
   if (scp_.IsOpen()) scp_.Close();
 }
 
+
+void TableWriter::WriteIntVecVec(const std::string& key, const IntVecVec& v) {
+  Begin(key);
+  xv::WriteIntVecVec(ark_, opts_.binary, v);
+  End();
+}
+
+void TableWriter::WritePosterior(const std::string& key, const Posterior& post) {
+  Begin(key);
+  xv::WritePosterior(ark_, opts_.binary, post);
+  End();
+}
+
+// ---------------------------------------------------------------------------------------------
+// GMM objects
+namespace {
+
+void CheckGmmShape(const char* what, size_t got, size_t want) {
+  if (got != want) throw KioError(std::string(what) + ": " + std::to_string(got) + " values where the model's shape asks for " + std::to_string(want));
+}
+
+// FP / DP (binary) or " [ rows ]" (text): dim (dim + 1) / 2 values appended to *packed; returns dim
+int ReadPacked(Input& in, bool binary, std::vector<float>* packed) {
+  if (binary) {
+    std::string tok;
+    ReadToken(in, true, &tok);
+    if (tok != "FP" && tok != "DP") throw KioError("expected token FP or DP, got " + tok);
+    const int32_t dim = ReadInt32(in, true);
+    if (dim < 0 || dim > 65535) throw KioError("bad packed-matrix dimension " + std::to_string(dim));
+    const size_t n = (size_t)dim * (dim + 1) / 2, at = packed->size();
+    if (tok == "FP") {
+      std::vector<float> v;
+      ReadGrow(in, &v, n);
+      packed->insert(packed->end(), v.begin(), v.end());
+    } else {
+      std::vector<double> v;
+      ReadGrow(in, &v, n);
+      packed->resize(at + n);
+      for (size_t i = 0; i < n; ++i) (*packed)[at + i] = (float)v[i];
+    }
+    return dim;
+  }
+  std::vector<float> v;
+  std::vector<int> ends;
+  ReadTextNumbers(in, &v, &ends);
+  int dim = 0;
+  while ((size_t)dim * (dim + 1) / 2 < v.size()) ++dim;
+  if ((size_t)dim * (dim + 1) / 2 != v.size()) throw KioError("a text packed matrix with " + std::to_string(v.size()) + " values is no triangle");
+  packed->insert(packed->end(), v.begin(), v.end());
+  return dim;
+}
+
+void WritePacked(Output& out, bool binary, const float* p, int dim) {
+  if (binary) {
+    out.Puts("FP ");
+    WriteInt32(out, true, dim);
+    out.Write(p, (size_t)dim * (dim + 1) / 2 * 4);
+    return;
+  }
+  if (dim == 0) {
+    out.Puts(" [ ]\n");
+    return;
+  }
+  out.Puts(" [\n");
+  for (int i = 0; i < dim; ++i) {
+    out.Puts("  ");
+    for (int j = 0; j <= i; ++j) {
+      PutFloatText(out, *p++);
+      out.Put(' ');
+    }
+    out.Puts(i + 1 == dim ? "]\n" : "\n");
+  }
+}
+
+Matrix AsMatrix(const std::vector<float>& v, int rows, int cols) {
+  Matrix m;
+  m.rows = rows;
+  m.cols = cols;
+  m.data = v;
+  return m;
+}
+
+}  // namespace
+
+void ReadDiagGmm(Input& in, bool binary, DiagGmmData* m) {
+  *m = DiagGmmData();
+  std::string tok;
+  ReadToken(in, binary, &tok);
+  if (tok != "<DiagGMM>" && tok != "<DiagGMMBegin>") throw KioError("expected token <DiagGMM>, got " + tok);
+  ReadToken(in, binary, &tok);
+  if (tok == "<GCONSTS>") {
+    ReadVector(in, binary, &m->gconsts);
+    ReadToken(in, binary, &tok);
+  }
+  if (tok != "<WEIGHTS>") throw KioError("expected token <WEIGHTS>, got " + tok);
+  ReadVector(in, binary, &m->weights);
+  ExpectToken(in, binary, "<MEANS_INVVARS>");
+  Matrix a, b;
+  ReadMatrix(in, binary, &a);
+  ExpectToken(in, binary, "<INV_VARS>");
+  ReadMatrix(in, binary, &b);
+  ReadToken(in, binary, &tok);
+  if (tok != "</DiagGMM>" && tok != "<DiagGMMEnd>") throw KioError("expected token </DiagGMM>, got " + tok);
+  m->num_gauss = (int)m->weights.size();
+  m->dim = a.cols;
+  if (a.rows != m->num_gauss || b.rows != a.rows || b.cols != a.cols || (a.rows > 0 && a.cols < 1))
+    throw KioError("the matrices of the diagonal GMM do not have the shape of its weights");
+  if (!m->gconsts.empty()) CheckGmmShape("<GCONSTS>", m->gconsts.size(), m->weights.size());
+  m->means_invvars.assign(a.Data(), a.Data() + (size_t)a.rows * a.cols);
+  m->inv_vars.assign(b.Data(), b.Data() + (size_t)b.rows * b.cols);
+}
+
+void WriteDiagGmm(Output& out, bool binary, const DiagGmmData& m) {
+  const size_t g = (size_t)m.num_gauss;
+  CheckGmmShape("<WEIGHTS>", m.weights.size(), g);
+  CheckGmmShape("<GCONSTS>", m.gconsts.size(), g);
+  CheckGmmShape("<MEANS_INVVARS>", m.means_invvars.size(), g * m.dim);
+  CheckGmmShape("<INV_VARS>", m.inv_vars.size(), g * m.dim);
+  WriteToken(out, binary, "<DiagGMM>");
+  if (!binary) out.Put('\n');
+  WriteToken(out, binary, "<GCONSTS>");
+  WriteVector(out, binary, m.gconsts.data(), m.num_gauss);
+  WriteToken(out, binary, "<WEIGHTS>");
+  WriteVector(out, binary, m.weights.data(), m.num_gauss);
+  WriteToken(out, binary, "<MEANS_INVVARS>");
+  WriteMatrix(out, binary, AsMatrix(m.means_invvars, m.num_gauss, m.dim));
+  WriteToken(out, binary, "<INV_VARS>");
+  WriteMatrix(out, binary, AsMatrix(m.inv_vars, m.num_gauss, m.dim));
+  WriteToken(out, binary, "</DiagGMM>");
+  if (!binary) out.Put('\n');
+}
+
+void ReadFullGmm(Input& in, bool binary, FullGmmData* m) {
+  *m = FullGmmData();
+  std::string tok;
+  ReadToken(in, binary, &tok);
+  if (tok != "<FullGMM>" && tok != "<FullGMMBegin>") throw KioError("expected token <FullGMM>, got " + tok);
+  ReadToken(in, binary, &tok);
+  if (tok == "<GCONSTS>") {
+    ReadVector(in, binary, &m->gconsts);
+    ReadToken(in, binary, &tok);
+  }
+  if (tok != "<WEIGHTS>") throw KioError("expected token <WEIGHTS>, got " + tok);
+  ReadVector(in, binary, &m->weights);
+  ExpectToken(in, binary, "<MEANS_INVCOVARS>");
+  Matrix a;
+  ReadMatrix(in, binary, &a);
+  m->num_gauss = (int)m->weights.size();
+  m->dim = a.cols;
+  if (a.rows != m->num_gauss || (a.rows > 0 && a.cols < 1)) throw KioError("<MEANS_INVCOVARS> does not have the shape of the weights");
+  if (!m->gconsts.empty()) CheckGmmShape("<GCONSTS>", m->gconsts.size(), m->weights.size());
+  m->means_invcovars.assign(a.Data(), a.Data() + (size_t)a.rows * a.cols);
+  ExpectToken(in, binary, "<INV_COVARS>");
+  for (int g = 0; g < m->num_gauss; ++g) {
+    const int dim = ReadPacked(in, binary, &m->inv_covars);
+    if (dim != m->dim) throw KioError("inverse covariance " + std::to_string(g) + " has dimension " + std::to_string(dim) + ", the means have " + std::to_string(m->dim));
+  }
+  ReadToken(in, binary, &tok);
+  if (tok != "</FullGMM>" && tok != "<FullGMMEnd>") throw KioError("expected token </FullGMM>, got " + tok);
+}
+
+void WriteFullGmm(Output& out, bool binary, const FullGmmData& m) {
+  const size_t g = (size_t)m.num_gauss, tri = (size_t)m.dim * (m.dim + 1) / 2;
+  CheckGmmShape("<WEIGHTS>", m.weights.size(), g);
+  CheckGmmShape("<GCONSTS>", m.gconsts.size(), g);
+  CheckGmmShape("<MEANS_INVCOVARS>", m.means_invcovars.size(), g * m.dim);
+  CheckGmmShape("<INV_COVARS>", m.inv_covars.size(), g * tri);
+  WriteToken(out, binary, "<FullGMM>");
+  if (!binary) out.Put('\n');
+  WriteToken(out, binary, "<GCONSTS>");
+  WriteVector(out, binary, m.gconsts.data(), m.num_gauss);
+  WriteToken(out, binary, "<WEIGHTS>");
+  WriteVector(out, binary, m.weights.data(), m.num_gauss);
+  WriteToken(out, binary, "<MEANS_INVCOVARS>");
+  WriteMatrix(out, binary, AsMatrix(m.means_invcovars, m.num_gauss, m.dim));
+  WriteToken(out, binary, "<INV_COVARS>");
+  for (int i = 0; i < m.num_gauss; ++i) WritePacked(out, binary, m.inv_covars.data() + (size_t)i * tri, m.dim);
+  WriteToken(out, binary, "</FullGMM>");
+  if (!binary) out.Put('\n');
+}
+
+// ---------------------------------------------------------------------------------------------
+// Gaussian selection and posteriors
+namespace {
+
+// the rest of a text entry's line, split at white space
+std::vector<std::string> ReadLineWords(Input& in) {
+  std::vector<std::string> words;
+  std::string w;
+  int c;
+  while ((c = in.Get()) >= 0 && c != '\n') {
+    if (isspace(c)) {
+      if (!w.empty()) words.push_back(std::move(w));
+      w.clear();
+    } else {
+      w.push_back((char)c);
+    }
+  }
+  if (!w.empty()) words.push_back(std::move(w));
+  return words;
+}
+
+int32_t WordToInt(const std::string& w) {
+  char* end = nullptr;
+  const long l = strtol(w.c_str(), &end, 10);
+  if (end == w.c_str() || *end) throw KioError("bad integer '" + w + "'");
+  return (int32_t)l;
+}
+
+}  // namespace
+
+void ReadIntVecVec(Input& in, bool binary, IntVecVec* v) {
+  v->clear();
+  if (binary) {
+    const int32_t n = ReadInt32(in, true);
+    if (n < 0) throw KioError("negative size of a vector of integer vectors");
+    for (int32_t i = 0; i < n; ++i) {
+      if (in.Get() != 4) throw KioError("expected an int32 vector (size byte 4) in " + in.Name());
+      int32_t k;
+      in.Read(&k, 4);
+      if (k < 0) throw KioError("negative size of an integer vector");
+      v->emplace_back();
+      ReadGrow(in, &v->back(), (size_t)k);
+    }
+    return;
+  }
+  std::vector<int32_t> cur;
+  for (const std::string& w : ReadLineWords(in)) {
+    if (w == ";") {
+      v->push_back(std::move(cur));
+      cur.clear();
+    } else {
+      cur.push_back(WordToInt(w));
+    }
+  }
+  if (!cur.empty()) throw KioError("a text vector of integer vectors must close every list with ';'");
+}
+
+void WriteIntVecVec(Output& out, bool binary, const IntVecVec& v) {
+  if (binary) {
+    WriteInt32(out, true, (int32_t)v.size());
+    for (const std::vector<int32_t>& l : v) {
+      out.Put((char)4);
+      const int32_t k = (int32_t)l.size();
+      out.Write(&k, 4);
+      out.Write(l.data(), (size_t)k * 4);
+    }
+    return;
+  }
+  for (const std::vector<int32_t>& l : v) {
+    for (int32_t x : l) WriteInt32(out, false, x);
+    out.Puts("; ");
+  }
+  out.Put('\n');
+}
+
+void ReadPosterior(Input& in, bool binary, Posterior* p) {
+  p->clear();
+  if (binary) {
+    const int32_t n = ReadInt32(in, true);
+    if (n < 0) throw KioError("negative size of a posterior");
+    for (int32_t i = 0; i < n; ++i) {
+      const int32_t k = ReadInt32(in, true);
+      if (k < 0) throw KioError("negative size of a posterior's frame");
+      p->emplace_back();
+      for (int32_t j = 0; j < k; ++j) {
+        const int32_t idx = ReadInt32(in, true);
+        const float w = (float)ReadFloatOrDouble(in, true);
+        p->back().emplace_back(idx, w);
+      }
+    }
+    return;
+  }
+  const std::vector<std::string> words = ReadLineWords(in);
+  for (size_t i = 0; i < words.size();) {
+    if (words[i] != "[") throw KioError("expected '[' in a text posterior, got " + words[i]);
+    p->emplace_back();
+    for (++i;; i += 2) {
+      if (i >= words.size()) throw KioError("a text posterior ends inside a frame");
+      if (words[i] == "]") break;
+      if (i + 1 >= words.size() || words[i + 1] == "]") throw KioError("a text posterior's frame holds an index without a value");
+      char* end = nullptr;
+      const float w = strtof(words[i + 1].c_str(), &end);
+      if (end == words[i + 1].c_str() || *end) throw KioError("bad number '" + words[i + 1] + "' in a text posterior");
+      p->back().emplace_back(WordToInt(words[i]), w);
+    }
+    ++i;
+  }
+}
+
+void WritePosterior(Output& out, bool binary, const Posterior& p) {
+  if (binary) {
+    WriteInt32(out, true, (int32_t)p.size());
+    for (const auto& frame : p) {
+      WriteInt32(out, true, (int32_t)frame.size());
+      for (const auto& e : frame) {
+        WriteInt32(out, true, e.first);
+        WriteFloat(out, true, e.second);
+      }
+    }
+    return;
+  }
+  for (const auto& frame : p) {
+    out.Puts("[ ");
+    for (const auto& e : frame) {
+      WriteInt32(out, false, e.first);
+      WriteFloat(out, false, e.second);
+    }
+    out.Puts("] ");
+  }
+  out.Put('\n');
+}
+
+SequentialObjectReader::SequentialObjectReader(const std::string& rspecifier) {
+  opts_ = ParseRspecifier(rspecifier);
+  in_.Open(opts_.rxfilename);
+}
+
+bool SequentialObjectReader::NextEntry(std::string* key, Input** obj, std::string* error) {
+  for (;;) {
+    error->clear();
+    if (!ReadKey(in_, key)) return false;
+    if (!opts_.is_scp) {
+      *obj = &in_;
+      return true;
+    }
+    std::string rx;
+    int c;
+    while ((c = in_.Get()) >= 0 && c != '\n') rx.push_back((char)c);
+    rx = Trim(rx);
+    try {
+      if (rx.empty()) throw KioError("empty rxfilename for key " + *key);
+      data_.Open(rx);
+      *obj = &data_;
+      return true;
+    } catch (const KioError& e) {
+      if (opts_.permissive) continue;
+      *error = e.what();
+      *obj = nullptr;
+      return true;
+    }
+  }
+}
+
+void SequentialObjectReader::DoneEntry() {
+  if (opts_.is_scp && data_.IsOpen()) data_.Close();
+}
+
+bool SequentialGselectReader::Next(std::string* key, IntVecVec* v, std::string* error) {
+  Input* obj = nullptr;
+  if (!NextEntry(key, &obj, error)) return false;
+  if (!obj) return true;
+  const bool binary = ReadBinaryHeader(*obj);
+  ReadIntVecVec(*obj, binary, v);
+  DoneEntry();
+  return true;
+}
+
+bool SequentialPosteriorReader::Next(std::string* key, Posterior* p, std::string* error) {
+  Input* obj = nullptr;
+  if (!NextEntry(key, &obj, error)) return false;
+  if (!obj) return true;
+  const bool binary = ReadBinaryHeader(*obj);
+  ReadPosterior(*obj, binary, p);
+  DoneEntry();
+  return true;
+}
+
+std::unordered_map<std::string, float> ReadFloatTable(const std::string& rspecifier) {
+  RspecifierOptions o = ParseRspecifier(rspecifier);
+  if (o.is_scp) throw KioError("float tables are read from archives (ark:...), not scp: " + rspecifier);
+  Input in;
+  in.Open(o.rxfilename);
+  std::unordered_map<std::string, float> out;
+  std::string key;
+  while (ReadKey(in, &key)) {
+    float v;
+    if (in.Peek() == 0) {
+      ReadBinaryHeader(in);
+      v = (float)ReadFloatOrDouble(in, true);
+    } else {
+      const std::string w = ReadTextWord(in);
+      char* end = nullptr;
+      v = strtof(w.c_str(), &end);
+      if (end == w.c_str() || *end) throw KioError("bad float value '" + w + "' for key " + key + " in " + rspecifier);
+    }
+    int c;
+    while ((c = in.Peek()) >= 0 && c != '\n' && isspace(c)) in.Get();
+    if (in.Peek() == '\n') in.Get();
+    out[key] = v;
+  }
+  in.Close();
+  return out;
+}
+
 }  // namespace xv

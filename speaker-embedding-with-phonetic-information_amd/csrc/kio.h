@@ -320,6 +320,9 @@ class TableWriter {
   void WriteCompressed(const std::string& key, const char* format, const void* bytes, size_t n);
   bool binary() const { return opts_.binary; }
   void WriteInt32(const std::string& key, int32_t v);   // Int32Writer (num_utts.ark)
+  // Int32VectorVectorWriter (Gaussian selection) and PosteriorWriter; the types are declared below the class
+  void WriteIntVecVec(const std::string& key, const std::vector<std::vector<int32_t>>& v);
+  void WritePosterior(const std::string& key, const std::vector<std::vector<std::pair<int32_t, float>>>& post);
   void Close();
 
  private:
@@ -329,5 +332,68 @@ class TableWriter {
   Output ark_, scp_;
   std::string pending_scp_line_;
 };
+
+// ---------------------------------------------------------------------------------------------
+// The objects of the GMM-UBM stage (sid/extract_ivectors.sh:58-70): restated from Kaldi's gmm/diag-gmm.cc, gmm/full-gmm.cc,
+// util/kaldi-holder-inl.h and hmm/posterior.cc of early 2018.
+//   <DiagGMM> [<GCONSTS> FV] <WEIGHTS> FV <MEANS_INVVARS> FM <INV_VARS> FM </DiagGMM>
+//   <FullGMM> [<GCONSTS> FV] <WEIGHTS> FV <MEANS_INVCOVARS> FM <INV_COVARS> (FP|DP, int32 dim, dim (dim + 1) / 2 values: the
+//             lower triangle row by row; text " [" rows "]") x num-components </FullGMM>
+//   (<DiagGMMBegin> / <DiagGMMEnd> and <FullGMMBegin> / <FullGMMEnd> are accepted as Kaldi accepts them.)
+// The readers leave the stored gconsts as they are (empty when the file has none); ubm.h recomputes them.
+struct DiagGmmData {
+  int num_gauss = 0, dim = 0;
+  std::vector<float> gconsts, weights;          // [num_gauss]
+  std::vector<float> means_invvars, inv_vars;   // [num_gauss][dim]
+};
+struct FullGmmData {
+  int num_gauss = 0, dim = 0;
+  std::vector<float> gconsts, weights;   // [num_gauss]
+  std::vector<float> means_invcovars;    // [num_gauss][dim]
+  std::vector<float> inv_covars;         // [num_gauss][dim (dim + 1) / 2], the packed lower triangles
+};
+void ReadDiagGmm(Input& in, bool binary, DiagGmmData* m);
+void WriteDiagGmm(Output& out, bool binary, const DiagGmmData& m);
+void ReadFullGmm(Input& in, bool binary, FullGmmData* m);
+void WriteFullGmm(Output& out, bool binary, const FullGmmData& m);
+
+// vector<vector<int32>> (binary: int32 size, then per list a size byte 4, a raw int32 count and the values; text: "a b ; c d ; \n")
+typedef std::vector<std::vector<int32_t>> IntVecVec;
+// Posterior (binary: int32 size, per frame int32 size and (int32, float) pairs, every scalar with its size byte; text:
+// "[ idx post idx post ] [ ... ] \n")
+typedef std::vector<std::vector<std::pair<int32_t, float>>> Posterior;
+void ReadIntVecVec(Input& in, bool binary, IntVecVec* v);
+void WriteIntVecVec(Output& out, bool binary, const IntVecVec& v);
+void ReadPosterior(Input& in, bool binary, Posterior* p);
+void WritePosterior(Output& out, bool binary, const Posterior& p);
+
+// Sequential readers of the two tables ("ark:", "ark,s,cs:-", "scp,p:...").  sorted(): the rspecifier promised sorted keys (s): the
+// caller may then merge by key instead of loading the table.  An unreadable scp entry comes back through `error` (permissive
+// (p): it is skipped silently instead); a corrupt archive is fatal.
+class SequentialObjectReader {
+ public:
+  explicit SequentialObjectReader(const std::string& rspecifier);
+  bool sorted() const { return opts_.sorted; }
+  int Close() { return in_.Close(); }
+
+ protected:
+  // the next entry: *obj is where to parse it from (owned by the reader); false at the end
+  bool NextEntry(std::string* key, Input** obj, std::string* error);
+  void DoneEntry();
+  RspecifierOptions opts_;
+  Input in_, data_;
+};
+class SequentialGselectReader : public SequentialObjectReader {
+ public:
+  using SequentialObjectReader::SequentialObjectReader;
+  bool Next(std::string* key, IntVecVec* v, std::string* error);
+};
+class SequentialPosteriorReader : public SequentialObjectReader {
+ public:
+  using SequentialObjectReader::SequentialObjectReader;
+  bool Next(std::string* key, Posterior* p, std::string* error);
+};
+// Random-access float table, text ("key 0.5") or binary entries (BaseFloatReader: the per-utterance scales of scale-post).
+std::unordered_map<std::string, float> ReadFloatTable(const std::string& rspecifier);
 
 }  // namespace xv

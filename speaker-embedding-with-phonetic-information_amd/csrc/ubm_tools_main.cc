@@ -1,0 +1,501 @@
+// add-deltas / fgmm-global-to-gmm / gmm-gselect / fgmm-global-gselect-to-post / scale-post - drop-in command lines for the
+// frame-rate half of the GMM-UBM i-vector baseline (egs/sre/v1: sid/extract_ivectors.sh:58-68; the same three commands open
+// sid/train_full_ubm.sh and sid/train_ivector_extractor.sh).  One executable, dispatching on its name:
+//   add-deltas [--delta-order=2 --delta-window=2 --truncate=0] <feats-rspecifier> <feats-wspecifier>
+//   fgmm-global-to-gmm [--binary=true] <full-gmm-in> <diag-gmm-out>
+//   gmm-gselect [--n=50] <diag-gmm-in> <feats-rspecifier> <gselect-wspecifier>
+//   fgmm-global-gselect-to-post [--min-post=0.0] <full-gmm-in> <feats-rspecifier> <gselect-rspecifier> <post-wspecifier>
+//   scale-post <post-rspecifier> (<scale>|<scale-rspecifier>) <post-wspecifier>
+//   fgmm-global-copy [--binary=true] <full-gmm-in> <full-gmm-out>;  gmm-global-copy [--binary=true] <diag-gmm-in> <diag-gmm-out>
+//   copy-gselect [--n=-1] <gselect-rspecifier> <gselect-wspecifier>
+// add-deltas, gmm-gselect and fgmm-global-gselect-to-post run on the device (ubm.h) and fail without a GPU (exit 255); the others
+// are host code and open no device (the three copies rewrite a model or a table, recomputing a model's gconsts on the way).  Models are rxfilenames ("final.ubm", "-", "fgmm-global-to-gmm final.ubm -|"); features
+// are read ahead in batches, so the recipes' "ark,s,cs:add-deltas ... | apply-cmvn-sliding ... | select-voiced-frames ... |" is
+// a child pipeline read front to back.  Refused by name: gmm-gselect --write-likes and --gselect.
+#include <math.h>
+#include <stdlib.h>
+
+#include <memory>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "cli.h"
+#include "cmvn.h"
+#include "kio.h"
+#include "ubm.h"
+#include "ubm_kernels.h"
+
+namespace {
+
+constexpr int64_t kBatchFrames = 1 << 16;   // frames read ahead per device call
+
+bool IsTable(const std::string& spec) {
+  const size_t colon = spec.find(':');
+  if (colon == std::string::npos) return false;
+  const std::string kind = spec.substr(0, spec.find_first_of(",:"));
+  return kind == "ark" || kind == "scp";
+}
+
+void ReportProblems(const std::vector<xv::FeatBatchReader::Problem>& problems, long* num_err) {
+  for (const auto& p : problems) {
+    if (p.what.empty()) XWARN("Empty feature matrix for utterance " << p.key);
+    else XWARN("Failed to read features for key " << p.key << ": " << p.what);
+    ++*num_err;
+  }
+}
+
+struct DeltaOptions {
+  int order = 2, window = 2, truncate = 0, device = -1;
+};
+
+int AddDeltas(const DeltaOptions& o, const std::vector<std::string>& pos) {
+  const int dev = xv::PickDevice(o.device);
+  xv::FeatBatchReader reader(pos[0], kBatchFrames, false);
+  xv::TableWriter writer(pos[1]);
+  long num_done = 0, num_err = 0;
+  xv::FeatBatchReader::Batch b;
+  std::vector<xv::FeatBatchReader::Problem> problems;
+  std::vector<float> out;
+  for (bool more = true; more;) {
+    problems.clear();
+    more = reader.Next(&b, &problems);
+    ReportProblems(problems, &num_err);
+    if (!more) break;
+    const int n = (int)b.keys.size();
+    const int oc = (o.order + 1) * (o.truncate > 0 ? o.truncate : b.cols);
+    out.resize((size_t)b.row_off[n] * oc);
+    xv::AddDeltas(dev, b.feats.data(), b.row_off.data(), n, b.cols, o.order, o.window, o.truncate, out.data());
+    for (int u = 0; u < n; ++u) {
+      xv::Matrix m;
+      m.rows = b.row_off[u + 1] - b.row_off[u];
+      m.cols = oc;
+      m.data.assign(out.begin() + (size_t)b.row_off[u] * oc, out.begin() + (size_t)b.row_off[u + 1] * oc);
+      writer.WriteMat(b.keys[u], m);
+      ++num_done;
+    }
+  }
+  writer.Close();
+  XLOG("Done " << num_done << " files, " << num_err << " with errors.");
+  return num_done != 0 ? 0 : 1;
+}
+
+int FgmmToGmm(bool binary, const std::vector<std::string>& pos) {
+  xv::FullGmmData full;
+  xv::ReadFullGmmFile(pos[0], &full);
+  xv::DiagGmmData diag;
+  xv::FullGmmToDiag(full, &diag);
+  xv::WriteDiagGmmFile(pos[1], binary, diag);
+  XLOG("Written diagonal GMM to " << pos[1]);
+  return 0;
+}
+
+// log sum_i exp(v_i), in fp64
+double LogSumExp(const float* v, int n) {
+  double mx = v[0];
+  for (int i = 1; i < n; ++i) mx = v[i] > mx ? v[i] : mx;
+  double s = 0.0;
+  for (int i = 0; i < n; ++i) s += exp((double)v[i] - mx);
+  return mx + log(s);
+}
+
+int GmmGselect(int n_opt, int device, const std::vector<std::string>& pos) {
+  if (n_opt < 1) throw xv::KioError("--n must be at least 1");
+  xv::DiagGmmData gmm;
+  xv::ReadDiagGmmFile(pos[0], &gmm);
+  int n = n_opt;
+  if (n > gmm.num_gauss) {
+    XWARN("You asked for " << n << " Gaussians but GMM only has " << gmm.num_gauss << ", returning this many. Note: this means the Gaussian selection is pointless.");
+    n = gmm.num_gauss;
+  }
+  if (n > xv::kUbmMaxSelect)
+    throw xv::KioError("--n=" + std::to_string(n) + " is above the limit of " + std::to_string(xv::kUbmMaxSelect) + " selected Gaussians per frame of the device kernel");
+  const int dev = xv::PickDevice(device);
+  std::unique_ptr<xv::UbmModel> model(xv::UbmDiagCreate(dev, gmm.num_gauss, gmm.dim, gmm.gconsts.data(), gmm.means_invvars.data(), gmm.inv_vars.data()));
+  xv::FeatBatchReader reader(pos[1], kBatchFrames, false);
+  xv::TableWriter writer(pos[2]);
+  long num_done = 0, num_err = 0;
+  double tot_like = 0.0;
+  int64_t tot_t = 0;
+  xv::FeatBatchReader::Batch b;
+  std::vector<xv::FeatBatchReader::Problem> problems;
+  std::vector<int32_t> idx;
+  std::vector<float> ll;
+  for (bool more = true; more;) {
+    problems.clear();
+    more = reader.Next(&b, &problems);
+    ReportProblems(problems, &num_err);
+    if (!more) break;
+    if (b.cols != gmm.dim) {
+      for (const std::string& key : b.keys) {
+        XWARN("Dimension mismatch for utterance " << key << ": the features have " << b.cols << " columns, the model " << gmm.dim);
+        ++num_err;
+      }
+      continue;
+    }
+    const int nu = (int)b.keys.size();
+    const size_t rows = (size_t)b.row_off[nu];
+    idx.resize(rows * n);
+    ll.resize(rows * n);
+    xv::UbmGselect(*model, b.feats.data(), b.row_off.data(), nu, n, idx.data(), ll.data());
+    for (int u = 0; u < nu; ++u) {
+      xv::IntVecVec gs;
+      for (int t = b.row_off[u]; t < b.row_off[u + 1]; ++t) {
+        gs.emplace_back(idx.begin() + (size_t)t * n, idx.begin() + (size_t)(t + 1) * n);
+        tot_like += LogSumExp(ll.data() + (size_t)t * n, n);
+      }
+      tot_t += b.row_off[u + 1] - b.row_off[u];
+      writer.WriteIntVecVec(b.keys[u], gs);
+      ++num_done;
+    }
+  }
+  writer.Close();
+  XLOG("Done " << num_done << " files, " << num_err << " with errors, average UBM log-likelihood is " << (tot_t ? tot_like / (double)tot_t : 0.0)
+               << " over " << tot_t << " frames.");
+  return num_done != 0 ? 0 : 1;
+}
+
+// The Gaussian selection of a key: a table that promised sorted keys (s) is merged front to back, any other is loaded.
+class GselectLookup {
+ public:
+  explicit GselectLookup(const std::string& rspecifier) : reader_(rspecifier) {
+    if (reader_.sorted()) return;
+    std::string key, err;
+    xv::IntVecVec v;
+    while (reader_.Next(&key, &v, &err)) {
+      if (!err.empty()) XWARN("Failed to read the Gaussian selection of " << key << ": " << err);
+      else all_.emplace(key, std::move(v));
+    }
+  }
+  bool Find(const std::string& key, xv::IntVecVec* out) {
+    if (!reader_.sorted()) {
+      auto it = all_.find(key);
+      if (it == all_.end()) return false;
+      *out = it->second;
+      return true;
+    }
+    for (;;) {
+      if (!held_) {
+        std::string err;
+        if (eof_ || !reader_.Next(&held_key_, &held_v_, &err)) {
+          eof_ = true;
+          return false;
+        }
+        if (!err.empty()) {
+          XWARN("Failed to read the Gaussian selection of " << held_key_ << ": " << err);
+          continue;
+        }
+        held_ = true;
+      }
+      const int c = held_key_.compare(key);
+      if (c > 0) return false;   // the table is past the key
+      held_ = false;
+      if (c == 0) {
+        *out = std::move(held_v_);
+        return true;
+      }
+    }
+  }
+
+ private:
+  xv::SequentialGselectReader reader_;
+  std::unordered_map<std::string, xv::IntVecVec> all_;
+  bool held_ = false, eof_ = false;
+  std::string held_key_;
+  xv::IntVecVec held_v_;
+};
+
+int GselectToPost(float min_post, int device, const std::vector<std::string>& pos) {
+  xv::FullGmmData gmm;
+  xv::ReadFullGmmFile(pos[0], &gmm);
+  const int dev = xv::PickDevice(device);
+  std::unique_ptr<xv::UbmModel> model(xv::UbmFullCreate(dev, gmm.num_gauss, gmm.dim, gmm.gconsts.data(), gmm.means_invcovars.data(), gmm.inv_covars.data()));
+  xv::FeatBatchReader reader(pos[1], kBatchFrames, false);
+  GselectLookup gselect(pos[2]);
+  xv::TableWriter writer(pos[3]);
+  long num_done = 0, num_err = 0;
+  double tot_like = 0.0;
+  int64_t tot_t = 0;
+  xv::FeatBatchReader::Batch b;
+  std::vector<xv::FeatBatchReader::Problem> problems;
+  std::vector<std::string> keys;
+  std::vector<float> feats, post, logsum;
+  std::vector<int32_t> off, gs, count, idx;
+  for (bool more = true; more;) {
+    problems.clear();
+    more = reader.Next(&b, &problems);
+    ReportProblems(problems, &num_err);
+    if (!more) break;
+    // the utterances of the batch that have a usable selection, grouped by the selection's width
+    keys.clear();
+    feats.clear();
+    gs.clear();
+    off.assign(1, 0);
+    int n = 0;
+    auto flush = [&] {
+      if (keys.empty()) return;
+      const int nu = (int)keys.size();
+      const size_t rows = (size_t)off[nu];
+      count.resize(rows);
+      idx.resize(rows * n);
+      post.resize(rows * n);
+      logsum.resize(rows);
+      xv::UbmPost(*model, feats.data(), off.data(), nu, gs.data(), n, min_post, count.data(), idx.data(), post.data(), nullptr, logsum.data());
+      for (int u = 0; u < nu; ++u) {
+        xv::Posterior p;
+        for (int t = off[u]; t < off[u + 1]; ++t) {
+          p.emplace_back();
+          for (int k = 0; k < count[t]; ++k) p.back().emplace_back(idx[(size_t)t * n + k], post[(size_t)t * n + k]);
+          tot_like += logsum[t];
+        }
+        tot_t += off[u + 1] - off[u];
+        writer.WritePosterior(keys[u], p);
+        ++num_done;
+      }
+      keys.clear();
+      feats.clear();
+      gs.clear();
+      off.assign(1, 0);
+    };
+    for (size_t u = 0; u < b.keys.size(); ++u) {
+      const int rows = b.row_off[u + 1] - b.row_off[u];
+      if (b.cols != gmm.dim) {
+        XWARN("Dimension mismatch for utterance " << b.keys[u] << ": the features have " << b.cols << " columns, the model " << gmm.dim);
+        ++num_err;
+        continue;
+      }
+      xv::IntVecVec sel;
+      if (!gselect.Find(b.keys[u], &sel)) {
+        XWARN("No Gaussian-selection info available for utterance " << b.keys[u] << " (skipping utterance)");
+        ++num_err;
+        continue;
+      }
+      if ((int)sel.size() != rows) {
+        XWARN("Mismatch in number of frames " << rows << " for features and Gaussian selection " << sel.size() << ", for utterance " << b.keys[u]);
+        ++num_err;
+        continue;
+      }
+      const size_t width = sel[0].size();
+      bool same = width >= 1;
+      for (const auto& l : sel) same = same && l.size() == width;
+      if (!same) {
+        XWARN("The Gaussian selection of utterance " << b.keys[u] << " does not have one length for every frame (skipping utterance)");
+        ++num_err;
+        continue;
+      }
+      if ((int)width != n) flush();
+      n = (int)width;
+      keys.push_back(b.keys[u]);
+      feats.insert(feats.end(), b.feats.begin() + (size_t)b.row_off[u] * b.cols, b.feats.begin() + (size_t)b.row_off[u + 1] * b.cols);
+      for (const auto& l : sel) gs.insert(gs.end(), l.begin(), l.end());
+      off.push_back(off.back() + rows);
+    }
+    flush();
+  }
+  writer.Close();
+  XLOG("Done " << num_done << " files, " << num_err << " with errors, average log-likelihood per frame is " << (tot_t ? tot_like / (double)tot_t : 0.0)
+               << " over " << tot_t << " frames.");
+  return num_done != 0 ? 0 : 1;
+}
+
+int ScalePost(const std::vector<std::string>& pos) {
+  const bool table = IsTable(pos[1]);
+  std::unordered_map<std::string, float> scales;
+  double global = 1.0;
+  if (table) scales = xv::ReadFloatTable(pos[1]);
+  else if (!xv::ParseDouble(pos[1], &global)) throw xv::KioError("Bad scale '" + pos[1] + "': expected a number or a table of scales (ark:...)");
+  xv::SequentialPosteriorReader reader(pos[0]);
+  xv::TableWriter writer(pos[2]);
+  long num_done = 0, num_no_scale = 0;
+  std::string key, err;
+  xv::Posterior p;
+  while (reader.Next(&key, &p, &err)) {
+    if (!err.empty()) {
+      XWARN("Failed to read the posterior of " << key << ": " << err);
+      ++num_no_scale;
+      continue;
+    }
+    float scale = (float)global;
+    if (table) {
+      auto it = scales.find(key);
+      if (it == scales.end()) {
+        XWARN("No scale available for key " << key);
+        ++num_no_scale;
+        continue;
+      }
+      scale = it->second;
+    }
+    if (scale == 0.f) {
+      for (auto& frame : p) frame.clear();
+    } else if (scale != 1.f) {
+      for (auto& frame : p)
+        for (auto& e : frame) e.second *= scale;
+    }
+    writer.WritePosterior(key, p);
+    ++num_done;
+  }
+  writer.Close();
+  XLOG("Done " << num_done << " posteriors;  " << num_no_scale << " had no scales.");
+  return num_done != 0 ? 0 : 1;
+}
+
+int GmmCopy(bool full, bool binary, const std::vector<std::string>& pos) {
+  if (full) {
+    xv::FullGmmData m;
+    xv::ReadFullGmmFile(pos[0], &m);
+    xv::WriteFullGmmFile(pos[1], binary, m);
+  } else {
+    xv::DiagGmmData m;
+    xv::ReadDiagGmmFile(pos[0], &m);
+    xv::WriteDiagGmmFile(pos[1], binary, m);
+  }
+  XLOG("Written model to " << pos[1]);
+  return 0;
+}
+
+int CopyGselect(int n, const std::vector<std::string>& pos) {
+  if (n == 0 || n < -1) throw xv::KioError("--n must be positive, or -1 to keep every index");
+  xv::SequentialGselectReader reader(pos[0]);
+  xv::TableWriter writer(pos[1]);
+  long num_done = 0, num_err = 0;
+  std::string key, err;
+  xv::IntVecVec v;
+  while (reader.Next(&key, &v, &err)) {
+    if (!err.empty()) {
+      XWARN("Failed to read the Gaussian selection of " << key << ": " << err);
+      ++num_err;
+      continue;
+    }
+    if (n > 0)
+      for (auto& l : v)
+        if ((int)l.size() > n) l.resize((size_t)n);
+    writer.WriteIntVecVec(key, v);
+    ++num_done;
+  }
+  writer.Close();
+  XLOG("Copied " << num_done << " gselect entries, " << num_err << " had errors.");
+  return num_done != 0 ? 0 : 1;
+}
+
+std::string Dashes(std::string n) {
+  for (char& c : n)
+    if (c == '_') c = '-';
+  return n;
+}
+
+bool Common(const std::string& n) { return n == "verbose" || n == "print-args" || n == "config"; }
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  const std::string prog = xv::ProgramName(argv[0]);
+  xv::CliTool t;
+  t.config_file = false;
+  if (prog.find("add-deltas") != std::string::npos) {
+    DeltaOptions o;
+    t.usage = "Add deltas (typically to raw mfcc or plp features).\n"
+              "Usage: add-deltas [options] <feats-rspecifier> <feats-wspecifier>\n"
+              "Options: --delta-order (2) --delta-window (2) --truncate (0) --device=<gpu>\n";
+    t.set = [&](const std::string& name, const std::string& val) {
+      const std::string n = Dashes(name);
+      if (Common(n)) return xv::OptionResult::kOk;
+      if (n == "delta-order") o.order = xv::ToInt(n, val);
+      else if (n == "delta-window") o.window = xv::ToInt(n, val);
+      else if (n == "truncate") o.truncate = xv::ToInt(n, val);
+      else if (n == "device") o.device = xv::ToInt(n, val);
+      else return xv::OptionResult::kUnknown;
+      return xv::OptionResult::kOk;
+    };
+    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : AddDeltas(o, pos); };
+    return xv::CliMain(argc, argv, t);
+  }
+  if (prog.find("fgmm-global-to-gmm") != std::string::npos) {
+    bool binary = true;
+    t.usage = "Convert single full-covariance GMM to single diagonal-covariance GMM.\n"
+              "Usage: fgmm-global-to-gmm [options] <full-gmm-in> <diag-gmm-out>\n"
+              "Options: --binary (true)\n";
+    t.set = [&](const std::string& name, const std::string& val) {
+      const std::string n = Dashes(name);
+      if (Common(n)) return xv::OptionResult::kOk;
+      if (n == "binary") binary = xv::ToBool(n, val);
+      else return xv::OptionResult::kUnknown;
+      return xv::OptionResult::kOk;
+    };
+    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : FgmmToGmm(binary, pos); };
+    return xv::CliMain(argc, argv, t);
+  }
+  if (prog.find("gmm-global-copy") != std::string::npos) {   // fgmm-global-copy as well
+    const bool full = prog.find("fgmm-global-copy") != std::string::npos;
+    bool binary = true;
+    t.usage = full ? "Copy a full-covariance GMM.\nUsage: fgmm-global-copy [options] <model-in> <model-out>\nOptions: --binary (true)\n"
+                   : "Copy a diagonal-covariance GMM.\nUsage: gmm-global-copy [options] <model-in> <model-out>\nOptions: --binary (true)\n";
+    t.set = [&](const std::string& name, const std::string& val) {
+      const std::string n = Dashes(name);
+      if (Common(n)) return xv::OptionResult::kOk;
+      if (n == "binary") binary = xv::ToBool(n, val);
+      else return xv::OptionResult::kUnknown;
+      return xv::OptionResult::kOk;
+    };
+    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : GmmCopy(full, binary, pos); };
+    return xv::CliMain(argc, argv, t);
+  }
+  if (prog.find("copy-gselect") != std::string::npos) {
+    int n = -1;
+    t.usage = "Copy Gaussian indices for pruning, possibly making the lists shorter.\n"
+              "Usage: copy-gselect [options] <gselect-rspecifier> <gselect-wspecifier>\nOptions: --n (-1)\n";
+    t.set = [&](const std::string& name, const std::string& val) {
+      const std::string nm = Dashes(name);
+      if (Common(nm)) return xv::OptionResult::kOk;
+      if (nm == "n") n = xv::ToInt(nm, val);
+      else return xv::OptionResult::kUnknown;
+      return xv::OptionResult::kOk;
+    };
+    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : CopyGselect(n, pos); };
+    return xv::CliMain(argc, argv, t);
+  }
+  if (prog.find("gselect-to-post") != std::string::npos) {
+    float min_post = 0.f;
+    int device = -1;
+    t.usage = "Given features and Gaussian-selection (gselect) information for a full-covariance GMM, output per-frame posteriors\n"
+              "for the selected indices.\n"
+              "Usage: fgmm-global-gselect-to-post [options] <full-gmm-in> <feats-rspecifier> <gselect-rspecifier> <post-wspecifier>\n"
+              "Options: --min-post (0.0) --device=<gpu>\n";
+    t.set = [&](const std::string& name, const std::string& val) {
+      const std::string n = Dashes(name);
+      if (Common(n)) return xv::OptionResult::kOk;
+      if (n == "min-post") min_post = xv::ToFloat(n, val);
+      else if (n == "device") device = xv::ToInt(n, val);
+      else return xv::OptionResult::kUnknown;
+      return xv::OptionResult::kOk;
+    };
+    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 4 ? xv::kUsageError : GselectToPost(min_post, device, pos); };
+    return xv::CliMain(argc, argv, t);
+  }
+  if (prog.find("gmm-gselect") != std::string::npos) {
+    int n_opt = 50, device = -1;
+    t.usage = "Precompute Gaussian indices for pruning (e.g. in training UBMs, SGMMs, tied-mixture systems).\n"
+              "For each frame, gives a list of the n best Gaussian indices, sorted from best to worst.\n"
+              "Usage: gmm-gselect [options] <model-in> <feature-rspecifier> <gselect-wspecifier>\n"
+              "Options: --n (50; at most 64) --device=<gpu>\n"
+              "Not built (refused): --write-likes, --gselect.\n";
+    t.set = [&](const std::string& name, const std::string& val) {
+      const std::string n = Dashes(name);
+      if (Common(n)) return xv::OptionResult::kOk;
+      if (n == "n") n_opt = xv::ToInt(n, val);
+      else if (n == "device") device = xv::ToInt(n, val);
+      else if (n == "write-likes") throw xv::KioError("--write-likes is not built: no script of the recipes passes it");
+      else if (n == "gselect") throw xv::KioError("--gselect is not built: no script of the recipes passes it");
+      else return xv::OptionResult::kUnknown;
+      return xv::OptionResult::kOk;
+    };
+    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : GmmGselect(n_opt, device, pos); };
+    return xv::CliMain(argc, argv, t);
+  }
+  t.usage = "Scale all the posteriors of a table, by one scale or by a scale per utterance.\n"
+            "Usage: scale-post <post-rspecifier> (<scale-rspecifier>|<scale>) <post-wspecifier>\n";
+  t.set = [&](const std::string& name, const std::string& val) {
+    return Common(Dashes(name)) ? xv::OptionResult::kOk : xv::OptionResult::kUnknown;
+  };
+  t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : ScalePost(pos); };
+  return xv::CliMain(argc, argv, t);
+}
