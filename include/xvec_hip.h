@@ -578,6 +578,40 @@ xv_status xv_fgmm_gconsts(int32_t num_gauss, int32_t dim, const float* weights, 
 xv_status xv_ubm_kernel_time(const xv_ubm* diag, const xv_ubm* full, const float* feats, const int32_t* row_off, int32_t n_utts,
                              int32_t n, float min_post, int32_t reps, float* ms5);
 
+/* ---- i-vector extraction (ivector-extract, sid/extract_ivectors.sh:69), without a model context.  Semantics: csrc/ivex.h.
+ * Everything on the device is fp64 on fp32 inputs with summation orders that depend on the utterance and the model alone: an
+ * utterance's results are the same bits alone, in any batch, at any position in it.  Limits: i-vector dimension <= 1024, feature
+ * dimension <= 96.  A model with i-vector-dependent weights (a <w> matrix with rows) is refused by name. */
+typedef struct xv_ivex xv_ivex;
+/* Host arrays: w_vec [G], M [G][D][S], sigma_inv [G][D (D + 1) / 2] (packed lower triangles).  The derived variables SigmaInvM and
+ * U are computed on the device here, once; the workspaces of a launch group are allocated here. */
+xv_status xv_ivex_create(int device, int32_t num_gauss, int32_t feat_dim, int32_t ivector_dim, const double* w_vec, const double* M,
+                         const double* sigma_inv, double prior_offset, xv_ivex** out);
+/* the same from a final.ie, binary or text: "file", "-", "cmd |" */
+xv_status xv_ivex_load(int device, const char* rxfilename, xv_ivex** out);
+void xv_ivex_destroy(xv_ivex* m);
+xv_status xv_ivex_info(const xv_ivex* m, int32_t* num_gauss, int32_t* feat_dim, int32_t* ivector_dim);
+/* downloads sigma_inv_m [G D][S] and U [G][S (S + 1) / 2]; either may be NULL */
+xv_status xv_ivex_derived(const xv_ivex* m, double* sigma_inv_m, double* U);
+/* host buffers, blocking.  feats [row_off[n_utts]][D]; frame t has the pairs post_off[t] .. post_off[t + 1] (post_off has rows + 1
+ * entries) of post_idx (Gaussian, in [0, G): anything else is XV_ERR_IO before anything is uploaded) and post_w.  ivectors
+ * [n_utts][S] and status [n_utts] (0, or 1 for an utterance whose Q is not positive definite: its i-vector is then zero) are
+ * always written; auxf_change [n_utts], gamma [n_utts][G], X [n_utts][G D], linear [n_utts][S] and quadratic
+ * [n_utts][S (S + 1) / 2] (the packed lower triangle of Q) may each be NULL. */
+xv_status xv_ivex_extract(xv_ivex* m, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* post_off,
+                          const int32_t* post_idx, const float* post_w, double acoustic_weight, double max_count, float* ivectors,
+                          int32_t* status, double* auxf_change, double* gamma, double* X, double* linear, double* quadratic);
+/* host only: a model file to host arrays and back (ivector-extractor-copy).  xv_ivex_read fills the three dimensions and whichever
+ * of the arrays are not NULL: call it once for the shape and once for the data. */
+xv_status xv_ivex_read(const char* rxfilename, int32_t* num_gauss, int32_t* feat_dim, int32_t* ivector_dim, double* w_vec, double* M,
+                       double* sigma_inv, double* prior_offset);
+xv_status xv_ivex_write(const char* wxfilename, int32_t binary, int32_t num_gauss, int32_t feat_dim, int32_t ivector_dim, const double* w_vec,
+                        const double* M, const double* sigma_inv, double prior_offset);
+/* the kernels' times in ms, the best of reps runs after one that warms up: ms5 = {statistics (sort included), quadratic GEMM, linear
+ * GEMM (second pass included), solve, the derivation at model creation}; the first four summed over the call's launch groups */
+xv_status xv_ivex_kernel_time(xv_ivex* m, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* post_off,
+                              const int32_t* post_idx, const float* post_w, int32_t reps, float* ms5);
+
 /* ---- kernel-level entries of the frame-level and small kernels (unit tests; same conventions: device pointers from the caller
  * unless stated, an optional stream, XV_ERR_ARG with a reason for geometry a kernel cannot run, no engine or context) ---------- */
 /* tdnn_first_kernel: the layer(s) that read the network input.  Chunk b holds rows [row_offsets[b], row_offsets[b + 1]) of feats

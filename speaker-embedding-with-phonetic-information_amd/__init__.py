@@ -139,6 +139,8 @@ ABI_SYMBOLS = [
     "xv_cmvn_stats", "xv_cmvn_norm", "xv_cmvn_apply", "xv_cmvn_kernel_time",
     "xv_add_deltas", "xv_ubm_diag_create", "xv_ubm_full_create", "xv_ubm_destroy", "xv_ubm_gselect", "xv_ubm_post",
     "xv_fgmm_to_gmm", "xv_fgmm_gconsts", "xv_ubm_kernel_time",
+    "xv_ivex_create", "xv_ivex_load", "xv_ivex_destroy", "xv_ivex_info", "xv_ivex_derived", "xv_ivex_extract", "xv_ivex_read",
+    "xv_ivex_write", "xv_ivex_kernel_time",
     "xv_kernel_first_layer", "xv_kernel_prep_input", "xv_kernel_pool_finalise", "xv_kernel_frame_output",
     "xv_wave_read", "xv_wave_free", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
 ]
@@ -1302,6 +1304,151 @@ def ubm_kernel_time(diag, full, feats_list, n=20, min_post=0.025, reps=5):
                                      ctypes.c_float, ctypes.c_int32, ctypes.c_void_p]
     _check(L.xv_ubm_kernel_time(diag._h, full._h, packed.ctypes.data, off.ctypes.data, len(off) - 1, n, float(min_post), reps, ms))
     return dict(zip(("deltas", "gselect", "sort", "full", "softmax"), [float(x) for x in ms]))
+
+
+def ivex_read(rxfilename):
+    """A final.ie (binary or text; "file", "-", "cmd |") as host arrays: dict(w_vec [G], M [G][D][S], sigma_inv [G][D (D + 1) / 2],
+    prior_offset).  Host only."""
+    import numpy as np
+    L = lib()
+    L.xv_ivex_read.argtypes = [ctypes.c_char_p] + [ctypes.POINTER(ctypes.c_int32)] * 3 + [ctypes.c_void_p] * 3 + [ctypes.POINTER(ctypes.c_double)]
+    g, d, s = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    _check(L.xv_ivex_read(rxfilename.encode(), ctypes.byref(g), ctypes.byref(d), ctypes.byref(s), None, None, None, None))
+    G, D, S = g.value, d.value, s.value
+    w_vec, M, sig = np.zeros(G), np.zeros((G, D, S)), np.zeros((G, D * (D + 1) // 2))
+    p = ctypes.c_double()
+    _check(L.xv_ivex_read(rxfilename.encode(), None, None, None, w_vec.ctypes.data, M.ctypes.data, sig.ctypes.data, ctypes.byref(p)))
+    return dict(w_vec=w_vec, M=M, sigma_inv=sig, prior_offset=p.value)
+
+
+def _ivex_arrays(w_vec, M, sigma_inv, who):
+    import numpy as np
+    M = np.ascontiguousarray(M, dtype=np.float64)
+    w_vec = np.ascontiguousarray(w_vec, dtype=np.float64)
+    sig = np.ascontiguousarray(sigma_inv, dtype=np.float64)
+    if M.ndim != 3 or w_vec.shape != (M.shape[0],) or sig.shape != (M.shape[0], M.shape[1] * (M.shape[1] + 1) // 2):
+        raise XvError(XV_ERR_ARG, who + ": w_vec [G], M [G][D][S], sigma_inv [G][D (D + 1) / 2]")
+    return w_vec, M, sig
+
+
+def ivex_write(wxfilename, w_vec, M, sigma_inv, prior_offset, binary=True):
+    """Host arrays to a final.ie (text: 17 significant digits).  Host only."""
+    L = lib()
+    w_vec, M, sig = _ivex_arrays(w_vec, M, sigma_inv, "ivex_write")
+    L.xv_ivex_write.argtypes = [ctypes.c_char_p] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 3 + [ctypes.c_double]
+    _check(L.xv_ivex_write(wxfilename.encode(), int(bool(binary)), M.shape[0], M.shape[1], M.shape[2], w_vec.ctypes.data, M.ctypes.data,
+                           sig.ctypes.data, float(prior_offset)))
+
+
+def _pack_posteriors(post_list, off, who):
+    """post_list[u][t] = (indices, weights) -> (post_off [rows + 1], post_idx, post_w)"""
+    import numpy as np
+    if len(post_list) != len(off) - 1 or any(len(p) != off[u + 1] - off[u] for u, p in enumerate(post_list)):
+        raise XvError(XV_ERR_ARG, who + ": one posterior per utterance, one (indices, weights) entry per frame")
+    counts = [len(f[0]) for p in post_list for f in p]
+    post_off = np.zeros(len(counts) + 1, dtype=np.int32)
+    np.cumsum(counts, out=post_off[1:])
+    idx = [np.asarray(f[0], dtype=np.int32).reshape(-1) for p in post_list for f in p]
+    w = [np.asarray(f[1], dtype=np.float32).reshape(-1) for p in post_list for f in p]
+    post_idx = np.ascontiguousarray(np.concatenate(idx)) if idx else np.zeros(0, np.int32)
+    post_w = np.ascontiguousarray(np.concatenate(w)) if w else np.zeros(0, np.float32)
+    if post_idx.shape != post_w.shape:
+        raise XvError(XV_ERR_ARG, who + ": a frame's indices and weights have one length")
+    return post_off, post_idx, post_w
+
+
+class IvectorExtractor:
+    """An i-vector extractor on one device (xv_ivex_create / xv_ivex_load): the derived variables are computed there once.
+    IvectorExtractor(w_vec, M, sigma_inv, prior_offset) from host arrays, IvectorExtractor.load(rxfilename) from a final.ie."""
+
+    def __init__(self, w_vec=None, M=None, sigma_inv=None, prior_offset=0.0, device=0, _handle=None):
+        L = lib()
+        self._h = _handle
+        if self._h is None:
+            w_vec, M, sig = _ivex_arrays(w_vec, M, sigma_inv, "IvectorExtractor")
+            L.xv_ivex_create.argtypes = [ctypes.c_int] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 3 + [ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)]
+            h = ctypes.c_void_p()
+            _check(L.xv_ivex_create(device, M.shape[0], M.shape[1], M.shape[2], w_vec.ctypes.data, M.ctypes.data, sig.ctypes.data,
+                                    float(prior_offset), ctypes.byref(h)))
+            self._h = h
+        L.xv_ivex_info.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int32)] * 3
+        g, d, s = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _check(L.xv_ivex_info(self._h, ctypes.byref(g), ctypes.byref(d), ctypes.byref(s)))
+        self.num_gauss, self.feat_dim, self.ivector_dim = g.value, d.value, s.value
+
+    @classmethod
+    def load(cls, rxfilename, device=0):
+        L = lib()
+        L.xv_ivex_load.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
+        h = ctypes.c_void_p()
+        _check(L.xv_ivex_load(device, rxfilename.encode(), ctypes.byref(h)))
+        return cls(_handle=h)
+
+    def close(self):
+        if self._h:
+            L = lib()
+            L.xv_ivex_destroy.argtypes = [ctypes.c_void_p]
+            L.xv_ivex_destroy.restype = None
+            L.xv_ivex_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def derived(self):
+        """(SigmaInvM [G D][S], U [G][S (S + 1) / 2]) as the device computed them."""
+        import numpy as np
+        L = lib()
+        G, D, S = self.num_gauss, self.feat_dim, self.ivector_dim
+        sim, U = np.zeros((G * D, S)), np.zeros((G, S * (S + 1) // 2))
+        L.xv_ivex_derived.argtypes = [ctypes.c_void_p] * 3
+        _check(L.xv_ivex_derived(self._h, sim.ctypes.data, U.ctypes.data))
+        return sim, U
+
+    def _inputs(self, feats_list, post_list, who):
+        packed, off, cols = _pack_matrices(feats_list, who)
+        if cols != self.feat_dim:
+            raise XvError(XV_ERR_ARG, "%s: the features have %d columns, the model %d" % (who, cols, self.feat_dim))
+        return (packed, off) + _pack_posteriors(post_list, off, who)
+
+    def extract(self, feats_list, post_list, return_details=False, acoustic_weight=1.0, max_count=0.0):
+        """feats_list[u]: float32 [frames, D]; post_list[u][t] = (Gaussian indices, posteriors) of frame t.  Returns (ivectors
+        float32 [n, S], status int32 [n], auxf_change float64 [n]); return_details: also a dict of gamma [n, G], X [n, G D],
+        linear [n, S] and quadratic [n, S, S] (Q, symmetric), all float64 as the device formed them."""
+        import numpy as np
+        L = lib()
+        packed, off, post_off, post_idx, post_w = self._inputs(feats_list, post_list, "extract")
+        n, G, D, S = len(off) - 1, self.num_gauss, self.feat_dim, self.ivector_dim
+        P = S * (S + 1) // 2
+        iv, status, auxf = np.zeros((n, S), np.float32), np.zeros(n, np.int32), np.zeros(n)
+        det = dict(gamma=np.zeros((n, G)), X=np.zeros((n, G * D)), linear=np.zeros((n, S)), quadratic=np.zeros((n, P))) if return_details else {}
+        ptr = lambda k: det[k].ctypes.data if return_details else None
+        L.xv_ivex_extract.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 7
+        _check(L.xv_ivex_extract(self._h, packed.ctypes.data, off.ctypes.data, n, post_off.ctypes.data, post_idx.ctypes.data,
+                                 post_w.ctypes.data, float(acoustic_weight), float(max_count), iv.ctypes.data, status.ctypes.data,
+                                 auxf.ctypes.data, ptr("gamma"), ptr("X"), ptr("linear"), ptr("quadratic")))
+        if not return_details:
+            return iv, status, auxf
+        r, c = np.tril_indices(S)
+        Q = np.zeros((n, S, S))
+        Q[:, r, c] = det["quadratic"]
+        Q[:, c, r] = det["quadratic"]
+        det["quadratic"] = Q
+        return iv, status, auxf, det
+
+    def kernel_time(self, feats_list, post_list, reps=5):
+        """{stats, quadratic, linear, solve, derive} kernel times in ms of one call (xv_ivex_kernel_time: the best of reps)."""
+        L = lib()
+        packed, off, post_off, post_idx, post_w = self._inputs(feats_list, post_list, "kernel_time")
+        ms = (ctypes.c_float * 5)()
+        L.xv_ivex_kernel_time.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int32] + [ctypes.c_void_p] * 3 + [ctypes.c_int32, ctypes.c_void_p]
+        _check(L.xv_ivex_kernel_time(self._h, packed.ctypes.data, off.ctypes.data, len(off) - 1, post_off.ctypes.data, post_idx.ctypes.data,
+                                     post_w.ctypes.data, reps, ms))
+        return dict(zip(("stats", "quadratic", "linear", "solve", "derive"), [float(x) for x in ms]))
 
 
 def kernel_tdnn_gemm(desc):

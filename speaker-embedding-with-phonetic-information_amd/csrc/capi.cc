@@ -27,6 +27,7 @@
 #include "plda_kernels.h"
 #include "program.h"
 #include "table_extract.h"
+#include "ivex.h"
 #include "ubm.h"
 
 struct xv_model {
@@ -1104,6 +1105,138 @@ xv_status xv_ubm_kernel_time(const xv_ubm* diag, const xv_ubm* full, const float
       for (int i = 0; i < 5; ++i)
         if (r == 1 || (r > 1 && ms[i] < ms5[i])) ms5[i] = ms[i];
     }
+    return XV_OK;
+  });
+}
+
+struct xv_ivex {
+  std::unique_ptr<xv::IvexModel> m;
+};
+
+namespace {
+
+void FillIvexData(int32_t G, int32_t D, int32_t S, const double* w_vec, const double* M, const double* sigma_inv, double prior_offset, xv::IvexData* d) {
+  if (G < 1 || D < 1 || S < 1 || !w_vec || !M || !sigma_inv) throw xv::KioError("i-vector extractor: bad argument");
+  d->G = G;
+  d->D = D;
+  d->S = S;
+  d->w_vec.assign(w_vec, w_vec + G);
+  d->M.assign(M, M + (size_t)G * D * S);
+  d->sigma_inv.assign(sigma_inv, sigma_inv + (size_t)G * ((size_t)D * (D + 1) / 2));
+  d->prior_offset = prior_offset;
+}
+
+}  // namespace
+
+xv_status xv_ivex_create(int device, int32_t num_gauss, int32_t feat_dim, int32_t ivector_dim, const double* w_vec, const double* M,
+                         const double* sigma_inv, double prior_offset, xv_ivex** out) {
+  if (!out) return Fail(XV_ERR_ARG, "xv_ivex_create: bad argument");
+  return Guard([&] {
+    xv::IvexData d;
+    FillIvexData(num_gauss, feat_dim, ivector_dim, w_vec, M, sigma_inv, prior_offset, &d);
+    std::unique_ptr<xv_ivex> h(new xv_ivex);
+    h->m.reset(xv::IvexCreate(device, d));
+    *out = h.release();
+    return XV_OK;
+  });
+}
+
+xv_status xv_ivex_load(int device, const char* rxfilename, xv_ivex** out) {
+  if (!out || !rxfilename) return Fail(XV_ERR_ARG, "xv_ivex_load: bad argument");
+  return Guard([&] {
+    xv::IvexData d;
+    xv::ReadIvexFile(rxfilename, &d);
+    std::unique_ptr<xv_ivex> h(new xv_ivex);
+    h->m.reset(xv::IvexCreate(device, d));
+    *out = h.release();
+    return XV_OK;
+  });
+}
+
+void xv_ivex_destroy(xv_ivex* m) { delete m; }
+
+xv_status xv_ivex_info(const xv_ivex* m, int32_t* num_gauss, int32_t* feat_dim, int32_t* ivector_dim) {
+  if (!m) return Fail(XV_ERR_ARG, "xv_ivex_info: bad argument");
+  if (num_gauss) *num_gauss = m->m->num_gauss();
+  if (feat_dim) *feat_dim = m->m->feat_dim();
+  if (ivector_dim) *ivector_dim = m->m->ivector_dim();
+  return XV_OK;
+}
+
+xv_status xv_ivex_derived(const xv_ivex* m, double* sigma_inv_m, double* U) {
+  if (!m) return Fail(XV_ERR_ARG, "xv_ivex_derived: bad argument");
+  return Guard([&] {
+    xv::IvexDerived(*m->m, sigma_inv_m, U);
+    return XV_OK;
+  });
+}
+
+xv_status xv_ivex_extract(xv_ivex* m, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* post_off,
+                          const int32_t* post_idx, const float* post_w, double acoustic_weight, double max_count, float* ivectors,
+                          int32_t* status, double* auxf_change, double* gamma, double* X, double* linear, double* quadratic) {
+  if (!m || !row_off || n_utts < 0) return Fail(XV_ERR_ARG, "xv_ivex_extract: bad argument");
+  return Guard([&] {
+    xv::IvexOutputs o;
+    o.ivectors = ivectors;
+    o.status = status;
+    o.auxf_change = auxf_change;
+    o.gamma = gamma;
+    o.X = X;
+    o.linear = linear;
+    o.quadratic = quadratic;
+    xv::IvexExtract(*m->m, feats, row_off, n_utts, post_off, post_idx, post_w, acoustic_weight, max_count, o);
+    return XV_OK;
+  });
+}
+
+xv_status xv_ivex_read(const char* rxfilename, int32_t* num_gauss, int32_t* feat_dim, int32_t* ivector_dim, double* w_vec, double* M,
+                       double* sigma_inv, double* prior_offset) {
+  if (!rxfilename) return Fail(XV_ERR_ARG, "xv_ivex_read: bad argument");
+  return Guard([&] {
+    xv::IvexData d;
+    xv::ReadIvexFile(rxfilename, &d);
+    if (num_gauss) *num_gauss = d.G;
+    if (feat_dim) *feat_dim = d.D;
+    if (ivector_dim) *ivector_dim = d.S;
+    if (w_vec) std::copy(d.w_vec.begin(), d.w_vec.end(), w_vec);
+    if (M) std::copy(d.M.begin(), d.M.end(), M);
+    if (sigma_inv) std::copy(d.sigma_inv.begin(), d.sigma_inv.end(), sigma_inv);
+    if (prior_offset) *prior_offset = d.prior_offset;
+    return XV_OK;
+  });
+}
+
+xv_status xv_ivex_write(const char* wxfilename, int32_t binary, int32_t num_gauss, int32_t feat_dim, int32_t ivector_dim, const double* w_vec,
+                        const double* M, const double* sigma_inv, double prior_offset) {
+  if (!wxfilename) return Fail(XV_ERR_ARG, "xv_ivex_write: bad argument");
+  return Guard([&] {
+    xv::IvexData d;
+    FillIvexData(num_gauss, feat_dim, ivector_dim, w_vec, M, sigma_inv, prior_offset, &d);
+    xv::WriteIvexFile(wxfilename, binary != 0, d);
+    return XV_OK;
+  });
+}
+
+xv_status xv_ivex_kernel_time(xv_ivex* m, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* post_off,
+                              const int32_t* post_idx, const float* post_w, int32_t reps, float* ms5) {
+  if (!m || !feats || !row_off || !post_off || n_utts < 1 || reps < 1 || !ms5) return Fail(XV_ERR_ARG, "xv_ivex_kernel_time: bad argument");
+  return Guard([&] {
+    const int S = m->m->ivector_dim();
+    std::vector<float> iv((size_t)n_utts * S);
+    std::vector<int32_t> status((size_t)n_utts);
+    std::vector<double> auxf((size_t)n_utts);
+    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
+      float ms[4] = {0.f, 0.f, 0.f, 0.f};
+      xv::IvexOutputs o;
+      o.ivectors = iv.data();
+      o.status = status.data();
+      o.auxf_change = auxf.data();
+      o.device_ms4 = ms;
+      xv::IvexExtract(*m->m, feats, row_off, n_utts, post_off, post_idx, post_w, 1.0, 0.0, o);
+      for (int i = 0; i < 4; ++i)
+        if (r == 1 || (r > 1 && ms[i] < ms5[i])) ms5[i] = ms[i];
+    }
+    ms5[4] = m->m->derive_ms();
     return XV_OK;
   });
 }

@@ -1,0 +1,252 @@
+// ivector-extract / ivector-extractor-copy - drop-in command lines for the last step of the GMM-UBM i-vector baseline
+// (egs/sre/v1: sid/extract_ivectors.sh:69).  One executable, dispatching on its name:
+//   ivector-extract [--compute-objf-change=true --acoustic-weight=1.0 --max-count=0 --num-threads=N] <model-rxfilename>
+//                   <feature-rspecifier> <posterior-rspecifier> <ivector-wspecifier>
+//   ivector-extractor-copy [--binary=true] <model-in> <model-out>
+// ivector-extract runs on the device (ivex.h) and fails without a GPU (exit 255); the copy is host code and opens no device.
+// --num-threads is accepted and ignored; --spk2utt is refused by name, and so is a model with i-vector-dependent weights.
+// Features are read ahead in batches, so the recipes' "ark,s,cs:add-deltas ... | select-voiced-frames ... |" is a child pipeline read
+// front to back; a posterior table that promised sorted keys (s) is merged against the feature keys, any other is loaded.
+// Per utterance, warned, counted and skipped: no posterior, a posterior of another length than the features, no rows, a Q that
+// is not positive definite.  Fatal (exit 255): a feature width that is not the model's, a Gaussian index outside the model, no GPU.
+#include <math.h>
+#include <stdlib.h>
+
+#include <memory>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "cli.h"
+#include "cmvn.h"
+#include "ivex.h"
+#include "kio.h"
+
+namespace {
+
+constexpr int64_t kBatchFrames = 1 << 16;   // frames read ahead per device call
+
+// The posterior of a key: a table that promised sorted keys (s) is merged front to back, any other is loaded.
+class PosteriorLookup {
+ public:
+  explicit PosteriorLookup(const std::string& rspecifier) : reader_(rspecifier) {
+    if (reader_.sorted()) return;
+    std::string key, err;
+    xv::Posterior v;
+    while (reader_.Next(&key, &v, &err)) {
+      if (!err.empty()) XWARN("Failed to read the posterior of " << key << ": " << err);
+      else all_.emplace(key, std::move(v));
+    }
+  }
+  bool Find(const std::string& key, xv::Posterior* out) {
+    if (!reader_.sorted()) {
+      auto it = all_.find(key);
+      if (it == all_.end()) return false;
+      *out = it->second;
+      return true;
+    }
+    for (;;) {
+      if (!held_) {
+        std::string err;
+        if (eof_ || !reader_.Next(&held_key_, &held_v_, &err)) {
+          eof_ = true;
+          return false;
+        }
+        if (!err.empty()) {
+          XWARN("Failed to read the posterior of " << held_key_ << ": " << err);
+          continue;
+        }
+        held_ = true;
+      }
+      const int c = held_key_.compare(key);
+      if (c > 0) return false;   // the table is past the key
+      held_ = false;
+      if (c == 0) {
+        *out = std::move(held_v_);
+        return true;
+      }
+    }
+  }
+
+ private:
+  xv::SequentialPosteriorReader reader_;
+  std::unordered_map<std::string, xv::Posterior> all_;
+  bool held_ = false, eof_ = false;
+  std::string held_key_;
+  xv::Posterior held_v_;
+};
+
+struct ExtractOptions {
+  bool compute_objf_change = true;
+  double acoustic_weight = 1.0, max_count = 0.0;
+  int verbose = 0, device = -1;
+};
+
+int IvectorExtract(const ExtractOptions& o, const std::vector<std::string>& pos) {
+  xv::IvexData data;
+  xv::ReadIvexFile(pos[0], &data);
+  const int dev = xv::PickDevice(o.device);
+  std::unique_ptr<xv::IvexModel> model(xv::IvexCreate(dev, data));
+  const int D = data.D, S = data.S;
+  xv::FeatBatchReader reader(pos[1], kBatchFrames, false);
+  PosteriorLookup posts(pos[2]);
+  xv::TableWriter writer(pos[3]);
+  long num_done = 0, num_err = 0;
+  double tot_t = 0.0, tot_auxf = 0.0;
+  xv::FeatBatchReader::Batch b;
+  std::vector<xv::FeatBatchReader::Problem> problems;
+  std::vector<std::string> keys;
+  std::vector<float> feats, post_w, ivectors;
+  std::vector<int32_t> off, post_off, post_idx, status;
+  std::vector<double> auxf, weighted;
+  for (bool more = true; more;) {
+    problems.clear();
+    more = reader.Next(&b, &problems);
+    for (const auto& p : problems) {
+      if (p.what.empty()) XWARN("Empty feature matrix for utterance " << p.key);
+      else XWARN("Failed to read features for key " << p.key << ": " << p.what);
+      ++num_err;
+    }
+    if (!more) break;
+    if (b.cols != D)
+      throw xv::KioError("Feature dimension mismatch: the features of " + b.keys[0] + " have " + std::to_string(b.cols) + " columns, the model " + std::to_string(D));
+    keys.clear();
+    feats.clear();
+    post_w.clear();
+    post_idx.clear();
+    weighted.clear();
+    off.assign(1, 0);
+    post_off.assign(1, 0);
+    for (size_t u = 0; u < b.keys.size(); ++u) {
+      const int rows = b.row_off[u + 1] - b.row_off[u];
+      xv::Posterior p;
+      if (!posts.Find(b.keys[u], &p)) {
+        XWARN("No posteriors for utterance " << b.keys[u]);
+        ++num_err;
+        continue;
+      }
+      if ((int)p.size() != rows) {
+        XWARN("Size mismatch between posterior " << p.size() << " and features " << rows << " for utterance " << b.keys[u]);
+        ++num_err;
+        continue;
+      }
+      const size_t first = post_w.size();
+      for (const auto& frame : p) {
+        for (const auto& e : frame) {
+          post_idx.push_back(e.first);
+          post_w.push_back(e.second);
+        }
+        post_off.push_back((int32_t)post_w.size());
+      }
+      bool clipped = false;
+      const float scale = xv::IvexPosteriorScale(post_w.data() + first, post_w.size() - first, o.acoustic_weight, o.max_count, &clipped);
+      if (clipped) XLOG("Scaling stats for utterance " << b.keys[u] << " by scale " << scale << " due to --max-count=" << o.max_count);
+      double t = 0.0;
+      for (size_t i = first; i < post_w.size(); ++i) t += (double)(post_w[i] * scale);
+      weighted.push_back(t);
+      keys.push_back(b.keys[u]);
+      feats.insert(feats.end(), b.feats.begin() + (size_t)b.row_off[u] * D, b.feats.begin() + (size_t)b.row_off[u + 1] * D);
+      off.push_back(off.back() + rows);
+    }
+    if (keys.empty()) continue;
+    const int n = (int)keys.size();
+    ivectors.resize((size_t)n * S);
+    status.resize((size_t)n);
+    auxf.assign((size_t)n, 0.0);
+    xv::IvexOutputs out;
+    out.ivectors = ivectors.data();
+    out.status = status.data();
+    out.auxf_change = o.compute_objf_change ? auxf.data() : nullptr;
+    xv::IvexExtract(*model, feats.data(), off.data(), n, post_off.data(), post_idx.data(), post_w.data(), o.acoustic_weight, o.max_count, out);
+    for (int u = 0; u < n; ++u) {
+      if (status[u] != 0) {
+        XWARN("The quadratic term of utterance " << keys[u] << " is not positive definite: no i-vector (skipping utterance)");
+        ++num_err;
+        continue;
+      }
+      const float* v = ivectors.data() + (size_t)u * S;
+      const double T = weighted[u];
+      if (o.compute_objf_change) {
+        tot_auxf += auxf[u];
+        if (o.verbose >= 2)
+          XLOG("Auxf change for utterance " << keys[u] << " was " << (T != 0.0 ? auxf[u] / T : 0.0) << " per frame over " << T << " frames (weighted)");
+      }
+      if (o.verbose >= 2) {
+        double norm = 0.0;
+        for (int s = 0; s < S; ++s) norm += (double)v[s] * (double)v[s];
+        XLOG("Ivector norm for utterance " << keys[u] << " was " << sqrt(norm));
+      }
+      tot_t += T;
+      writer.WriteVec(keys[u], v, S);
+      ++num_done;
+    }
+  }
+  writer.Close();
+  XLOG("Done " << num_done << " files, " << num_err << " with errors.  Total (weighted) frames " << tot_t);
+  if (o.compute_objf_change)
+    XLOG("Overall average objective-function change from estimating ivector was " << (tot_t != 0.0 ? tot_auxf / tot_t : 0.0) << " per frame  over "
+                                                                                    << tot_t << " (weighted) frames.");
+  return num_done != 0 ? 0 : 1;
+}
+
+int ExtractorCopy(bool binary, const std::vector<std::string>& pos) {
+  xv::IvexData m;
+  xv::ReadIvexFile(pos[0], &m);
+  xv::WriteIvexFile(pos[1], binary, m);
+  XLOG("Copied the i-vector extractor to " << pos[1]);
+  return 0;
+}
+
+double ToDouble(const std::string& name, const std::string& v) {
+  double d;
+  if (!xv::ParseDouble(v, &d)) throw xv::KioError("Invalid floating-point option --" + name + "=" + v);
+  return d;
+}
+
+std::string Dashes(std::string n) {
+  for (char& c : n)
+    if (c == '_') c = '-';
+  return n;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  const std::string prog = xv::ProgramName(argv[0]);
+  xv::CliTool t;
+  t.config_file = false;
+  if (prog.find("ivector-extractor-copy") != std::string::npos) {
+    bool binary = true;
+    t.usage = "Copy the i-vector extractor to a different file (possibly changing binary/text format).\n"
+              "Usage: ivector-extractor-copy [options] <ivector-extractor-in> <ivector-extractor-out>\nOptions: --binary (true)\n";
+    t.set = [&](const std::string& name, const std::string& val) {
+      const std::string n = Dashes(name);
+      if (n == "verbose" || n == "print-args" || n == "config") return xv::OptionResult::kOk;
+      if (n == "binary") binary = xv::ToBool(n, val);
+      else return xv::OptionResult::kUnknown;
+      return xv::OptionResult::kOk;
+    };
+    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : ExtractorCopy(binary, pos); };
+    return xv::CliMain(argc, argv, t);
+  }
+  ExtractOptions o;
+  t.usage = "Extract iVectors for utterances, using a trained iVector extractor, and features and Gaussian-level posteriors.\n"
+            "Usage: ivector-extract [options] <model-in> <feature-rspecifier> <posterior-rspecifier> <ivector-wspecifier>\n"
+            "e.g.: fgmm-global-gselect-to-post 1.ubm '$feats' 'ark:gunzip -c gselect.1.gz|' ark:- | ivector-extract final.ie '$feats' ark,s,cs:- ark,t:ivectors.1.ark\n"
+            "Options: --compute-objf-change (true) --acoustic-weight (1.0) --max-count (0) --num-threads (accepted, ignored) --verbose --device=<gpu>\n"
+            "Limits: i-vector dimension <= 1024, feature dimension <= 96.  Not built (refused): --spk2utt, models with i-vector-dependent weights.\n";
+  t.set = [&](const std::string& name, const std::string& val) {
+    const std::string n = Dashes(name);
+    if (n == "print-args" || n == "config" || n == "num-threads") return xv::OptionResult::kOk;
+    if (n == "verbose") o.verbose = xv::ToInt(n, val);
+    else if (n == "compute-objf-change") o.compute_objf_change = xv::ToBool(n, val);
+    else if (n == "acoustic-weight") o.acoustic_weight = ToDouble(n, val);
+    else if (n == "max-count") o.max_count = ToDouble(n, val);
+    else if (n == "device") o.device = xv::ToInt(n, val);
+    else if (n == "spk2utt") throw xv::KioError("--spk2utt is not built: no script of the recipes passes it (they average per speaker with ivector-mean)");
+    else return xv::OptionResult::kUnknown;
+    return xv::OptionResult::kOk;
+  };
+  t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 4 ? xv::kUsageError : IvectorExtract(o, pos); };
+  return xv::CliMain(argc, argv, t);
+}

@@ -12,6 +12,7 @@
 // are host code and open no device (the three copies rewrite a model or a table, recomputing a model's gconsts on the way).  Models are rxfilenames ("final.ubm", "-", "fgmm-global-to-gmm final.ubm -|"); features
 // are read ahead in batches, so the recipes' "ark,s,cs:add-deltas ... | apply-cmvn-sliding ... | select-voiced-frames ... |" is
 // a child pipeline read front to back.  Refused by name: gmm-gselect --write-likes and --gselect.
+// ivector-extract, line 69 of that script, takes the posteriors from here: ivex_tools_main.cc.
 #include <math.h>
 #include <stdlib.h>
 
