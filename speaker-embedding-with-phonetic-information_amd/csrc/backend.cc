@@ -5,32 +5,13 @@
 #include <string>
 
 #include "cli.h"
-#include "engine.h"
+#include "device.h"
 #include "kernels.h"
 
 namespace xv {
 namespace {
 
-void Check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw EngineError(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-// Device buffer that frees itself.
-struct DevBuf {
-  void* p = nullptr;
-  explicit DevBuf(size_t n) { Check(hipMalloc(&p, n ? n : 4), "hipMalloc"); }
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-};
-
-void UseDevice(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-    throw EngineError("no HIP device available: the back-end kernels need a gfx950 GPU (there is no CPU path)");
-  if (device < 0 || device >= n) throw EngineError("device index out of range");
-  Check(hipSetDevice(device), "hipSetDevice");
-}
+const char kWhoNeeds[] = "the back-end kernels need";
 
 }  // namespace
 
@@ -39,7 +20,7 @@ void BackendApply(int device, const float* x, int n, int dim, const BackendOptio
   if (opt.transform && opt.t_cols != dim && opt.t_cols != dim + 1)
     throw EngineError("Dimension mismatch: input vector has dimension " + std::to_string(dim) + " and transform has " +
                       std::to_string(opt.t_cols) + " columns");
-  UseDevice(device);
+  UseDevice(device, kWhoNeeds);
   if (n == 0) return;
   const int out_dim = opt.transform ? opt.t_rows : dim;
   DevBuf dx((size_t)n * dim * 4), dout((size_t)n * out_dim * 4), dratio((size_t)n * 4);
@@ -69,7 +50,7 @@ void BackendApply(int device, const float* x, int n, int dim, const BackendOptio
 void SegmentMean(int device, const float* x, int n, int dim, const int32_t* seg_off, const int32_t* idx, int n_seg,
                  bool acc64, float* out) {
   if (n < 0 || dim < 1 || n_seg < 0) throw EngineError("SegmentMean: bad shape");
-  UseDevice(device);
+  UseDevice(device, kWhoNeeds);
   if (n_seg == 0) return;
   const int n_idx = seg_off[n_seg];
   for (int i = 0; i < n_idx; ++i)

@@ -7,7 +7,7 @@
 #include <string.h>
 
 #include "cmvn_kernels.h"
-#include "engine.h"
+#include "device.h"
 #include "kernels.h"
 
 // CmvnNorm is compared with tests/cmvn_ref.py for equality: var = s / n - mean * mean in two roundings, not a fused one
@@ -16,83 +16,28 @@
 namespace xv {
 namespace {
 
-void Check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw EngineError(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  void Alloc(size_t n) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    Check(hipMalloc(&p, n ? n : 8), "hipMalloc");
-  }
-  void Upload(const void* src, size_t n, const char* what) {
-    Alloc(n);
-    if (n) Check(hipMemcpy(p, src, n, hipMemcpyHostToDevice), what);
-  }
-  template <typename T>
-  void Upload(const std::vector<T>& v, const char* what) { Upload(v.data(), v.size() * sizeof(T), what); }
-  template <typename T> T* as() const { return (T*)p; }
-};
-
-struct Events {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  explicit Events(bool on) {
-    if (!on) return;
-    Check(hipEventCreate(&e0), "hipEventCreate");
-    Check(hipEventCreate(&e1), "hipEventCreate");
-  }
-  ~Events() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-  void Start() { if (e0) Check(hipEventRecord(e0, nullptr), "hipEventRecord"); }
-  void Stop(float* ms) {
-    if (!e1) return;
-    Check(hipEventRecord(e1, nullptr), "hipEventRecord");
-    Check(hipEventSynchronize(e1), "hipEventSynchronize");
-    Check(hipEventElapsedTime(ms, e0, e1), "hipEventElapsedTime");
-  }
-};
-
-void UseDevice(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-    throw EngineError("no HIP device available: the CMVN kernels need a gfx950 GPU (there is no CPU path)");
-  if (device < 0 || device >= n) throw EngineError("device index out of range");
-  Check(hipSetDevice(device), "hipSetDevice");
-}
+const char kWhoNeeds[] = "the CMVN kernels need";
 
 // The batch on the device: row offsets, the float rows (uploaded, or expanded from the stored objects) and the work items of
 // the matrices that take part (keep == nullptr: all of them).
 struct DeviceBatch {
-  DevBuf feats, row_off, item_mat, item_blk, mat_item0, cm, cm_off;
+  DevBuf feats, row_off, mat_item0, cm, cm_off;
+  WorkItems items;
   std::vector<int32_t> h_item0;
   int n_items = 0;
   CmvnArgs args;
   DeviceBatch(const char* who, const float* host_feats, const int32_t* off, int n, int cols, const CmvnCompressed* c,
               const int32_t* keep) {
-    if (off[0] != 0) throw KioError(std::string(who) + ": row offsets must start at 0");
-    std::vector<int32_t> mat, blk;
+    CheckOffsets(who, off, n);
     h_item0.assign(1, 0);
     int max_rows = 0;
     for (int u = 0; u < n; ++u) {
       const int rows = off[u + 1] - off[u];
-      if (rows < 0) throw KioError(std::string(who) + ": row offsets must not decrease");
       max_rows = rows > max_rows ? rows : max_rows;
-      if (!keep || keep[u] >= 0)
-        for (int b = 0; b < (rows + kCmvnRowBlock - 1) / kCmvnRowBlock; ++b) {
-          mat.push_back(u);
-          blk.push_back(b);
-        }
-      h_item0.push_back((int32_t)mat.size());
+      if (!keep || keep[u] >= 0) items.Add(u, CeilDiv(rows, kCmvnRowBlock));
+      h_item0.push_back(items.size());
     }
-    n_items = (int)mat.size();
+    n_items = items.size();
     const size_t total = (size_t)off[n] * cols;
     memset(&args, 0, sizeof args);
     row_off.Upload(off, (size_t)(n + 1) * 4, "copy row offsets");
@@ -123,15 +68,14 @@ struct DeviceBatch {
       if (total && !host_feats) throw KioError(std::string(who) + ": null input");
       feats.Upload(host_feats, total * 4, "copy features");
     }
-    item_mat.Upload(mat, "copy work items");
-    item_blk.Upload(blk, "copy work items");
+    items.Upload();
     mat_item0.Upload(h_item0, "copy work items");
     args.feats = feats.as<float>();
     args.row_off = row_off.as<int32_t>();
     args.n = n;
     args.cols = cols;
-    args.item_mat = item_mat.as<int32_t>();
-    args.item_blk = item_blk.as<int32_t>();
+    args.item_mat = items.d_unit.as<int32_t>();
+    args.item_blk = items.d_blk.as<int32_t>();
     args.n_items = n_items;
     args.mat_item0 = mat_item0.as<int32_t>();
   }
@@ -206,7 +150,7 @@ void CmvnStats(int device, const float* feats, const int32_t* row_off, int n, in
   if (device_ms) *device_ms = 0.f;
   if (n < 0 || cols < 1 || !row_off || (n > 0 && !stats)) throw KioError("cmvn-stats: bad argument");
   if (n == 0) return;
-  UseDevice(device);
+  UseDevice(device, kWhoNeeds);
   DeviceBatch b("cmvn-stats", feats, row_off, n, cols, cm, nullptr);
   DevBuf partial, d_stats;
   partial.Alloc((size_t)b.n_items * 2 * cols * 8);
@@ -214,11 +158,11 @@ void CmvnStats(int device, const float* feats, const int32_t* row_off, int n, in
   d_stats.Alloc(sbytes);
   b.args.partial = partial.as<double>();
   b.args.stats = d_stats.as<double>();
-  Events ev(device_ms != nullptr);
-  ev.Start();
+  EventTimer tm(device_ms != nullptr);
+  tm.Start();
   Check(launch_cmvn_stats(b.args, nullptr), "cmvn_stats launch");
-  ev.Stop(device_ms);
-  Check(hipMemcpy(stats, d_stats.p, sbytes, hipMemcpyDeviceToHost), "copy statistics");
+  if (device_ms) *device_ms = tm.Stop();
+  d_stats.Download(stats, sbytes, "copy statistics");
 }
 
 void CmvnApply(int device, const float* feats, const int32_t* row_off, int n, int cols, const float* norms, int n_norms,
@@ -230,7 +174,7 @@ void CmvnApply(int device, const float* feats, const int32_t* row_off, int n, in
   for (int u = 0; u < n; ++u)
     if (utt_norm[u] < -1 || utt_norm[u] >= n_norms) throw KioError("cmvn-apply: a matrix names a norm that is not in the table");
   if (n_norms > 0 && !norms) throw KioError("cmvn-apply: null norm table");
-  UseDevice(device);
+  UseDevice(device, kWhoNeeds);
   DeviceBatch b("cmvn-apply", feats, row_off, n, cols, cm, utt_norm);
   if (b.n_items == 0) return;
   const size_t bytes = (size_t)row_off[n] * cols * 4;
@@ -241,10 +185,10 @@ void CmvnApply(int device, const float* feats, const int32_t* row_off, int n, in
   b.args.norms = d_norms.as<float>();
   b.args.utt_norm = d_utt_norm.as<int32_t>();
   b.args.out = d_out.as<float>();
-  Events ev(device_ms != nullptr);
-  ev.Start();
+  EventTimer tm(device_ms != nullptr);
+  tm.Start();
   Check(launch_cmvn_apply(b.args, nullptr), "cmvn_apply launch");
-  ev.Stop(device_ms);
+  if (device_ms) *device_ms = tm.Stop();
   // rows of the matrices that were left out hold nothing: only the others are copied back
   Check(hipDeviceSynchronize(), "hipDeviceSynchronize");
   for (int u = 0; u < n; ++u) {

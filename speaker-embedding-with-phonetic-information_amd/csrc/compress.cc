@@ -4,63 +4,11 @@
 #include <string.h>
 
 #include "compress_kernels.h"
+#include "device.h"
 #include "engine.h"
 #include "kio.h"
 
 namespace xv {
-namespace {
-
-void Check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw EngineError(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  void Alloc(size_t n) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    Check(hipMalloc(&p, n ? n : 8), "hipMalloc");
-  }
-  template <typename T>
-  void Upload(const std::vector<T>& v, const char* what) {
-    Alloc(v.size() * sizeof(T));
-    if (!v.empty()) Check(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice), what);
-  }
-  template <typename T> T* as() const { return (T*)p; }
-};
-
-void UseDevice(int device, const char* what) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-    throw EngineError(std::string("no HIP device available: ") + what + " need a gfx950 GPU (there is no CPU path)");
-  if (device < 0 || device >= n) throw EngineError("device index out of range");
-  Check(hipSetDevice(device), "hipSetDevice");
-}
-
-// Work items (matrix, block) of one launch.
-struct Items {
-  std::vector<int32_t> mat, blk;
-  DevBuf d_mat, d_blk;
-  void Add(int u, int64_t blocks) {
-    for (int64_t b = 0; b < blocks; ++b) {
-      mat.push_back(u);
-      blk.push_back((int32_t)b);
-    }
-  }
-  int size() const { return (int)mat.size(); }
-  void Upload() {
-    d_mat.Upload(mat, "copy work items");
-    d_blk.Upload(blk, "copy work items");
-  }
-};
-
-int64_t CeilDiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-}  // namespace
 
 std::string CompressionMethodError(int method) {
   if (method == 1 || method == 2 || method == 3 || method == 5) return "";
@@ -93,7 +41,7 @@ void CompressMatrices(int device, const float* feats, const int32_t* row_off, in
   std::vector<int64_t> dev_off(n);
   int64_t dev_total = 0;
   out_off[0] = 0;
-  Items minmax, select, encode;
+  WorkItems minmax, select, encode;
   for (int u = 0; u < n; ++u) {
     const int rows = row_off[u + 1] - row_off[u];
     if (rows < 0) throw KioError("compress: row offsets must not decrease");
@@ -113,11 +61,10 @@ void CompressMatrices(int device, const float* feats, const int32_t* row_off, in
   std::vector<uint8_t> host((size_t)dev_total, 0);
   if (encode.size() > 0) {
     if (!feats) throw KioError("compress: null input");
-    UseDevice(device, "the compression kernels");
+    UseDevice(device, "the compression kernels need");
     DevBuf d_feats, d_row_off, d_obj_off, d_stats, d_out;
     const size_t total_rows = (size_t)row_off[n];
-    d_feats.Alloc(total_rows * cols * 4);
-    Check(hipMemcpy(d_feats.p, feats, total_rows * cols * 4, hipMemcpyHostToDevice), "copy features");
+    d_feats.Upload(feats, total_rows * cols * 4, "copy features");
     d_row_off.Upload(std::vector<int32_t>(row_off, row_off + n + 1), "copy row offsets");
     d_obj_off.Upload(dev_off, "copy object offsets");
     CmpStats init;
@@ -139,44 +86,28 @@ void CompressMatrices(int device, const float* feats, const int32_t* row_off, in
     a.n = n;
     a.cols = cols;
     a.method = method;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (device_ms) {
-      Check(hipEventCreate(&e0), "hipEventCreate");
-      Check(hipEventCreate(&e1), "hipEventCreate");
+    EventTimer tm(device_ms != nullptr);
+    d_stats.Upload(stats0, "copy statistics");
+    a.stats = d_stats.as<CmpStats>();
+    tm.Start();
+    a.item_mat = minmax.d_unit.as<int32_t>();
+    a.item_blk = minmax.d_blk.as<int32_t>();
+    a.n_items = minmax.size();
+    Check(launch_cmp_minmax(a, nullptr), "minimum / maximum kernel launch");
+    if (select.size() > 0) {
+      a.item_mat = select.d_unit.as<int32_t>();
+      a.item_blk = select.d_blk.as<int32_t>();
+      a.n_items = select.size();
+      Check(launch_cmp_select(a, nullptr), "selection kernel launch");
     }
-    try {
-      d_stats.Upload(stats0, "copy statistics");
-      a.stats = d_stats.as<CmpStats>();
-      if (device_ms) Check(hipEventRecord(e0, nullptr), "hipEventRecord");
-      a.item_mat = minmax.d_mat.as<int32_t>();
-      a.item_blk = minmax.d_blk.as<int32_t>();
-      a.n_items = minmax.size();
-      Check(launch_cmp_minmax(a, nullptr), "minimum / maximum kernel launch");
-      if (select.size() > 0) {
-        a.item_mat = select.d_mat.as<int32_t>();
-        a.item_blk = select.d_blk.as<int32_t>();
-        a.n_items = select.size();
-        Check(launch_cmp_select(a, nullptr), "selection kernel launch");
-      }
-      a.item_mat = encode.d_mat.as<int32_t>();
-      a.item_blk = encode.d_blk.as<int32_t>();
-      a.n_items = encode.size();
-      Check(launch_cmp_encode(a, nullptr), "encode kernel launch");
-      if (device_ms) {
-        Check(hipEventRecord(e1, nullptr), "hipEventRecord");
-        Check(hipEventSynchronize(e1), "hipEventSynchronize");
-        Check(hipEventElapsedTime(device_ms, e0, e1), "hipEventElapsedTime");
-      }
-    } catch (...) {
-      if (e0) (void)hipEventDestroy(e0);
-      if (e1) (void)hipEventDestroy(e1);
-      throw;
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    Check(hipMemcpy(host.data(), d_out.p, (size_t)dev_total, hipMemcpyDeviceToHost), "copy objects");
+    a.item_mat = encode.d_unit.as<int32_t>();
+    a.item_blk = encode.d_blk.as<int32_t>();
+    a.n_items = encode.size();
+    Check(launch_cmp_encode(a, nullptr), "encode kernel launch");
+    if (device_ms) *device_ms = tm.Stop();
+    d_out.Download(host.data(), (size_t)dev_total, "copy objects");
     std::vector<CmpStats> stats((size_t)n);
-    Check(hipMemcpy(stats.data(), d_stats.p, (size_t)n * sizeof(CmpStats), hipMemcpyDeviceToHost), "copy statistics");
+    d_stats.Download(stats.data(), (size_t)n * sizeof(CmpStats), "copy statistics");
     for (int u = 0; u < n; ++u) {
       if (row_off[u + 1] == row_off[u]) continue;
       float range;
@@ -204,7 +135,7 @@ void CmvnSliding(int device, const float* raw, const int32_t* raw_off, int n, in
       sel_row[r] = r;
       sel_utt[r] = u;
     }
-  UseDevice(device, "the feature front-end's kernels");
+  UseDevice(device, "the feature front-end's kernels need");
   const FrontEndBytes z = FrontEndSizes(rows, n, rows, cols);
   DevBuf d_raw, d_prefix, d_out, d_tab;
   d_raw.Alloc(z.raw);

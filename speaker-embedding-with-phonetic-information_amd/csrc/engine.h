@@ -14,14 +14,11 @@
 #include <string>
 #include <vector>
 
+#include "device.h"
 #include "kernels.h"
 #include "program.h"
 
 namespace xv {
-
-struct EngineError : public std::runtime_error {
-  explicit EngineError(const std::string& m) : std::runtime_error(m) {}
-};
 
 // Flat, position-independent image of a lowered + padded + precision-split model.  This is what one
 // rank broadcasts to the others over RCCL and what an Engine is built from.

@@ -8,46 +8,14 @@
 #include <limits>
 
 #include "cli.h"
-#include "engine.h"
+#include "device.h"
 #include "feat_kernels.h"
 #include "kio.h"
 
 namespace xv {
 namespace {
 
-void Check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw EngineError(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-// Device buffer that grows and frees itself.
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  DevBuf() = default;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  void Reserve(size_t n) {
-    if (n <= cap && p) return;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = n ? n + n / 4 : 8;
-    Check(hipMalloc(&p, cap), "hipMalloc");
-  }
-  void Upload(const void* src, size_t n, const char* what) {
-    Reserve(n);
-    if (n) Check(hipMemcpy(p, src, n, hipMemcpyHostToDevice), what);
-  }
-  template <typename T> T* as() const { return (T*)p; }
-};
-
-void UseDevice(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-    throw EngineError("no HIP device available: the feature kernels need a gfx950 GPU (there is no CPU path)");
-  if (device < 0 || device >= n) throw EngineError("device index out of range");
-  Check(hipSetDevice(device), "hipSetDevice");
-}
+const char kWhoNeeds[] = "the feature kernels need";
 
 double MelScale(double f) { return 1127.0 * log(1.0 + f / 700.0); }
 
@@ -203,25 +171,27 @@ struct MfccComputer::Impl {
   int device = 0;
   MfccTables t;
   DevBuf window, twiddle, mel_w, dct_t, lifter, mel_first, mel_len, mel_woff;
-  DevBuf samples, sample_off, row_off, seeds, out;
+  // of one batch: they grow with a quarter to spare, so that batches of slowly rising size do not reallocate every time
+  static constexpr DevBuf::Growth kSpare = DevBuf::Growth::kQuarterMore;
+  DevBuf samples{kSpare}, sample_off{kSpare}, row_off{kSpare}, seeds{kSpare}, out{kSpare};
 };
 
 MfccComputer::MfccComputer(int device, const xv_mfcc_options& o) : p_(nullptr), o_(o) {
   MfccTables t = BuildMfccTables(o);   // option errors come before any device is touched
-  UseDevice(device);
+  UseDevice(device, kWhoNeeds);
   p_ = new Impl;
   p_->device = device;
   p_->t = std::move(t);
   try {
     const MfccTables& tt = p_->t;
-    p_->window.Upload(tt.window.data(), tt.window.size() * 4, "copy window");
-    p_->twiddle.Upload(tt.twiddle.data(), tt.twiddle.size() * 4, "copy twiddles");
-    p_->mel_w.Upload(tt.mel_w.data(), tt.mel_w.size() * 4, "copy mel weights");
-    p_->dct_t.Upload(tt.dct_t.data(), tt.dct_t.size() * 4, "copy DCT");
-    p_->lifter.Upload(tt.lifter.data(), tt.lifter.size() * 4, "copy lifter");
-    p_->mel_first.Upload(tt.mel_first.data(), tt.mel_first.size() * 4, "copy mel bank");
-    p_->mel_len.Upload(tt.mel_len.data(), tt.mel_len.size() * 4, "copy mel bank");
-    p_->mel_woff.Upload(tt.mel_woff.data(), tt.mel_woff.size() * 4, "copy mel bank");
+    p_->window.Upload(tt.window, "copy window");
+    p_->twiddle.Upload(tt.twiddle, "copy twiddles");
+    p_->mel_w.Upload(tt.mel_w, "copy mel weights");
+    p_->dct_t.Upload(tt.dct_t, "copy DCT");
+    p_->lifter.Upload(tt.lifter, "copy lifter");
+    p_->mel_first.Upload(tt.mel_first, "copy mel bank");
+    p_->mel_len.Upload(tt.mel_len, "copy mel bank");
+    p_->mel_woff.Upload(tt.mel_woff, "copy mel bank");
   } catch (...) {
     delete p_;
     throw;
@@ -254,7 +224,7 @@ void MfccComputer::Compute(const void* samples, bool is_i16, const int64_t* samp
   std::vector<int64_t> rel(n_utts + 1);
   for (int u = 0; u <= n_utts; ++u) rel[u] = sample_off[u] - sample_off[0];
   p_->samples.Upload((const char*)samples + (size_t)sample_off[0] * esz, (size_t)total * esz, "copy samples");
-  p_->sample_off.Upload(rel.data(), rel.size() * 8, "copy sample offsets");
+  p_->sample_off.Upload(rel, "copy sample offsets");
   p_->row_off.Upload(row_off, (size_t)(n_utts + 1) * 4, "copy row offsets");
   if (o_.dither != 0.f) p_->seeds.Upload(seeds, (size_t)n_utts * 8, "copy seeds");
   p_->out.Reserve((size_t)rows * o_.num_ceps * 4);
@@ -289,21 +259,11 @@ void MfccComputer::Compute(const void* samples, bool is_i16, const int64_t* samp
   a.dct_t = p_->dct_t.as<float>();
   a.lifter = p_->lifter.as<float>();
   a.out = p_->out.as<float>();
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (device_ms) {
-    Check(hipEventCreate(&e0), "hipEventCreate");
-    Check(hipEventCreate(&e1), "hipEventCreate");
-    Check(hipEventRecord(e0, nullptr), "hipEventRecord");
-  }
+  EventTimer tm(device_ms != nullptr);
+  tm.Start();
   Check(is_i16 ? launch_mfcc_i16(a, nullptr) : launch_mfcc_f32(a, nullptr), "MFCC kernel launch");
-  if (device_ms) {
-    Check(hipEventRecord(e1, nullptr), "hipEventRecord");
-    Check(hipEventSynchronize(e1), "hipEventSynchronize");
-    Check(hipEventElapsedTime(device_ms, e0, e1), "hipEventElapsedTime");
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
-  Check(hipMemcpy(out->data(), p_->out.p, out->size() * 4, hipMemcpyDeviceToHost), "copy features");
+  if (device_ms) *device_ms = tm.Stop();
+  p_->out.Download(out->data(), out->size() * 4, "copy features");
 }
 
 void VadEnergy(int device, const xv_vad_options& o, const float* feats, const int32_t* row_off, int n_utts, int dim, float* out) {
@@ -314,7 +274,7 @@ void VadEnergy(int device, const xv_vad_options& o, const float* feats, const in
   for (int u = 0; u < n_utts; ++u)
     if (row_off[u + 1] < row_off[u]) throw EngineError("VadEnergy: row offsets must not decrease");
   if (n_utts > 0 && row_off[0] != 0) throw EngineError("VadEnergy: row offsets must start at 0");
-  UseDevice(device);
+  UseDevice(device, kWhoNeeds);
   const int rows = n_utts > 0 ? row_off[n_utts] : 0;
   if (rows == 0) return;
   DevBuf df, doff, dthr, dout;
@@ -335,7 +295,7 @@ void VadEnergy(int device, const xv_vad_options& o, const float* feats, const in
   a.thr = dthr.as<float>();
   a.out = dout.as<float>();
   Check(launch_vad_energy(a, nullptr), "VAD kernel launch");
-  Check(hipMemcpy(out, dout.p, (size_t)rows * 4, hipMemcpyDeviceToHost), "copy VAD decisions");
+  dout.Download(out, (size_t)rows * 4, "copy VAD decisions");
 }
 
 // ---------------------------------------------------------------------------------------------- options

@@ -6,76 +6,13 @@
 
 #include <algorithm>
 
-#include "engine.h"
+#include "device.h"
 #include "ivex_kernels.h"
 
 namespace xv {
 namespace {
 
-void Check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw EngineError(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-// a device buffer that only grows
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  DevBuf() = default;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  void Free() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  void Reserve(size_t n) {
-    if (n <= cap && p) return;
-    Free();
-    Check(hipMalloc(&p, n ? n : 8), "hipMalloc");
-    cap = n ? n : 8;
-  }
-  void Upload(const void* src, size_t n, const char* what) {
-    Reserve(n);
-    if (n) Check(hipMemcpy(p, src, n, hipMemcpyHostToDevice), what);
-  }
-  template <typename T>
-  void Upload(const std::vector<T>& v, const char* what) { Upload(v.data(), v.size() * sizeof(T), what); }
-  template <typename T> T* as() const { return (T*)p; }
-};
-
-// elapsed time between marks on the null stream
-struct Timer {
-  std::vector<hipEvent_t> ev;
-  size_t used = 0;
-  explicit Timer(int marks) {
-    for (int i = 0; i < marks; ++i) {
-      hipEvent_t e = nullptr;
-      Check(hipEventCreate(&e), "hipEventCreate");
-      ev.push_back(e);
-    }
-  }
-  ~Timer() {
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
-  void Mark() {
-    if (used < ev.size()) Check(hipEventRecord(ev[used++], nullptr), "hipEventRecord");
-  }
-  float Span(size_t i) {
-    float ms = 0.f;
-    Check(hipEventSynchronize(ev[i + 1]), "hipEventSynchronize");
-    Check(hipEventElapsedTime(&ms, ev[i], ev[i + 1]), "hipEventElapsedTime");
-    return ms;
-  }
-};
-
-void UseDevice(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-    throw EngineError("no HIP device available: i-vector extraction needs a gfx950 GPU (there is no CPU path)");
-  if (device < 0 || device >= n) throw EngineError("device index out of range");
-  Check(hipSetDevice(device), "hipSetDevice");
-}
+const char kWhoNeeds[] = "i-vector extraction needs";
 
 // DP / FP (binary) or " [ rows ]" (text): one packed lower triangle appended to *packed; returns its dimension
 int ReadPackedDouble(Input& in, bool binary, std::vector<double>* packed) {
@@ -242,7 +179,7 @@ float IvexModel::derive_ms() const { return impl_->derive_ms; }
 
 IvexModel* IvexCreate(int device, const IvexData& m) {
   CheckShape(m);
-  UseDevice(device);
+  UseDevice(device, kWhoNeeds);
   std::unique_ptr<IvexModel> h(new IvexModel);
   h->impl_.reset(new IvexModel::Impl);
   IvexModel::Impl& I = *h->impl_;
@@ -269,11 +206,10 @@ IvexModel* IvexCreate(int device, const IvexData& m) {
     a.S = m.S;
     a.sigma_inv_m = I.sigma_inv_m.as<double>();
     a.U = I.U.as<double>();
-    Timer tm(2);
-    tm.Mark();
+    EventTimer tm(true);
+    tm.Start();
     Check(launch_ivex_derive(a, nullptr), "ivex_derive launch");
-    tm.Mark();
-    I.derive_ms = tm.Span(0);
+    I.derive_ms = tm.Stop();
     Check(hipDeviceSynchronize(), "ivex_derive");
   }
   const size_t B = kIvexMaxBatch;
@@ -294,7 +230,7 @@ IvexModel* IvexCreate(int device, const IvexData& m) {
 
 void IvexDerived(const IvexModel& m, double* sigma_inv_m, double* U) {
   const IvexModel::Impl& I = *m.impl_;
-  UseDevice(I.device);
+  UseDevice(I.device, kWhoNeeds);
   if (sigma_inv_m) Check(hipMemcpy(sigma_inv_m, I.sigma_inv_m.p, (size_t)I.G * I.D * I.S * 8, hipMemcpyDeviceToHost), "copy SigmaInvM");
   if (U) Check(hipMemcpy(U, I.U.p, (size_t)I.G * I.P * 8, hipMemcpyDeviceToHost), "copy U");
 }
@@ -317,7 +253,7 @@ void IvexExtract(IvexModel& m, const float* feats, const int32_t* row_off, int n
   for (int64_t i = 0; i < pairs_all; ++i)
     if (post_idx[i] < 0 || post_idx[i] >= I.G)
       throw KioError("ivector-extract: the posteriors name Gaussian " + std::to_string(post_idx[i]) + "; the model has " + std::to_string(I.G));
-  UseDevice(I.device);
+  UseDevice(I.device, kWhoNeeds);
   constexpr int64_t kBatchFrames = 1 << 16;
   const int G = I.G, D = I.D, S = I.S;
   const int64_t K = (int64_t)G * D;
@@ -429,7 +365,7 @@ void IvexExtract(IvexModel& m, const float* feats, const int32_t* row_off, int n
     so.auxf_change = out.auxf_change ? I.auxf.as<double>() : nullptr;
     so.status = I.status.as<int32_t>();
 
-    Timer tm(out.device_ms4 ? 5 : 0);
+    EventTimer tm(out.device_ms4 != nullptr, 5);
     tm.Mark();
     Check(launch_ivex_bucket_sort(st, nullptr), "ivex_bucket_sort launch");
     Check(launch_ivex_stats(st, nullptr), "ivex_stats launch");

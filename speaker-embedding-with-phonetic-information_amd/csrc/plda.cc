@@ -8,63 +8,14 @@
 #include <sstream>
 #include <string>
 
-#include "engine.h"
+#include "device.h"
 #include "kio.h"
 #include "plda_kernels.h"
 
 namespace xv {
 namespace {
 
-void Check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw EngineError(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-// Device buffer that frees itself.
-struct DevBuf {
-  void* p = nullptr;
-  explicit DevBuf(size_t n) { Check(hipMalloc(&p, n ? n : 8), "hipMalloc"); }
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  template <typename T> T* as() const { return (T*)p; }
-};
-
-void UseDevice(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-    throw EngineError("no HIP device available: the PLDA back-end kernels need a gfx950 GPU (there is no CPU path)");
-  if (device < 0 || device >= n) throw EngineError("device index out of range");
-  Check(hipSetDevice(device), "hipSetDevice");
-}
-
-void Upload(void* dst, const void* src, size_t bytes, const char* what) {
-  if (bytes) Check(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), what);
-}
-void Download(void* dst, const void* src, size_t bytes, const char* what) {
-  if (bytes) Check(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), what);
-}
-
-// Kernel time between two events around the launches (device_ms != null).
-struct Timer {
-  hipEvent_t a = nullptr, b = nullptr;
-  float* out;
-  explicit Timer(float* o) : out(o) {
-    if (!out) return;
-    Check(hipEventCreate(&a), "hipEventCreate");
-    Check(hipEventCreate(&b), "hipEventCreate");
-    Check(hipEventRecord(a, nullptr), "hipEventRecord");
-  }
-  void Stop() {
-    if (!out) return;
-    Check(hipEventRecord(b, nullptr), "hipEventRecord");
-    Check(hipEventSynchronize(b), "hipEventSynchronize");
-    Check(hipEventElapsedTime(out, a, b), "hipEventElapsedTime");
-  }
-  ~Timer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
+const char kWhoNeeds[] = "the PLDA back-end kernels need";
 
 using Mat = std::vector<double>;   // row-major n x n
 
@@ -602,13 +553,13 @@ void ScatterStats(int device, const float* x, int n, int dim, const int32_t* seg
   const int n_idx = seg_off[n_seg];
   for (int i = 0; i < n_idx; ++i)
     if (idx[i] < 0 || idx[i] >= n) throw EngineError("ScatterStats: row index out of range");
-  UseDevice(device);
+  UseDevice(device, kWhoNeeds);
   const size_t dd = (size_t)dim * dim;
   DevBuf dx((size_t)n * dim * 4), doff((size_t)(n_seg + 1) * 4), didx((size_t)n_idx * 4), dsums((size_t)n_seg * dim * 8);
   DevBuf dtot(dd * 8), dbet(dd * 8), dwork(scatter_stats_workspace(dim, n_idx, n_seg) * 8);
-  Upload(dx.p, x, (size_t)n * dim * 4, "copy vectors");
-  Upload(doff.p, seg_off, (size_t)(n_seg + 1) * 4, "copy segment offsets");
-  Upload(didx.p, idx, (size_t)n_idx * 4, "copy row indices");
+  dx.Upload(x, (size_t)n * dim * 4, "copy vectors");
+  doff.Upload(seg_off, (size_t)(n_seg + 1) * 4, "copy segment offsets");
+  didx.Upload(idx, (size_t)n_idx * 4, "copy row indices");
   ScatterArgs a;
   a.x = dx.as<float>();
   a.dim = dim;
@@ -621,12 +572,13 @@ void ScatterStats(int device, const float* x, int n, int dim, const int32_t* seg
   a.s_tot = dtot.as<double>();
   a.s_bet = dbet.as<double>();
   a.work = dwork.as<double>();
-  Timer tm(device_ms);
+  EventTimer tm(device_ms != nullptr);
+  tm.Start();
   Check(launch_scatter_stats(a, nullptr), "scatter statistics kernel launch");
-  tm.Stop();
-  if (s_tot) Download(s_tot, dtot.p, dd * 8, "copy total scatter");
-  if (s_bet) Download(s_bet, dbet.p, dd * 8, "copy between-class scatter");
-  if (sums) Download(sums, dsums.p, (size_t)n_seg * dim * 8, "copy speaker sums");
+  if (device_ms) *device_ms = tm.Stop();
+  if (s_tot) dtot.Download(s_tot, dd * 8, "copy total scatter");
+  if (s_bet) dbet.Download(s_bet, dd * 8, "copy between-class scatter");
+  if (sums) dsums.Download(sums, (size_t)n_seg * dim * 8, "copy speaker sums");
 }
 
 void PldaTransform(int device, const float* x, int n, int dim, const double* transform, const double* offset,
@@ -638,7 +590,7 @@ void PldaTransform(int device, const float* x, int n, int dim, const double* tra
                       std::to_string(kPldaMaxDim) + ")");
   for (int i = 0; i < n; ++i)
     if (!(num[i] > 0)) throw EngineError("PldaTransform: example counts must be positive");
-  UseDevice(device);
+  UseDevice(device, kWhoNeeds);
   if (n == 0) return;
   const size_t dd = (size_t)dim * dim;
   std::vector<double> tt(dd);
@@ -646,11 +598,11 @@ void PldaTransform(int device, const float* x, int n, int dim, const double* tra
     for (int k = 0; k < dim; ++k) tt[(size_t)k * dim + d] = transform[(size_t)d * dim + k];
   DevBuf dx((size_t)n * dim * 4), dt(dd * 8), doff((size_t)dim * 8), dpsi((size_t)dim * 8), dnum((size_t)n * 8);
   DevBuf dy((size_t)n * dim * 4), dscale((size_t)n * 8);
-  Upload(dx.p, x, (size_t)n * dim * 4, "copy vectors");
-  Upload(dt.p, tt.data(), dd * 8, "copy transform");
-  Upload(doff.p, offset, (size_t)dim * 8, "copy offset");
-  Upload(dpsi.p, psi, (size_t)dim * 8, "copy psi");
-  Upload(dnum.p, num, (size_t)n * 8, "copy counts");
+  dx.Upload(x, (size_t)n * dim * 4, "copy vectors");
+  dt.Upload(tt.data(), dd * 8, "copy transform");
+  doff.Upload(offset, (size_t)dim * 8, "copy offset");
+  dpsi.Upload(psi, (size_t)dim * 8, "copy psi");
+  dnum.Upload(num, (size_t)n * 8, "copy counts");
   PldaTransformArgs a;
   a.x = dx.as<float>();
   a.n = n;
@@ -663,11 +615,12 @@ void PldaTransform(int device, const float* x, int n, int dim, const double* tra
   a.simple = simple ? 1 : 0;
   a.y = dy.as<float>();
   a.scale = dscale.as<double>();
-  Timer tm(device_ms);
+  EventTimer tm(device_ms != nullptr);
+  tm.Start();
   Check(launch_plda_transform(a, nullptr), "PLDA transform kernel launch");
-  tm.Stop();
-  Download(y, dy.p, (size_t)n * dim * 4, "copy transformed vectors");
-  if (scale) Download(scale, dscale.p, (size_t)n * 8, "copy scales");
+  if (device_ms) *device_ms = tm.Stop();
+  dy.Download(y, (size_t)n * dim * 4, "copy transformed vectors");
+  if (scale) dscale.Download(scale, (size_t)n * 8, "copy scales");
 }
 
 void PldaScore(int device, const float* u, const double* num_u, int n_u, const float* v, int n_v, int dim,
@@ -681,18 +634,18 @@ void PldaScore(int device, const float* u, const double* num_u, int n_u, const f
       throw EngineError("PldaScore: trial " + std::to_string(i) + " indexes a row that does not exist");
   for (int k = 0; k < n_u; ++k)
     if (!(num_u[k] > 0)) throw EngineError("PldaScore: example counts must be positive");
-  UseDevice(device);
+  UseDevice(device, kWhoNeeds);
   if (n_trials == 0) return;
   std::vector<double> inv_psi1(dim);
   for (int d = 0; d < dim; ++d) inv_psi1[d] = 1.0 / (1.0 + psi[d]);
   DevBuf du((size_t)n_u * dim * 4), dnum((size_t)n_u * 8), dv((size_t)n_v * dim * 4), dpsi((size_t)dim * 8);
   DevBuf dip((size_t)dim * 8), dtr((size_t)n_trials * 8), dwork((size_t)n_u * (2 * dim + 1) * 8), dsc((size_t)n_trials * 8);
-  Upload(du.p, u, (size_t)n_u * dim * 4, "copy enrolment vectors");
-  Upload(dnum.p, num_u, (size_t)n_u * 8, "copy counts");
-  Upload(dv.p, v, (size_t)n_v * dim * 4, "copy test vectors");
-  Upload(dpsi.p, psi, (size_t)dim * 8, "copy psi");
-  Upload(dip.p, inv_psi1.data(), (size_t)dim * 8, "copy psi");
-  Upload(dtr.p, trials, (size_t)n_trials * 8, "copy trials");
+  du.Upload(u, (size_t)n_u * dim * 4, "copy enrolment vectors");
+  dnum.Upload(num_u, (size_t)n_u * 8, "copy counts");
+  dv.Upload(v, (size_t)n_v * dim * 4, "copy test vectors");
+  dpsi.Upload(psi, (size_t)dim * 8, "copy psi");
+  dip.Upload(inv_psi1.data(), (size_t)dim * 8, "copy psi");
+  dtr.Upload(trials, (size_t)n_trials * 8, "copy trials");
   PldaScoreArgs a;
   a.u = du.as<float>();
   a.num_u = dnum.as<double>();
@@ -706,10 +659,11 @@ void PldaScore(int device, const float* u, const double* num_u, int n_u, const f
   a.n_trials = n_trials;
   a.work = dwork.as<double>();
   a.scores = dsc.as<double>();
-  Timer tm(device_ms);
+  EventTimer tm(device_ms != nullptr);
+  tm.Start();
   Check(launch_plda_score(a, nullptr), "PLDA scoring kernel launch");
-  tm.Stop();
-  Download(scores, dsc.p, (size_t)n_trials * 8, "copy scores");
+  if (device_ms) *device_ms = tm.Stop();
+  dsc.Download(scores, (size_t)n_trials * 8, "copy scores");
 }
 
 }  // namespace xv

@@ -7,90 +7,12 @@
 
 #include <algorithm>
 
-#include "engine.h"
+#include "device.h"
 #include "kio.h"
 #include "knobs.h"
 #include "reverb_kernels.h"
 
 namespace xv {
-namespace {
-
-void Check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw EngineError(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  void Alloc(size_t n) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    Check(hipMalloc(&p, n ? n : 8), "hipMalloc");
-  }
-  template <typename T>
-  void Upload(const std::vector<T>& v, const char* what) {
-    Alloc(v.size() * sizeof(T));
-    if (!v.empty()) Check(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice), what);
-  }
-  template <typename T> T* as() const { return (T*)p; }
-};
-
-void UseDevice(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-    throw EngineError("no HIP device available: the reverberation kernels need a gfx950 GPU (there is no CPU path)");
-  if (device < 0 || device >= n) throw EngineError("device index out of range");
-  Check(hipSetDevice(device), "hipSetDevice");
-}
-
-// Sums the kernels' time when asked to.
-struct KernelClock {
-  float* total;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  explicit KernelClock(float* t) : total(t) {
-    if (!total) return;
-    *total = 0.f;
-    Check(hipEventCreate(&e0), "hipEventCreate");
-    Check(hipEventCreate(&e1), "hipEventCreate");
-  }
-  ~KernelClock() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-  void Start() { if (total) Check(hipEventRecord(e0, nullptr), "hipEventRecord"); }
-  void Stop() {
-    if (!total) return;
-    float ms = 0.f;
-    Check(hipEventRecord(e1, nullptr), "hipEventRecord");
-    Check(hipEventSynchronize(e1), "hipEventSynchronize");
-    Check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-    *total += ms;
-  }
-};
-
-int64_t CeilDiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// Work items (utterance, block) of one kernel.
-struct Items {
-  std::vector<int32_t> utt, blk;
-  DevBuf d_utt, d_blk;
-  void Add(int u, int64_t blocks) {
-    for (int64_t b = 0; b < blocks; ++b) {
-      utt.push_back(u);
-      blk.push_back((int32_t)b);
-    }
-  }
-  int size() const { return (int)utt.size(); }
-  void Upload() {
-    d_utt.Upload(utt, "copy work items");
-    d_blk.Upload(blk, "copy work items");
-  }
-};
-
-}  // namespace
 
 xv_reverb_options ReverbDefaults() {
   xv_reverb_options o;
@@ -229,8 +151,10 @@ void Reverberate(int device, const xv_reverb_options& o, const ReverbBatch& b, i
   }
   if (out_total > 0 && !out_f32) throw KioError("wav-reverberate: null output");
 
-  UseDevice(device);
-  KernelClock clock(device_ms);
+  UseDevice(device, "the reverberation kernels need");
+  EventTimer clock(device_ms != nullptr);
+  float unasked = 0.f;
+  float& kernel_ms = device_ms ? *device_ms : unasked;   // the sum of the kernels' times
   DevBuf d_sig, d_utts, d_adds, d_y;
   d_sig.Upload(sig, "copy signals");
   d_y.Alloc((size_t)y_total * 4);
@@ -263,7 +187,7 @@ void Reverberate(int device, const xv_reverb_options& o, const ReverbBatch& b, i
     a.out = d_part.as<double>();
     clock.Start();
     Check(launch_rv_power(a, nullptr), "power kernel launch");
-    clock.Stop();
+    kernel_ms += clock.Stop();
     std::vector<double> part(chunk_off.size());
     Check(hipMemcpy(part.data(), d_part.p, part.size() * 8, hipMemcpyDeviceToHost), "copy powers");
     for (size_t s = 0; s + 1 < first_chunk.size(); ++s) {
@@ -301,15 +225,14 @@ void Reverberate(int device, const xv_reverb_options& o, const ReverbBatch& b, i
       a.hspec = d_hspec.as<float2>();
       clock.Start();
       Check(launch_rv_rir_spectra(a, nullptr), "RIR spectra kernel launch");
-      clock.Stop();
+      kernel_ms += clock.Stop();
     }
     // the block spectra of the signals take 16 bytes per sample: utterances go through in groups of bounded size
     const int64_t kGroupBlocks = std::max(1, DebugKnobInt("reverb_group_blocks", 16384));   // 16384: 512 MiB of spectra
     DevBuf d_xspec;
-    int64_t xspec_cap = 0;
     int u0 = 0;
     while (u0 < U) {
-      Items fft, direct;
+      WorkItems fft, direct;
       int64_t blocks = 0;
       int u1 = u0;
       for (; u1 < U; ++u1) {
@@ -325,10 +248,7 @@ void Reverberate(int device, const xv_reverb_options& o, const ReverbBatch& b, i
         }
       }
       d_utts.Upload(utts, "copy utterances");
-      if (blocks > xspec_cap) {
-        d_xspec.Alloc((size_t)blocks * kRvN * sizeof(float2));
-        xspec_cap = blocks;
-      }
+      if (blocks > 0) d_xspec.Reserve((size_t)blocks * kRvN * sizeof(float2));
       RvConvArgs a;
       memset(&a, 0, sizeof a);
       a.sig = d_sig.as<float>();
@@ -340,22 +260,22 @@ void Reverberate(int device, const xv_reverb_options& o, const ReverbBatch& b, i
       a.epart = d_epart.as<double>();
       if (fft.size()) {
         fft.Upload();
-        a.item_utt = fft.d_utt.as<int32_t>();
+        a.item_utt = fft.d_unit.as<int32_t>();
         a.item_blk = fft.d_blk.as<int32_t>();
         a.n_items = fft.size();
         clock.Start();
         Check(launch_rv_sig_spectra(a, nullptr), "signal spectra kernel launch");
         Check(launch_rv_conv(a, nullptr), "convolution kernel launch");
-        clock.Stop();
+        kernel_ms += clock.Stop();
       }
       if (direct.size()) {
         direct.Upload();
-        a.item_utt = direct.d_utt.as<int32_t>();
+        a.item_utt = direct.d_unit.as<int32_t>();
         a.item_blk = direct.d_blk.as<int32_t>();
         a.n_items = direct.size();
         clock.Start();
         Check(launch_rv_conv_direct(a, nullptr), "direct convolution kernel launch");
-        clock.Stop();
+        kernel_ms += clock.Stop();
       }
       Check(hipDeviceSynchronize(), "convolution kernels");
       u0 = u1;
@@ -382,7 +302,7 @@ void Reverberate(int device, const xv_reverb_options& o, const ReverbBatch& b, i
     }
   std::vector<double> after(U, 0.0);
   {
-    Items mix;
+    WorkItems mix;
     for (int u = 0; u < U; ++u) mix.Add(u, CeilDiv(utts[u].ext_len, kRvChunk));
     mix.Upload();
     d_utts.Upload(utts, "copy utterances");
@@ -393,14 +313,14 @@ void Reverberate(int device, const xv_reverb_options& o, const ReverbBatch& b, i
     a.sig = d_sig.as<float>();
     a.utts = d_utts.as<RvUtt>();
     a.adds = d_adds.as<RvAdd>();
-    a.item_utt = mix.d_utt.as<int32_t>();
+    a.item_utt = mix.d_unit.as<int32_t>();
     a.item_blk = mix.d_blk.as<int32_t>();
     a.n_items = mix.size();
     a.y = d_y.as<float>();
     a.apart = d_apart.as<double>();
     clock.Start();
     Check(launch_rv_mix(a, nullptr), "mix kernel launch");
-    clock.Stop();
+    kernel_ms += clock.Stop();
     std::vector<double> ap((size_t)apart_total);
     Check(hipMemcpy(ap.data(), d_apart.p, ap.size() * 8, hipMemcpyDeviceToHost), "copy powers");
     for (int u = 0; u < U; ++u) {
@@ -419,7 +339,7 @@ void Reverberate(int device, const xv_reverb_options& o, const ReverbBatch& b, i
   // ---- the outputs
   if (out_total == 0) return;
   {
-    Items fin;
+    WorkItems fin;
     for (int u = 0; u < U; ++u) fin.Add(u, CeilDiv(utts[u].out_len, kRvChunk));
     fin.Upload();
     d_utts.Upload(utts, "copy utterances");
@@ -432,7 +352,7 @@ void Reverberate(int device, const xv_reverb_options& o, const ReverbBatch& b, i
     }
     RvFinishArgs a;
     a.utts = d_utts.as<RvUtt>();
-    a.item_utt = fin.d_utt.as<int32_t>();
+    a.item_utt = fin.d_unit.as<int32_t>();
     a.item_blk = fin.d_blk.as<int32_t>();
     a.n_items = fin.size();
     a.y = d_y.as<float>();
@@ -441,7 +361,7 @@ void Reverberate(int device, const xv_reverb_options& o, const ReverbBatch& b, i
     a.clipped = out_i16 ? d_clip.as<unsigned long long>() : nullptr;
     clock.Start();
     Check(launch_rv_finish(a, nullptr), "finish kernel launch");
-    clock.Stop();
+    kernel_ms += clock.Stop();
     Check(hipMemcpy(out_f32, d_f32.p, (size_t)out_total * 4, hipMemcpyDeviceToHost), "copy output");
     if (out_i16) {
       Check(hipMemcpy(out_i16, d_i16.p, (size_t)out_total * 2, hipMemcpyDeviceToHost), "copy output");

@@ -7,7 +7,7 @@
 #include <algorithm>
 #include <limits>
 
-#include "engine.h"
+#include "device.h"
 #include "ubm_kernels.h"
 
 // DeltaScales is compared with tests/ubm_ref.py for equality: float(j) * scale and the sum are two roundings, not a fused one
@@ -16,71 +16,7 @@
 namespace xv {
 namespace {
 
-void Check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw EngineError(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  void Alloc(size_t n) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    Check(hipMalloc(&p, n ? n : 8), "hipMalloc");
-  }
-  void Upload(const void* src, size_t n, const char* what) {
-    Alloc(n);
-    if (n) Check(hipMemcpy(p, src, n, hipMemcpyHostToDevice), what);
-  }
-  template <typename T>
-  void Upload(const std::vector<T>& v, const char* what) { Upload(v.data(), v.size() * sizeof(T), what); }
-  template <typename T> T* as() const { return (T*)p; }
-};
-
-// elapsed time between marks on the null stream
-struct Timer {
-  std::vector<hipEvent_t> ev;
-  size_t used = 0;
-  explicit Timer(int marks) {
-    for (int i = 0; i < marks; ++i) {
-      hipEvent_t e = nullptr;
-      Check(hipEventCreate(&e), "hipEventCreate");
-      ev.push_back(e);
-    }
-  }
-  ~Timer() {
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
-  void Mark() {
-    if (used < ev.size()) Check(hipEventRecord(ev[used++], nullptr), "hipEventRecord");
-  }
-  // ms between mark i and mark i + 1
-  float Span(size_t i) {
-    float ms = 0.f;
-    Check(hipEventSynchronize(ev[i + 1]), "hipEventSynchronize");
-    Check(hipEventElapsedTime(&ms, ev[i], ev[i + 1]), "hipEventElapsedTime");
-    return ms;
-  }
-};
-
-void UseDevice(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-    throw EngineError("no HIP device available: the UBM kernels need a gfx950 GPU (there is no CPU path)");
-  if (device < 0 || device >= n) throw EngineError("device index out of range");
-  Check(hipSetDevice(device), "hipSetDevice");
-}
-
-int64_t CheckOffsets(const char* who, const int32_t* off, int n) {
-  if (n < 0 || !off) throw KioError(std::string(who) + ": bad argument");
-  if (off[0] != 0) throw KioError(std::string(who) + ": row offsets must start at 0");
-  for (int u = 0; u < n; ++u)
-    if (off[u + 1] < off[u]) throw KioError(std::string(who) + ": row offsets must not decrease");
-  return off[n];
-}
+const char kWhoNeeds[] = "the UBM kernels need";
 
 // Cholesky factor of the packed lower triangle `p` (as doubles): l [dim][dim] lower; false: not positive definite
 bool Cholesky(const float* p, int dim, std::vector<double>* l) {
@@ -150,7 +86,7 @@ void AddDeltas(int device, const float* feats, const int32_t* row_off, int n, in
   if (rows == 0) return;
   if (!feats || !out) throw KioError("add-deltas: null buffer");
   const int dim = truncate > 0 ? truncate : cols;
-  UseDevice(device);
+  UseDevice(device, kWhoNeeds);
   DeltaArgs a;
   memset(&a, 0, sizeof a);
   std::vector<float> flat;
@@ -158,18 +94,13 @@ void AddDeltas(int device, const float* feats, const int32_t* row_off, int n, in
     a.scale_off[i] = (int)flat.size();
     flat.insert(flat.end(), scales[i].begin(), scales[i].end());
   }
-  std::vector<int32_t> mat, blk;
-  for (int u = 0; u < n; ++u)
-    for (int b = 0; b < (row_off[u + 1] - row_off[u] + kDeltaRowBlock - 1) / kDeltaRowBlock; ++b) {
-      mat.push_back(u);
-      blk.push_back(b);
-    }
-  DevBuf d_feats, d_off, d_scales, d_mat, d_blk, d_out;
+  WorkItems items;
+  for (int u = 0; u < n; ++u) items.Add(u, CeilDiv(row_off[u + 1] - row_off[u], kDeltaRowBlock));
+  DevBuf d_feats, d_off, d_scales, d_out;
   d_feats.Upload(feats, (size_t)rows * cols * 4, "copy features");
   d_off.Upload(row_off, (size_t)(n + 1) * 4, "copy row offsets");
   d_scales.Upload(flat, "copy delta scales");
-  d_mat.Upload(mat, "copy work items");
-  d_blk.Upload(blk, "copy work items");
+  items.Upload();
   const size_t out_bytes = (size_t)rows * (order + 1) * dim * 4;
   d_out.Alloc(out_bytes);
   a.feats = d_feats.as<float>();
@@ -180,16 +111,15 @@ void AddDeltas(int device, const float* feats, const int32_t* row_off, int n, in
   a.order = order;
   a.window = window;
   a.scales = d_scales.as<float>();
-  a.item_mat = d_mat.as<int32_t>();
-  a.item_blk = d_blk.as<int32_t>();
-  a.n_items = (int)mat.size();
+  a.item_mat = items.d_unit.as<int32_t>();
+  a.item_blk = items.d_blk.as<int32_t>();
+  a.n_items = items.size();
   a.out = d_out.as<float>();
-  Timer tm(device_ms ? 2 : 0);
-  tm.Mark();
+  EventTimer tm(device_ms != nullptr);
+  tm.Start();
   Check(launch_add_deltas(a, nullptr), "add_deltas launch");
-  tm.Mark();
-  if (device_ms) *device_ms = tm.Span(0);
-  Check(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost), "copy delta features");
+  if (device_ms) *device_ms = tm.Stop();
+  d_out.Download(out, out_bytes, "copy delta features");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -332,7 +262,7 @@ void CheckModelShape(int num_gauss, int dim, const void* p0, const void* p1, con
 
 UbmModel* UbmDiagCreate(int device, int num_gauss, int dim, const float* gconsts, const float* means_invvars, const float* inv_vars) {
   CheckModelShape(num_gauss, dim, gconsts, means_invvars, inv_vars);
-  UseDevice(device);
+  UseDevice(device, kWhoNeeds);
   std::unique_ptr<UbmModel> m(new UbmModel);
   m->impl_.reset(new UbmModel::Impl);
   UbmModel::Impl& I = *m->impl_;
@@ -357,7 +287,7 @@ UbmModel* UbmDiagCreate(int device, int num_gauss, int dim, const float* gconsts
 
 UbmModel* UbmFullCreate(int device, int num_gauss, int dim, const float* gconsts, const float* means_invcovars, const float* inv_covars) {
   CheckModelShape(num_gauss, dim, gconsts, means_invcovars, inv_covars);
-  UseDevice(device);
+  UseDevice(device, kWhoNeeds);
   std::unique_ptr<UbmModel> m(new UbmModel);
   m->impl_.reset(new UbmModel::Impl);
   UbmModel::Impl& I = *m->impl_;
@@ -381,7 +311,7 @@ void UbmGselect(const UbmModel& diag, const float* feats, const int32_t* row_off
   if (n > I.num_gauss) throw KioError("gselect: n = " + std::to_string(n) + " is above the model's " + std::to_string(I.num_gauss) + " Gaussians");
   if (rows == 0) return;
   if (!feats || !idx) throw KioError("gselect: null buffer");
-  UseDevice(I.device);
+  UseDevice(I.device, kWhoNeeds);
   DevBuf d_feats, d_idx, d_ll;
   d_feats.Upload(feats, (size_t)rows * I.dim * 4, "copy features");
   d_idx.Alloc((size_t)rows * n * 4);
@@ -399,11 +329,10 @@ void UbmGselect(const UbmModel& diag, const float* feats, const int32_t* row_off
   a.n = n;
   a.out_idx = d_idx.as<int32_t>();
   a.out_ll = ll ? d_ll.as<float>() : nullptr;
-  Timer tm(device_ms ? 2 : 0);
-  tm.Mark();
+  EventTimer tm(device_ms != nullptr);
+  tm.Start();
   Check(launch_ubm_diag_gselect(a, nullptr), "ubm_diag_gselect launch");
-  tm.Mark();
-  if (device_ms) *device_ms = tm.Span(0);
+  if (device_ms) *device_ms = tm.Stop();
   Check(hipMemcpy(idx, d_idx.p, (size_t)rows * n * 4, hipMemcpyDeviceToHost), "copy the selection");
   if (ll) Check(hipMemcpy(ll, d_ll.p, (size_t)rows * n * 4, hipMemcpyDeviceToHost), "copy the log-likelihoods");
 }
@@ -421,7 +350,7 @@ void UbmPost(const UbmModel& full, const float* feats, const int32_t* row_off, i
   for (int64_t i = 0; i < rows * n; ++i)
     if (gselect[i] < 0 || gselect[i] >= I.num_gauss)
       throw KioError("gselect-to-post: the selection names Gaussian " + std::to_string(gselect[i]) + "; the model has " + std::to_string(I.num_gauss));
-  UseDevice(I.device);
+  UseDevice(I.device, kWhoNeeds);
   // A call's frames go through in parts: the sort's (Gaussian, chunk) table stays small.  A frame's results do not depend on
   // the part it is in.
   constexpr int64_t kPart = 1 << 16;
@@ -469,7 +398,7 @@ void UbmPost(const UbmModel& full, const float* feats, const int32_t* row_off, i
     a.out_idx = d_idx.as<int32_t>();
     a.out_post = d_post.as<float>();
     a.out_logsum = d_logsum.as<float>();
-    Timer tm(device_ms3 ? 4 : 0);
+    EventTimer tm(device_ms3 != nullptr, 4);
     tm.Mark();
     Check(launch_ubm_bucket_sort(a, nullptr), "ubm_bucket_sort launch");
     tm.Mark();
