@@ -578,6 +578,38 @@ xv_status xv_fgmm_gconsts(int32_t num_gauss, int32_t dim, const float* weights, 
 xv_status xv_ubm_kernel_time(const xv_ubm* diag, const xv_ubm* full, const float* feats, const int32_t* row_off, int32_t n_utts,
                              int32_t n, float min_post, int32_t reps, float* ms5);
 
+/* ---- full-covariance UBM training (fgmm-global-acc-stats, fgmm-global-est; sid/train_full_ubm.sh:69-118), without a model context.
+ * Semantics: csrc/ubm_train.h.  The accumulators are fp64 on the device; no floating-point value goes through an atomic, and what a
+ * call adds is a function of the call's frames and pairs alone.  Limits: dimension <= 96, n <= 64 selected Gaussians. */
+typedef struct xv_fgmm_acc xv_fgmm_acc;
+/* update_flags: letters of "mvw" (v implies m, m implies w, as Kaldi augments them).  The accumulators start at zero. */
+xv_status xv_fgmm_acc_create(int device, int32_t num_gauss, int32_t dim, const char* update_flags, xv_fgmm_acc** out);
+void xv_fgmm_acc_destroy(xv_fgmm_acc* a);
+/* host buffers, blocking, one call with no internal blocking: feats [rows][dim]; frame t has the pairs post_off[t] .. post_off[t + 1]
+ * (post_off has rows + 1 entries) of post_idx (Gaussian, in [0, G): anything else is XV_ERR_IO before anything is uploaded) and
+ * post_w.  A pair whose weight is 0 adds nothing. */
+xv_status xv_fgmm_acc_add(xv_fgmm_acc* a, const float* feats, int32_t rows, const int32_t* post_off, const int32_t* post_idx,
+                          const float* post_w);
+/* the fused E-step: the posteriors of xv_ubm_post (min_post = 0) over gselect [rows][n] are accumulated without leaving the device;
+ * logsum [rows] comes back.  The model must have the accumulators' shape and device. */
+xv_status xv_fgmm_acc_add_gselect(xv_fgmm_acc* a, const xv_ubm* full, const float* feats, int32_t rows, const int32_t* gselect, int32_t n,
+                                  float* logsum);
+/* downloads occ [G], mean [G][D] and cov [G][D (D + 1) / 2] (packed lower triangles); any of them may be NULL */
+xv_status xv_fgmm_acc_get(const xv_fgmm_acc* a, double* occ, double* mean, double* cov);
+/* host only (fp64): the M-step of fgmm-global-est on host arrays.  acc_flags: the accumulators' letters; update_flags must be among
+ * them (after augmentation).  weights [G], means_invcovars [G][D] and inv_covars [G][D (D + 1) / 2] are updated in place, the
+ * Gaussians that survive moved to the front; gconsts [G] is written.  *num_gauss_out: how many survive; removed [G]: the first
+ * G - *num_gauss_out entries are the indices taken out.  floored2 = {eigenvalues floored, Gaussians they belong to}; objf3 = {the
+ * objective before, after, the sum of occ}.  removed, floored2 and objf3 may be NULL. */
+xv_status xv_fgmm_est(int32_t num_gauss, int32_t dim, const char* acc_flags, const double* occ, const double* mean, const double* cov,
+                      const char* update_flags, double min_gaussian_weight, double min_gaussian_occupancy, double variance_floor,
+                      double max_condition, int32_t remove_low_count_gaussians, float* weights, float* means_invcovars, float* inv_covars,
+                      float* gconsts, int32_t* num_gauss_out, int32_t* removed, int32_t* floored2, double* objf3);
+/* the kernels' times in ms of one fused call, the best of reps runs after one that warms up: ms4 = {sort, full-covariance scores,
+ * softmax, fgmm_acc (its work-item pass included)}.  Every run adds the call's statistics to the accumulators. */
+xv_status xv_fgmm_acc_kernel_time(xv_fgmm_acc* a, const xv_ubm* full, const float* feats, int32_t rows, const int32_t* gselect, int32_t n,
+                                  int32_t reps, float* ms4);
+
 /* ---- i-vector extraction (ivector-extract, sid/extract_ivectors.sh:69), without a model context.  Semantics: csrc/ivex.h.
  * Everything on the device is fp64 on fp32 inputs with summation orders that depend on the utterance and the model alone: an
  * utterance's results are the same bits alone, in any batch, at any position in it.  Limits: i-vector dimension <= 1024, feature

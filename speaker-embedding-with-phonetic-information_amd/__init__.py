@@ -139,6 +139,8 @@ ABI_SYMBOLS = [
     "xv_cmvn_stats", "xv_cmvn_norm", "xv_cmvn_apply", "xv_cmvn_kernel_time",
     "xv_add_deltas", "xv_ubm_diag_create", "xv_ubm_full_create", "xv_ubm_destroy", "xv_ubm_gselect", "xv_ubm_post",
     "xv_fgmm_to_gmm", "xv_fgmm_gconsts", "xv_ubm_kernel_time",
+    "xv_fgmm_acc_create", "xv_fgmm_acc_destroy", "xv_fgmm_acc_add", "xv_fgmm_acc_add_gselect", "xv_fgmm_acc_get", "xv_fgmm_est",
+    "xv_fgmm_acc_kernel_time",
     "xv_ivex_create", "xv_ivex_load", "xv_ivex_destroy", "xv_ivex_info", "xv_ivex_derived", "xv_ivex_extract", "xv_ivex_read",
     "xv_ivex_write", "xv_ivex_kernel_time",
     "xv_kernel_first_layer", "xv_kernel_prep_input", "xv_kernel_pool_finalise", "xv_kernel_frame_output",
@@ -1304,6 +1306,125 @@ def ubm_kernel_time(diag, full, feats_list, n=20, min_post=0.025, reps=5):
                                      ctypes.c_float, ctypes.c_int32, ctypes.c_void_p]
     _check(L.xv_ubm_kernel_time(diag._h, full._h, packed.ctypes.data, off.ctypes.data, len(off) - 1, n, float(min_post), reps, ms))
     return dict(zip(("deltas", "gselect", "sort", "full", "softmax"), [float(x) for x in ms]))
+
+
+class FgmmAccumulator:
+    """The fp64 accumulators of full-covariance UBM training on one device (xv_fgmm_acc_create): occ [G], mean [G][D] and the packed
+    lower triangles cov [G][D (D + 1) / 2].  flags: letters of "mvw" (v implies m, m implies w)."""
+
+    def __init__(self, num_gauss, dim, flags="mvw", device=0):
+        L = lib()
+        self._h = ctypes.c_void_p()
+        self.num_gauss, self.dim, self.flags = int(num_gauss), int(dim), flags
+        L.xv_fgmm_acc_create.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
+        _check(L.xv_fgmm_acc_create(device, self.num_gauss, self.dim, flags.encode(), ctypes.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            L = lib()
+            L.xv_fgmm_acc_destroy.argtypes = [ctypes.c_void_p]
+            L.xv_fgmm_acc_destroy.restype = None
+            L.xv_fgmm_acc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _feats(self, feats, who):
+        import numpy as np
+        x = np.ascontiguousarray(feats, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise XvError(XV_ERR_ARG, "%s: the features are not [frames, %d]" % (who, self.dim))
+        return x
+
+    def accumulate(self, feats, post):
+        """One call: feats [frames, D]; post: per frame (indices, posteriors), as Ubm.post returns them for one utterance."""
+        import numpy as np
+        L = lib()
+        x = self._feats(feats, "accumulate")
+        if len(post) != x.shape[0]:
+            raise XvError(XV_ERR_ARG, "accumulate: one (indices, posteriors) pair per frame")
+        off = np.zeros(x.shape[0] + 1, dtype=np.int32)
+        for t, (i, _) in enumerate(post):
+            off[t + 1] = off[t] + len(i)
+        idx = np.ascontiguousarray(np.concatenate([np.asarray(i, np.int32) for i, _ in post]) if len(post) else np.zeros(0), dtype=np.int32)
+        w = np.ascontiguousarray(np.concatenate([np.asarray(p, np.float32) for _, p in post]) if len(post) else np.zeros(0), dtype=np.float32)
+        L.xv_fgmm_acc_add.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        _check(L.xv_fgmm_acc_add(self._h, x.ctypes.data, x.shape[0], off.ctypes.data, idx.ctypes.data, w.ctypes.data))
+
+    def accumulate_gselect(self, full, feats, gselect):
+        """The fused E-step: the posteriors of full.post(min_post=0) over gselect [frames, n] never leave the device.  Returns the
+        per-frame log-sums, float32 [frames]."""
+        import numpy as np
+        L = lib()
+        x = self._feats(feats, "accumulate_gselect")
+        gs = np.ascontiguousarray(gselect, dtype=np.int32)
+        if gs.ndim != 2 or gs.shape[0] != x.shape[0]:
+            raise XvError(XV_ERR_ARG, "accumulate_gselect: a [frames, n] selection")
+        logsum = np.zeros(x.shape[0], dtype=np.float32)
+        L.xv_fgmm_acc_add_gselect.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.c_void_p]
+        _check(L.xv_fgmm_acc_add_gselect(self._h, full._h, x.ctypes.data, x.shape[0], gs.ctypes.data, gs.shape[1], logsum.ctypes.data))
+        return logsum
+
+    def get(self):
+        """(occ [G], mean [G, D], cov [G, D (D + 1) / 2]) as float64."""
+        import numpy as np
+        L = lib()
+        g, d = self.num_gauss, self.dim
+        occ, mean, cov = np.zeros(g), np.zeros((g, d)), np.zeros((g, d * (d + 1) // 2))
+        L.xv_fgmm_acc_get.argtypes = [ctypes.c_void_p] * 4
+        _check(L.xv_fgmm_acc_get(self._h, occ.ctypes.data, mean.ctypes.data, cov.ctypes.data))
+        return occ, mean, cov
+
+    def kernel_time(self, full, feats, gselect, reps=5):
+        """{sort, full, softmax, acc} kernel times in ms of one fused call (xv_fgmm_acc_kernel_time: the best of reps).  Every run adds
+        to the accumulators."""
+        import numpy as np
+        L = lib()
+        x = self._feats(feats, "kernel_time")
+        gs = np.ascontiguousarray(gselect, dtype=np.int32)
+        ms = (ctypes.c_float * 4)()
+        L.xv_fgmm_acc_kernel_time.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_void_p]
+        _check(L.xv_fgmm_acc_kernel_time(self._h, full._h, x.ctypes.data, x.shape[0], gs.ctypes.data, gs.shape[1], reps, ms))
+        return dict(zip(("sort", "full", "softmax", "acc"), [float(v) for v in ms]))
+
+
+def fgmm_est(weights, means_invcovars, inv_covars, occ, mean, cov, acc_flags="mvw", update_flags="mvw", min_gaussian_weight=1e-5,
+             min_gaussian_occupancy=100.0, variance_floor=0.001, max_condition=1e5, remove_low_count_gaussians=True):
+    """The M-step of fgmm-global-est on host arrays (xv_fgmm_est, fp64): dict(weights, means_invcovars, inv_covars, gconsts) of the
+    Gaussians that survive, removed (indices), floored (eigenvalues, Gaussians), objf_before, objf_after, count."""
+    import numpy as np
+    L = lib()
+    w = np.array(weights, dtype=np.float32)
+    b = np.array(means_invcovars, dtype=np.float32)
+    ic = np.array(inv_covars, dtype=np.float32)
+    if b.ndim != 2 or w.shape != (b.shape[0],) or ic.shape != (b.shape[0], b.shape[1] * (b.shape[1] + 1) // 2):
+        raise XvError(XV_ERR_ARG, "fgmm_est: weights [G], means_invcovars [G][D], inv_covars [G][D (D + 1) / 2]")
+    g, d = b.shape
+    o = np.ascontiguousarray(occ, dtype=np.float64)
+    m = np.ascontiguousarray(mean, dtype=np.float64)
+    c = np.ascontiguousarray(cov, dtype=np.float64)
+    if o.shape != (g,) or m.shape != (g, d) or c.shape != ic.shape:
+        raise XvError(XV_ERR_ARG, "fgmm_est: occ [G], mean [G][D], cov [G][D (D + 1) / 2]")
+    gc = np.zeros(g, np.float32)
+    removed = np.zeros(g, np.int32)
+    floored = np.zeros(2, np.int32)
+    objf = np.zeros(3)
+    left = ctypes.c_int32()
+    L.xv_fgmm_est.argtypes = ([ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p] + [ctypes.c_void_p] * 3 + [ctypes.c_char_p] + [ctypes.c_double] * 4
+                              + [ctypes.c_int32] + [ctypes.c_void_p] * 4 + [ctypes.POINTER(ctypes.c_int32)] + [ctypes.c_void_p] * 3)
+    _check(L.xv_fgmm_est(g, d, acc_flags.encode(), o.ctypes.data, m.ctypes.data, c.ctypes.data, update_flags.encode(), min_gaussian_weight,
+                         min_gaussian_occupancy, variance_floor, max_condition, int(bool(remove_low_count_gaussians)), w.ctypes.data, b.ctypes.data,
+                         ic.ctypes.data, gc.ctypes.data, ctypes.byref(left), removed.ctypes.data, floored.ctypes.data, objf.ctypes.data))
+    k = left.value
+    return dict(weights=w[:k].copy(), means_invcovars=b[:k].copy(), inv_covars=ic[:k].copy(), gconsts=gc[:k].copy(),
+                removed=removed[:g - k].tolist(), floored=(int(floored[0]), int(floored[1])), objf_before=float(objf[0]),
+                objf_after=float(objf[1]), count=float(objf[2]))
 
 
 def ivex_read(rxfilename):

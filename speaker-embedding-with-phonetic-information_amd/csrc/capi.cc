@@ -29,6 +29,8 @@
 #include "table_extract.h"
 #include "ivex.h"
 #include "ubm.h"
+#include "ubm_train.h"
+#include "ubm_train_kernels.h"
 
 struct xv_model {
   xv::TdnnProgram prog;
@@ -1104,6 +1106,116 @@ xv_status xv_ubm_kernel_time(const xv_ubm* diag, const xv_ubm* full, const float
       xv::UbmPost(*full->m, feats, row_off, n_utts, gs.data(), n, min_post, count.data(), idx.data(), post.data(), nullptr, nullptr, &ms[2]);
       for (int i = 0; i < 5; ++i)
         if (r == 1 || (r > 1 && ms[i] < ms5[i])) ms5[i] = ms[i];
+    }
+    return XV_OK;
+  });
+}
+
+struct xv_fgmm_acc {
+  std::unique_ptr<xv::FgmmAccumulator> a;
+};
+
+xv_status xv_fgmm_acc_create(int device, int32_t num_gauss, int32_t dim, const char* update_flags, xv_fgmm_acc** out) {
+  if (!out || !update_flags) return Fail(XV_ERR_ARG, "xv_fgmm_acc_create: bad argument");
+  return Guard([&] {
+    std::unique_ptr<xv_fgmm_acc> h(new xv_fgmm_acc);
+    h->a.reset(xv::FgmmAccCreate(device, num_gauss, dim, xv::ParseGmmFlags(update_flags)));
+    *out = h.release();
+    return XV_OK;
+  });
+}
+
+void xv_fgmm_acc_destroy(xv_fgmm_acc* a) { delete a; }
+
+xv_status xv_fgmm_acc_add(xv_fgmm_acc* a, const float* feats, int32_t rows, const int32_t* post_off, const int32_t* post_idx,
+                          const float* post_w) {
+  if (!a || rows < 0 || !post_off) return Fail(XV_ERR_ARG, "xv_fgmm_acc_add: bad argument");
+  return Guard([&] {
+    xv::FgmmAccAdd(a->a.get(), feats, rows, post_off, post_idx, post_w);
+    return XV_OK;
+  });
+}
+
+xv_status xv_fgmm_acc_add_gselect(xv_fgmm_acc* a, const xv_ubm* full, const float* feats, int32_t rows, const int32_t* gselect, int32_t n,
+                                  float* logsum) {
+  if (!a || !full || rows < 0) return Fail(XV_ERR_ARG, "xv_fgmm_acc_add_gselect: bad argument");
+  return Guard([&] {
+    xv::FgmmAccAddGselect(a->a.get(), *full->m, feats, rows, gselect, n, logsum);
+    return XV_OK;
+  });
+}
+
+xv_status xv_fgmm_acc_get(const xv_fgmm_acc* a, double* occ, double* mean, double* cov) {
+  if (!a) return Fail(XV_ERR_ARG, "xv_fgmm_acc_get: bad argument");
+  return Guard([&] {
+    xv::FgmmAccGet(*a->a, occ, mean, cov);
+    return XV_OK;
+  });
+}
+
+xv_status xv_fgmm_est(int32_t num_gauss, int32_t dim, const char* acc_flags, const double* occ, const double* mean, const double* cov,
+                      const char* update_flags, double min_gaussian_weight, double min_gaussian_occupancy, double variance_floor,
+                      double max_condition, int32_t remove_low_count_gaussians, float* weights, float* means_invcovars, float* inv_covars,
+                      float* gconsts, int32_t* num_gauss_out, int32_t* removed, int32_t* floored2, double* objf3) {
+  if (num_gauss < 1 || dim < 1 || !acc_flags || !occ || !update_flags || !weights || !means_invcovars || !inv_covars || !gconsts || !num_gauss_out)
+    return Fail(XV_ERR_ARG, "xv_fgmm_est: bad argument");
+  return Guard([&] {
+    const size_t tri = (size_t)dim * (dim + 1) / 2;
+    xv::FgmmAccs accs;
+    accs.Init(num_gauss, dim, xv::ParseGmmFlags(acc_flags));
+    std::copy(occ, occ + num_gauss, accs.occ.begin());
+    if (accs.flags & xv::kFgmmFlagMeans) {
+      if (!mean) throw xv::KioError("xv_fgmm_est: the flags ask for mean accumulators");
+      std::copy(mean, mean + (size_t)num_gauss * dim, accs.mean.begin());
+    }
+    if (accs.flags & xv::kFgmmFlagVariances) {
+      if (!cov) throw xv::KioError("xv_fgmm_est: the flags ask for covariance accumulators");
+      std::copy(cov, cov + (size_t)num_gauss * tri, accs.cov.begin());
+    }
+    xv::FullGmmData m;
+    m.num_gauss = num_gauss;
+    m.dim = dim;
+    m.weights.assign(weights, weights + num_gauss);
+    m.means_invcovars.assign(means_invcovars, means_invcovars + (size_t)num_gauss * dim);
+    m.inv_covars.assign(inv_covars, inv_covars + (size_t)num_gauss * tri);
+    xv::ComputeGconsts(&m);
+    xv::FgmmEstOptions o;
+    o.min_gaussian_weight = min_gaussian_weight;
+    o.min_gaussian_occupancy = min_gaussian_occupancy;
+    o.variance_floor = variance_floor;
+    o.max_condition = max_condition;
+    o.remove_low_count_gaussians = remove_low_count_gaussians != 0;
+    xv::FgmmEstResult r;
+    xv::FgmmEst(accs, xv::ParseGmmFlags(update_flags), o, &m, &r);
+    std::copy(m.weights.begin(), m.weights.end(), weights);
+    std::copy(m.means_invcovars.begin(), m.means_invcovars.end(), means_invcovars);
+    std::copy(m.inv_covars.begin(), m.inv_covars.end(), inv_covars);
+    std::copy(m.gconsts.begin(), m.gconsts.end(), gconsts);
+    *num_gauss_out = m.num_gauss;
+    if (removed) std::copy(r.removed.begin(), r.removed.end(), removed);
+    if (floored2) {
+      floored2[0] = r.floored_elements;
+      floored2[1] = r.floored_gauss;
+    }
+    if (objf3) {
+      objf3[0] = r.objf_before;
+      objf3[1] = r.objf_after;
+      objf3[2] = r.count;
+    }
+    return XV_OK;
+  });
+}
+
+xv_status xv_fgmm_acc_kernel_time(xv_fgmm_acc* a, const xv_ubm* full, const float* feats, int32_t rows, const int32_t* gselect, int32_t n,
+                                  int32_t reps, float* ms4) {
+  if (!a || !full || !feats || !gselect || rows < 1 || reps < 1 || !ms4) return Fail(XV_ERR_ARG, "xv_fgmm_acc_kernel_time: bad argument");
+  return Guard([&] {
+    std::vector<float> logsum((size_t)rows);
+    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
+      float ms[4];
+      xv::FgmmAccAddGselect(a->a.get(), *full->m, feats, rows, gselect, n, logsum.data(), ms);
+      for (int i = 0; i < 4; ++i)
+        if (r == 1 || (r > 1 && ms[i] < ms4[i])) ms4[i] = ms[i];
     }
     return XV_OK;
   });

@@ -1627,6 +1627,9 @@ Matrix AsMatrix(const std::vector<float>& v, int rows, int cols) {
 
 }  // namespace
 
+int ReadPackedMatrix(Input& in, bool binary, std::vector<float>* packed) { return ReadPacked(in, binary, packed); }
+void WritePackedMatrix(Output& out, bool binary, const float* p, int dim) { WritePacked(out, binary, p, dim); }
+
 void ReadDiagGmm(Input& in, bool binary, DiagGmmData* m) {
   *m = DiagGmmData();
   std::string tok;

@@ -356,6 +356,10 @@ void ReadDiagGmm(Input& in, bool binary, DiagGmmData* m);
 void WriteDiagGmm(Output& out, bool binary, const DiagGmmData& m);
 void ReadFullGmm(Input& in, bool binary, FullGmmData* m);
 void WriteFullGmm(Output& out, bool binary, const FullGmmData& m);
+// One packed lower triangle as the full model stores it (FP / DP; text " [ rows ]"): dim (dim + 1) / 2 values appended to
+// *packed, the dimension returned; and its writer (FP).  The accumulators of ubm_train.h use them.
+int ReadPackedMatrix(Input& in, bool binary, std::vector<float>* packed);
+void WritePackedMatrix(Output& out, bool binary, const float* p, int dim);
 
 // vector<vector<int32>> (binary: int32 size, then per list a size byte 4, a raw int32 count and the values; text: "a b ; c d ; \n")
 typedef std::vector<std::vector<int32_t>> IntVecVec;

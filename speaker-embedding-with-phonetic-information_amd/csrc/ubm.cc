@@ -337,82 +337,98 @@ void UbmGselect(const UbmModel& diag, const float* feats, const int32_t* row_off
   if (ll) Check(hipMemcpy(ll, d_ll.p, (size_t)rows * n * 4, hipMemcpyDeviceToHost), "copy the log-likelihoods");
 }
 
+void CheckUbmSelection(const char* who, const UbmModel& full, const int32_t* gselect, int64_t rows, int n) {
+  const UbmModel::Impl& I = *full.impl_;
+  if (!I.full) throw KioError(std::string(who) + ": the model is a diagonal one; the posteriors take a full-covariance model");
+  if (n < 1 || n > kUbmMaxSelect)
+    throw KioError(std::string(who) + ": " + std::to_string(n) + " selected Gaussians per frame; the device kernels take 1 to " + std::to_string(kUbmMaxSelect));
+  if (rows == 0) return;
+  if (!gselect) throw KioError(std::string(who) + ": null buffer");
+  for (int64_t i = 0; i < rows * n; ++i)
+    if (gselect[i] < 0 || gselect[i] >= I.num_gauss)
+      throw KioError(std::string(who) + ": the selection names Gaussian " + std::to_string(gselect[i]) + "; the model has " + std::to_string(I.num_gauss));
+}
+
+void UbmPostDevice::Run(const UbmModel& full, const float* host_feats, const int32_t* host_gselect, int64_t rows, int n, float min_post,
+                        bool with_slot_post, float* device_ms3) {
+  const UbmModel::Impl& I = *full.impl_;
+  const size_t pairs = (size_t)rows * n;
+  UbmFullArgs a;
+  memset(&a, 0, sizeof a);
+  a.num_chunks = (int)((pairs + kUbmSortChunk - 1) / kUbmSortChunk);
+  const size_t hist_bytes = (size_t)I.num_gauss * a.num_chunks * 4;
+  rank.Reserve(pairs * 4);
+  hist.Reserve(hist_bytes);
+  start.Reserve((size_t)(I.num_gauss + 1) * 4);
+  sorted.Reserve(pairs * 4);
+  ll.Reserve(pairs * 4);
+  count.Reserve((size_t)rows * 4);
+  idx.Reserve(pairs * 4);
+  post.Reserve(pairs * 4);
+  logsum.Reserve((size_t)rows * 4);
+  if (with_slot_post) slot_post.Reserve(pairs * 4);
+  feats.Upload(host_feats, (size_t)rows * I.dim * 4, "copy features");
+  gselect.Upload(host_gselect, pairs * 4, "copy the selection");
+  Check(hipMemsetAsync(hist.p, 0, hist_bytes, nullptr), "hipMemsetAsync");
+  a.feats = feats.as<float>();
+  a.rows = rows;
+  a.dim = I.dim;
+  a.num_gauss = I.num_gauss;
+  a.inv_covars = I.b.as<float>();
+  a.lin = I.a.as<float>();
+  a.gconst = I.gconst.as<float>();
+  a.n = n;
+  a.gselect = gselect.as<int32_t>();
+  a.local_rank = rank.as<int32_t>();
+  a.chunk_hist = hist.as<int32_t>();
+  a.bucket_start = start.as<int32_t>();
+  a.sorted = sorted.as<int32_t>();
+  // enough workgroups per Gaussian that an average bucket is a few passes of each
+  const int64_t per_gauss = (int64_t)pairs / I.num_gauss;
+  a.split = (int)std::max<int64_t>(1, std::min<int64_t>(64, per_gauss / (4 * kUbmFullFrameTile)));
+  a.ll = ll.as<float>();
+  a.min_post = min_post;
+  a.out_count = count.as<int32_t>();
+  a.out_idx = idx.as<int32_t>();
+  a.out_post = post.as<float>();
+  a.out_logsum = logsum.as<float>();
+  a.out_slot_post = with_slot_post ? slot_post.as<float>() : nullptr;
+  EventTimer tm(device_ms3 != nullptr, 4);
+  tm.Mark();
+  Check(launch_ubm_bucket_sort(a, nullptr), "ubm_bucket_sort launch");
+  tm.Mark();
+  Check(launch_ubm_full_loglike(a, nullptr), "ubm_full_loglike launch");
+  tm.Mark();
+  Check(launch_ubm_post(a, nullptr), "ubm_post launch");
+  tm.Mark();
+  if (device_ms3)
+    for (int i = 0; i < 3; ++i) device_ms3[i] += tm.Span(i);
+}
+
 void UbmPost(const UbmModel& full, const float* feats, const int32_t* row_off, int n_utts, const int32_t* gselect, int n, float min_post,
              int32_t* count, int32_t* idx, float* post, float* ll, float* logsum, float* device_ms3) {
   if (device_ms3) device_ms3[0] = device_ms3[1] = device_ms3[2] = 0.f;
   const UbmModel::Impl& I = *full.impl_;
   if (!I.full) throw KioError("gselect-to-post: the model is a diagonal one; the posteriors take a full-covariance model");
   const int64_t rows = CheckOffsets("gselect-to-post", row_off, n_utts);
-  if (n < 1 || n > kUbmMaxSelect)
-    throw KioError("gselect-to-post: " + std::to_string(n) + " selected Gaussians per frame; the device kernels take 1 to " + std::to_string(kUbmMaxSelect));
+  CheckUbmSelection("gselect-to-post", full, nullptr, 0, n);   // n before the buffers ...
   if (rows == 0) return;
   if (!feats || !gselect || !count || !idx || !post) throw KioError("gselect-to-post: null buffer");
-  for (int64_t i = 0; i < rows * n; ++i)
-    if (gselect[i] < 0 || gselect[i] >= I.num_gauss)
-      throw KioError("gselect-to-post: the selection names Gaussian " + std::to_string(gselect[i]) + "; the model has " + std::to_string(I.num_gauss));
+  CheckUbmSelection("gselect-to-post", full, gselect, rows, n);   // ... and the entries last
   UseDevice(I.device, kWhoNeeds);
   // A call's frames go through in parts: the sort's (Gaussian, chunk) table stays small.  A frame's results do not depend on
   // the part it is in.
   constexpr int64_t kPart = 1 << 16;
-  DevBuf d_feats, d_gs, d_rank, d_hist, d_start, d_sorted, d_ll, d_count, d_idx, d_post, d_logsum;
+  UbmPostDevice dev;
   for (int64_t r0 = 0; r0 < rows; r0 += kPart) {
     const int64_t nr = rows - r0 < kPart ? rows - r0 : kPart;
     const size_t pairs = (size_t)nr * n;
-    UbmFullArgs a;
-    memset(&a, 0, sizeof a);
-    a.num_chunks = (int)((pairs + kUbmSortChunk - 1) / kUbmSortChunk);
-    const size_t hist_bytes = (size_t)I.num_gauss * a.num_chunks * 4;
-    if (r0 == 0) {
-      d_rank.Alloc(pairs * 4);
-      d_hist.Alloc(hist_bytes);
-      d_start.Alloc((size_t)(I.num_gauss + 1) * 4);
-      d_sorted.Alloc(pairs * 4);
-      d_ll.Alloc(pairs * 4);
-      d_count.Alloc((size_t)nr * 4);
-      d_idx.Alloc(pairs * 4);
-      d_post.Alloc(pairs * 4);
-      d_logsum.Alloc((size_t)nr * 4);
-    }
-    d_feats.Upload(feats + (size_t)r0 * I.dim, (size_t)nr * I.dim * 4, "copy features");
-    d_gs.Upload(gselect + (size_t)r0 * n, pairs * 4, "copy the selection");
-    Check(hipMemsetAsync(d_hist.p, 0, hist_bytes, nullptr), "hipMemsetAsync");
-    a.feats = d_feats.as<float>();
-    a.rows = nr;
-    a.dim = I.dim;
-    a.num_gauss = I.num_gauss;
-    a.inv_covars = I.b.as<float>();
-    a.lin = I.a.as<float>();
-    a.gconst = I.gconst.as<float>();
-    a.n = n;
-    a.gselect = d_gs.as<int32_t>();
-    a.local_rank = d_rank.as<int32_t>();
-    a.chunk_hist = d_hist.as<int32_t>();
-    a.bucket_start = d_start.as<int32_t>();
-    a.sorted = d_sorted.as<int32_t>();
-    // enough workgroups per Gaussian that an average bucket is a few passes of each
-    const int64_t per_gauss = (int64_t)pairs / I.num_gauss;
-    a.split = (int)std::max<int64_t>(1, std::min<int64_t>(64, per_gauss / (4 * kUbmFullFrameTile)));
-    a.ll = d_ll.as<float>();
-    a.min_post = min_post;
-    a.out_count = d_count.as<int32_t>();
-    a.out_idx = d_idx.as<int32_t>();
-    a.out_post = d_post.as<float>();
-    a.out_logsum = d_logsum.as<float>();
-    EventTimer tm(device_ms3 != nullptr, 4);
-    tm.Mark();
-    Check(launch_ubm_bucket_sort(a, nullptr), "ubm_bucket_sort launch");
-    tm.Mark();
-    Check(launch_ubm_full_loglike(a, nullptr), "ubm_full_loglike launch");
-    tm.Mark();
-    Check(launch_ubm_post(a, nullptr), "ubm_post launch");
-    tm.Mark();
-    if (device_ms3)
-      for (int i = 0; i < 3; ++i) device_ms3[i] += tm.Span(i);
-    Check(hipMemcpy(count + r0, d_count.p, (size_t)nr * 4, hipMemcpyDeviceToHost), "copy the posterior counts");
-    Check(hipMemcpy(idx + (size_t)r0 * n, d_idx.p, pairs * 4, hipMemcpyDeviceToHost), "copy the posterior indices");
-    Check(hipMemcpy(post + (size_t)r0 * n, d_post.p, pairs * 4, hipMemcpyDeviceToHost), "copy the posteriors");
-    if (ll) Check(hipMemcpy(ll + (size_t)r0 * n, d_ll.p, pairs * 4, hipMemcpyDeviceToHost), "copy the log-likelihoods");
-    if (logsum) Check(hipMemcpy(logsum + r0, d_logsum.p, (size_t)nr * 4, hipMemcpyDeviceToHost), "copy the log-sums");
+    dev.Run(full, feats + (size_t)r0 * I.dim, gselect + (size_t)r0 * n, nr, n, min_post, false, device_ms3);
+    dev.count.Download(count + r0, (size_t)nr * 4, "copy the posterior counts");
+    dev.idx.Download(idx + (size_t)r0 * n, pairs * 4, "copy the posterior indices");
+    dev.post.Download(post + (size_t)r0 * n, pairs * 4, "copy the posteriors");
+    if (ll) dev.ll.Download(ll + (size_t)r0 * n, pairs * 4, "copy the log-likelihoods");
+    if (logsum) dev.logsum.Download(logsum + r0, (size_t)nr * 4, "copy the log-sums");
   }
 }
 

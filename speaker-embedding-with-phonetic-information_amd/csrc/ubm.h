@@ -32,6 +32,7 @@
 #include <string>
 #include <vector>
 
+#include "device.h"
 #include "kio.h"
 
 namespace xv {
@@ -76,5 +77,19 @@ void UbmGselect(const UbmModel& diag, const float* feats, const int32_t* row_off
 // ll ([rows][n], the log-likelihoods before the softmax) and logsum ([rows]) may be null.  device_ms: {sort, scores, softmax}.
 void UbmPost(const UbmModel& full, const float* feats, const int32_t* row_off, int n_utts, const int32_t* gselect, int n, float min_post,
              int32_t* count, int32_t* idx, float* post, float* ll, float* logsum, float* device_ms3 = nullptr);
+
+// What UbmPost does on the device for one part of a call's frames, for the callers that keep the results there (ubm_train.h):
+// upload, sort, scores, softmax.  The buffers live as long as the object and only grow.  Run checks nothing: CheckUbmSelection
+// comes first.  KioError from the check names `who`.
+void CheckUbmSelection(const char* who, const UbmModel& full, const int32_t* gselect, int64_t rows, int n);
+struct UbmPostDevice {
+  DevBuf feats, gselect;                // the inputs of the part: [rows][dim], [rows][n]
+  DevBuf rank, hist, start, sorted;     // the sort: start [num_gauss + 1] buckets of `sorted` [rows * n] pair indices
+  DevBuf ll, count, idx, post, logsum;  // UbmPost's results
+  DevBuf slot_post;                     // with_slot_post: [rows][n] the posterior of selection slot i at i, zeros kept
+  // device_ms3 (may be null): {sort, scores, softmax} are added to it
+  void Run(const UbmModel& full, const float* host_feats, const int32_t* host_gselect, int64_t rows, int n, float min_post, bool with_slot_post,
+           float* device_ms3);
+};
 
 }  // namespace xv

@@ -89,6 +89,7 @@ struct UbmFullArgs {
   int32_t* out_idx;          // [rows][n] the first out_count[t] are set
   float* out_post;           // [rows][n]
   float* out_logsum;         // [rows] or null
+  float* out_slot_post;      // [rows][n] or null: the same posteriors where the selection has them, zeros kept (ubm_train.h)
 };
 
 hipError_t launch_add_deltas(const DeltaArgs& a, hipStream_t s);

@@ -321,6 +321,7 @@ __global__ __launch_bounds__(kUbmThreads) void ubm_post_kernel(const UbmFullArgs
       float p = expf(ll[i] - mx) * inv;
       if (p < a.min_post) p = 0.f;
       p = kept == 0.f ? (i == arg ? 1.f : 0.f) : p * rescale;
+      if (a.out_slot_post) a.out_slot_post[t * n + i] = p;
       if (p != 0.f) {
         idx[count] = gs[i];
         post[count] = p;
@@ -330,6 +331,7 @@ __global__ __launch_bounds__(kUbmThreads) void ubm_post_kernel(const UbmFullArgs
   } else {
     for (int i = 0; i < n; ++i) {
       const float p = expf(ll[i] - mx) * inv;
+      if (a.out_slot_post) a.out_slot_post[t * n + i] = p;
       if (p != 0.f) {
         idx[count] = gs[i];
         post[count] = p;
