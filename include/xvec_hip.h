@@ -644,6 +644,51 @@ xv_status xv_ivex_write(const char* wxfilename, int32_t binary, int32_t num_gaus
 xv_status xv_ivex_kernel_time(xv_ivex* m, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* post_off,
                               const int32_t* post_idx, const float* post_w, int32_t reps, float* ms5);
 
+/* ---- i-vector extractor training (ivector-extractor-init / -acc-stats / -sum-accs / -est, sid/train_ivector_extractor.sh:97-160).
+ * Semantics: csrc/ivex_train.h.  The statistics are fp64 and a function of the model and the ordered sequence of accepted utterances
+ * alone: how the utterances are split over calls changes no bit.  P = S (S + 1) / 2; packed arrays are lower triangles. */
+typedef struct xv_ivex_acc xv_ivex_acc;
+/* the accumulators on the model's device, at zero.  The model must outlive them. */
+xv_status xv_ivex_acc_create(const xv_ivex* m, int32_t update_variances, int32_t compute_auxf, xv_ivex_acc** out);
+void xv_ivex_acc_destroy(xv_ivex_acc* a);
+/* the arguments of xv_ivex_extract.  status [n_utts] (may be NULL): 0, or 1 for an utterance whose Q is not positive definite: it
+ * contributes to nothing. */
+xv_status xv_ivex_acc_add(xv_ivex_acc* a, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* post_off,
+                          const int32_t* post_idx, const float* post_w, int32_t* status);
+/* flushes what is pending and downloads: scalars3 = {num_ivectors, the objective, the weighted frame count}, gamma [G], Y [G][D][S],
+ * R [G][P], Sg [G][D (D + 1) / 2] (written only with update_variances), ivector_sum [S], ivector_scatter [P].  Any may be NULL. */
+xv_status xv_ivex_acc_get(xv_ivex_acc* a, double* scalars3, double* gamma, double* Y, double* R, double* Sg, double* ivector_sum,
+                          double* ivector_scatter);
+/* the pending utterances (fewer than 64) as the posterior kernel left them: m [count][S], scatter [count][P], logdet [count] (of
+ * the posterior covariance) and auxf [count] (the utterance's part of the objective that needs the posterior).  Any may be NULL. */
+xv_status xv_ivex_acc_pending(xv_ivex_acc* a, int32_t* count, double* m, double* scatter, double* logdet, double* auxf);
+/* the kernels' times in ms of one xv_ivex_acc_add followed by a flush, the best of reps runs after one that warms up: ms3 =
+ * {posterior kernel, R update, Y update}.  Every run adds the call's statistics to the accumulators. */
+xv_status xv_ivex_acc_kernel_time(xv_ivex_acc* a, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* post_off,
+                                  const int32_t* post_idx, const float* post_w, int32_t reps, float* ms3);
+/* the update kernel alone, on host arrays: C [c_rows][ldc] += A' B on rows < M and columns < N, A [64][M], B [64][N], of which the
+ * first `slots` rows count.  c_rows >= M, ldc >= N: what lies outside [M][N] must come back untouched. */
+xv_status xv_ivex_rank_update(int device, const double* A, const double* B, double* C, int32_t slots, int64_t M, int64_t N, int64_t c_rows,
+                              int64_t ldc);
+/* host only: ivector-extractor-init from a full-covariance UBM (weights [G], means_invcovars [G][D], inv_covars [G][D (D + 1) / 2]).
+ * w_vec [G], M [G][D][S], sigma_inv [G][D (D + 1) / 2] and *prior_offset (100) are written.  The same seed gives the same bytes. */
+xv_status xv_ivex_init(int32_t num_gauss, int32_t feat_dim, const float* weights, const float* means_invcovars, const float* inv_covars,
+                       int32_t ivector_dim, uint64_t seed, double* w_vec, double* M, double* sigma_inv, double* prior_offset);
+/* host only (fp64): the M-step of ivector-extractor-est.  Sg may be NULL without has_variances.  M, sigma_inv and *prior_offset are
+ * updated in place.  counts6 = {Gaussians updated, skipped, eigenvalues of R floored, variances floored, Gaussians they belong to,
+ * eigenvalues of the i-vector covariance floored}; impr3 = the objective improvements per frame of {projections, variances,
+ * prior}; V [S][S]: the transform of the i-vectors the prior update applied.  The last three may be NULL. */
+xv_status xv_ivex_est(int32_t num_gauss, int32_t feat_dim, int32_t ivector_dim, int32_t has_variances, const double* scalars3, const double* gamma,
+                      const double* Y, const double* R, const double* Sg, const double* ivector_sum, const double* ivector_scatter,
+                      double variance_floor_factor, double gaussian_min_count, int32_t diagonalize, int32_t num_threads, const double* w_vec, double* M,
+                      double* sigma_inv, double* prior_offset, int32_t* counts6, double* impr3, double* V);
+/* host only: the statistics file to host arrays and back.  xv_ivex_stats_read fills the shape and whichever arrays are not NULL. */
+xv_status xv_ivex_stats_read(const char* rxfilename, int32_t* num_gauss, int32_t* feat_dim, int32_t* ivector_dim, int32_t* has_variances, double* scalars3,
+                             double* gamma, double* Y, double* R, double* Sg, double* ivector_sum, double* ivector_scatter);
+xv_status xv_ivex_stats_write(const char* wxfilename, int32_t binary, int32_t num_gauss, int32_t feat_dim, int32_t ivector_dim, int32_t has_variances,
+                              const double* scalars3, const double* gamma, const double* Y, const double* R, const double* Sg, const double* ivector_sum,
+                              const double* ivector_scatter);
+
 /* ---- kernel-level entries of the frame-level and small kernels (unit tests; same conventions: device pointers from the caller
  * unless stated, an optional stream, XV_ERR_ARG with a reason for geometry a kernel cannot run, no engine or context) ---------- */
 /* tdnn_first_kernel: the layer(s) that read the network input.  Chunk b holds rows [row_offsets[b], row_offsets[b + 1]) of feats

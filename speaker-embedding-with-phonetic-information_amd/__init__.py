@@ -143,6 +143,8 @@ ABI_SYMBOLS = [
     "xv_fgmm_acc_kernel_time",
     "xv_ivex_create", "xv_ivex_load", "xv_ivex_destroy", "xv_ivex_info", "xv_ivex_derived", "xv_ivex_extract", "xv_ivex_read",
     "xv_ivex_write", "xv_ivex_kernel_time",
+    "xv_ivex_acc_create", "xv_ivex_acc_destroy", "xv_ivex_acc_add", "xv_ivex_acc_get", "xv_ivex_acc_pending", "xv_ivex_acc_kernel_time",
+    "xv_ivex_rank_update", "xv_ivex_init", "xv_ivex_est", "xv_ivex_stats_read", "xv_ivex_stats_write",
     "xv_kernel_first_layer", "xv_kernel_prep_input", "xv_kernel_pool_finalise", "xv_kernel_frame_output",
     "xv_wave_read", "xv_wave_free", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
 ]
@@ -1570,6 +1572,199 @@ class IvectorExtractor:
         _check(L.xv_ivex_kernel_time(self._h, packed.ctypes.data, off.ctypes.data, len(off) - 1, post_off.ctypes.data, post_idx.ctypes.data,
                                      post_w.ctypes.data, reps, ms))
         return dict(zip(("stats", "quadratic", "linear", "solve", "derive"), [float(x) for x in ms]))
+
+
+def _ivex_stats_arrays(G, D, S, has_variances):
+    import numpy as np
+    P = S * (S + 1) // 2
+    return dict(scalars=np.zeros(3), gamma=np.zeros(G), Y=np.zeros((G, D, S)), R=np.zeros((G, P)),
+                S=np.zeros((G, D * (D + 1) // 2)) if has_variances else None, ivector_sum=np.zeros(S), ivector_scatter=np.zeros(P))
+
+
+def _ivex_stats_out(a):
+    out = dict(num_ivectors=float(a["scalars"][0]), auxf=float(a["scalars"][1]), frames=float(a["scalars"][2]))
+    out.update({k: a[k] for k in ("gamma", "Y", "R", "S", "ivector_sum", "ivector_scatter")})
+    return out
+
+
+def _ivex_stats_in(stats, who):
+    """the dict of IvexAccumulator.get() -> (G, D, S, has_variances, the seven pointers' arrays)"""
+    import numpy as np
+    Y = np.ascontiguousarray(stats["Y"], dtype=np.float64)
+    if Y.ndim != 3:
+        raise XvError(XV_ERR_ARG, who + ": Y [G][D][S]")
+    G, D, S = Y.shape
+    P = S * (S + 1) // 2
+    has = stats.get("S") is not None
+    arr = dict(scalars=np.array([stats["num_ivectors"], stats["auxf"], stats["frames"]], dtype=np.float64), Y=Y)
+    for k, shape in (("gamma", (G,)), ("R", (G, P)), ("S", (G, D * (D + 1) // 2)), ("ivector_sum", (S,)), ("ivector_scatter", (P,))):
+        if k == "S" and not has:
+            arr[k] = None
+            continue
+        arr[k] = np.ascontiguousarray(stats[k], dtype=np.float64)
+        if arr[k].shape != shape:
+            raise XvError(XV_ERR_ARG, "%s: %s has shape %s, the statistics ask for %s" % (who, k, arr[k].shape, shape))
+    return G, D, S, has, arr
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def ivex_stats_read(rxfilename):
+    """The statistics file of ivector-extractor-acc-stats as the dict of IvexAccumulator.get().  Host only."""
+    L = lib()
+    L.xv_ivex_stats_read.argtypes = [ctypes.c_char_p] + [ctypes.POINTER(ctypes.c_int32)] * 4 + [ctypes.c_void_p] * 7
+    g, d, s, v = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    _check(L.xv_ivex_stats_read(rxfilename.encode(), ctypes.byref(g), ctypes.byref(d), ctypes.byref(s), ctypes.byref(v), *([None] * 7)))
+    a = _ivex_stats_arrays(g.value, d.value, s.value, bool(v.value))
+    _check(L.xv_ivex_stats_read(rxfilename.encode(), None, None, None, None, a["scalars"].ctypes.data, a["gamma"].ctypes.data, a["Y"].ctypes.data,
+                                a["R"].ctypes.data, _ptr(a["S"]), a["ivector_sum"].ctypes.data, a["ivector_scatter"].ctypes.data))
+    return _ivex_stats_out(a)
+
+
+def ivex_stats_write(wxfilename, stats, binary=True):
+    """The dict of IvexAccumulator.get() to a statistics file (text: 17 significant digits).  Host only."""
+    L = lib()
+    G, D, S, has, a = _ivex_stats_in(stats, "ivex_stats_write")
+    L.xv_ivex_stats_write.argtypes = [ctypes.c_char_p] + [ctypes.c_int32] * 5 + [ctypes.c_void_p] * 7
+    _check(L.xv_ivex_stats_write(wxfilename.encode(), int(bool(binary)), G, D, S, int(has), a["scalars"].ctypes.data, a["gamma"].ctypes.data,
+                                 a["Y"].ctypes.data, a["R"].ctypes.data, _ptr(a["S"]), a["ivector_sum"].ctypes.data, a["ivector_scatter"].ctypes.data))
+
+
+def ivex_init(weights, means_invcovars, inv_covars, ivector_dim=400, seed=0):
+    """ivector-extractor-init on host arrays: a full-covariance UBM (float32 weights [G], means_invcovars [G][D], inv_covars
+    [G][D (D + 1) / 2]) -> dict(w_vec, M, sigma_inv, prior_offset).  The same seed gives the same bytes.  Host only."""
+    import numpy as np
+    L = lib()
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    b = np.ascontiguousarray(means_invcovars, dtype=np.float32)
+    ic = np.ascontiguousarray(inv_covars, dtype=np.float32)
+    if b.ndim != 2 or w.shape != (b.shape[0],) or ic.shape != (b.shape[0], b.shape[1] * (b.shape[1] + 1) // 2):
+        raise XvError(XV_ERR_ARG, "ivex_init: weights [G], means_invcovars [G][D], inv_covars [G][D (D + 1) / 2]")
+    G, D = b.shape
+    S = int(ivector_dim)
+    w_vec, M, sig = np.zeros(G), np.zeros((G, D, max(S, 1))), np.zeros((G, D * (D + 1) // 2))
+    p = ctypes.c_double()
+    L.xv_ivex_init.argtypes = [ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 3 + [ctypes.c_int32, ctypes.c_uint64] + [ctypes.c_void_p] * 3 + [
+        ctypes.POINTER(ctypes.c_double)]
+    _check(L.xv_ivex_init(G, D, w.ctypes.data, b.ctypes.data, ic.ctypes.data, S, int(seed) & (2 ** 64 - 1), w_vec.ctypes.data, M.ctypes.data,
+                          sig.ctypes.data, ctypes.byref(p)))
+    return dict(w_vec=w_vec, M=M, sigma_inv=sig, prior_offset=p.value)
+
+
+def ivex_est(stats, w_vec, M, sigma_inv, prior_offset, variance_floor_factor=0.1, gaussian_min_count=100.0, diagonalize=True, num_threads=1):
+    """The M-step of ivector-extractor-est (host, fp64) on the dict of IvexAccumulator.get().  Returns dict(w_vec, M, sigma_inv,
+    prior_offset, V [S][S], gauss_updated, gauss_skipped, eig_floored, var_floored, var_floored_gauss, prior_floored, impr_proj,
+    impr_var, impr_prior); the improvements are per frame."""
+    import numpy as np
+    L = lib()
+    w_vec, M, sig = _ivex_arrays(w_vec, M, sigma_inv, "ivex_est")
+    M, sig = M.copy(), sig.copy()
+    G, D, S, has, a = _ivex_stats_in(stats, "ivex_est")
+    if M.shape != (G, D, S):
+        raise XvError(XV_ERR_ARG, "ivex_est: the statistics' shape %s is not the model's %s" % ((G, D, S), M.shape))
+    p = ctypes.c_double(float(prior_offset))
+    counts, impr, V = np.zeros(6, np.int32), np.zeros(3), np.zeros((S, S))
+    L.xv_ivex_est.argtypes = [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 7 + [ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int32] + [
+        ctypes.c_void_p] * 3 + [ctypes.POINTER(ctypes.c_double)] + [ctypes.c_void_p] * 3
+    _check(L.xv_ivex_est(G, D, S, int(has), a["scalars"].ctypes.data, a["gamma"].ctypes.data, a["Y"].ctypes.data, a["R"].ctypes.data, _ptr(a["S"]),
+                         a["ivector_sum"].ctypes.data, a["ivector_scatter"].ctypes.data, float(variance_floor_factor), float(gaussian_min_count),
+                         int(bool(diagonalize)), int(num_threads), w_vec.ctypes.data, M.ctypes.data, sig.ctypes.data, ctypes.byref(p),
+                         counts.ctypes.data, impr.ctypes.data, V.ctypes.data))
+    out = dict(w_vec=w_vec, M=M, sigma_inv=sig, prior_offset=p.value, V=V)
+    out.update(zip(("gauss_updated", "gauss_skipped", "eig_floored", "var_floored", "var_floored_gauss", "prior_floored"), [int(c) for c in counts]))
+    out.update(zip(("impr_proj", "impr_var", "impr_prior"), [float(x) for x in impr]))
+    return out
+
+
+def ivex_rank_update(A, B, C, slots, M, N, device=0):
+    """The update kernel of extractor training alone (xv_ivex_rank_update): C[:M, :N] += A[:slots, :M].T @ B[:slots, :N] on the
+    device; A [64][M], B [64][N], C [rows >= M][ld >= N] float64.  Returns the new C; what lies outside [M][N] comes back as it went."""
+    import numpy as np
+    L = lib()
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    B = np.ascontiguousarray(B, dtype=np.float64)
+    C = np.array(C, dtype=np.float64, order="C")
+    if A.shape != (64, M) or B.shape != (64, N) or C.ndim != 2:
+        raise XvError(XV_ERR_ARG, "ivex_rank_update: A [64][M], B [64][N], C [rows][ld]")
+    L.xv_ivex_rank_update.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int32] + [ctypes.c_int64] * 4
+    _check(L.xv_ivex_rank_update(device, A.ctypes.data, B.ctypes.data, C.ctypes.data, int(slots), int(M), int(N), C.shape[0], C.shape[1]))
+    return C
+
+
+class IvexAccumulator:
+    """The fp64 statistics of i-vector extractor training on the model's device (xv_ivex_acc_create; semantics in csrc/ivex_train.h).
+    They are a function of the model and the ordered sequence of accepted utterances: how accumulate() calls split them changes no bit."""
+
+    def __init__(self, model, update_variances=True, compute_auxf=True):
+        L = lib()
+        self.model = model   # the device model must outlive the accumulators
+        self.update_variances = bool(update_variances)
+        self._h = ctypes.c_void_p()
+        L.xv_ivex_acc_create.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]
+        _check(L.xv_ivex_acc_create(model._h, int(self.update_variances), int(bool(compute_auxf)), ctypes.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            L = lib()
+            L.xv_ivex_acc_destroy.argtypes = [ctypes.c_void_p]
+            L.xv_ivex_acc_destroy.restype = None
+            L.xv_ivex_acc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def accumulate(self, feats_list, post_list):
+        """The inputs of IvectorExtractor.extract.  Returns status int32 [n]: 1 for an utterance whose Q is not positive definite (it
+        contributes to nothing)."""
+        import numpy as np
+        L = lib()
+        packed, off, post_off, post_idx, post_w = self.model._inputs(feats_list, post_list, "accumulate")
+        status = np.zeros(len(off) - 1, np.int32)
+        L.xv_ivex_acc_add.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_void_p] * 4
+        _check(L.xv_ivex_acc_add(self._h, packed.ctypes.data, off.ctypes.data, len(off) - 1, post_off.ctypes.data, post_idx.ctypes.data,
+                                 post_w.ctypes.data, status.ctypes.data))
+        return status
+
+    def get(self):
+        """Flushes what is pending and returns dict(num_ivectors, auxf, frames, gamma [G], Y [G][D][S], R [G][P], S [G][D (D + 1) / 2]
+        or None, ivector_sum [S], ivector_scatter [P])."""
+        L = lib()
+        m = self.model
+        a = _ivex_stats_arrays(m.num_gauss, m.feat_dim, m.ivector_dim, self.update_variances)
+        L.xv_ivex_acc_get.argtypes = [ctypes.c_void_p] * 8
+        _check(L.xv_ivex_acc_get(self._h, a["scalars"].ctypes.data, a["gamma"].ctypes.data, a["Y"].ctypes.data, a["R"].ctypes.data, _ptr(a["S"]),
+                                 a["ivector_sum"].ctypes.data, a["ivector_scatter"].ctypes.data))
+        return _ivex_stats_out(a)
+
+    def pending(self):
+        """The pending utterances as the posterior kernel left them: dict(m [n][S], scatter [n][P], logdet [n], auxf [n])."""
+        import numpy as np
+        L = lib()
+        S = self.model.ivector_dim
+        P = S * (S + 1) // 2
+        m, sc, ld, ax = np.zeros((64, S)), np.zeros((64, P)), np.zeros(64), np.zeros(64)
+        n = ctypes.c_int32()
+        L.xv_ivex_acc_pending.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)] + [ctypes.c_void_p] * 4
+        _check(L.xv_ivex_acc_pending(self._h, ctypes.byref(n), m.ctypes.data, sc.ctypes.data, ld.ctypes.data, ax.ctypes.data))
+        k = n.value
+        return dict(m=m[:k].copy(), scatter=sc[:k].copy(), logdet=ld[:k].copy(), auxf=ax[:k].copy())
+
+    def kernel_time(self, feats_list, post_list, reps=3):
+        """{posterior, rank_update_R, rank_update_Y} kernel times in ms of one accumulate() and flush (the best of reps).  Every run
+        adds the call's statistics to the accumulators."""
+        L = lib()
+        packed, off, post_off, post_idx, post_w = self.model._inputs(feats_list, post_list, "kernel_time")
+        ms = (ctypes.c_float * 3)()
+        L.xv_ivex_acc_kernel_time.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int32] + [ctypes.c_void_p] * 3 + [ctypes.c_int32, ctypes.c_void_p]
+        _check(L.xv_ivex_acc_kernel_time(self._h, packed.ctypes.data, off.ctypes.data, len(off) - 1, post_off.ctypes.data, post_idx.ctypes.data,
+                                         post_w.ctypes.data, reps, ms))
+        return dict(zip(("posterior", "rank_update_R", "rank_update_Y"), [float(x) for x in ms]))
 
 
 def kernel_tdnn_gemm(desc):

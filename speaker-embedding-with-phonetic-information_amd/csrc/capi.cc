@@ -28,6 +28,7 @@
 #include "program.h"
 #include "table_extract.h"
 #include "ivex.h"
+#include "ivex_train.h"
 #include "ubm.h"
 #include "ubm_train.h"
 #include "ubm_train_kernels.h"
@@ -1349,6 +1350,197 @@ xv_status xv_ivex_kernel_time(xv_ivex* m, const float* feats, const int32_t* row
         if (r == 1 || (r > 1 && ms[i] < ms5[i])) ms5[i] = ms[i];
     }
     ms5[4] = m->m->derive_ms();
+    return XV_OK;
+  });
+}
+
+// ---- i-vector extractor training (ivex_train.h)
+struct xv_ivex_acc {
+  std::unique_ptr<xv::IvexAccumulator> a;
+};
+
+namespace {
+
+size_t TriOf(int32_t d) { return (size_t)d * (d + 1) / 2; }
+
+void FillIvexStats(int32_t G, int32_t D, int32_t S, int32_t has_variances, const double* scalars3, const double* gamma, const double* Y, const double* R,
+                   const double* Sg, const double* ivector_sum, const double* ivector_scatter, xv::IvexStats* st) {
+  if (!scalars3 || !gamma || !Y || !R || !ivector_sum || !ivector_scatter || (has_variances && !Sg)) throw xv::KioError("i-vector extractor statistics: null array");
+  st->Init(G, D, S, has_variances != 0);
+  st->num_ivectors = scalars3[0];
+  st->auxf = scalars3[1];
+  st->frames = scalars3[2];
+  std::copy(gamma, gamma + st->gamma.size(), st->gamma.begin());
+  std::copy(Y, Y + st->Y.size(), st->Y.begin());
+  std::copy(R, R + st->R.size(), st->R.begin());
+  if (has_variances) std::copy(Sg, Sg + st->Sg.size(), st->Sg.begin());
+  std::copy(ivector_sum, ivector_sum + st->ivector_sum.size(), st->ivector_sum.begin());
+  std::copy(ivector_scatter, ivector_scatter + st->ivector_scatter.size(), st->ivector_scatter.begin());
+}
+
+void CopyIvexStats(const xv::IvexStats& st, double* scalars3, double* gamma, double* Y, double* R, double* Sg, double* ivector_sum, double* ivector_scatter) {
+  if (scalars3) {
+    scalars3[0] = st.num_ivectors;
+    scalars3[1] = st.auxf;
+    scalars3[2] = st.frames;
+  }
+  if (gamma) std::copy(st.gamma.begin(), st.gamma.end(), gamma);
+  if (Y) std::copy(st.Y.begin(), st.Y.end(), Y);
+  if (R) std::copy(st.R.begin(), st.R.end(), R);
+  if (Sg) std::copy(st.Sg.begin(), st.Sg.end(), Sg);
+  if (ivector_sum) std::copy(st.ivector_sum.begin(), st.ivector_sum.end(), ivector_sum);
+  if (ivector_scatter) std::copy(st.ivector_scatter.begin(), st.ivector_scatter.end(), ivector_scatter);
+}
+
+}  // namespace
+
+xv_status xv_ivex_acc_create(const xv_ivex* m, int32_t update_variances, int32_t compute_auxf, xv_ivex_acc** out) {
+  if (!m || !out) return Fail(XV_ERR_ARG, "xv_ivex_acc_create: bad argument");
+  return Guard([&] {
+    std::unique_ptr<xv_ivex_acc> h(new xv_ivex_acc);
+    h->a.reset(xv::IvexAccCreate(m->m.get(), update_variances != 0, compute_auxf != 0));
+    *out = h.release();
+    return XV_OK;
+  });
+}
+
+void xv_ivex_acc_destroy(xv_ivex_acc* a) { delete a; }
+
+xv_status xv_ivex_acc_add(xv_ivex_acc* a, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* post_off, const int32_t* post_idx,
+                          const float* post_w, int32_t* status) {
+  if (!a || !row_off || n_utts < 0) return Fail(XV_ERR_ARG, "xv_ivex_acc_add: bad argument");
+  return Guard([&] {
+    xv::IvexAccAdd(a->a.get(), feats, row_off, n_utts, post_off, post_idx, post_w, status);
+    return XV_OK;
+  });
+}
+
+xv_status xv_ivex_acc_get(xv_ivex_acc* a, double* scalars3, double* gamma, double* Y, double* R, double* Sg, double* ivector_sum,
+                          double* ivector_scatter) {
+  if (!a) return Fail(XV_ERR_ARG, "xv_ivex_acc_get: bad argument");
+  return Guard([&] {
+    xv::IvexStats st;
+    xv::IvexAccGet(a->a.get(), &st);
+    CopyIvexStats(st, scalars3, gamma, Y, R, st.has_variances ? Sg : nullptr, ivector_sum, ivector_scatter);
+    return XV_OK;
+  });
+}
+
+xv_status xv_ivex_acc_pending(xv_ivex_acc* a, int32_t* count, double* m, double* scatter, double* logdet, double* auxf) {
+  if (!a || !count) return Fail(XV_ERR_ARG, "xv_ivex_acc_pending: bad argument");
+  return Guard([&] {
+    *count = xv::IvexAccPending(a->a.get(), m, scatter, logdet, auxf);
+    return XV_OK;
+  });
+}
+
+xv_status xv_ivex_acc_kernel_time(xv_ivex_acc* a, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* post_off,
+                                  const int32_t* post_idx, const float* post_w, int32_t reps, float* ms3) {
+  if (!a || !feats || !row_off || !post_off || n_utts < 1 || reps < 1 || !ms3) return Fail(XV_ERR_ARG, "xv_ivex_acc_kernel_time: bad argument");
+  return Guard([&] {
+    xv::IvexStats st;
+    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
+      float add[3], get[3];
+      xv::IvexAccAdd(a->a.get(), feats, row_off, n_utts, post_off, post_idx, post_w, nullptr, add);
+      xv::IvexAccGet(a->a.get(), &st, get);
+      for (int i = 0; i < 3; ++i) {
+        const float ms = add[i] + get[i];
+        if (r == 1 || (r > 1 && ms < ms3[i])) ms3[i] = ms;
+      }
+    }
+    return XV_OK;
+  });
+}
+
+xv_status xv_ivex_rank_update(int device, const double* A, const double* B, double* C, int32_t slots, int64_t M, int64_t N, int64_t c_rows, int64_t ldc) {
+  return Guard([&] {
+    xv::IvexRankUpdateHost(device, A, B, C, slots, M, N, c_rows, ldc);
+    return XV_OK;
+  });
+}
+
+xv_status xv_ivex_init(int32_t num_gauss, int32_t feat_dim, const float* weights, const float* means_invcovars, const float* inv_covars,
+                       int32_t ivector_dim, uint64_t seed, double* w_vec, double* M, double* sigma_inv, double* prior_offset) {
+  if (num_gauss < 1 || feat_dim < 1 || !weights || !means_invcovars || !inv_covars || !w_vec || !M || !sigma_inv || !prior_offset)
+    return Fail(XV_ERR_ARG, "xv_ivex_init: bad argument");
+  return Guard([&] {
+    xv::FullGmmData ubm;
+    ubm.num_gauss = num_gauss;
+    ubm.dim = feat_dim;
+    ubm.weights.assign(weights, weights + num_gauss);
+    ubm.means_invcovars.assign(means_invcovars, means_invcovars + (size_t)num_gauss * feat_dim);
+    ubm.inv_covars.assign(inv_covars, inv_covars + (size_t)num_gauss * TriOf(feat_dim));
+    xv::IvexData d;
+    xv::IvexInit(ubm, ivector_dim, seed, &d);
+    std::copy(d.w_vec.begin(), d.w_vec.end(), w_vec);
+    std::copy(d.M.begin(), d.M.end(), M);
+    std::copy(d.sigma_inv.begin(), d.sigma_inv.end(), sigma_inv);
+    *prior_offset = d.prior_offset;
+    return XV_OK;
+  });
+}
+
+xv_status xv_ivex_est(int32_t num_gauss, int32_t feat_dim, int32_t ivector_dim, int32_t has_variances, const double* scalars3, const double* gamma,
+                      const double* Y, const double* R, const double* Sg, const double* ivector_sum, const double* ivector_scatter,
+                      double variance_floor_factor, double gaussian_min_count, int32_t diagonalize, int32_t num_threads, const double* w_vec, double* M,
+                      double* sigma_inv, double* prior_offset, int32_t* counts6, double* impr3, double* V) {
+  if (!prior_offset) return Fail(XV_ERR_ARG, "xv_ivex_est: bad argument");
+  return Guard([&] {
+    xv::IvexStats st;
+    FillIvexStats(num_gauss, feat_dim, ivector_dim, has_variances, scalars3, gamma, Y, R, Sg, ivector_sum, ivector_scatter, &st);
+    xv::IvexData d;
+    FillIvexData(num_gauss, feat_dim, ivector_dim, w_vec, M, sigma_inv, *prior_offset, &d);
+    xv::IvexEstOptions o;
+    o.variance_floor_factor = variance_floor_factor;
+    o.gaussian_min_count = gaussian_min_count;
+    o.diagonalize = diagonalize != 0;
+    o.num_threads = num_threads;
+    xv::IvexEstResult r;
+    xv::IvexEst(st, o, &d, &r);
+    std::copy(d.M.begin(), d.M.end(), M);
+    std::copy(d.sigma_inv.begin(), d.sigma_inv.end(), sigma_inv);
+    *prior_offset = d.prior_offset;
+    if (counts6) {
+      counts6[0] = r.gauss_updated;
+      counts6[1] = r.gauss_skipped;
+      counts6[2] = r.eig_floored;
+      counts6[3] = r.var_floored;
+      counts6[4] = r.var_floored_gauss;
+      counts6[5] = r.prior_floored;
+    }
+    if (impr3) {
+      impr3[0] = r.impr_proj;
+      impr3[1] = r.impr_var;
+      impr3[2] = r.impr_prior;
+    }
+    if (V) std::copy(r.V.begin(), r.V.end(), V);
+    return XV_OK;
+  });
+}
+
+xv_status xv_ivex_stats_read(const char* rxfilename, int32_t* num_gauss, int32_t* feat_dim, int32_t* ivector_dim, int32_t* has_variances, double* scalars3,
+                             double* gamma, double* Y, double* R, double* Sg, double* ivector_sum, double* ivector_scatter) {
+  if (!rxfilename) return Fail(XV_ERR_ARG, "xv_ivex_stats_read: bad argument");
+  return Guard([&] {
+    xv::IvexStats st;
+    xv::ReadIvexStatsFile(rxfilename, &st);
+    if (num_gauss) *num_gauss = st.G;
+    if (feat_dim) *feat_dim = st.D;
+    if (ivector_dim) *ivector_dim = st.S;
+    if (has_variances) *has_variances = st.has_variances ? 1 : 0;
+    CopyIvexStats(st, scalars3, gamma, Y, R, st.has_variances ? Sg : nullptr, ivector_sum, ivector_scatter);
+    return XV_OK;
+  });
+}
+
+xv_status xv_ivex_stats_write(const char* wxfilename, int32_t binary, int32_t num_gauss, int32_t feat_dim, int32_t ivector_dim, int32_t has_variances,
+                              const double* scalars3, const double* gamma, const double* Y, const double* R, const double* Sg, const double* ivector_sum,
+                              const double* ivector_scatter) {
+  if (!wxfilename) return Fail(XV_ERR_ARG, "xv_ivex_stats_write: bad argument");
+  return Guard([&] {
+    xv::IvexStats st;
+    FillIvexStats(num_gauss, feat_dim, ivector_dim, has_variances, scalars3, gamma, Y, R, Sg, ivector_sum, ivector_scatter, &st);
+    xv::WriteIvexStatsFile(wxfilename, binary != 0, st);
     return XV_OK;
   });
 }

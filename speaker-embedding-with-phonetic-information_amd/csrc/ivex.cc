@@ -163,7 +163,9 @@ struct IvexModel::Impl {
   int64_t P = 0;
   double prior_offset = 0.0;
   float derive_ms = 0.f;
+  std::vector<double> w_vec, sigma_inv;   // host
   DevBuf sigma_inv_m, U;
+  DevBuf solution;                        // [B][S] fp64, allocated by the first call that has a group hook
   // workspaces of one launch group, allocated once
   DevBuf gamma, X, partial, linear, quadratic, work, ivec, auxf, status, bucket_start;
   // what follows the group's frames and pairs: grown when a group needs more
@@ -176,6 +178,9 @@ int IvexModel::num_gauss() const { return impl_->G; }
 int IvexModel::feat_dim() const { return impl_->D; }
 int IvexModel::ivector_dim() const { return impl_->S; }
 float IvexModel::derive_ms() const { return impl_->derive_ms; }
+double IvexModel::prior_offset() const { return impl_->prior_offset; }
+const std::vector<double>& IvexModel::w_vec() const { return impl_->w_vec; }
+const std::vector<double>& IvexModel::sigma_inv() const { return impl_->sigma_inv; }
 
 IvexModel* IvexCreate(int device, const IvexData& m) {
   CheckShape(m);
@@ -189,6 +194,8 @@ IvexModel* IvexCreate(int device, const IvexData& m) {
   I.S = m.S;
   I.P = (int64_t)m.S * (m.S + 1) / 2;
   I.prior_offset = m.prior_offset;
+  I.w_vec = m.w_vec;
+  I.sigma_inv = m.sigma_inv;
   const int64_t K = (int64_t)m.G * m.D;
   I.lin_chunks = (int)((K + kIvexKChunk - 1) / kIvexKChunk);
   I.sigma_inv_m.Reserve((size_t)K * m.S * 8);
@@ -236,7 +243,7 @@ void IvexDerived(const IvexModel& m, double* sigma_inv_m, double* U) {
 }
 
 void IvexExtract(IvexModel& m, const float* feats, const int32_t* row_off, int n_utts, const int32_t* post_off, const int32_t* post_idx,
-                 const float* post_w, double acoustic_weight, double max_count, const IvexOutputs& out) {
+                 const float* post_w, double acoustic_weight, double max_count, const IvexOutputs& out, const IvexGroupHook* after_group) {
   IvexModel::Impl& I = *m.impl_;
   if (out.device_ms4) out.device_ms4[0] = out.device_ms4[1] = out.device_ms4[2] = out.device_ms4[3] = 0.f;
   if (n_utts < 0 || !row_off || row_off[0] != 0) throw KioError("ivector-extract: bad argument");
@@ -254,6 +261,7 @@ void IvexExtract(IvexModel& m, const float* feats, const int32_t* row_off, int n
     if (post_idx[i] < 0 || post_idx[i] >= I.G)
       throw KioError("ivector-extract: the posteriors name Gaussian " + std::to_string(post_idx[i]) + "; the model has " + std::to_string(I.G));
   UseDevice(I.device, kWhoNeeds);
+  if (after_group) I.solution.Reserve((size_t)kIvexMaxBatch * I.S * 8);
   constexpr int64_t kBatchFrames = 1 << 16;
   const int G = I.G, D = I.D, S = I.S;
   const int64_t K = (int64_t)G * D;
@@ -364,6 +372,7 @@ void IvexExtract(IvexModel& m, const float* feats, const int32_t* row_off, int n
     so.ivector = I.ivec.as<float>();
     so.auxf_change = out.auxf_change ? I.auxf.as<double>() : nullptr;
     so.status = I.status.as<int32_t>();
+    so.solution = after_group ? I.solution.as<double>() : nullptr;
 
     EventTimer tm(out.device_ms4 != nullptr, 5);
     tm.Mark();
@@ -387,6 +396,19 @@ void IvexExtract(IvexModel& m, const float* feats, const int32_t* row_off, int n
     if (out.linear) Check(hipMemcpy(out.linear + (size_t)u0 * S, I.linear.p, (size_t)B * S * 8, hipMemcpyDeviceToHost), "copy the linear term");
     if (out.quadratic)
       Check(hipMemcpy(out.quadratic + (size_t)u0 * I.P, I.quadratic.p, (size_t)B * I.P * 8, hipMemcpyDeviceToHost), "copy the quadratic term");
+    if (after_group) {
+      IvexGroupView v;
+      v.u0 = u0;
+      v.B = B;
+      v.status = out.status + u0;
+      v.gamma = I.gamma.as<double>();
+      v.X = I.X.as<double>();
+      v.linear = I.linear.as<double>();
+      v.quadratic = I.quadratic.as<double>();
+      v.work = I.work.as<double>();
+      v.solution = I.solution.as<double>();
+      (*after_group)(v);
+    }
     u0 = u1;
   }
 }

@@ -29,6 +29,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -60,6 +61,9 @@ class IvexModel {
   int feat_dim() const;
   int ivector_dim() const;
   float derive_ms() const;
+  double prior_offset() const;
+  const std::vector<double>& w_vec() const;       // host copies of the two small arrays of the model
+  const std::vector<double>& sigma_inv() const;
   struct Impl;
   std::unique_ptr<Impl> impl_;
 };
@@ -80,7 +84,22 @@ struct IvexOutputs {
 };
 // feats [row_off[n_utts]][D]; frame t has the pairs post_off[t] .. post_off[t + 1] of (post_idx, post_w).  Blocking.  KioError: a
 // Gaussian index outside the model (checked before anything is uploaded).
+// after_group (may be null; out.status is required with or without it, and is what the hook's status points into) is called once
+// per launch group, after the group's status came back and before the next group's
+// launches: the E-step of training (ivex_train.h) reads the group's device results there.
+struct IvexGroupView {
+  int u0, B;                // the group is the utterances u0 .. u0 + B of the call
+  const int32_t* status;    // host, [B]
+  // device, per utterance of the group
+  const double* gamma;      // [B][G]
+  const double* X;          // [B][G D]
+  const double* linear;     // [B][S]
+  const double* quadratic;  // [B][S (S + 1) / 2] packed Q
+  const double* work;       // [B][S + 1][S]: the Cholesky factor of Q in the lower triangle
+  const double* solution;   // [B][S] the fp64 solution, with the prior offset
+};
+typedef std::function<void(const IvexGroupView&)> IvexGroupHook;
 void IvexExtract(IvexModel& m, const float* feats, const int32_t* row_off, int n_utts, const int32_t* post_off, const int32_t* post_idx,
-                 const float* post_w, double acoustic_weight, double max_count, const IvexOutputs& out);
+                 const float* post_w, double acoustic_weight, double max_count, const IvexOutputs& out, const IvexGroupHook* after_group = nullptr);
 
 }  // namespace xv

@@ -98,6 +98,7 @@ struct IvexSolveArgs {
   float* ivector;            // [B][S]: x with the prior offset taken off element 0 before rounding
   double* auxf_change;       // [B] or null
   int32_t* status;           // [B]: 0, or 1 for a Q that is not positive definite
+  double* solution;          // [B][S] or null: x in fp64, with the prior offset (the E-step of training reads it; ivex_train_kernels.h)
 };
 
 hipError_t launch_ivex_derive(const IvexDeriveArgs& a, hipStream_t s);

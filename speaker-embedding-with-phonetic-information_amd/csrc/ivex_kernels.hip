@@ -340,6 +340,8 @@ __global__ __launch_bounds__(kIvexThreads) void ivex_solve_kernel(const IvexSolv
   for (int c = tid; c < S; c += kIvexThreads)
     a.ivector[(int64_t)u * S + c] = fail ? 0.f : (float)(xs[c] - (c == 0 ? a.prior_offset : 0.0));
   if (tid == 0) a.status[u] = fail ? 1 : 0;
+  if (a.solution)
+    for (int c = tid; c < S; c += kIvexThreads) a.solution[(int64_t)u * S + c] = fail ? 0.0 : xs[c];
   if (!a.auxf_change) return;
   // F(x) - F(p e_0), F(v) = l . v - v' Q v / 2, from the unfactored Q
   double t = 0.0;

@@ -14,67 +14,17 @@
 
 #include <memory>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "cli.h"
 #include "cmvn.h"
 #include "ivex.h"
 #include "kio.h"
+#include "posterior_lookup.h"
 
 namespace {
 
 constexpr int64_t kBatchFrames = 1 << 16;   // frames read ahead per device call
-
-// The posterior of a key: a table that promised sorted keys (s) is merged front to back, any other is loaded.
-class PosteriorLookup {
- public:
-  explicit PosteriorLookup(const std::string& rspecifier) : reader_(rspecifier) {
-    if (reader_.sorted()) return;
-    std::string key, err;
-    xv::Posterior v;
-    while (reader_.Next(&key, &v, &err)) {
-      if (!err.empty()) XWARN("Failed to read the posterior of " << key << ": " << err);
-      else all_.emplace(key, std::move(v));
-    }
-  }
-  bool Find(const std::string& key, xv::Posterior* out) {
-    if (!reader_.sorted()) {
-      auto it = all_.find(key);
-      if (it == all_.end()) return false;
-      *out = it->second;
-      return true;
-    }
-    for (;;) {
-      if (!held_) {
-        std::string err;
-        if (eof_ || !reader_.Next(&held_key_, &held_v_, &err)) {
-          eof_ = true;
-          return false;
-        }
-        if (!err.empty()) {
-          XWARN("Failed to read the posterior of " << held_key_ << ": " << err);
-          continue;
-        }
-        held_ = true;
-      }
-      const int c = held_key_.compare(key);
-      if (c > 0) return false;   // the table is past the key
-      held_ = false;
-      if (c == 0) {
-        *out = std::move(held_v_);
-        return true;
-      }
-    }
-  }
-
- private:
-  xv::SequentialPosteriorReader reader_;
-  std::unordered_map<std::string, xv::Posterior> all_;
-  bool held_ = false, eof_ = false;
-  std::string held_key_;
-  xv::Posterior held_v_;
-};
 
 struct ExtractOptions {
   bool compute_objf_change = true;
@@ -89,7 +39,7 @@ int IvectorExtract(const ExtractOptions& o, const std::vector<std::string>& pos)
   std::unique_ptr<xv::IvexModel> model(xv::IvexCreate(dev, data));
   const int D = data.D, S = data.S;
   xv::FeatBatchReader reader(pos[1], kBatchFrames, false);
-  PosteriorLookup posts(pos[2]);
+  xv::PosteriorLookup posts(pos[2]);
   xv::TableWriter writer(pos[3]);
   long num_done = 0, num_err = 0;
   double tot_t = 0.0, tot_auxf = 0.0;
