@@ -610,6 +610,44 @@ xv_status xv_fgmm_est(int32_t num_gauss, int32_t dim, const char* acc_flags, con
 xv_status xv_fgmm_acc_kernel_time(xv_fgmm_acc* a, const xv_ubm* full, const float* feats, int32_t rows, const int32_t* gselect, int32_t n,
                                   int32_t reps, float* ms4);
 
+/* ---- diagonal UBM training (gmm-global-init-from-feats, gmm-global-acc-stats, gmm-global-est; sid/train_diag_ubm.sh:105-137), without
+ * a model context.  Semantics: csrc/dubm_train.h.  The accumulators are fp64 on the device; no floating-point value goes through an
+ * atomic, and what a call adds is a function of the call's frames, pairs and model alone.  A (frame, Gaussian) score is bit for bit
+ * the one xv_ubm_gselect ranks.  Limits: dimension <= 96, n <= 64 selected Gaussians. */
+typedef struct xv_dgmm_acc xv_dgmm_acc;
+/* update_flags: letters of "mvw" (v implies m, m implies w).  The accumulators start at zero. */
+xv_status xv_dgmm_acc_create(int device, int32_t num_gauss, int32_t dim, const char* update_flags, xv_dgmm_acc** out);
+void xv_dgmm_acc_destroy(xv_dgmm_acc* a);
+/* the caller's sparse pairs through the accumulator kernels alone; the arguments of xv_fgmm_acc_add */
+xv_status xv_dgmm_acc_add(xv_dgmm_acc* a, const float* feats, int32_t rows, const int32_t* post_off, const int32_t* post_idx,
+                          const float* post_w);
+/* the fused sparse E-step on a diagonal model: scores on gselect [rows][n], the fp32 softmax of xv_ubm_post (min_post = 0), the
+ * accumulation.  loglikes [rows][n] may be NULL; logsum [rows] comes back. */
+xv_status xv_dgmm_acc_add_gselect(xv_dgmm_acc* a, const xv_ubm* diag, const float* feats, int32_t rows, const int32_t* gselect, int32_t n,
+                                  float* loglikes, float* logsum);
+/* a caller's dense posteriors post [rows][G] through the matrix-core accumulation kernel and the reduction alone */
+xv_status xv_dgmm_acc_add_dense_post(xv_dgmm_acc* a, const float* feats, int32_t rows, const float* post);
+/* the fused dense E-step: every frame against every Gaussian.  logsum [rows] (may be NULL) comes back. */
+xv_status xv_dgmm_acc_add_dense(xv_dgmm_acc* a, const xv_ubm* diag, const float* feats, int32_t rows, float* logsum);
+/* downloads occ [G], mean [G][D] and var [G][D] (the sums of p x x); any of them may be NULL */
+xv_status xv_dgmm_acc_get(const xv_dgmm_acc* a, double* occ, double* mean, double* var);
+/* host only (fp64): the M-step of gmm-global-est on host arrays, then Split(mix_up, perturb_factor) keyed by seed when mix_up is above
+ * the number of Gaussians that survive.  weights, means_invvars [.][D], inv_vars [.][D] and gconsts have room for max(num_gauss,
+ * mix_up) Gaussians; the first num_gauss are read, the first *num_gauss_out are written.  removed [num_gauss]: the first entries are
+ * the indices taken out, *num_removed (may be NULL with removed) how many.  floored2 = {variances floored, Gaussians they belong to};
+ * objf3 = {the objective before, after, the sum of occ}; split_of [max(0, mix_up)]: for every Gaussian the split added, the index it
+ * was copied from.  removed, floored2, objf3 and split_of may be NULL. */
+xv_status xv_dgmm_est(int32_t num_gauss, int32_t dim, const char* acc_flags, const double* occ, const double* mean, const double* var,
+                      const char* update_flags, double min_gaussian_weight, double min_gaussian_occupancy, double min_variance,
+                      int32_t remove_low_count_gaussians, int32_t mix_up, double perturb_factor, uint64_t seed, float* weights,
+                      float* means_invvars, float* inv_vars, float* gconsts, int32_t* num_gauss_out, int32_t* removed, int32_t* num_removed,
+                      int32_t* floored2, double* objf3, int32_t* split_of);
+/* the kernels' times in ms, the best of reps runs after one that warms up: ms7 = {sort, selected scores, softmax, sparse accumulation
+ * (work items and reduction included)} of one fused sparse call when gselect is not NULL, then {dense log-sum, dense accumulation,
+ * reduction} of one fused dense call when dense is not 0.  Every run adds to the accumulators. */
+xv_status xv_dgmm_acc_kernel_time(xv_dgmm_acc* a, const xv_ubm* diag, const float* feats, int32_t rows, const int32_t* gselect, int32_t n,
+                                  int32_t dense, int32_t reps, float* ms7);
+
 /* ---- i-vector extraction (ivector-extract, sid/extract_ivectors.sh:69), without a model context.  Semantics: csrc/ivex.h.
  * Everything on the device is fp64 on fp32 inputs with summation orders that depend on the utterance and the model alone: an
  * utterance's results are the same bits alone, in any batch, at any position in it.  Limits: i-vector dimension <= 1024, feature

@@ -141,6 +141,8 @@ ABI_SYMBOLS = [
     "xv_fgmm_to_gmm", "xv_fgmm_gconsts", "xv_ubm_kernel_time",
     "xv_fgmm_acc_create", "xv_fgmm_acc_destroy", "xv_fgmm_acc_add", "xv_fgmm_acc_add_gselect", "xv_fgmm_acc_get", "xv_fgmm_est",
     "xv_fgmm_acc_kernel_time",
+    "xv_dgmm_acc_create", "xv_dgmm_acc_destroy", "xv_dgmm_acc_add", "xv_dgmm_acc_add_gselect", "xv_dgmm_acc_add_dense_post",
+    "xv_dgmm_acc_add_dense", "xv_dgmm_acc_get", "xv_dgmm_est", "xv_dgmm_acc_kernel_time",
     "xv_ivex_create", "xv_ivex_load", "xv_ivex_destroy", "xv_ivex_info", "xv_ivex_derived", "xv_ivex_extract", "xv_ivex_read",
     "xv_ivex_write", "xv_ivex_kernel_time",
     "xv_ivex_acc_create", "xv_ivex_acc_destroy", "xv_ivex_acc_add", "xv_ivex_acc_get", "xv_ivex_acc_pending", "xv_ivex_acc_kernel_time",
@@ -1427,6 +1429,156 @@ def fgmm_est(weights, means_invcovars, inv_covars, occ, mean, cov, acc_flags="mv
     return dict(weights=w[:k].copy(), means_invcovars=b[:k].copy(), inv_covars=ic[:k].copy(), gconsts=gc[:k].copy(),
                 removed=removed[:g - k].tolist(), floored=(int(floored[0]), int(floored[1])), objf_before=float(objf[0]),
                 objf_after=float(objf[1]), count=float(objf[2]))
+
+
+class DgmmAccumulator:
+    """The fp64 accumulators of diagonal UBM training on one device (xv_dgmm_acc_create): occ [G], mean [G][D] and var [G][D] (the sums
+    of p x x).  flags: letters of "mvw" (v implies m, m implies w)."""
+
+    def __init__(self, num_gauss, dim, flags="mvw", device=0):
+        L = lib()
+        self._h = ctypes.c_void_p()
+        self.num_gauss, self.dim, self.flags = int(num_gauss), int(dim), flags
+        L.xv_dgmm_acc_create.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
+        _check(L.xv_dgmm_acc_create(device, self.num_gauss, self.dim, flags.encode(), ctypes.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            L = lib()
+            L.xv_dgmm_acc_destroy.argtypes = [ctypes.c_void_p]
+            L.xv_dgmm_acc_destroy.restype = None
+            L.xv_dgmm_acc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _feats(self, feats, who):
+        import numpy as np
+        x = np.ascontiguousarray(feats, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise XvError(XV_ERR_ARG, "%s: the features are not [frames, %d]" % (who, self.dim))
+        return x
+
+    def accumulate(self, feats, post):
+        """One call: feats [frames, D]; post: per frame (indices, posteriors).  The accumulator kernels alone."""
+        import numpy as np
+        L = lib()
+        x = self._feats(feats, "accumulate")
+        if len(post) != x.shape[0]:
+            raise XvError(XV_ERR_ARG, "accumulate: one (indices, posteriors) pair per frame")
+        off = np.zeros(x.shape[0] + 1, dtype=np.int32)
+        for t, (i, _) in enumerate(post):
+            off[t + 1] = off[t] + len(i)
+        idx = np.ascontiguousarray(np.concatenate([np.asarray(i, np.int32) for i, _ in post]) if len(post) else np.zeros(0), dtype=np.int32)
+        w = np.ascontiguousarray(np.concatenate([np.asarray(p, np.float32) for _, p in post]) if len(post) else np.zeros(0), dtype=np.float32)
+        L.xv_dgmm_acc_add.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        _check(L.xv_dgmm_acc_add(self._h, x.ctypes.data, x.shape[0], off.ctypes.data, idx.ctypes.data, w.ctypes.data))
+
+    def accumulate_gselect(self, diag, feats, gselect, return_loglikes=False):
+        """The fused sparse E-step on a diagonal Ubm over gselect [frames, n].  Returns the per-frame log-sums, float32 [frames] (and
+        the scores [frames, n])."""
+        import numpy as np
+        L = lib()
+        x = self._feats(feats, "accumulate_gselect")
+        gs = np.ascontiguousarray(gselect, dtype=np.int32)
+        if gs.ndim != 2 or gs.shape[0] != x.shape[0]:
+            raise XvError(XV_ERR_ARG, "accumulate_gselect: a [frames, n] selection")
+        logsum = np.zeros(x.shape[0], dtype=np.float32)
+        ll = np.zeros(gs.shape, dtype=np.float32)
+        L.xv_dgmm_acc_add_gselect.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.c_void_p, ctypes.c_void_p]
+        _check(L.xv_dgmm_acc_add_gselect(self._h, diag._h, x.ctypes.data, x.shape[0], gs.ctypes.data, gs.shape[1],
+                                         ll.ctypes.data if return_loglikes else None, logsum.ctypes.data))
+        return (logsum, ll) if return_loglikes else logsum
+
+    def accumulate_dense_post(self, feats, post):
+        """A caller's dense posteriors [frames, G] through the matrix-core accumulation kernel alone."""
+        import numpy as np
+        L = lib()
+        x = self._feats(feats, "accumulate_dense_post")
+        p = np.ascontiguousarray(post, dtype=np.float32)
+        if p.shape != (x.shape[0], self.num_gauss):
+            raise XvError(XV_ERR_ARG, "accumulate_dense_post: posteriors [frames, %d]" % self.num_gauss)
+        L.xv_dgmm_acc_add_dense_post.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+        _check(L.xv_dgmm_acc_add_dense_post(self._h, x.ctypes.data, x.shape[0], p.ctypes.data))
+
+    def accumulate_dense(self, diag, feats):
+        """The fused dense E-step: every frame against every Gaussian of a diagonal Ubm.  Returns the per-frame log-sums."""
+        import numpy as np
+        L = lib()
+        x = self._feats(feats, "accumulate_dense")
+        logsum = np.zeros(x.shape[0], dtype=np.float32)
+        L.xv_dgmm_acc_add_dense.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+        _check(L.xv_dgmm_acc_add_dense(self._h, diag._h, x.ctypes.data, x.shape[0], logsum.ctypes.data))
+        return logsum
+
+    def get(self):
+        """(occ [G], mean [G, D], var [G, D]) as float64."""
+        import numpy as np
+        L = lib()
+        g, d = self.num_gauss, self.dim
+        occ, mean, var = np.zeros(g), np.zeros((g, d)), np.zeros((g, d))
+        L.xv_dgmm_acc_get.argtypes = [ctypes.c_void_p] * 4
+        _check(L.xv_dgmm_acc_get(self._h, occ.ctypes.data, mean.ctypes.data, var.ctypes.data))
+        return occ, mean, var
+
+    def kernel_time(self, diag, feats, gselect=None, dense=True, reps=3):
+        """{sort, scores, softmax, acc} of one fused sparse call (with gselect) and {dense_logsum, dense_acc, dense_reduce} of one fused
+        dense call, in ms (xv_dgmm_acc_kernel_time: the best of reps).  Every run adds to the accumulators."""
+        import numpy as np
+        L = lib()
+        x = self._feats(feats, "kernel_time")
+        gs = None if gselect is None else np.ascontiguousarray(gselect, dtype=np.int32)
+        ms = (ctypes.c_float * 7)()
+        L.xv_dgmm_acc_kernel_time.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
+        _check(L.xv_dgmm_acc_kernel_time(self._h, diag._h, x.ctypes.data, x.shape[0], None if gs is None else gs.ctypes.data,
+                                         0 if gs is None else gs.shape[1], int(bool(dense)), reps, ms))
+        return dict(zip(("sort", "scores", "softmax", "acc", "dense_logsum", "dense_acc", "dense_reduce"), [float(v) for v in ms]))
+
+
+def dgmm_est(weights, means_invvars, inv_vars, occ, mean, var, acc_flags="mvw", update_flags="mvw", min_gaussian_weight=1e-5,
+             min_gaussian_occupancy=10.0, min_variance=0.001, remove_low_count_gaussians=True, mix_up=0, perturb_factor=0.01, seed=0):
+    """The M-step of gmm-global-est on host arrays (xv_dgmm_est, fp64), then the split to mix_up Gaussians: dict(weights, means_invvars,
+    inv_vars, gconsts) of the model that results, removed (indices), floored (variances, Gaussians), objf_before, objf_after, count,
+    split_of (for every Gaussian the split added, the index it was copied from)."""
+    import numpy as np
+    L = lib()
+    w0 = np.asarray(weights, dtype=np.float32)
+    b0 = np.asarray(means_invvars, dtype=np.float32)
+    iv0 = np.asarray(inv_vars, dtype=np.float32)
+    if b0.ndim != 2 or w0.shape != (b0.shape[0],) or iv0.shape != b0.shape:
+        raise XvError(XV_ERR_ARG, "dgmm_est: weights [G], means_invvars [G][D], inv_vars [G][D]")
+    g, d = b0.shape
+    o = np.ascontiguousarray(occ, dtype=np.float64)
+    m = np.ascontiguousarray(mean, dtype=np.float64)
+    c = np.ascontiguousarray(var, dtype=np.float64)
+    if o.shape != (g,) or m.shape != (g, d) or c.shape != (g, d):
+        raise XvError(XV_ERR_ARG, "dgmm_est: occ [G], mean [G][D], var [G][D]")
+    cap = max(g, int(mix_up))
+    w, b, iv = np.zeros(cap, np.float32), np.zeros((cap, d), np.float32), np.zeros((cap, d), np.float32)
+    w[:g], b[:g], iv[:g] = w0, b0, iv0
+    gc = np.zeros(cap, np.float32)
+    removed = np.zeros(g, np.int32)
+    split_of = np.zeros(max(cap, 1), np.int32)
+    floored = np.zeros(2, np.int32)
+    objf = np.zeros(3)
+    left, n_removed = ctypes.c_int32(), ctypes.c_int32()
+    L.xv_dgmm_est.argtypes = ([ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p] + [ctypes.c_void_p] * 3 + [ctypes.c_char_p] + [ctypes.c_double] * 3
+                              + [ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_uint64] + [ctypes.c_void_p] * 4
+                              + [ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)] + [ctypes.c_void_p] * 3)
+    _check(L.xv_dgmm_est(g, d, acc_flags.encode(), o.ctypes.data, m.ctypes.data, c.ctypes.data, update_flags.encode(), min_gaussian_weight,
+                         min_gaussian_occupancy, min_variance, int(bool(remove_low_count_gaussians)), int(mix_up), perturb_factor, int(seed),
+                         w.ctypes.data, b.ctypes.data, iv.ctypes.data, gc.ctypes.data, ctypes.byref(left), removed.ctypes.data,
+                         ctypes.byref(n_removed), floored.ctypes.data, objf.ctypes.data, split_of.ctypes.data))
+    k, nr = left.value, n_removed.value
+    return dict(weights=w[:k].copy(), means_invvars=b[:k].copy(), inv_vars=iv[:k].copy(), gconsts=gc[:k].copy(),
+                removed=removed[:nr].tolist(), floored=(int(floored[0]), int(floored[1])), objf_before=float(objf[0]),
+                objf_after=float(objf[1]), count=float(objf[2]), split_of=split_of[:max(0, k - (g - nr))].tolist())
 
 
 def ivex_read(rxfilename):

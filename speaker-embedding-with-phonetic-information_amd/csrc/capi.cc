@@ -30,6 +30,7 @@
 #include "ivex.h"
 #include "ivex_train.h"
 #include "ubm.h"
+#include "dubm_train.h"
 #include "ubm_train.h"
 #include "ubm_train_kernels.h"
 
@@ -1217,6 +1218,137 @@ xv_status xv_fgmm_acc_kernel_time(xv_fgmm_acc* a, const xv_ubm* full, const floa
       xv::FgmmAccAddGselect(a->a.get(), *full->m, feats, rows, gselect, n, logsum.data(), ms);
       for (int i = 0; i < 4; ++i)
         if (r == 1 || (r > 1 && ms[i] < ms4[i])) ms4[i] = ms[i];
+    }
+    return XV_OK;
+  });
+}
+
+struct xv_dgmm_acc {
+  std::unique_ptr<xv::DgmmAccumulator> a;
+};
+
+xv_status xv_dgmm_acc_create(int device, int32_t num_gauss, int32_t dim, const char* update_flags, xv_dgmm_acc** out) {
+  if (!out || !update_flags) return Fail(XV_ERR_ARG, "xv_dgmm_acc_create: bad argument");
+  return Guard([&] {
+    std::unique_ptr<xv_dgmm_acc> h(new xv_dgmm_acc);
+    h->a.reset(xv::DgmmAccCreate(device, num_gauss, dim, xv::ParseGmmFlags(update_flags)));
+    *out = h.release();
+    return XV_OK;
+  });
+}
+
+void xv_dgmm_acc_destroy(xv_dgmm_acc* a) { delete a; }
+
+xv_status xv_dgmm_acc_add(xv_dgmm_acc* a, const float* feats, int32_t rows, const int32_t* post_off, const int32_t* post_idx,
+                          const float* post_w) {
+  if (!a || rows < 0 || !post_off) return Fail(XV_ERR_ARG, "xv_dgmm_acc_add: bad argument");
+  return Guard([&] {
+    xv::DgmmAccAdd(a->a.get(), feats, rows, post_off, post_idx, post_w);
+    return XV_OK;
+  });
+}
+
+xv_status xv_dgmm_acc_add_gselect(xv_dgmm_acc* a, const xv_ubm* diag, const float* feats, int32_t rows, const int32_t* gselect, int32_t n,
+                                  float* loglikes, float* logsum) {
+  if (!a || !diag || rows < 0) return Fail(XV_ERR_ARG, "xv_dgmm_acc_add_gselect: bad argument");
+  return Guard([&] {
+    xv::DgmmAccAddGselect(a->a.get(), *diag->m, feats, rows, gselect, n, loglikes, logsum);
+    return XV_OK;
+  });
+}
+
+xv_status xv_dgmm_acc_add_dense_post(xv_dgmm_acc* a, const float* feats, int32_t rows, const float* post) {
+  if (!a || rows < 0) return Fail(XV_ERR_ARG, "xv_dgmm_acc_add_dense_post: bad argument");
+  return Guard([&] {
+    xv::DgmmAccAddDensePost(a->a.get(), feats, rows, post);
+    return XV_OK;
+  });
+}
+
+xv_status xv_dgmm_acc_add_dense(xv_dgmm_acc* a, const xv_ubm* diag, const float* feats, int32_t rows, float* logsum) {
+  if (!a || !diag || rows < 0 || (rows > 0 && !feats)) return Fail(XV_ERR_ARG, "xv_dgmm_acc_add_dense: bad argument");
+  return Guard([&] {
+    xv::DgmmAccAddDense(a->a.get(), *diag->m, feats, rows, logsum);
+    return XV_OK;
+  });
+}
+
+xv_status xv_dgmm_acc_get(const xv_dgmm_acc* a, double* occ, double* mean, double* var) {
+  if (!a) return Fail(XV_ERR_ARG, "xv_dgmm_acc_get: bad argument");
+  return Guard([&] {
+    xv::DgmmAccGet(*a->a, occ, mean, var);
+    return XV_OK;
+  });
+}
+
+xv_status xv_dgmm_est(int32_t num_gauss, int32_t dim, const char* acc_flags, const double* occ, const double* mean, const double* var,
+                      const char* update_flags, double min_gaussian_weight, double min_gaussian_occupancy, double min_variance,
+                      int32_t remove_low_count_gaussians, int32_t mix_up, double perturb_factor, uint64_t seed, float* weights,
+                      float* means_invvars, float* inv_vars, float* gconsts, int32_t* num_gauss_out, int32_t* removed, int32_t* num_removed,
+                      int32_t* floored2, double* objf3, int32_t* split_of) {
+  if (num_gauss < 1 || dim < 1 || !acc_flags || !occ || !update_flags || !weights || !means_invvars || !inv_vars || !gconsts || !num_gauss_out)
+    return Fail(XV_ERR_ARG, "xv_dgmm_est: bad argument");
+  return Guard([&] {
+    xv::DgmmAccs accs;
+    accs.Init(num_gauss, dim, xv::ParseGmmFlags(acc_flags));
+    std::copy(occ, occ + num_gauss, accs.occ.begin());
+    if (accs.flags & xv::kFgmmFlagMeans) {
+      if (!mean) throw xv::KioError("xv_dgmm_est: the flags ask for mean accumulators");
+      std::copy(mean, mean + (size_t)num_gauss * dim, accs.mean.begin());
+    }
+    if (accs.flags & xv::kFgmmFlagVariances) {
+      if (!var) throw xv::KioError("xv_dgmm_est: the flags ask for variance accumulators");
+      std::copy(var, var + (size_t)num_gauss * dim, accs.var.begin());
+    }
+    xv::DiagGmmData m;
+    m.num_gauss = num_gauss;
+    m.dim = dim;
+    m.weights.assign(weights, weights + num_gauss);
+    m.means_invvars.assign(means_invvars, means_invvars + (size_t)num_gauss * dim);
+    m.inv_vars.assign(inv_vars, inv_vars + (size_t)num_gauss * dim);
+    xv::ComputeGconsts(&m);
+    xv::DgmmEstOptions o;
+    o.min_gaussian_weight = min_gaussian_weight;
+    o.min_gaussian_occupancy = min_gaussian_occupancy;
+    o.min_variance = min_variance;
+    o.remove_low_count_gaussians = remove_low_count_gaussians != 0;
+    xv::DgmmEstResult r;
+    xv::DgmmEst(accs, xv::ParseGmmFlags(update_flags), o, &m, &r);
+    std::vector<int32_t> from;
+    xv::DgmmSplit(&m, mix_up, perturb_factor, seed, 0, &from);
+    std::copy(m.weights.begin(), m.weights.end(), weights);
+    std::copy(m.means_invvars.begin(), m.means_invvars.end(), means_invvars);
+    std::copy(m.inv_vars.begin(), m.inv_vars.end(), inv_vars);
+    std::copy(m.gconsts.begin(), m.gconsts.end(), gconsts);
+    *num_gauss_out = m.num_gauss;
+    if (removed) std::copy(r.removed.begin(), r.removed.end(), removed);
+    if (num_removed) *num_removed = (int32_t)r.removed.size();
+    if (split_of) std::copy(from.begin(), from.end(), split_of);
+    if (floored2) {
+      floored2[0] = r.floored_elements;
+      floored2[1] = r.floored_gauss;
+    }
+    if (objf3) {
+      objf3[0] = r.objf_before;
+      objf3[1] = r.objf_after;
+      objf3[2] = r.count;
+    }
+    return XV_OK;
+  });
+}
+
+xv_status xv_dgmm_acc_kernel_time(xv_dgmm_acc* a, const xv_ubm* diag, const float* feats, int32_t rows, const int32_t* gselect, int32_t n,
+                                  int32_t dense, int32_t reps, float* ms7) {
+  if (!a || !diag || !feats || rows < 1 || reps < 1 || !ms7) return Fail(XV_ERR_ARG, "xv_dgmm_acc_kernel_time: bad argument");
+  return Guard([&] {
+    std::vector<float> logsum((size_t)rows);
+    for (int i = 0; i < 7; ++i) ms7[i] = 0.f;
+    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
+      float ms[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if (gselect) xv::DgmmAccAddGselect(a->a.get(), *diag->m, feats, rows, gselect, n, nullptr, logsum.data(), ms);
+      if (dense) xv::DgmmAccAddDense(a->a.get(), *diag->m, feats, rows, logsum.data(), ms + 4);
+      for (int i = 0; i < 7; ++i)
+        if (r == 1 || (r > 1 && ms[i] < ms7[i])) ms7[i] = ms[i];
     }
     return XV_OK;
   });

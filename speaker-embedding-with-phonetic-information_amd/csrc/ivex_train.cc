@@ -96,6 +96,8 @@ uint64_t Mix(uint64_t seed, uint64_t counter) {
 
 }  // namespace
 
+uint64_t Mix53(uint64_t seed, uint64_t counter) { return Mix(seed, counter); }
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 void IvexStats::Init(int g, int d, int s, bool var) {
   if (g < 1 || d < 1 || s < 1) throw KioError("i-vector extractor statistics: bad shape");

@@ -87,6 +87,8 @@ void WriteIvexStatsFile(const std::string& wxfilename, bool binary, const IvexSt
 // ivector-extractor-init from a full-covariance UBM (host)
 constexpr double kIvexInitPriorOffset = 100.0;
 void IvexInit(const FullGmmData& ubm, int ivector_dim, uint64_t seed, IvexData* out);
+// mix(s, c) of the header comment: 53 bits.  dubm_train.h draws from the same generator.
+uint64_t Mix53(uint64_t seed, uint64_t counter);
 
 struct IvexEstOptions {
   double variance_floor_factor = 0.1, gaussian_min_count = 100.0;

@@ -301,6 +301,12 @@ UbmModel* UbmFullCreate(int device, int num_gauss, int dim, const float* gconsts
   return m.release();
 }
 
+UbmDiagView UbmDiagArrays(const UbmModel& diag) {
+  const UbmModel::Impl& I = *diag.impl_;
+  if (I.full) throw KioError("the model is a full-covariance one; a diagonal model is needed here");
+  return UbmDiagView{I.device, I.num_gauss, I.dim, I.gauss_pad, I.a.as<float>(), I.b.as<float>(), I.gconst.as<float>()};
+}
+
 void UbmGselect(const UbmModel& diag, const float* feats, const int32_t* row_off, int n_utts, int n, int32_t* idx, float* ll, float* device_ms) {
   if (device_ms) *device_ms = 0.f;
   const UbmModel::Impl& I = *diag.impl_;

@@ -70,6 +70,14 @@ UbmModel* UbmDiagCreate(int device, int num_gauss, int dim, const float* gconsts
 // gconsts [G], means_invcovars [G][D], inv_covars [G][D (D + 1) / 2] packed lower triangles
 UbmModel* UbmFullCreate(int device, int num_gauss, int dim, const float* gconsts, const float* means_invcovars, const float* inv_covars);
 
+// The device arrays of a diagonal model, as the selection kernel reads them (ubm_kernels.h: UbmDiagArgs), for the E-steps of
+// dubm_train.h.  KioError for a full-covariance model.
+struct UbmDiagView {
+  int device, num_gauss, dim, gauss_pad;
+  const float *m_t, *v_t, *gconst;
+};
+UbmDiagView UbmDiagArrays(const UbmModel& diag);
+
 // feats: [row_off[n_utts]][dim] packed; idx: [rows][n]; ll: the same shape or null.  n <= min(64, num_gauss).  Blocking.
 void UbmGselect(const UbmModel& diag, const float* feats, const int32_t* row_off, int n_utts, int n, int32_t* idx, float* ll,
                 float* device_ms = nullptr);
