@@ -1155,6 +1155,37 @@ xv_status xv_fgmm_acc_get(const xv_fgmm_acc* a, double* occ, double* mean, doubl
   });
 }
 
+namespace {
+
+// the caller's arrays into accumulators of either kind; `second` (named by second_name in the error) is cov or var
+void FillGmmAccs(const char* who, const char* second_name, int32_t num_gauss, int32_t dim, const char* acc_flags, const double* occ, const double* mean,
+                 const double* second, xv::GmmAccs* accs) {
+  accs->Init(num_gauss, dim, xv::ParseGmmFlags(acc_flags));
+  std::copy(occ, occ + num_gauss, accs->occ.begin());
+  if (accs->flags & xv::kFgmmFlagMeans) {
+    if (!mean) throw xv::KioError(std::string(who) + ": the flags ask for mean accumulators");
+    std::copy(mean, mean + (size_t)num_gauss * dim, accs->mean.begin());
+  }
+  if (accs->flags & xv::kFgmmFlagVariances) {
+    if (!second) throw xv::KioError(std::string(who) + ": the flags ask for " + second_name + " accumulators");
+    std::copy(second, second + (size_t)num_gauss * accs->second_width(), accs->second.begin());
+  }
+}
+
+void CopyGmmEstResult(const xv::GmmEstResult& r, int32_t* floored2, double* objf3) {
+  if (floored2) {
+    floored2[0] = r.floored_elements;
+    floored2[1] = r.floored_gauss;
+  }
+  if (objf3) {
+    objf3[0] = r.objf_before;
+    objf3[1] = r.objf_after;
+    objf3[2] = r.count;
+  }
+}
+
+}  // namespace
+
 xv_status xv_fgmm_est(int32_t num_gauss, int32_t dim, const char* acc_flags, const double* occ, const double* mean, const double* cov,
                       const char* update_flags, double min_gaussian_weight, double min_gaussian_occupancy, double variance_floor,
                       double max_condition, int32_t remove_low_count_gaussians, float* weights, float* means_invcovars, float* inv_covars,
@@ -1164,16 +1195,7 @@ xv_status xv_fgmm_est(int32_t num_gauss, int32_t dim, const char* acc_flags, con
   return Guard([&] {
     const size_t tri = (size_t)dim * (dim + 1) / 2;
     xv::FgmmAccs accs;
-    accs.Init(num_gauss, dim, xv::ParseGmmFlags(acc_flags));
-    std::copy(occ, occ + num_gauss, accs.occ.begin());
-    if (accs.flags & xv::kFgmmFlagMeans) {
-      if (!mean) throw xv::KioError("xv_fgmm_est: the flags ask for mean accumulators");
-      std::copy(mean, mean + (size_t)num_gauss * dim, accs.mean.begin());
-    }
-    if (accs.flags & xv::kFgmmFlagVariances) {
-      if (!cov) throw xv::KioError("xv_fgmm_est: the flags ask for covariance accumulators");
-      std::copy(cov, cov + (size_t)num_gauss * tri, accs.cov.begin());
-    }
+    FillGmmAccs("xv_fgmm_est", "covariance", num_gauss, dim, acc_flags, occ, mean, cov, &accs);
     xv::FullGmmData m;
     m.num_gauss = num_gauss;
     m.dim = dim;
@@ -1195,15 +1217,7 @@ xv_status xv_fgmm_est(int32_t num_gauss, int32_t dim, const char* acc_flags, con
     std::copy(m.gconsts.begin(), m.gconsts.end(), gconsts);
     *num_gauss_out = m.num_gauss;
     if (removed) std::copy(r.removed.begin(), r.removed.end(), removed);
-    if (floored2) {
-      floored2[0] = r.floored_elements;
-      floored2[1] = r.floored_gauss;
-    }
-    if (objf3) {
-      objf3[0] = r.objf_before;
-      objf3[1] = r.objf_after;
-      objf3[2] = r.count;
-    }
+    CopyGmmEstResult(r, floored2, objf3);
     return XV_OK;
   });
 }
@@ -1290,16 +1304,7 @@ xv_status xv_dgmm_est(int32_t num_gauss, int32_t dim, const char* acc_flags, con
     return Fail(XV_ERR_ARG, "xv_dgmm_est: bad argument");
   return Guard([&] {
     xv::DgmmAccs accs;
-    accs.Init(num_gauss, dim, xv::ParseGmmFlags(acc_flags));
-    std::copy(occ, occ + num_gauss, accs.occ.begin());
-    if (accs.flags & xv::kFgmmFlagMeans) {
-      if (!mean) throw xv::KioError("xv_dgmm_est: the flags ask for mean accumulators");
-      std::copy(mean, mean + (size_t)num_gauss * dim, accs.mean.begin());
-    }
-    if (accs.flags & xv::kFgmmFlagVariances) {
-      if (!var) throw xv::KioError("xv_dgmm_est: the flags ask for variance accumulators");
-      std::copy(var, var + (size_t)num_gauss * dim, accs.var.begin());
-    }
+    FillGmmAccs("xv_dgmm_est", "variance", num_gauss, dim, acc_flags, occ, mean, var, &accs);
     xv::DiagGmmData m;
     m.num_gauss = num_gauss;
     m.dim = dim;
@@ -1324,15 +1329,7 @@ xv_status xv_dgmm_est(int32_t num_gauss, int32_t dim, const char* acc_flags, con
     if (removed) std::copy(r.removed.begin(), r.removed.end(), removed);
     if (num_removed) *num_removed = (int32_t)r.removed.size();
     if (split_of) std::copy(from.begin(), from.end(), split_of);
-    if (floored2) {
-      floored2[0] = r.floored_elements;
-      floored2[1] = r.floored_gauss;
-    }
-    if (objf3) {
-      objf3[0] = r.objf_before;
-      objf3[1] = r.objf_after;
-      objf3[2] = r.count;
-    }
+    CopyGmmEstResult(r, floored2, objf3);
     return XV_OK;
   });
 }

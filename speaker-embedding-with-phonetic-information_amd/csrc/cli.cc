@@ -50,17 +50,34 @@ bool ToBool(const std::string& name, const std::string& v) {
   return b;
 }
 
-float ToFloat(const std::string& name, const std::string& v) {
-  double d;
-  if (!ParseDouble(v, &d)) throw KioError("Invalid floating-point option --" + name + "=" + v);
-  return (float)d;
-}
+float ToFloat(const std::string& name, const std::string& v) { return (float)ToDouble(name, v); }
 
 int ToInt(const std::string& name, const std::string& v) {
   int i;
   if (!ParseInt(v, &i)) throw KioError("Invalid integer option --" + name + "=" + v);
   return i;
 }
+
+double ToDouble(const std::string& name, const std::string& v) {
+  double d;
+  if (!ParseDouble(v, &d)) throw KioError("Invalid floating-point option --" + name + "=" + v);
+  return d;
+}
+
+uint64_t ToSeed(const std::string& name, const std::string& v) {
+  char* end = nullptr;
+  const unsigned long long s = strtoull(v.c_str(), &end, 10);
+  if (v.empty() || *end != '\0' || v[0] == '-') throw KioError("Invalid option --" + name + "=" + v + ": a non-negative integer is expected");
+  return (uint64_t)s;
+}
+
+std::string Dashes(std::string name) {
+  for (char& c : name)
+    if (c == '_') c = '-';
+  return name;
+}
+
+bool CommonOption(const std::string& n) { return n == "verbose" || n == "print-args" || n == "config"; }
 
 int PickDevice(int requested) {
   if (requested >= 0) return requested;

@@ -2,6 +2,8 @@
 // the program name and Kaldi-style log lines, scalar option parsing, device selection, --config files and the command-line
 // driver.  Host only: kio.h and the standard library.  (nnet3-xvector-compute keeps its own, different, conventions.)
 #pragma once
+#include <stdint.h>
+
 #include <functional>
 #include <sstream>
 #include <string>
@@ -36,6 +38,14 @@ bool ParseDouble(const std::string& v, double* out);
 bool ToBool(const std::string& name, const std::string& v);
 float ToFloat(const std::string& name, const std::string& v);
 int ToInt(const std::string& name, const std::string& v);
+double ToDouble(const std::string& name, const std::string& v);
+// A seed of our own generators: a non-negative decimal integer.
+uint64_t ToSeed(const std::string& name, const std::string& v);
+
+// An option's name with '-' for every '_': the tools that take both spellings compare this.
+std::string Dashes(std::string name);
+// --verbose, --print-args and --config: what the tools without config_file accept and ignore.
+bool CommonOption(const std::string& dashed_name);
 
 // --device if it was given (>= 0), else $XVEC_DEVICE, else 0.
 int PickDevice(int requested);

@@ -6,10 +6,10 @@
 
 #include <algorithm>
 #include <set>
-#include <sstream>
 
 #include "device.h"
 #include "dubm_train_kernels.h"
+#include "gmm_sparse_acc.h"
 #include "ivex_train.h"
 #include "ubm_kernels.h"
 
@@ -17,14 +17,6 @@ namespace xv {
 namespace {
 
 const char kWhoNeeds[] = "diagonal UBM training needs";
-
-std::string FlagLetters(int flags) {
-  std::string s;
-  if (flags & kFgmmFlagMeans) s += 'm';
-  if (flags & kFgmmFlagVariances) s += 'v';
-  if (flags & kFgmmFlagWeights) s += 'w';
-  return s;
-}
 
 }  // namespace
 
@@ -34,97 +26,6 @@ double DgmmGauss(uint64_t seed, uint64_t e) {
   const double two_pi = 6.283185307179586476925286766559;
   const double u1 = ((double)DgmmDrawA(seed, e) + 1.0) / 9007199254740992.0, u2 = (double)DgmmDrawB(seed, e) / 9007199254740992.0;
   return sqrt(-2.0 * log(u1)) * cos(two_pi * u2);
-}
-
-void DgmmAccs::Init(int g, int d, int f) {
-  if (g < 1 || d < 1 || f < 0 || f > 7) throw KioError("GMM accumulators: bad shape or flags");
-  num_gauss = g;
-  dim = d;
-  flags = AugmentGmmFlags(f);
-  occ.assign((size_t)g, 0.0);
-  mean.assign((size_t)g * d, 0.0);
-  var.assign((size_t)g * d, 0.0);
-}
-
-void ReadDgmmAccsFile(const std::string& rxfilename, bool add, DgmmAccs* a) {
-  Input in;
-  in.Open(rxfilename);
-  const bool binary = ReadBinaryHeader(in);
-  ExpectToken(in, binary, "<GMMACCS>");
-  ExpectToken(in, binary, "<VECSIZE>");
-  const int dim = ReadInt32(in, binary);
-  ExpectToken(in, binary, "<NUMCOMPONENTS>");
-  const int G = ReadInt32(in, binary);
-  ExpectToken(in, binary, "<FLAGS>");
-  int flags;
-  if (binary) {
-    if (in.Get() != 2) throw KioError("expected uint16 (size byte 2) in " + in.Name());
-    uint16_t v;
-    in.Read(&v, 2);
-    flags = v;
-  } else {
-    flags = ReadInt32(in, false);
-  }
-  if (dim < 1 || G < 1 || flags < 0 || flags > 7 || AugmentGmmFlags(flags) != flags)
-    throw KioError("GMM accumulators with dimension " + std::to_string(dim) + ", " + std::to_string(G) + " components and flags " + std::to_string(flags));
-  if (!add) a->Init(G, dim, flags);
-  else if (a->dim != dim || a->num_gauss != G || a->flags != flags)
-    throw KioError("the accumulators of " + in.Name() + " (dimension " + std::to_string(dim) + ", " + std::to_string(G) + " components, flags " +
-                   FlagLetters(flags) + ") cannot be added to ones of dimension " + std::to_string(a->dim) + ", " + std::to_string(a->num_gauss) +
-                   " components, flags " + FlagLetters(a->flags));
-  ExpectToken(in, binary, "<OCCUPANCY>");
-  std::vector<float> v;
-  ReadVector(in, binary, &v);
-  if ((int)v.size() != G) throw KioError("<OCCUPANCY> has " + std::to_string(v.size()) + " values for " + std::to_string(G) + " components");
-  for (int g = 0; g < G; ++g) a->occ[g] += (double)v[g];
-  ExpectToken(in, binary, "<MEANACCS>");
-  Matrix m;
-  ReadMatrix(in, binary, &m);
-  if (m.rows != G || m.cols != dim) throw KioError("<MEANACCS> is " + std::to_string(m.rows) + " x " + std::to_string(m.cols));
-  for (size_t i = 0; i < (size_t)G * dim; ++i) a->mean[i] += (double)m.Data()[i];
-  if (flags & kFgmmFlagVariances) {
-    ExpectToken(in, binary, "<DIAGVARACCS>");
-    ReadMatrix(in, binary, &m);
-    if (m.rows != G || m.cols != dim) throw KioError("<DIAGVARACCS> is " + std::to_string(m.rows) + " x " + std::to_string(m.cols));
-    for (size_t i = 0; i < (size_t)G * dim; ++i) a->var[i] += (double)m.Data()[i];
-  }
-  ExpectToken(in, binary, "</GMMACCS>");
-  if (in.Close() != 0) throw KioError("the command of " + rxfilename + " failed");
-}
-
-void WriteDgmmAccsFile(const std::string& wxfilename, bool binary, const DgmmAccs& a) {
-  Output out;
-  out.Open(wxfilename);
-  if (binary) out.Write("\0B", 2);
-  WriteToken(out, binary, "<GMMACCS>");
-  WriteToken(out, binary, "<VECSIZE>");
-  WriteInt32(out, binary, a.dim);
-  WriteToken(out, binary, "<NUMCOMPONENTS>");
-  WriteInt32(out, binary, a.num_gauss);
-  WriteToken(out, binary, "<FLAGS>");
-  if (binary) {
-    const uint16_t v = (uint16_t)a.flags;
-    out.Put((char)2);
-    out.Write(&v, 2);
-  } else {
-    WriteInt32(out, false, a.flags);
-  }
-  std::vector<float> f(a.occ.begin(), a.occ.end());   // the one rounding
-  WriteToken(out, binary, "<OCCUPANCY>");
-  WriteVector(out, binary, f.data(), a.num_gauss);
-  Matrix m;
-  m.rows = a.num_gauss;
-  m.cols = a.dim;
-  m.data.assign(a.mean.begin(), a.mean.end());
-  WriteToken(out, binary, "<MEANACCS>");
-  WriteMatrix(out, binary, m);
-  if (a.flags & kFgmmFlagVariances) {
-    m.data.assign(a.var.begin(), a.var.end());
-    WriteToken(out, binary, "<DIAGVARACCS>");
-    WriteMatrix(out, binary, m);
-  }
-  WriteToken(out, binary, "</GMMACCS>");
-  if (out.Close() != 0) throw KioError("error closing output " + wxfilename);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -138,7 +39,7 @@ double MlObjective(const DgmmAccs& a, const DiagGmmData& m) {
     for (size_t i = 0; i < G * D; ++i) obj += a.mean[i] * (double)m.means_invvars[i];
   if (a.flags & kFgmmFlagVariances) {
     double q = 0.0;
-    for (size_t i = 0; i < G * D; ++i) q += a.var[i] * (double)m.inv_vars[i];
+    for (size_t i = 0; i < G * D; ++i) q += a.second[i] * (double)m.inv_vars[i];
     obj -= 0.5 * q;
   }
   return obj;
@@ -147,94 +48,52 @@ double MlObjective(const DgmmAccs& a, const DiagGmmData& m) {
 }  // namespace
 
 void DgmmEst(const DgmmAccs& accs, int update_flags, const DgmmEstOptions& o, DiagGmmData* model, DgmmEstResult* res) {
-  const int G = model->num_gauss, D = model->dim;
-  if (accs.num_gauss != G || accs.dim != D)
-    throw KioError("the accumulators (" + std::to_string(accs.num_gauss) + " components of dimension " + std::to_string(accs.dim) + ") are not the model's (" +
-                   std::to_string(G) + " of dimension " + std::to_string(D) + ")");
-  if (update_flags & ~accs.flags)
-    throw KioError("the update flags '" + FlagLetters(update_flags) + "' name statistics that the accumulators (flags '" + FlagLetters(accs.flags) + "') do not have");
-  *res = DgmmEstResult();
-  const bool upd_m = update_flags & kFgmmFlagMeans, upd_v = update_flags & kFgmmFlagVariances, upd_w = update_flags & kFgmmFlagWeights;
+  const int D = model->dim;
+  const bool upd_m = update_flags & kFgmmFlagMeans, upd_v = update_flags & kFgmmFlagVariances;
   const bool has_m = accs.flags & kFgmmFlagMeans, has_v = accs.flags & kFgmmFlagVariances;
-  ComputeGconsts(model);
-  res->objf_before = MlObjective(accs, *model);
-  double occ_sum = 0.0;
-  for (int g = 0; g < G; ++g) occ_sum += accs.occ[g];
-  res->count = occ_sum;
-  std::vector<double> w((size_t)G), mu((size_t)D), var((size_t)D);
-  std::vector<char> remove((size_t)G, 0);
-  for (int g = 0; g < G; ++g) {
-    const double occ = accs.occ[g];
-    const double prob = occ_sum > 0.0 ? occ / occ_sum : 1.0 / G;
+  std::vector<double> mu((size_t)D), var((size_t)D);
+  GmmEstKind k;
+  k.num_gauss = &model->num_gauss;
+  k.dim = D;
+  k.weights = &model->weights;
+  k.rows = {{&model->means_invvars, (size_t)D}, {&model->inv_vars, (size_t)D}};
+  k.min_gaussian_weight = o.min_gaussian_weight;
+  k.min_gaussian_occupancy = o.min_gaussian_occupancy;
+  k.remove_low_count_gaussians = o.remove_low_count_gaussians;
+  k.gconsts_before = true;
+  k.gconsts = [&] { ComputeGconsts(model); };
+  k.objective = [&] { return MlObjective(accs, *model); };
+  k.update = [&](int g, double occ) {
+    if (!has_m) return;
     float* iv = model->inv_vars.data() + (size_t)g * D;
     float* mi = model->means_invvars.data() + (size_t)g * D;
-    if (occ > o.min_gaussian_occupancy && prob > o.min_gaussian_weight) {
-      w[g] = prob;
-      if (!has_m) continue;
-      int floored = 0;
-      for (int d = 0; d < D; ++d) {
-        const double mu_old = (double)mi[d] / (double)iv[d];
-        mu[d] = accs.mean[(size_t)g * D + d] / occ;
-        if (has_v) {
-          double v = accs.var[(size_t)g * D + d] / occ - mu[d] * mu[d];
-          if (!upd_m) v += (mu[d] - mu_old) * (mu[d] - mu_old);
-          if (v < o.min_variance) {
-            v = o.min_variance;
-            ++floored;
-          }
-          var[d] = v;
+    int floored = 0;
+    for (int d = 0; d < D; ++d) {
+      const double mu_old = (double)mi[d] / (double)iv[d];
+      mu[d] = accs.mean[(size_t)g * D + d] / occ;
+      if (has_v) {
+        double v = accs.second[(size_t)g * D + d] / occ - mu[d] * mu[d];
+        if (!upd_m) v += (mu[d] - mu_old) * (mu[d] - mu_old);
+        if (v < o.min_variance) {
+          v = o.min_variance;
+          ++floored;
         }
-        if (!upd_m) mu[d] = mu_old;
+        var[d] = v;
       }
-      if (floored) {
-        res->floored_elements += floored;
-        ++res->floored_gauss;
-      }
-      if (!upd_m && !upd_v) continue;
-      for (int d = 0; d < D; ++d) {
-        const double inv = upd_v ? 1.0 / var[d] : (double)iv[d];
-        if (upd_v) iv[d] = (float)inv;
-        mi[d] = (float)(mu[d] * inv);
-      }
-    } else if (o.remove_low_count_gaussians && (int)res->removed.size() < G - 1) {
-      std::ostringstream msg;
-      msg << "Too little data - removing Gaussian (weight " << prob << ", occupation count " << occ << ", vector size " << D << ")";
-      res->warnings.push_back(msg.str());
-      res->removed.push_back(g);
-      remove[g] = 1;
-      w[g] = (double)model->weights[g];   // until it is taken out it counts with its old weight
-    } else {
-      std::ostringstream msg;
-      msg << "Gaussian has too little data but not removing it because "
-          << (o.remove_low_count_gaussians ? "it is the last Gaussian: i = " : "remove-low-count-gaussians == false: i = ") << g << ", occ = " << occ
-          << ", weight = " << prob;
-      res->warnings.push_back(msg.str());
-      w[g] = std::max(prob, o.min_gaussian_weight);
+      if (!upd_m) mu[d] = mu_old;
     }
-  }
-  if (upd_w) {
-    double sum = 0.0;
-    for (int g = 0; g < G; ++g) sum += w[g];
-    for (int g = 0; g < G; ++g) model->weights[g] = (float)(w[g] / sum);
-  }
-  ComputeGconsts(model);
-  res->objf_after = MlObjective(accs, *model);
-  if (!res->removed.empty()) {
-    DiagGmmData out;
-    out.dim = D;
-    double sum = 0.0;
-    for (int g = 0; g < G; ++g)
-      if (!remove[g]) sum += (double)model->weights[g];
-    for (int g = 0; g < G; ++g) {
-      if (remove[g]) continue;
-      ++out.num_gauss;
-      out.weights.push_back((float)((double)model->weights[g] / sum));
-      out.means_invvars.insert(out.means_invvars.end(), model->means_invvars.begin() + (size_t)g * D, model->means_invvars.begin() + (size_t)(g + 1) * D);
-      out.inv_vars.insert(out.inv_vars.end(), model->inv_vars.begin() + (size_t)g * D, model->inv_vars.begin() + (size_t)(g + 1) * D);
+    if (floored) {
+      res->floored_elements += floored;
+      ++res->floored_gauss;
     }
-    ComputeGconsts(&out);
-    *model = out;
-  }
+    if (!upd_m && !upd_v) return;
+    for (int d = 0; d < D; ++d) {
+      const double inv = upd_v ? 1.0 / var[d] : (double)iv[d];
+      if (upd_v) iv[d] = (float)inv;
+      mi[d] = (float)(mu[d] * inv);
+    }
+  };
+  GmmEst(accs, update_flags, k, res);
 }
 
 void DgmmSplit(DiagGmmData* m, int target, double perturb, uint64_t seed, uint64_t stream, std::vector<int32_t>* split_of) {
@@ -318,26 +177,18 @@ void DgmmInitFromFrames(const float* feats, int64_t rows, int dim, int num_gauss
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct DgmmAccumulator::Impl {
-  int device = 0, num_gauss = 0, dim = 0, flags = 0;
-  DevBuf occ, mean, var;                                        // the running accumulators
-  DevBuf feats, idx, w, frame, gselect;                         // a call's inputs
-  DevBuf rank, hist, start, sorted;                             // the sort
+  GmmSparseAcc acc;                                             // the running accumulators and the sparse path
+  DevBuf gselect;                                               // DgmmAccAddGselect's input
   DevBuf ll, count, pidx, post, logsum, slot_post;              // the sparse E-step
-  DevBuf item_start, partial, dense_post;
+  DevBuf dense_post;
   DevBuf resident;                                              // DgmmAccSetFrames
   int64_t resident_rows = 0;
-
-  void Zero() {
-    Check(hipMemset(occ.p, 0, (size_t)num_gauss * 8), "hipMemset");
-    Check(hipMemset(mean.p, 0, (size_t)num_gauss * dim * 8), "hipMemset");
-    Check(hipMemset(var.p, 0, (size_t)num_gauss * dim * 8), "hipMemset");
-  }
 };
 
 DgmmAccumulator::~DgmmAccumulator() {}
-int DgmmAccumulator::num_gauss() const { return impl_->num_gauss; }
-int DgmmAccumulator::dim() const { return impl_->dim; }
-int DgmmAccumulator::flags() const { return impl_->flags; }
+int DgmmAccumulator::num_gauss() const { return impl_->acc.num_gauss; }
+int DgmmAccumulator::dim() const { return impl_->acc.dim; }
+int DgmmAccumulator::flags() const { return impl_->acc.flags; }
 
 DgmmAccumulator* DgmmAccCreate(int device, int num_gauss, int dim, int flags) {
   if (num_gauss < 1 || dim < 1 || flags < 0 || flags > 7) throw KioError("dgmm accumulator: bad argument");
@@ -347,87 +198,43 @@ DgmmAccumulator* DgmmAccCreate(int device, int num_gauss, int dim, int flags) {
   UseDevice(device, kWhoNeeds);
   std::unique_ptr<DgmmAccumulator> a(new DgmmAccumulator);
   a->impl_.reset(new DgmmAccumulator::Impl);
-  DgmmAccumulator::Impl& I = *a->impl_;
-  I.device = device;
-  I.dim = dim;
-  I.flags = AugmentGmmFlags(flags);
+  GmmSparseAcc& A = a->impl_->acc;
+  A.device = device;
+  A.dim = dim;
+  A.flags = AugmentGmmFlags(flags);
+  A.second_width = (size_t)dim;
+  A.who_needs = kWhoNeeds;
   DgmmAccReset(a.get(), num_gauss);
   return a.release();
 }
 
 void DgmmAccReset(DgmmAccumulator* acc, int num_gauss) {
-  DgmmAccumulator::Impl& I = *acc->impl_;
   if (num_gauss < 1 || num_gauss > (1 << 20)) throw KioError("dgmm accumulator: bad number of components");
-  UseDevice(I.device, kWhoNeeds);
-  I.num_gauss = num_gauss;
-  I.occ.Reserve((size_t)num_gauss * 8);
-  I.mean.Reserve((size_t)num_gauss * I.dim * 8);
-  I.var.Reserve((size_t)num_gauss * I.dim * 8);
-  I.Zero();
+  acc->impl_->acc.Reset(num_gauss);
 }
 
 namespace {
 
 using Impl = DgmmAccumulator::Impl;
 
-// the counting sort of ubm_kernels.h on `pairs` pairs whose Gaussians are d_gauss; returns the ms when timed
-float SortPairs(Impl& I, const int32_t* d_gauss, int64_t pairs, bool timed) {
-  UbmFullArgs s;
-  memset(&s, 0, sizeof s);
-  s.rows = pairs;
-  s.n = 1;
-  s.dim = I.dim;
-  s.num_gauss = I.num_gauss;
-  s.num_chunks = (int)((pairs + kUbmSortChunk - 1) / kUbmSortChunk);
-  const size_t hist_bytes = (size_t)I.num_gauss * s.num_chunks * 4;
-  I.rank.Reserve((size_t)pairs * 4);
-  I.hist.Reserve(hist_bytes);
-  I.start.Reserve((size_t)(I.num_gauss + 1) * 4);
-  I.sorted.Reserve((size_t)pairs * 4);
-  Check(hipMemsetAsync(I.hist.p, 0, hist_bytes, nullptr), "hipMemsetAsync");
-  s.gselect = d_gauss;
-  s.local_rank = I.rank.as<int32_t>();
-  s.chunk_hist = I.hist.as<int32_t>();
-  s.bucket_start = I.start.as<int32_t>();
-  s.sorted = I.sorted.as<int32_t>();
-  EventTimer tm(timed);
-  tm.Start();
-  Check(launch_ubm_bucket_sort(s, nullptr), "ubm_bucket_sort launch");
-  return timed ? tm.Stop() : 0.f;
-}
-
-// the work items, the partial sums and the reduction.  a: feats, rows, pairs, pair_frame / n, pair_w.
-float RunSparseAcc(Impl& I, FgmmAccArgs a, bool timed) {
-  I.item_start.Reserve((size_t)(I.num_gauss + 1) * 4);
-  a.dim = I.dim;
-  a.num_gauss = I.num_gauss;
-  a.flags = I.flags;
-  a.sorted = I.sorted.as<int32_t>();
-  a.bucket_start = I.start.as<int32_t>();
-  a.item_start = I.item_start.as<int32_t>();
-  a.occ = I.occ.as<double>();
-  a.mean = I.mean.as<double>();
-  a.cov = I.var.as<double>();
-  // a bucket that is not empty has at most one chunk that is not full: a bound that needs no count from the device
-  const int64_t bound = a.pairs / kFgmmAccPairChunk + std::min<int64_t>(I.num_gauss, a.pairs);
-  const size_t partial_bytes = (size_t)bound * (1 + 2 * I.dim) * 8;
-  if (bound >= INT32_MAX) throw KioError("dgmm accumulate: too many pairs in one call");
-  a.num_items = (int)bound;
-  I.partial.Reserve(partial_bytes);
-  a.partial = I.partial.as<double>();
-  EventTimer tm(timed);
-  tm.Start();
-  Check(launch_fgmm_acc_items(a, nullptr), "fgmm_acc_items launch");
-  Check(launch_dgmm_acc(a, nullptr), "dgmm_acc launch");
-  return timed ? tm.Stop() : 0.f;
+// the work items, the partial sums and the reduction on the pairs that A.Sort bucketed.  a: feats, rows, pairs, pair_frame / n, pair_w.
+float RunSparseAcc(GmmSparseAcc& A, FgmmAccArgs a, bool timed) {
+  a.sorted = A.sorted.as<int32_t>();
+  a.bucket_start = A.start.as<int32_t>();
+  return A.Accumulate(
+      a,
+      [](int64_t bound, size_t) {
+        if (bound >= INT32_MAX) throw KioError("dgmm accumulate: too many pairs in one call");
+      },
+      launch_dgmm_acc, "dgmm_acc launch", timed);
 }
 
 DgmmModelArgs ModelArgs(const Impl& I, const UbmModel& diag, const char* who) {
   const UbmDiagView v = UbmDiagArrays(diag);
-  if (v.num_gauss != I.num_gauss || v.dim != I.dim)
+  if (v.num_gauss != I.acc.num_gauss || v.dim != I.acc.dim)
     throw KioError(std::string(who) + ": the model has " + std::to_string(v.num_gauss) + " components of dimension " + std::to_string(v.dim) +
-                   ", the accumulators " + std::to_string(I.num_gauss) + " of dimension " + std::to_string(I.dim));
-  if (v.device != I.device) throw KioError(std::string(who) + ": the model and the accumulators are on different devices");
+                   ", the accumulators " + std::to_string(I.acc.num_gauss) + " of dimension " + std::to_string(I.acc.dim));
+  if (v.device != I.acc.device) throw KioError(std::string(who) + ": the model and the accumulators are on different devices");
   DgmmModelArgs m;
   m.dim = v.dim;
   m.num_gauss = v.num_gauss;
@@ -441,12 +248,12 @@ DgmmModelArgs ModelArgs(const Impl& I, const UbmModel& diag, const char* who) {
 // the dense accumulation and the reduction on frames that are on the device
 void RunDense(Impl& I, DgmmDenseArgs a, float* ms_acc, float* ms_reduce) {
   a.num_chunks = (int)((a.rows + kDgmmDenseFrameChunk - 1) / kDgmmDenseFrameChunk);
-  const size_t partial_bytes = (size_t)I.num_gauss * a.num_chunks * (1 + 2 * I.dim) * 8;
+  const size_t partial_bytes = (size_t)I.acc.num_gauss * a.num_chunks * (1 + 2 * I.acc.dim) * 8;
   if (partial_bytes > ((size_t)8 << 30))
-    throw KioError("dgmm dense accumulate: " + std::to_string(a.rows) + " frames on " + std::to_string(I.num_gauss) + " Gaussians of dimension " +
-                   std::to_string(I.dim) + " need " + std::to_string(partial_bytes >> 20) + " MiB of partial sums; the limit of one call is 8192 MiB");
-  I.partial.Reserve(partial_bytes);
-  a.partial = I.partial.as<double>();
+    throw KioError("dgmm dense accumulate: " + std::to_string(a.rows) + " frames on " + std::to_string(I.acc.num_gauss) + " Gaussians of dimension " +
+                   std::to_string(I.acc.dim) + " need " + std::to_string(partial_bytes >> 20) + " MiB of partial sums; the limit of one call is 8192 MiB");
+  I.acc.partial.Reserve(partial_bytes);
+  a.partial = I.acc.partial.as<double>();
   const bool timed = ms_acc != nullptr;
   EventTimer tm(timed, 3);
   tm.Mark();
@@ -454,14 +261,14 @@ void RunDense(Impl& I, DgmmDenseArgs a, float* ms_acc, float* ms_reduce) {
   tm.Mark();
   DgmmReduceArgs r;
   memset(&r, 0, sizeof r);
-  r.dim = I.dim;
-  r.num_gauss = I.num_gauss;
-  r.flags = I.flags;
+  r.dim = I.acc.dim;
+  r.num_gauss = I.acc.num_gauss;
+  r.flags = I.acc.flags;
   r.num_chunks = a.num_chunks;
   r.partial = a.partial;
-  r.occ = I.occ.as<double>();
-  r.mean = I.mean.as<double>();
-  r.var = I.var.as<double>();
+  r.occ = I.acc.occ.as<double>();
+  r.mean = I.acc.mean.as<double>();
+  r.var = I.acc.second.as<double>();
   Check(launch_dgmm_acc_reduce(r, nullptr), "dgmm_acc_reduce launch");
   tm.Mark();
   if (timed) {
@@ -475,35 +282,19 @@ void RunDense(Impl& I, DgmmDenseArgs a, float* ms_acc, float* ms_reduce) {
 void DgmmAccAdd(DgmmAccumulator* acc, const float* feats, int64_t rows, const int32_t* post_off, const int32_t* post_idx, const float* post_w,
                 float* device_ms2) {
   if (device_ms2) device_ms2[0] = device_ms2[1] = 0.f;
-  Impl& I = *acc->impl_;
-  if (rows < 0 || rows > INT32_MAX - 1 || !post_off) throw KioError("dgmm accumulate: bad argument");
-  if (post_off[0] != 0) throw KioError("dgmm accumulate: the posterior offsets must start at 0");
-  for (int64_t t = 0; t < rows; ++t)
-    if (post_off[t + 1] < post_off[t]) throw KioError("dgmm accumulate: the posterior offsets must not decrease");
-  const int64_t pairs = post_off[rows];
+  GmmSparseAcc& A = acc->impl_->acc;
+  const int64_t pairs = A.UploadPairs("dgmm accumulate", feats, rows, post_off, post_idx, post_w);
   if (pairs == 0) return;
-  if (!feats || !post_idx || !post_w) throw KioError("dgmm accumulate: null buffer");
-  for (int64_t i = 0; i < pairs; ++i)
-    if (post_idx[i] < 0 || post_idx[i] >= I.num_gauss)
-      throw KioError("dgmm accumulate: the posteriors name Gaussian " + std::to_string(post_idx[i]) + "; the accumulators have " + std::to_string(I.num_gauss));
-  std::vector<int32_t> frame((size_t)pairs);
-  for (int64_t t = 0; t < rows; ++t)
-    for (int32_t i = post_off[t]; i < post_off[t + 1]; ++i) frame[i] = (int32_t)t;
-  UseDevice(I.device, kWhoNeeds);
-  I.feats.Upload(feats, (size_t)rows * I.dim * 4, "copy features");
-  I.idx.Upload(post_idx, (size_t)pairs * 4, "copy the posterior indices");
-  I.w.Upload(post_w, (size_t)pairs * 4, "copy the posteriors");
-  I.frame.Upload(frame, "copy the posteriors' frames");
-  const float ms_sort = SortPairs(I, I.idx.as<int32_t>(), pairs, device_ms2 != nullptr);
+  const float ms_sort = A.Sort(A.idx.as<int32_t>(), pairs, device_ms2 != nullptr);
   FgmmAccArgs a;
   memset(&a, 0, sizeof a);
-  a.feats = I.feats.as<float>();
+  a.feats = A.feats.as<float>();
   a.rows = rows;
   a.pairs = pairs;
-  a.pair_frame = I.frame.as<int32_t>();
+  a.pair_frame = A.frame.as<int32_t>();
   a.n = 1;
-  a.pair_w = I.w.as<float>();
-  const float ms = RunSparseAcc(I, a, device_ms2 != nullptr);
+  a.pair_w = A.w.as<float>();
+  const float ms = RunSparseAcc(A, a, device_ms2 != nullptr);
   if (device_ms2) {
     device_ms2[0] = ms_sort;
     device_ms2[1] = ms;
@@ -526,11 +317,11 @@ void DgmmAccAddGselect(DgmmAccumulator* acc, const UbmModel& diag, const float* 
   if (rows * n >= INT32_MAX) throw KioError("dgmm accumulate: more than 2^31 pairs in one call");
   const int64_t pairs = rows * n;
   for (int64_t i = 0; i < pairs; ++i)
-    if (gselect[i] < 0 || gselect[i] >= I.num_gauss)
-      throw KioError("dgmm accumulate: the selection names Gaussian " + std::to_string(gselect[i]) + "; the model has " + std::to_string(I.num_gauss));
-  UseDevice(I.device, kWhoNeeds);
+    if (gselect[i] < 0 || gselect[i] >= I.acc.num_gauss)
+      throw KioError("dgmm accumulate: the selection names Gaussian " + std::to_string(gselect[i]) + "; the model has " + std::to_string(I.acc.num_gauss));
+  UseDevice(I.acc.device, kWhoNeeds);
   const bool timed = device_ms4 != nullptr;
-  I.feats.Upload(feats, (size_t)rows * I.dim * 4, "copy features");
+  I.acc.feats.Upload(feats, (size_t)rows * I.acc.dim * 4, "copy features");
   I.gselect.Upload(gselect, (size_t)pairs * 4, "copy the selection");
   I.ll.Reserve((size_t)pairs * 4);
   I.count.Reserve((size_t)rows * 4);
@@ -539,8 +330,8 @@ void DgmmAccAddGselect(DgmmAccumulator* acc, const UbmModel& diag, const float* 
   I.slot_post.Reserve((size_t)pairs * 4);
   I.logsum.Reserve((size_t)rows * 4);
   // the pairs (frame, slot) are bucketed by their Gaussian: n = 1 over rows * n pairs is the same sort as n over rows frames
-  const float ms_sort = SortPairs(I, I.gselect.as<int32_t>(), pairs, timed);
-  sel.feats = I.feats.as<float>();
+  const float ms_sort = I.acc.Sort(I.gselect.as<int32_t>(), pairs, timed);
+  sel.feats = I.acc.feats.as<float>();
   sel.rows = rows;
   sel.n = n;
   sel.gselect = I.gselect.as<int32_t>();
@@ -548,12 +339,12 @@ void DgmmAccAddGselect(DgmmAccumulator* acc, const UbmModel& diag, const float* 
   UbmFullArgs p;
   memset(&p, 0, sizeof p);
   p.rows = rows;
-  p.dim = I.dim;
-  p.num_gauss = I.num_gauss;
+  p.dim = I.acc.dim;
+  p.num_gauss = I.acc.num_gauss;
   p.n = n;
   p.gselect = I.gselect.as<int32_t>();
-  p.bucket_start = I.start.as<int32_t>();
-  p.sorted = I.sorted.as<int32_t>();
+  p.bucket_start = I.acc.start.as<int32_t>();
+  p.sorted = I.acc.sorted.as<int32_t>();
   p.ll = I.ll.as<float>();
   p.min_post = 0.f;
   p.out_count = I.count.as<int32_t>();
@@ -569,13 +360,13 @@ void DgmmAccAddGselect(DgmmAccumulator* acc, const UbmModel& diag, const float* 
   tm.Mark();
   FgmmAccArgs a;
   memset(&a, 0, sizeof a);
-  a.feats = I.feats.as<float>();
+  a.feats = I.acc.feats.as<float>();
   a.rows = rows;
   a.pairs = pairs;
   a.pair_frame = nullptr;
   a.n = n;
   a.pair_w = I.slot_post.as<float>();
-  const float ms = RunSparseAcc(I, a, timed);
+  const float ms = RunSparseAcc(I.acc, a, timed);
   if (timed) {
     device_ms4[0] = ms_sort;
     device_ms4[1] = tm.Span(0);
@@ -591,14 +382,14 @@ void DgmmAccAddDensePost(DgmmAccumulator* acc, const float* feats, int64_t rows,
   if (rows < 0) throw KioError("dgmm dense accumulate: bad argument");
   if (rows == 0) return;
   if (!feats || !post) throw KioError("dgmm dense accumulate: null buffer");
-  UseDevice(I.device, kWhoNeeds);
-  I.feats.Upload(feats, (size_t)rows * I.dim * 4, "copy features");
-  I.dense_post.Upload(post, (size_t)rows * I.num_gauss * 4, "copy the posteriors");
+  UseDevice(I.acc.device, kWhoNeeds);
+  I.acc.feats.Upload(feats, (size_t)rows * I.acc.dim * 4, "copy features");
+  I.dense_post.Upload(post, (size_t)rows * I.acc.num_gauss * 4, "copy the posteriors");
   DgmmDenseArgs a;
   memset(&a, 0, sizeof a);
-  a.model.dim = I.dim;
-  a.model.num_gauss = I.num_gauss;
-  a.feats = I.feats.as<float>();
+  a.model.dim = I.acc.dim;
+  a.model.num_gauss = I.acc.num_gauss;
+  a.feats = I.acc.feats.as<float>();
   a.rows = rows;
   a.post = I.dense_post.as<float>();
   RunDense(I, a, nullptr, nullptr);
@@ -608,8 +399,8 @@ void DgmmAccAddDensePost(DgmmAccumulator* acc, const float* feats, int64_t rows,
 void DgmmAccSetFrames(DgmmAccumulator* acc, const float* feats, int64_t rows) {
   Impl& I = *acc->impl_;
   if (rows < 1 || !feats) throw KioError("dgmm dense accumulate: no frames");
-  UseDevice(I.device, kWhoNeeds);
-  I.resident.Upload(feats, (size_t)rows * I.dim * 4, "copy features");
+  UseDevice(I.acc.device, kWhoNeeds);
+  I.resident.Upload(feats, (size_t)rows * I.acc.dim * 4, "copy features");
   I.resident_rows = rows;
 }
 
@@ -622,10 +413,10 @@ void DgmmAccAddDense(DgmmAccumulator* acc, const UbmModel& diag, const float* fe
   a.model = ModelArgs(I, diag, "dgmm dense accumulate");
   if (rows == 0) return;
   if (!feats && rows != I.resident_rows) throw KioError("dgmm dense accumulate: the frames on the device are not the " + std::to_string(rows) + " asked for");
-  UseDevice(I.device, kWhoNeeds);
-  if (feats) I.feats.Upload(feats, (size_t)rows * I.dim * 4, "copy features");
+  UseDevice(I.acc.device, kWhoNeeds);
+  if (feats) I.acc.feats.Upload(feats, (size_t)rows * I.acc.dim * 4, "copy features");
   I.logsum.Reserve((size_t)rows * 4);
-  a.feats = feats ? I.feats.as<float>() : I.resident.as<float>();
+  a.feats = feats ? I.acc.feats.as<float>() : I.resident.as<float>();
   a.rows = rows;
   a.logsum = I.logsum.as<float>();
   EventTimer tm(device_ms3 != nullptr);
@@ -638,11 +429,7 @@ void DgmmAccAddDense(DgmmAccumulator* acc, const UbmModel& diag, const float* fe
 }
 
 void DgmmAccGet(const DgmmAccumulator& acc, double* occ, double* mean, double* var) {
-  const Impl& I = *acc.impl_;
-  UseDevice(I.device, kWhoNeeds);
-  if (occ) I.occ.Download(occ, (size_t)I.num_gauss * 8, "copy the occupancies");
-  if (mean) I.mean.Download(mean, (size_t)I.num_gauss * I.dim * 8, "copy the mean accumulators");
-  if (var) I.var.Download(var, (size_t)I.num_gauss * I.dim * 8, "copy the variance accumulators");
+  acc.impl_->acc.Get(occ, mean, var, "copy the variance accumulators");
 }
 
 }  // namespace xv

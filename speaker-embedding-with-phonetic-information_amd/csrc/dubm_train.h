@@ -12,8 +12,9 @@
 //
 // gmm-global-acc-stats [--binary=true] [--update-flags=mvw] --gselect=<rspecifier> <model-in> <feature-rspecifier> <stats-out>  (device)
 //   Reading, the per-utterance errors (no gselect entry, wrong length, wrong width, no rows) and the closing log lines are
-//   fgmm-global-acc-stats' (ubm_train.h).  Per frame x (fp32) with selected Gaussians s_1 .. s_n: the scores are the diagonal model's
-//   on the selection, bit for bit what gmm-gselect ranked; the posteriors are ubm_post's fp32 softmax with min_post = 0, kept in the
+//   fgmm-global-acc-stats' (ubm_train.h): the two tools run one driver, GmmAccStats of gmm_acc_tool.h.
+//   Per frame x (fp32) with selected Gaussians s_1 .. s_n: the scores are the diagonal model's on the selection, bit for bit what
+//   gmm-gselect ranked; the posteriors are ubm_post's fp32 softmax with min_post = 0, kept in the
 //   selection's slots; the frame's log-sum is added to the total log-likelihood.  Per pair (g, p) with p != 0, in fp64:
 //   occ_g += p; with m: mean_g += p x; with v: var_g += p (x x) (the flags augmented: v implies m, m implies w).
 //   The accepted frames are concatenated and cut into blocks of exactly kDgmmAccFrameBlock frames, one device call each, the last
@@ -73,9 +74,9 @@
 #include <string>
 #include <vector>
 
+#include "gmm_train.h"
 #include "kio.h"
 #include "ubm.h"
-#include "ubm_train.h"
 
 namespace xv {
 
@@ -85,26 +86,14 @@ uint64_t DgmmDrawB(uint64_t seed, uint64_t e);
 double DgmmGauss(uint64_t seed, uint64_t e);
 constexpr uint64_t kDgmmEntrySample = (uint64_t)1 << 60, kDgmmEntryInit = (uint64_t)2 << 60, kDgmmEntrySplit = (uint64_t)3 << 60;
 
-// ---- the accumulators on the host
-struct DgmmAccs {
-  int num_gauss = 0, dim = 0, flags = 0;   // flags: augmented
-  std::vector<double> occ, mean, var;      // [G], [G][D], [G][D]; mean / var are all zeros without m / v
-  void Init(int num_gauss, int dim, int flags);
-};
-void ReadDgmmAccsFile(const std::string& rxfilename, bool add, DgmmAccs* a);
-void WriteDgmmAccsFile(const std::string& wxfilename, bool binary, const DgmmAccs& a);
+// The accumulators on the host (DgmmAccs: `second` holds var [G][D]) and their file: gmm_train.h.
 
 // ---- the M-step (host, fp64)
 struct DgmmEstOptions {
   double min_gaussian_weight = 1e-5, min_gaussian_occupancy = 10.0, min_variance = 0.001;
   bool remove_low_count_gaussians = true;
 };
-struct DgmmEstResult {
-  double objf_before = 0.0, objf_after = 0.0, count = 0.0;
-  int floored_elements = 0, floored_gauss = 0;
-  std::vector<int32_t> removed;   // ascending
-  std::vector<std::string> warnings;
-};
+using DgmmEstResult = GmmEstResult;
 void DgmmEst(const DgmmAccs& accs, int update_flags, const DgmmEstOptions& opts, DiagGmmData* model, DgmmEstResult* res);
 // No-op when target <= the model's size.  split_of (may be null): for every Gaussian added, the index it was copied from.
 void DgmmSplit(DiagGmmData* model, int target, double perturb_factor, uint64_t seed, uint64_t stream, std::vector<int32_t>* split_of = nullptr);

@@ -20,7 +20,7 @@
 #include "cmvn.h"
 #include "dubm_train.h"
 #include "dubm_train_kernels.h"
-#include "gselect_lookup.h"
+#include "gmm_acc_tool.h"
 #include "kio.h"
 #include "ubm.h"
 #include "ubm_kernels.h"
@@ -33,13 +33,7 @@ std::unique_ptr<xv::UbmModel> Upload(int dev, const xv::DiagGmmData& gmm) {
   return std::unique_ptr<xv::UbmModel>(xv::UbmDiagCreate(dev, gmm.num_gauss, gmm.dim, gmm.gconsts.data(), gmm.means_invvars.data(), gmm.inv_vars.data()));
 }
 
-struct AccOptions {
-  bool binary = true;
-  std::string update_flags = "mvw", gselect;
-  int device = -1, verbose = 0;
-};
-
-int AccStats(const AccOptions& o, const std::vector<std::string>& pos) {
+int AccStats(const xv::GmmAccOptions& o, const std::vector<std::string>& pos) {
   if (o.gselect.empty())
     throw xv::KioError("gmm-global-acc-stats without --gselect is not built: sid/train_diag_ubm.sh always passes the Gaussian selection");
   const int flags = xv::ParseGmmFlags(o.update_flags);
@@ -48,99 +42,14 @@ int AccStats(const AccOptions& o, const std::vector<std::string>& pos) {
   const int dev = xv::PickDevice(o.device);
   std::unique_ptr<xv::DgmmAccumulator> acc(xv::DgmmAccCreate(dev, gmm.num_gauss, gmm.dim, flags));
   std::unique_ptr<xv::UbmModel> model = Upload(dev, gmm);
-  xv::FeatBatchReader reader(pos[1], kBatchFrames, false);
-  xv::GselectLookup gselect(o.gselect);
-  long num_done = 0, num_err = 0;
-  double tot_like = 0.0;
-  int64_t tot_t = 0;
-  // the stream of accepted frames, cut into blocks of exactly kDgmmAccFrameBlock: what is pending is less than one block
-  std::vector<float> feats, logsum;
-  std::vector<int32_t> gs;
-  int n = 0;
-  const int D = gmm.dim;
-  size_t head = 0;   // frames at the front of the pending buffers that have been through the device
-  auto accumulate = [&](size_t rows) {
-    logsum.resize(rows);
-    xv::DgmmAccAddGselect(acc.get(), *model, feats.data() + head * D, (int64_t)rows, gs.data() + head * n, n, nullptr, logsum.data());
-    for (size_t t = 0; t < rows; ++t) tot_like += logsum[t];
-    tot_t += (int64_t)rows;
-    head += rows;
-  };
-  xv::FeatBatchReader::Batch b;
-  std::vector<xv::FeatBatchReader::Problem> problems;
-  for (bool more = true; more;) {
-    problems.clear();
-    more = reader.Next(&b, &problems);
-    for (const auto& p : problems) {
-      if (p.what.empty()) {
-        XWARN("Empty feature matrix for utterance " << p.key);   // no frames: skipped, not an error
-      } else {
-        XWARN("Failed to read features for key " << p.key << ": " << p.what);
-        ++num_err;
-      }
-    }
-    if (!more) break;
-    for (size_t u = 0; u < b.keys.size(); ++u) {
-      const int rows = b.row_off[u + 1] - b.row_off[u];
-      if (b.cols != D) {
-        XWARN("Dimension mismatch for utterance " << b.keys[u] << ": the features have " << b.cols << " columns, the model " << D);
-        ++num_err;
-        continue;
-      }
-      xv::IntVecVec sel;
-      if (!gselect.Find(b.keys[u], &sel)) {
-        XWARN("No gselect information for utterance " << b.keys[u]);
-        ++num_err;
-        continue;
-      }
-      if ((int)sel.size() != rows) {
-        XWARN("gselect information for utterance " << b.keys[u] << " has wrong size " << sel.size() << " vs. " << rows);
-        ++num_err;
-        continue;
-      }
-      const size_t width = sel[0].size();
-      bool same = width >= 1;
-      for (const auto& l : sel) same = same && l.size() == width;
-      if (!same || (n != 0 && (int)width != n)) {
-        XWARN("The Gaussian selection of utterance " << b.keys[u] << " does not have " << (n ? "the " + std::to_string(n) + " indices per frame of the utterances before it" : "one length for every frame")
-                                                    << " (skipping utterance)");
-        ++num_err;
-        continue;
-      }
-      if (width > (size_t)xv::kUbmMaxSelect)
-        throw xv::KioError("the Gaussian selection has " + std::to_string(width) + " indices per frame; the device kernels take at most " + std::to_string(xv::kUbmMaxSelect));
-      n = (int)width;
-      feats.insert(feats.end(), b.feats.begin() + (size_t)b.row_off[u] * D, b.feats.begin() + (size_t)b.row_off[u + 1] * D);
-      for (const auto& l : sel) gs.insert(gs.end(), l.begin(), l.end());
-      while (feats.size() / D - head >= (size_t)xv::kDgmmAccFrameBlock) accumulate((size_t)xv::kDgmmAccFrameBlock);
-      if (head) {   // drop what was consumed, once per utterance that filled a block
-        feats.erase(feats.begin(), feats.begin() + head * D);
-        gs.erase(gs.begin(), gs.begin() + head * n);
-        head = 0;
-      }
-      ++num_done;
-      if (o.verbose >= 1 && num_done % 10 == 0)   // over the frames that have been through the device: whole blocks
-        XLOG("Avg like per frame so far is " << (tot_t ? tot_like / (double)tot_t : 0.0));
-    }
-  }
-  if (!feats.empty()) accumulate(feats.size() / D);
-  XLOG("Done " << num_done << " files; " << num_err << " with errors.");
-  XLOG("Overall likelihood per frame = " << (tot_t ? tot_like / (double)tot_t : 0.0) << " over " << tot_t << " (weighted) frames.");
   xv::DgmmAccs host;
   host.Init(gmm.num_gauss, gmm.dim, flags);
-  xv::DgmmAccGet(*acc, host.occ.data(), host.mean.data(), host.var.data());
-  xv::WriteDgmmAccsFile(pos[2], o.binary, host);
-  XLOG("Written accs to " << pos[2]);
-  return num_done != 0 ? 0 : 1;
-}
-
-int SumAccs(bool binary, const std::vector<std::string>& pos) {
-  xv::DgmmAccs sum;
-  for (size_t i = 1; i < pos.size(); ++i) xv::ReadDgmmAccsFile(pos[i], i > 1, &sum);
-  xv::WriteDgmmAccsFile(pos[0], binary, sum);
-  XLOG("Summed " << pos.size() - 1 << " stats");
-  XLOG("Written stats to " << pos[0]);
-  return 0;
+  return xv::GmmAccStats(
+      o, pos, &host, xv::kDgmmAccFrameBlock,
+      [&](const float* feats, int64_t rows, const int32_t* gselect, int n, float* logsum) {
+        xv::DgmmAccAddGselect(acc.get(), *model, feats, rows, gselect, n, nullptr, logsum);
+      },
+      [&] { xv::DgmmAccGet(*acc, host.occ.data(), host.mean.data(), host.second.data()); });
 }
 
 struct EstOptions {
@@ -157,7 +66,7 @@ int Est(const EstOptions& o, const std::vector<std::string>& pos) {
   xv::DiagGmmData gmm;
   xv::ReadDiagGmmFile(pos[0], &gmm);
   xv::DgmmAccs accs;
-  xv::ReadDgmmAccsFile(pos[1], false, &accs);
+  xv::ReadGmmAccsFile(pos[1], false, &accs);
   xv::DgmmEstResult r;
   xv::DgmmEst(accs, flags, o.est, &gmm, &r);
   for (const std::string& w : r.warnings) XWARN(w);
@@ -229,7 +138,7 @@ int InitFromFeats(const InitOptions& o, const std::vector<std::string>& pos) {
     for (int64_t t = 0; t < T; ++t) tot_like += logsum[t];
     XLOG("Likelihood per frame on iteration " << iter << " was " << tot_like / (double)T << " over " << T << " frames.");
     host.Init(gmm.num_gauss, D, 7);
-    xv::DgmmAccGet(*acc, host.occ.data(), host.mean.data(), host.var.data());
+    xv::DgmmAccGet(*acc, host.occ.data(), host.mean.data(), host.second.data());
     xv::DgmmEstResult r;
     xv::DgmmEst(host, 7, o.est, &gmm, &r);
     for (const std::string& w : r.warnings) XWARN(w);
@@ -246,32 +155,11 @@ int InitFromFeats(const InitOptions& o, const std::vector<std::string>& pos) {
   return 0;
 }
 
-std::string Dashes(std::string n) {
-  for (char& c : n)
-    if (c == '_') c = '-';
-  return n;
-}
-
-bool Common(const std::string& n) { return n == "verbose" || n == "print-args" || n == "config"; }
-
-double ToDouble(const std::string& name, const std::string& v) {
-  double d = 0.0;
-  if (!xv::ParseDouble(v, &d)) throw xv::KioError("Invalid floating-point option --" + name + "=" + v);
-  return d;
-}
-
-uint64_t ToSeed(const std::string& name, const std::string& v) {
-  char* end = nullptr;
-  const unsigned long long s = strtoull(v.c_str(), &end, 10);
-  if (v.empty() || *end != '\0' || v[0] == '-') throw xv::KioError("Invalid option --" + name + "=" + v + ": a non-negative integer is expected");
-  return (uint64_t)s;
-}
-
 // the four options of the M-step that gmm-global-est and gmm-global-init-from-feats share
 bool SetEstOption(const std::string& n, const std::string& val, xv::DgmmEstOptions* est) {
-  if (n == "min-gaussian-weight") est->min_gaussian_weight = ToDouble(n, val);
-  else if (n == "min-gaussian-occupancy") est->min_gaussian_occupancy = ToDouble(n, val);
-  else if (n == "min-variance") est->min_variance = ToDouble(n, val);
+  if (n == "min-gaussian-weight") est->min_gaussian_weight = xv::ToDouble(n, val);
+  else if (n == "min-gaussian-occupancy") est->min_gaussian_occupancy = xv::ToDouble(n, val);
+  else if (n == "min-variance") est->min_variance = xv::ToDouble(n, val);
   else if (n == "remove-low-count-gaussians") est->remove_low_count_gaussians = xv::ToBool(n, val);
   else return false;
   return true;
@@ -289,13 +177,13 @@ int main(int argc, char** argv) {
               "Usage: gmm-global-sum-accs [options] <stats-out> <stats-in1> <stats-in2> ...\n"
               "Options: --binary (true)\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "binary") binary = xv::ToBool(n, val);
       else return xv::OptionResult::kUnknown;
       return xv::OptionResult::kOk;
     };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() < 2 ? xv::kUsageError : SumAccs(binary, pos); };
+    t.run = [&](const std::vector<std::string>& pos) { return pos.size() < 2 ? xv::kUsageError : xv::GmmSumAccs(false, binary, pos); };
     return xv::CliMain(argc, argv, t);
   }
   if (prog == "gmm-global-est") {
@@ -305,14 +193,14 @@ int main(int argc, char** argv) {
               "Options: --binary (true) --update-flags (mvw) --min-gaussian-weight (1e-5) --min-gaussian-occupancy (10)\n"
               "         --min-variance (0.001) --remove-low-count-gaussians (true) --mix-up (0) --perturb-factor (0.01) --seed (0)\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "binary") o.binary = xv::ToBool(n, val);
       else if (n == "update-flags") o.update_flags = val;
       else if (SetEstOption(n, val, &o.est)) return xv::OptionResult::kOk;
       else if (n == "mix-up") o.mix_up = xv::ToInt(n, val);
-      else if (n == "perturb-factor") o.perturb_factor = ToDouble(n, val);
-      else if (n == "seed") o.seed = ToSeed(n, val);
+      else if (n == "perturb-factor") o.perturb_factor = xv::ToDouble(n, val);
+      else if (n == "seed") o.seed = xv::ToSeed(n, val);
       else return xv::OptionResult::kUnknown;
       return xv::OptionResult::kOk;
     };
@@ -327,8 +215,8 @@ int main(int argc, char** argv) {
               "         --num-threads (4; accepted and ignored) --min-gaussian-weight (1e-5) --min-gaussian-occupancy (10)\n"
               "         --min-variance (0.001) --remove-low-count-gaussians (true) --seed (0) --verbose --device=<gpu>\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "binary") o.binary = xv::ToBool(n, val);
       else if (n == "num-gauss") o.num_gauss = xv::ToInt(n, val);
       else if (n == "num-gauss-init") o.num_gauss_init = xv::ToInt(n, val);
@@ -336,7 +224,7 @@ int main(int argc, char** argv) {
       else if (n == "num-frames") o.num_frames = xv::ToInt(n, val);
       else if (n == "num-threads") (void)xv::ToInt(n, val);
       else if (SetEstOption(n, val, &o.est)) return xv::OptionResult::kOk;
-      else if (n == "seed") o.seed = ToSeed(n, val);
+      else if (n == "seed") o.seed = xv::ToSeed(n, val);
       else if (n == "device") o.device = xv::ToInt(n, val);
       else return xv::OptionResult::kUnknown;
       return xv::OptionResult::kOk;
@@ -348,22 +236,15 @@ int main(int argc, char** argv) {
     fprintf(stderr, "%s: not one of gmm-global-acc-stats, gmm-global-init-from-feats, gmm-global-sum-accs, gmm-global-est\n", prog.c_str());
     return 255;
   }
-  AccOptions o;
+  xv::GmmAccOptions o;
   t.usage = "Accumulate stats for training a diagonal-covariance GMM.\n"
             "Usage: gmm-global-acc-stats [options] --gselect=<gselect-rspecifier> <model-in> <feature-rspecifier> <stats-out>\n"
             "Options: --binary (true) --update-flags (mvw) --gselect (required) --verbose --device=<gpu>\n"
             "Not built (refused): running without --gselect, --weights.\n";
   t.set = [&](const std::string& name, const std::string& val) {
-    const std::string n = Dashes(name);
-    if (n == "verbose") o.verbose = xv::ToInt(n, val);
-    else if (Common(n)) return xv::OptionResult::kOk;
-    else if (n == "binary") o.binary = xv::ToBool(n, val);
-    else if (n == "update-flags") o.update_flags = val;
-    else if (n == "gselect") o.gselect = val;
-    else if (n == "device") o.device = xv::ToInt(n, val);
-    else if (n == "weights") throw xv::KioError("--weights is not built: sid/train_diag_ubm.sh passes no per-frame weights");
-    else return xv::OptionResult::kUnknown;
-    return xv::OptionResult::kOk;
+    const std::string n = xv::Dashes(name);
+    if (n == "weights") throw xv::KioError("--weights is not built: sid/train_diag_ubm.sh passes no per-frame weights");
+    return xv::SetGmmAccOption(n, val, &o);
   };
   t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : AccStats(o, pos); };
   return xv::CliMain(argc, argv, t);

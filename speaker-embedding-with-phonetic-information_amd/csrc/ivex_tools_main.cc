@@ -147,18 +147,6 @@ int ExtractorCopy(bool binary, const std::vector<std::string>& pos) {
   return 0;
 }
 
-double ToDouble(const std::string& name, const std::string& v) {
-  double d;
-  if (!xv::ParseDouble(v, &d)) throw xv::KioError("Invalid floating-point option --" + name + "=" + v);
-  return d;
-}
-
-std::string Dashes(std::string n) {
-  for (char& c : n)
-    if (c == '_') c = '-';
-  return n;
-}
-
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -170,8 +158,8 @@ int main(int argc, char** argv) {
     t.usage = "Copy the i-vector extractor to a different file (possibly changing binary/text format).\n"
               "Usage: ivector-extractor-copy [options] <ivector-extractor-in> <ivector-extractor-out>\nOptions: --binary (true)\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (n == "verbose" || n == "print-args" || n == "config") return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "binary") binary = xv::ToBool(n, val);
       else return xv::OptionResult::kUnknown;
       return xv::OptionResult::kOk;
@@ -186,12 +174,12 @@ int main(int argc, char** argv) {
             "Options: --compute-objf-change (true) --acoustic-weight (1.0) --max-count (0) --num-threads (accepted, ignored) --verbose --device=<gpu>\n"
             "Limits: i-vector dimension <= 1024, feature dimension <= 96.  Not built (refused): --spk2utt, models with i-vector-dependent weights.\n";
   t.set = [&](const std::string& name, const std::string& val) {
-    const std::string n = Dashes(name);
+    const std::string n = xv::Dashes(name);
     if (n == "print-args" || n == "config" || n == "num-threads") return xv::OptionResult::kOk;
     if (n == "verbose") o.verbose = xv::ToInt(n, val);
     else if (n == "compute-objf-change") o.compute_objf_change = xv::ToBool(n, val);
-    else if (n == "acoustic-weight") o.acoustic_weight = ToDouble(n, val);
-    else if (n == "max-count") o.max_count = ToDouble(n, val);
+    else if (n == "acoustic-weight") o.acoustic_weight = xv::ToDouble(n, val);
+    else if (n == "max-count") o.max_count = xv::ToDouble(n, val);
     else if (n == "device") o.device = xv::ToInt(n, val);
     else if (n == "spk2utt") throw xv::KioError("--spk2utt is not built: no script of the recipes passes it (they average per speaker with ivector-mean)");
     else return xv::OptionResult::kUnknown;

@@ -162,20 +162,6 @@ int Est(bool binary, const xv::IvexEstOptions& o, const std::vector<std::string>
   return 0;
 }
 
-double ToDouble(const std::string& name, const std::string& v) {
-  double d;
-  if (!xv::ParseDouble(v, &d)) throw xv::KioError("Invalid floating-point option --" + name + "=" + v);
-  return d;
-}
-
-std::string Dashes(std::string n) {
-  for (char& c : n)
-    if (c == '_') c = '-';
-  return n;
-}
-
-bool Common(const std::string& n) { return n == "print-args" || n == "config" || n == "verbose"; }
-
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -191,8 +177,8 @@ int main(int argc, char** argv) {
               "Options: --binary (true) --ivector-dim (400) --seed (0: the generator of the projections; not an upstream option)\n"
               "Limits: i-vector dimension <= 1024, feature dimension <= 96.  Not built (refused): --use-weights=true.\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "binary") binary = xv::ToBool(n, val);
       else if (n == "ivector-dim") ivector_dim = xv::ToInt(n, val);
       else if (n == "seed") seed = (uint64_t)(int64_t)xv::ToInt(n, val);
@@ -210,8 +196,8 @@ int main(int argc, char** argv) {
               "Usage: ivector-extractor-sum-accs [options] <stats-in1> <stats-in2> ... <stats-inN> <stats-out>\n"
               "Options: --binary (true) --parallel (accepted; the inputs are read one after another either way)\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "binary") binary = xv::ToBool(n, val);
       else if (n == "parallel") (void)xv::ToBool(n, val);
       else return xv::OptionResult::kUnknown;
@@ -226,12 +212,12 @@ int main(int argc, char** argv) {
               "Usage: ivector-extractor-est [options] <model-in> <stats-in> <model-out>\n"
               "Options: --binary (true) --num-threads (1) --variance-floor-factor (0.1) --gaussian-min-count (100) --diagonalize (true)\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "binary") binary = xv::ToBool(n, val);
       else if (n == "num-threads") o.num_threads = xv::ToInt(n, val);
-      else if (n == "variance-floor-factor") o.variance_floor_factor = ToDouble(n, val);
-      else if (n == "gaussian-min-count") o.gaussian_min_count = ToDouble(n, val);
+      else if (n == "variance-floor-factor") o.variance_floor_factor = xv::ToDouble(n, val);
+      else if (n == "gaussian-min-count") o.gaussian_min_count = xv::ToDouble(n, val);
       else if (n == "diagonalize") o.diagonalize = xv::ToBool(n, val);
       else return xv::OptionResult::kUnknown;
       return xv::OptionResult::kOk;
@@ -246,7 +232,7 @@ int main(int argc, char** argv) {
             "--num-samples-for-weights and --cache-size are accepted and ignored.\n"
             "Limits: i-vector dimension <= 1024, feature dimension <= 96.\n";
   t.set = [&](const std::string& name, const std::string& val) {
-    const std::string n = Dashes(name);
+    const std::string n = xv::Dashes(name);
     if (n == "print-args" || n == "config" || n == "num-threads" || n == "num-samples-for-weights" || n == "cache-size") return xv::OptionResult::kOk;
     if (n == "verbose") o.verbose = xv::ToInt(n, val);
     else if (n == "binary") o.binary = xv::ToBool(n, val);

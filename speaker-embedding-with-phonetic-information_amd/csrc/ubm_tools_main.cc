@@ -329,14 +329,6 @@ int CopyGselect(int n, const std::vector<std::string>& pos) {
   return num_done != 0 ? 0 : 1;
 }
 
-std::string Dashes(std::string n) {
-  for (char& c : n)
-    if (c == '_') c = '-';
-  return n;
-}
-
-bool Common(const std::string& n) { return n == "verbose" || n == "print-args" || n == "config"; }
-
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -349,8 +341,8 @@ int main(int argc, char** argv) {
               "Usage: add-deltas [options] <feats-rspecifier> <feats-wspecifier>\n"
               "Options: --delta-order (2) --delta-window (2) --truncate (0) --device=<gpu>\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "delta-order") o.order = xv::ToInt(n, val);
       else if (n == "delta-window") o.window = xv::ToInt(n, val);
       else if (n == "truncate") o.truncate = xv::ToInt(n, val);
@@ -367,8 +359,8 @@ int main(int argc, char** argv) {
               "Usage: fgmm-global-to-gmm [options] <full-gmm-in> <diag-gmm-out>\n"
               "Options: --binary (true)\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "binary") binary = xv::ToBool(n, val);
       else return xv::OptionResult::kUnknown;
       return xv::OptionResult::kOk;
@@ -382,8 +374,8 @@ int main(int argc, char** argv) {
     t.usage = full ? "Copy a full-covariance GMM.\nUsage: fgmm-global-copy [options] <model-in> <model-out>\nOptions: --binary (true)\n"
                    : "Copy a diagonal-covariance GMM.\nUsage: gmm-global-copy [options] <model-in> <model-out>\nOptions: --binary (true)\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "binary") binary = xv::ToBool(n, val);
       else return xv::OptionResult::kUnknown;
       return xv::OptionResult::kOk;
@@ -396,8 +388,8 @@ int main(int argc, char** argv) {
     t.usage = "Copy Gaussian indices for pruning, possibly making the lists shorter.\n"
               "Usage: copy-gselect [options] <gselect-rspecifier> <gselect-wspecifier>\nOptions: --n (-1)\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string nm = Dashes(name);
-      if (Common(nm)) return xv::OptionResult::kOk;
+      const std::string nm = xv::Dashes(name);
+      if (xv::CommonOption(nm)) return xv::OptionResult::kOk;
       if (nm == "n") n = xv::ToInt(nm, val);
       else return xv::OptionResult::kUnknown;
       return xv::OptionResult::kOk;
@@ -413,8 +405,8 @@ int main(int argc, char** argv) {
               "Usage: fgmm-global-gselect-to-post [options] <full-gmm-in> <feats-rspecifier> <gselect-rspecifier> <post-wspecifier>\n"
               "Options: --min-post (0.0) --device=<gpu>\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "min-post") min_post = xv::ToFloat(n, val);
       else if (n == "device") device = xv::ToInt(n, val);
       else return xv::OptionResult::kUnknown;
@@ -431,8 +423,8 @@ int main(int argc, char** argv) {
               "Options: --n (50; at most 64) --device=<gpu>\n"
               "Not built (refused): --write-likes, --gselect.\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "n") n_opt = xv::ToInt(n, val);
       else if (n == "device") device = xv::ToInt(n, val);
       else if (n == "write-likes") throw xv::KioError("--write-likes is not built: no script of the recipes passes it");
@@ -446,7 +438,7 @@ int main(int argc, char** argv) {
   t.usage = "Scale all the posteriors of a table, by one scale or by a scale per utterance.\n"
             "Usage: scale-post <post-rspecifier> (<scale-rspecifier>|<scale>) <post-wspecifier>\n";
   t.set = [&](const std::string& name, const std::string& val) {
-    return Common(Dashes(name)) ? xv::OptionResult::kOk : xv::OptionResult::kUnknown;
+    return xv::CommonOption(xv::Dashes(name)) ? xv::OptionResult::kOk : xv::OptionResult::kUnknown;
   };
   t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : ScalePost(pos); };
   return xv::CliMain(argc, argv, t);

@@ -69,37 +69,21 @@
 #include <string>
 #include <vector>
 
+#include "gmm_train.h"
 #include "kio.h"
 #include "ubm.h"
 
 namespace xv {
 
-// "mvw" in any order -> the bits of ubm_train_kernels.h (m = 1, v = 2, w = 4), not augmented; KioError for any other letter.
-int ParseGmmFlags(const std::string& letters);
-int AugmentGmmFlags(int flags);   // v implies m, m implies w
-
-// ---- the accumulators on the host
-struct FgmmAccs {
-  int num_gauss = 0, dim = 0, flags = 0;   // flags: augmented
-  std::vector<double> occ, mean, cov;      // [G], [G][D], [G][D (D + 1) / 2]; mean / cov are all zeros without m / v
-  void Init(int num_gauss, int dim, int flags);
-};
-// add = false: *a becomes the file's.  add = true: the file's values are added to *a, whose shape and flags must be the file's.
-void ReadFgmmAccs(Input& in, bool binary, bool add, FgmmAccs* a);
-void ReadFgmmAccsFile(const std::string& rxfilename, bool add, FgmmAccs* a);
-void WriteFgmmAccsFile(const std::string& wxfilename, bool binary, const FgmmAccs& a);
+// The update flags, the accumulators on the host (FgmmAccs: `second` holds the packed lower triangles cov [G][D (D + 1) / 2]) and
+// their file: gmm_train.h.
 
 // ---- the M-step (host, fp64)
 struct FgmmEstOptions {
   double min_gaussian_weight = 1e-5, min_gaussian_occupancy = 100.0, variance_floor = 0.001, max_condition = 1e5;
   bool remove_low_count_gaussians = true;
 };
-struct FgmmEstResult {
-  double objf_before = 0.0, objf_after = 0.0, count = 0.0;   // count: sum of occ
-  int floored_elements = 0, floored_gauss = 0;
-  std::vector<int32_t> removed;                                // ascending
-  std::vector<std::string> warnings;
-};
+using FgmmEstResult = GmmEstResult;
 // Updates *model in place (num_gauss shrinks by removed.size()).  KioError: shapes that do not agree, update flags the
 // accumulators do not have, a covariance that cannot be inverted.
 void FgmmEst(const FgmmAccs& accs, int update_flags, const FgmmEstOptions& opts, FullGmmData* model, FgmmEstResult* res);

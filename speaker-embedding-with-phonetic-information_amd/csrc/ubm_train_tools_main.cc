@@ -17,8 +17,7 @@
 #include <vector>
 
 #include "cli.h"
-#include "cmvn.h"
-#include "gselect_lookup.h"
+#include "gmm_acc_tool.h"
 #include "kio.h"
 #include "ubm.h"
 #include "ubm_kernels.h"
@@ -26,8 +25,6 @@
 #include "ubm_train_kernels.h"
 
 namespace {
-
-constexpr int64_t kBatchFrames = 1 << 16;   // frames read ahead; the accumulate calls do not depend on it
 
 int GmmToFgmm(bool binary, const std::vector<std::string>& pos) {
   xv::DiagGmmData diag;
@@ -93,13 +90,7 @@ int SubsampleFeats(int n, int offset, const std::vector<std::string>& pos) {
   return num_done != 0 ? 0 : 1;
 }
 
-struct AccOptions {
-  bool binary = true;
-  std::string update_flags = "mvw", gselect;
-  int device = -1, verbose = 0;
-};
-
-int AccStats(const AccOptions& o, const std::vector<std::string>& pos) {
+int AccStats(const xv::GmmAccOptions& o, const std::vector<std::string>& pos) {
   if (o.gselect.empty())
     throw xv::KioError("fgmm-global-acc-stats without --gselect is not built: every script of the recipes passes the Gaussian selection");
   const int flags = xv::ParseGmmFlags(o.update_flags);
@@ -108,99 +99,14 @@ int AccStats(const AccOptions& o, const std::vector<std::string>& pos) {
   const int dev = xv::PickDevice(o.device);
   std::unique_ptr<xv::FgmmAccumulator> acc(xv::FgmmAccCreate(dev, gmm.num_gauss, gmm.dim, flags));
   std::unique_ptr<xv::UbmModel> model(xv::UbmFullCreate(dev, gmm.num_gauss, gmm.dim, gmm.gconsts.data(), gmm.means_invcovars.data(), gmm.inv_covars.data()));
-  xv::FeatBatchReader reader(pos[1], kBatchFrames, false);
-  xv::GselectLookup gselect(o.gselect);
-  long num_done = 0, num_err = 0;
-  double tot_like = 0.0;
-  int64_t tot_t = 0;
-  // the stream of accepted frames, cut into blocks of exactly kFgmmAccFrameBlock: what is pending is less than one block
-  std::vector<float> feats, logsum;
-  std::vector<int32_t> gs;
-  int n = 0;
-  const int D = gmm.dim;
-  size_t head = 0;   // frames at the front of the pending buffers that have been through the device
-  auto accumulate = [&](size_t rows) {   // the next `rows` pending frames
-    logsum.resize(rows);
-    xv::FgmmAccAddGselect(acc.get(), *model, feats.data() + head * D, (int64_t)rows, gs.data() + head * n, n, logsum.data());
-    for (size_t t = 0; t < rows; ++t) tot_like += logsum[t];
-    tot_t += (int64_t)rows;
-    head += rows;
-  };
-  xv::FeatBatchReader::Batch b;
-  std::vector<xv::FeatBatchReader::Problem> problems;
-  for (bool more = true; more;) {
-    problems.clear();
-    more = reader.Next(&b, &problems);
-    for (const auto& p : problems) {
-      if (p.what.empty()) {
-        XWARN("Empty feature matrix for utterance " << p.key);   // no frames: skipped, not an error
-      } else {
-        XWARN("Failed to read features for key " << p.key << ": " << p.what);
-        ++num_err;
-      }
-    }
-    if (!more) break;
-    for (size_t u = 0; u < b.keys.size(); ++u) {
-      const int rows = b.row_off[u + 1] - b.row_off[u];
-      if (b.cols != D) {
-        XWARN("Dimension mismatch for utterance " << b.keys[u] << ": the features have " << b.cols << " columns, the model " << D);
-        ++num_err;
-        continue;
-      }
-      xv::IntVecVec sel;
-      if (!gselect.Find(b.keys[u], &sel)) {
-        XWARN("No gselect information for utterance " << b.keys[u]);
-        ++num_err;
-        continue;
-      }
-      if ((int)sel.size() != rows) {
-        XWARN("gselect information for utterance " << b.keys[u] << " has wrong size " << sel.size() << " vs. " << rows);
-        ++num_err;
-        continue;
-      }
-      const size_t width = sel[0].size();
-      bool same = width >= 1;
-      for (const auto& l : sel) same = same && l.size() == width;
-      if (!same || (n != 0 && (int)width != n)) {
-        XWARN("The Gaussian selection of utterance " << b.keys[u] << " does not have " << (n ? "the " + std::to_string(n) + " indices per frame of the utterances before it" : "one length for every frame")
-                                                    << " (skipping utterance)");
-        ++num_err;
-        continue;
-      }
-      if (width > (size_t)xv::kUbmMaxSelect)
-        throw xv::KioError("the Gaussian selection has " + std::to_string(width) + " indices per frame; the device kernels take at most " + std::to_string(xv::kUbmMaxSelect));
-      n = (int)width;
-      feats.insert(feats.end(), b.feats.begin() + (size_t)b.row_off[u] * D, b.feats.begin() + (size_t)b.row_off[u + 1] * D);
-      for (const auto& l : sel) gs.insert(gs.end(), l.begin(), l.end());
-      while (feats.size() / D - head >= (size_t)xv::kFgmmAccFrameBlock) accumulate((size_t)xv::kFgmmAccFrameBlock);
-      if (head) {   // drop what was consumed, once per utterance that filled a block
-        feats.erase(feats.begin(), feats.begin() + head * D);
-        gs.erase(gs.begin(), gs.begin() + head * n);
-        head = 0;
-      }
-      ++num_done;
-      if (o.verbose >= 1 && num_done % 10 == 0)   // over the frames that have been through the device: whole blocks
-        XLOG("Avg like per frame so far is " << (tot_t ? tot_like / (double)tot_t : 0.0));
-    }
-  }
-  if (!feats.empty()) accumulate(feats.size() / D);
-  XLOG("Done " << num_done << " files; " << num_err << " with errors.");
-  XLOG("Overall likelihood per frame = " << (tot_t ? tot_like / (double)tot_t : 0.0) << " over " << tot_t << " (weighted) frames.");
   xv::FgmmAccs host;
   host.Init(gmm.num_gauss, gmm.dim, flags);
-  xv::FgmmAccGet(*acc, host.occ.data(), host.mean.data(), host.cov.data());
-  xv::WriteFgmmAccsFile(pos[2], o.binary, host);
-  XLOG("Written accs to " << pos[2]);
-  return num_done != 0 ? 0 : 1;
-}
-
-int SumAccs(bool binary, const std::vector<std::string>& pos) {
-  xv::FgmmAccs sum;
-  for (size_t i = 1; i < pos.size(); ++i) xv::ReadFgmmAccsFile(pos[i], i > 1, &sum);
-  xv::WriteFgmmAccsFile(pos[0], binary, sum);
-  XLOG("Summed " << pos.size() - 1 << " stats");
-  XLOG("Written stats to " << pos[0]);
-  return 0;
+  return xv::GmmAccStats(
+      o, pos, &host, xv::kFgmmAccFrameBlock,
+      [&](const float* feats, int64_t rows, const int32_t* gselect, int n, float* logsum) {
+        xv::FgmmAccAddGselect(acc.get(), *model, feats, rows, gselect, n, logsum);
+      },
+      [&] { xv::FgmmAccGet(*acc, host.occ.data(), host.mean.data(), host.second.data()); });
 }
 
 struct EstOptions {
@@ -214,7 +120,7 @@ int Est(const EstOptions& o, const std::vector<std::string>& pos) {
   xv::FullGmmData gmm;
   xv::ReadFullGmmFile(pos[0], &gmm);
   xv::FgmmAccs accs;
-  xv::ReadFgmmAccsFile(pos[1], false, &accs);
+  xv::ReadGmmAccsFile(pos[1], false, &accs);
   xv::FgmmEstResult r;
   xv::FgmmEst(accs, flags, o.est, &gmm, &r);
   for (const std::string& w : r.warnings) XWARN(w);
@@ -223,20 +129,6 @@ int Est(const EstOptions& o, const std::vector<std::string>& pos) {
   xv::WriteFullGmmFile(pos[2], o.binary, gmm);
   XLOG("Written model to " << pos[2]);
   return 0;
-}
-
-std::string Dashes(std::string n) {
-  for (char& c : n)
-    if (c == '_') c = '-';
-  return n;
-}
-
-bool Common(const std::string& n) { return n == "verbose" || n == "print-args" || n == "config"; }
-
-double ToDouble(const std::string& name, const std::string& v) {
-  double d = 0.0;
-  if (!xv::ParseDouble(v, &d)) throw xv::KioError("Invalid floating-point option --" + name + "=" + v);
-  return d;
 }
 
 }  // namespace
@@ -251,8 +143,8 @@ int main(int argc, char** argv) {
               "Usage: gmm-global-to-fgmm [options] <diag-gmm-in> <full-gmm-out>\n"
               "Options: --binary (true)\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "binary") binary = xv::ToBool(n, val);
       else return xv::OptionResult::kUnknown;
       return xv::OptionResult::kOk;
@@ -267,8 +159,8 @@ int main(int argc, char** argv) {
               "Usage: subsample-feats [options] <in-rspecifier> <out-wspecifier>\n"
               "Options: --n (1) --offset (0; must be 0 with a negative --n)\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string nm = Dashes(name);
-      if (Common(nm)) return xv::OptionResult::kOk;
+      const std::string nm = xv::Dashes(name);
+      if (xv::CommonOption(nm)) return xv::OptionResult::kOk;
       if (nm == "n") n = xv::ToInt(nm, val);
       else if (nm == "offset") offset = xv::ToInt(nm, val);
       else return xv::OptionResult::kUnknown;
@@ -283,13 +175,13 @@ int main(int argc, char** argv) {
               "Usage: fgmm-global-sum-accs [options] <stats-out> <stats-in1> <stats-in2> ...\n"
               "Options: --binary (true)\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "binary") binary = xv::ToBool(n, val);
       else return xv::OptionResult::kUnknown;
       return xv::OptionResult::kOk;
     };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() < 2 ? xv::kUsageError : SumAccs(binary, pos); };
+    t.run = [&](const std::vector<std::string>& pos) { return pos.size() < 2 ? xv::kUsageError : xv::GmmSumAccs(true, binary, pos); };
     return xv::CliMain(argc, argv, t);
   }
   if (prog == "fgmm-global-est") {
@@ -300,14 +192,14 @@ int main(int argc, char** argv) {
               "         --variance-floor (0.001) --max-condition (1e5) --remove-low-count-gaussians (true)\n"
               "Not built (refused): --mix-up other than 0.\n";
     t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = Dashes(name);
-      if (Common(n)) return xv::OptionResult::kOk;
+      const std::string n = xv::Dashes(name);
+      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
       if (n == "binary") o.binary = xv::ToBool(n, val);
       else if (n == "update-flags") o.update_flags = val;
-      else if (n == "min-gaussian-weight") o.est.min_gaussian_weight = ToDouble(n, val);
-      else if (n == "min-gaussian-occupancy") o.est.min_gaussian_occupancy = ToDouble(n, val);
-      else if (n == "variance-floor") o.est.variance_floor = ToDouble(n, val);
-      else if (n == "max-condition") o.est.max_condition = ToDouble(n, val);
+      else if (n == "min-gaussian-weight") o.est.min_gaussian_weight = xv::ToDouble(n, val);
+      else if (n == "min-gaussian-occupancy") o.est.min_gaussian_occupancy = xv::ToDouble(n, val);
+      else if (n == "variance-floor") o.est.variance_floor = xv::ToDouble(n, val);
+      else if (n == "max-condition") o.est.max_condition = xv::ToDouble(n, val);
       else if (n == "remove-low-count-gaussians") o.est.remove_low_count_gaussians = xv::ToBool(n, val);
       else if (n == "mix-up") {
         if (xv::ToInt(n, val) != 0) throw xv::KioError("--mix-up is not built: no script of the recipes increases the number of Gaussians here");
@@ -321,22 +213,15 @@ int main(int argc, char** argv) {
     fprintf(stderr, "%s: not one of fgmm-global-acc-stats, gmm-global-to-fgmm, subsample-feats, fgmm-global-sum-accs, fgmm-global-est\n", prog.c_str());
     return 255;
   }
-  AccOptions o;
+  xv::GmmAccOptions o;
   t.usage = "Accumulate stats for training a full-covariance GMM.\n"
             "Usage: fgmm-global-acc-stats [options] --gselect=<gselect-rspecifier> <model-in> <feature-rspecifier> <stats-out>\n"
             "Options: --binary (true) --update-flags (mvw) --gselect (required) --verbose --device=<gpu>\n"
             "Not built (refused): running without --gselect, --weights.\n";
   t.set = [&](const std::string& name, const std::string& val) {
-    const std::string n = Dashes(name);
-    if (n == "verbose") o.verbose = xv::ToInt(n, val);
-    else if (Common(n)) return xv::OptionResult::kOk;
-    else if (n == "binary") o.binary = xv::ToBool(n, val);
-    else if (n == "update-flags") o.update_flags = val;
-    else if (n == "gselect") o.gselect = val;
-    else if (n == "device") o.device = xv::ToInt(n, val);
-    else if (n == "weights") throw xv::KioError("--weights is not built: no script of the recipes passes per-frame weights");
-    else return xv::OptionResult::kUnknown;
-    return xv::OptionResult::kOk;
+    const std::string n = xv::Dashes(name);
+    if (n == "weights") throw xv::KioError("--weights is not built: no script of the recipes passes per-frame weights");
+    return xv::SetGmmAccOption(n, val, &o);
   };
   t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : AccStats(o, pos); };
   return xv::CliMain(argc, argv, t);

@@ -11,6 +11,7 @@ import pytest
 import dubm_train_ref as T
 import helpers as H
 import ubm_ref as R
+import ubm_train_ref as FT
 from oracle import kaldi_io as kio
 
 BIN = os.path.join(H.ROOT, H.PKG_NAME, "bin")
@@ -92,6 +93,22 @@ def test_sum_accs_refuses_what_does_not_agree(tmp_path):
     data = handmade_accs(*random_accs(1), 7)
     r = run(["gmm-global-sum-accs", "-", "-"], stdin=data.replace(b"<DIAGVARACCS>", b"<FULLVARACCS>"))
     assert r.returncode == 255 and b"expected token <DIAGVARACCS>, got <FULLVARACCS>" in r.stderr
+
+
+def test_sum_accs_takes_a_full_covariance_file_only_without_variances(tmp_path):
+    """the mirror of test_ubm_train_host's: <FULLVARACCS> is refused by name; a file with flags 5 has no such section, and both
+    tools sum two of them to the same bytes"""
+    (occ, mean, _), (occ2, mean2, _) = random_accs(1), random_accs(2)
+    cov = np.random.default_rng(4).normal(0, 900, size=(3, FT.tri(4))).astype(F)
+    r = run(["gmm-global-sum-accs", "-", "-"], stdin=FT.accs_bytes(occ, mean, cov, 7, True))
+    assert r.returncode == 255 and b"expected token <DIAGVARACCS>, got <FULLVARACCS>" in r.stderr and r.stdout == b""
+    a, b = str(tmp_path / "a.acc"), str(tmp_path / "b.acc")
+    open(a, "wb").write(FT.accs_bytes(occ, mean, np.zeros_like(cov), 5, True))
+    open(b, "wb").write(FT.accs_bytes(occ2, mean2, np.zeros_like(cov), 5, True))
+    diag, full = run(["gmm-global-sum-accs", "-", a, b]), run(["fgmm-global-sum-accs", "-", a, b])
+    assert diag.returncode == 0 and full.returncode == 0, (diag.stderr, full.stderr)
+    want = [(np.asarray(x, np.float64) + y).astype(F) for x, y in ((occ, occ2), (mean, mean2))]
+    assert diag.stdout == full.stdout == T.accs_bytes(*want, np.zeros_like(mean), 5, True)
 
 
 # ------------------------------------------------------------------------------------------------------------- gmm-global-est

@@ -10,6 +10,7 @@ import pytest
 
 import helpers as H
 import ubm_ref as R
+import dubm_train_ref as DT
 import ubm_train_ref as T
 from oracle import kaldi_io as kio
 
@@ -172,6 +173,22 @@ def test_sum_accs_refuses_what_does_not_agree(tmp_path):
     assert r.returncode == 255
     r = run(["fgmm-global-sum-accs", "-", "-"], stdin=data.replace(b"<MEANACCS>", b"<MEANACCZ>"))
     assert r.returncode == 255 and b"expected token <MEANACCS>, got <MEANACCZ>" in r.stderr
+
+
+def test_sum_accs_takes_a_diagonal_file_only_without_variances(tmp_path):
+    """the two kinds of file differ in the section that v adds: with it the other kind's token is refused by name; without it the
+    files are the same, and both tools sum them to the same bytes"""
+    (occ, mean, _), (occ2, mean2, _) = random_accs(1), random_accs(2)
+    var = np.random.default_rng(4).uniform(1, 900, size=mean.shape).astype(F)
+    r = run(["fgmm-global-sum-accs", "-", "-"], stdin=DT.accs_bytes(occ, mean, var, 7, True))
+    assert r.returncode == 255 and b"expected token <FULLVARACCS>, got <DIAGVARACCS>" in r.stderr and r.stdout == b""
+    a, b = str(tmp_path / "a.acc"), str(tmp_path / "b.acc")
+    open(a, "wb").write(DT.accs_bytes(occ, mean, np.zeros_like(var), 5, True))
+    open(b, "wb").write(DT.accs_bytes(occ2, mean2, np.zeros_like(var), 5, True))
+    full, diag = run(["fgmm-global-sum-accs", "-", a, b]), run(["gmm-global-sum-accs", "-", a, b])
+    assert full.returncode == 0 and diag.returncode == 0, (full.stderr, diag.stderr)
+    want = [(np.asarray(x, np.float64) + y).astype(F) for x, y in ((occ, occ2), (mean, mean2))]
+    assert full.stdout == diag.stdout == T.accs_bytes(*want, np.zeros((3, T.tri(4)), F), 5, True)
 
 
 # ------------------------------------------------------------------------------------------------------------- fgmm-global-est
