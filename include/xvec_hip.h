@@ -610,6 +610,32 @@ xv_status xv_fgmm_est(int32_t num_gauss, int32_t dim, const char* acc_flags, con
 xv_status xv_fgmm_acc_kernel_time(xv_fgmm_acc* a, const xv_ubm* full, const float* feats, int32_t rows, const int32_t* gselect, int32_t n,
                                   int32_t reps, float* ms4);
 
+/* ---- the phonetic i-vector path (logprob-to-post, fgmm-global-init-from-accs; sid/extract_post_nnet3.sh:85-91,
+ * sid/init_full_ubm_from_nnet3.sh:118-136), without a model context.  Semantics: csrc/post.h. */
+/* host buffers, blocking: logprobs [row_off[n_utts]][cols] packed, utterance by utterance (row_off[0] = 0); keys [n_utts] are the
+ * utterance keys that key the random pruning (may be NULL with random_prune == 0 or min_post <= 0).  frame_budget: rows per launch,
+ * <= 0 for the default; the result does not depend on it.  pair_off [rows + 1] is always written: row r has the pairs
+ * pair_off[r] .. pair_off[r + 1], columns ascending.  *need is their number; idx and post (room for `capacity` pairs each, may be
+ * NULL with capacity 0) are written only if *need <= capacity: otherwise call again with that much room.  num_nan (may be NULL):
+ * the NaN inputs that were dropped.  device_ms3 (may be NULL): the times of the count, the scan and the write kernels. */
+xv_status xv_logprob_to_post(int device, const float* logprobs, const int32_t* row_off, int32_t n_utts, int32_t cols, const char* const* keys,
+                             float min_post, int32_t random_prune, int32_t frame_budget, int64_t capacity, int64_t* pair_off, int32_t* idx,
+                             float* post, int64_t* need, int64_t* num_nan, float* device_ms3);
+/* the kernels' times in ms of one utterance of rows x cols, the best of reps runs after one that warms up: ms4 = {count, scan, write,
+ * a device-to-device copy of the input}.  The copy reads and writes the input once: its time is what two reads of the input cost at
+ * the copy bandwidth of the same run, the floor of the count and write passes together. */
+xv_status xv_logprob_to_post_kernel_time(int device, const float* logprobs, int32_t rows, int32_t cols, const char* key, float min_post,
+                                         int32_t random_prune, int32_t reps, float* ms4);
+/* host only (fp64): a full-covariance model from accumulators that carry m, v and w: occ [G], mean [G][D], cov [G][D (D + 1) / 2].
+ * weights_out [G], means_invcovars_out [G][D], inv_covars_out [G][D (D + 1) / 2] and gconsts_out [G] get the Gaussians that
+ * survive, at the front; *num_gauss_out how many.  removed [G] (may be NULL): the first G - *num_gauss_out entries are the indices
+ * taken out.  With remove_low_count_gaussians == 0 a bad Gaussian is XV_ERR_IO and names it.  num_bad_gconsts may be NULL.
+ * inv_covars_f64 (may be NULL): [G][D (D + 1) / 2], the inverse covariance of every Gaussian as given (none moved; zeros for one
+ * taken out) before it is rounded to float. */
+xv_status xv_fgmm_init_from_accs(int32_t num_gauss, int32_t dim, const double* occ, const double* mean, const double* cov,
+                                 int32_t remove_low_count_gaussians, float* weights_out, float* means_invcovars_out, float* inv_covars_out,
+                                 float* gconsts_out, int32_t* num_gauss_out, int32_t* removed, int32_t* num_bad_gconsts, double* inv_covars_f64);
+
 /* ---- diagonal UBM training (gmm-global-init-from-feats, gmm-global-acc-stats, gmm-global-est; sid/train_diag_ubm.sh:105-137), without
  * a model context.  Semantics: csrc/dubm_train.h.  The accumulators are fp64 on the device; no floating-point value goes through an
  * atomic, and what a call adds is a function of the call's frames, pairs and model alone.  A (frame, Gaussian) score is bit for bit

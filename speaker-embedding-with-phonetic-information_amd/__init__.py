@@ -141,6 +141,7 @@ ABI_SYMBOLS = [
     "xv_fgmm_to_gmm", "xv_fgmm_gconsts", "xv_ubm_kernel_time",
     "xv_fgmm_acc_create", "xv_fgmm_acc_destroy", "xv_fgmm_acc_add", "xv_fgmm_acc_add_gselect", "xv_fgmm_acc_get", "xv_fgmm_est",
     "xv_fgmm_acc_kernel_time",
+    "xv_logprob_to_post", "xv_logprob_to_post_kernel_time", "xv_fgmm_init_from_accs",
     "xv_dgmm_acc_create", "xv_dgmm_acc_destroy", "xv_dgmm_acc_add", "xv_dgmm_acc_add_gselect", "xv_dgmm_acc_add_dense_post",
     "xv_dgmm_acc_add_dense", "xv_dgmm_acc_get", "xv_dgmm_est", "xv_dgmm_acc_kernel_time",
     "xv_ivex_create", "xv_ivex_load", "xv_ivex_destroy", "xv_ivex_info", "xv_ivex_derived", "xv_ivex_extract", "xv_ivex_read",
@@ -1429,6 +1430,82 @@ def fgmm_est(weights, means_invcovars, inv_covars, occ, mean, cov, acc_flags="mv
     return dict(weights=w[:k].copy(), means_invcovars=b[:k].copy(), inv_covars=ic[:k].copy(), gconsts=gc[:k].copy(),
                 removed=removed[:g - k].tolist(), floored=(int(floored[0]), int(floored[1])), objf_before=float(objf[0]),
                 objf_after=float(objf[1]), count=float(objf[2]))
+
+
+def logprob_to_post(logprobs_list, keys, min_post=0.01, random_prune=True, frame_budget=0, device=0, return_details=False):
+    """logprob-to-post on the device (xv_logprob_to_post): per utterance a list (one entry per row) of (int32 columns, float32
+    weights), columns ascending.  keys: the utterance keys, which key the random pruning.  frame_budget: rows per launch (0: the
+    default); the result does not depend on it.  return_details: also dict(num_nan, ms=(count, scan, write))."""
+    import numpy as np
+    L = lib()
+    packed, off, cols = _pack_matrices(logprobs_list, "logprob_to_post")
+    nu, rows = len(off) - 1, packed.shape[0]
+    if len(keys) != nu:
+        raise XvError(XV_ERR_ARG, "logprob_to_post: one key per matrix")
+    if rows == 0:
+        out = [[] for _ in range(nu)]
+        return (out, dict(num_nan=0, ms=(0.0, 0.0, 0.0))) if return_details else out
+    ckeys = (ctypes.c_char_p * max(nu, 1))(*[k.encode() for k in keys])
+    pair_off = np.zeros(rows + 1, dtype=np.int64)
+    need, num_nan = ctypes.c_int64(0), ctypes.c_int64(0)
+    ms = (ctypes.c_float * 3)()
+    L.xv_logprob_to_post.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_float,
+                                     ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]
+    capacity = min(rows * cols, max(1 << 16, rows * 64))
+    while True:
+        idx = np.zeros(capacity, dtype=np.int32)
+        w = np.zeros(capacity, dtype=np.float32)
+        _check(L.xv_logprob_to_post(device, packed.ctypes.data, off.ctypes.data, nu, cols, ckeys, float(min_post), int(bool(random_prune)),
+                                    int(frame_budget), capacity, pair_off.ctypes.data, idx.ctypes.data, w.ctypes.data, ctypes.byref(need),
+                                    ctypes.byref(num_nan), ms))
+        if need.value <= capacity:
+            break
+        capacity = need.value
+    out = [[(idx[pair_off[t]:pair_off[t + 1]].copy(), w[pair_off[t]:pair_off[t + 1]].copy()) for t in range(off[u], off[u + 1])] for u in range(nu)]
+    return (out, dict(num_nan=int(num_nan.value), ms=tuple(float(v) for v in ms))) if return_details else out
+
+
+def logprob_to_post_kernel_time(logprobs, key="utt", min_post=0.01, random_prune=True, reps=5, device=0):
+    """{count, scan, write, copy} times in ms of one rows x cols matrix in one launch (xv_logprob_to_post_kernel_time: the best of
+    reps).  copy: a device-to-device copy of the input, which is what two reads of it cost at the copy bandwidth of this run."""
+    import numpy as np
+    L = lib()
+    x = np.ascontiguousarray(logprobs, dtype=np.float32)
+    if x.ndim != 2:
+        raise XvError(XV_ERR_ARG, "logprob_to_post_kernel_time: a [rows, cols] matrix")
+    ms = (ctypes.c_float * 4)()
+    L.xv_logprob_to_post_kernel_time.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.c_float,
+                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
+    _check(L.xv_logprob_to_post_kernel_time(device, x.ctypes.data, x.shape[0], x.shape[1], key.encode(), float(min_post), int(bool(random_prune)), reps, ms))
+    return dict(zip(("count", "scan", "write", "copy"), [float(v) for v in ms]))
+
+
+def fgmm_init_from_accs(occ, mean, cov, remove_low_count_gaussians=True):
+    """fgmm-global-init-from-accs on host arrays (xv_fgmm_init_from_accs, fp64): dict(weights, means_invcovars, inv_covars, gconsts) of
+    the Gaussians that survive, removed (indices), bad_gconsts, and inv_covars_f64: the survivors' inverse covariances before they are
+    rounded to float32."""
+    import numpy as np
+    L = lib()
+    o = np.ascontiguousarray(occ, dtype=np.float64)
+    m = np.ascontiguousarray(mean, dtype=np.float64)
+    c = np.ascontiguousarray(cov, dtype=np.float64)
+    if m.ndim != 2 or o.shape != (m.shape[0],) or c.shape != (m.shape[0], m.shape[1] * (m.shape[1] + 1) // 2):
+        raise XvError(XV_ERR_ARG, "fgmm_init_from_accs: occ [G], mean [G][D], cov [G][D (D + 1) / 2]")
+    g, d = m.shape
+    w, b, ic, gc = np.zeros(g, np.float32), np.zeros((g, d), np.float32), np.zeros(c.shape, np.float32), np.zeros(g, np.float32)
+    removed = np.zeros(g, np.int32)
+    ic64 = np.zeros(c.shape, np.float64)
+    left, bad = ctypes.c_int32(), ctypes.c_int32()
+    L.xv_fgmm_init_from_accs.argtypes = ([ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 3 + [ctypes.c_int32] + [ctypes.c_void_p] * 4
+                                         + [ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p])
+    _check(L.xv_fgmm_init_from_accs(g, d, o.ctypes.data, m.ctypes.data, c.ctypes.data, int(bool(remove_low_count_gaussians)), w.ctypes.data,
+                                    b.ctypes.data, ic.ctypes.data, gc.ctypes.data, ctypes.byref(left), removed.ctypes.data, ctypes.byref(bad),
+                                    ic64.ctypes.data))
+    k = left.value
+    gone = removed[:g - k].tolist()
+    return dict(weights=w[:k].copy(), means_invcovars=b[:k].copy(), inv_covars=ic[:k].copy(), gconsts=gc[:k].copy(), removed=gone,
+                bad_gconsts=int(bad.value), inv_covars_f64=np.delete(ic64, gone, axis=0))
 
 
 class DgmmAccumulator:

@@ -25,6 +25,7 @@
 #include "nnet3_raw.h"
 #include "plda.h"
 #include "plda_kernels.h"
+#include "post.h"
 #include "program.h"
 #include "table_extract.h"
 #include "ivex.h"
@@ -1233,6 +1234,74 @@ xv_status xv_fgmm_acc_kernel_time(xv_fgmm_acc* a, const xv_ubm* full, const floa
       for (int i = 0; i < 4; ++i)
         if (r == 1 || (r > 1 && ms[i] < ms4[i])) ms4[i] = ms[i];
     }
+    return XV_OK;
+  });
+}
+
+xv_status xv_logprob_to_post(int device, const float* logprobs, const int32_t* row_off, int32_t n_utts, int32_t cols, const char* const* keys,
+                             float min_post, int32_t random_prune, int32_t frame_budget, int64_t capacity, int64_t* pair_off, int32_t* idx,
+                             float* post, int64_t* need, int64_t* num_nan, float* device_ms3) {
+  if (!row_off || n_utts < 0 || !pair_off || !need || capacity < 0 || (capacity > 0 && (!idx || !post)))
+    return Fail(XV_ERR_ARG, "xv_logprob_to_post: bad argument");
+  return Guard([&] {
+    std::vector<uint64_t> seeds;
+    if (keys)
+      for (int32_t u = 0; u < n_utts; ++u) {
+        if (!keys[u]) return Fail(XV_ERR_ARG, "xv_logprob_to_post: null key");
+        seeds.push_back(xv::UttSeed(keys[u]));
+      }
+    xv::LogprobPostResult r;
+    xv::LogprobToPost(device, logprobs, row_off, n_utts, cols, keys ? seeds.data() : nullptr, min_post, random_prune != 0, frame_budget,
+                      device_ms3 != nullptr, &r);
+    std::copy(r.off.begin(), r.off.end(), pair_off);
+    *need = r.off.back();
+    if (num_nan) *num_nan = r.num_nan;
+    if (device_ms3) std::copy(r.ms, r.ms + 3, device_ms3);
+    if (*need <= capacity) {
+      std::copy(r.idx.begin(), r.idx.end(), idx);
+      std::copy(r.w.begin(), r.w.end(), post);
+    }
+    return XV_OK;
+  });
+}
+
+xv_status xv_logprob_to_post_kernel_time(int device, const float* logprobs, int32_t rows, int32_t cols, const char* key, float min_post,
+                                         int32_t random_prune, int32_t reps, float* ms4) {
+  if (!logprobs || rows < 1 || cols < 1 || !key || reps < 1 || !ms4) return Fail(XV_ERR_ARG, "xv_logprob_to_post_kernel_time: bad argument");
+  if ((int64_t)rows * cols > INT32_MAX) return Fail(XV_ERR_ARG, "xv_logprob_to_post_kernel_time: rows * cols must fit one launch (below 2^31)");
+  return Guard([&] {
+    const int32_t row_off[2] = {0, rows};
+    const uint64_t seed = xv::UttSeed(key);
+    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
+      xv::LogprobPostResult res;
+      xv::LogprobToPost(device, logprobs, row_off, 1, cols, &seed, min_post, random_prune != 0, rows, true, &res);
+      for (int i = 0; i < 3; ++i)
+        if (r == 1 || (r > 1 && res.ms[i] < ms4[i])) ms4[i] = res.ms[i];
+    }
+    ms4[3] = xv::DeviceCopyMs(device, (size_t)rows * cols * 4, reps);
+    return XV_OK;
+  });
+}
+
+xv_status xv_fgmm_init_from_accs(int32_t num_gauss, int32_t dim, const double* occ, const double* mean, const double* cov,
+                                 int32_t remove_low_count_gaussians, float* weights_out, float* means_invcovars_out, float* inv_covars_out,
+                                 float* gconsts_out, int32_t* num_gauss_out, int32_t* removed, int32_t* num_bad_gconsts, double* inv_covars_f64) {
+  if (num_gauss < 1 || dim < 1 || !occ || !mean || !cov || !weights_out || !means_invcovars_out || !inv_covars_out || !gconsts_out || !num_gauss_out)
+    return Fail(XV_ERR_ARG, "xv_fgmm_init_from_accs: bad argument");
+  return Guard([&] {
+    xv::FgmmAccs accs;
+    FillGmmAccs("xv_fgmm_init_from_accs", "covariance", num_gauss, dim, "mvw", occ, mean, cov, &accs);
+    xv::FullGmmData m;
+    xv::FgmmInitResult r;
+    xv::FgmmInitFromAccs(accs, remove_low_count_gaussians != 0, &m, &r);
+    std::copy(m.weights.begin(), m.weights.end(), weights_out);
+    std::copy(m.means_invcovars.begin(), m.means_invcovars.end(), means_invcovars_out);
+    std::copy(m.inv_covars.begin(), m.inv_covars.end(), inv_covars_out);
+    std::copy(m.gconsts.begin(), m.gconsts.end(), gconsts_out);
+    *num_gauss_out = m.num_gauss;
+    if (removed) std::copy(r.removed.begin(), r.removed.end(), removed);
+    if (num_bad_gconsts) *num_bad_gconsts = r.bad_gconsts;
+    if (inv_covars_f64) std::copy(r.inv_covars64.begin(), r.inv_covars64.end(), inv_covars_f64);
     return XV_OK;
   });
 }

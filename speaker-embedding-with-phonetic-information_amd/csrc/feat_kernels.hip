@@ -6,6 +6,8 @@
 
 #include <float.h>
 
+#include "counter_rng.h"
+
 namespace xv {
 
 namespace {
@@ -35,19 +37,10 @@ __device__ inline int find_segment(const int32_t* off, int n, int r) {
   return lo;
 }
 
-// Counter-based generator for the dither: 64 bits from (utterance seed, frame, sample), murmur3's finaliser twice.
-__device__ inline uint64_t mix64(uint64_t x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdULL;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ULL;
-  x ^= x >> 33;
-  return x;
-}
+// The dither: 64 bits from (utterance seed, frame, sample) of the generator in counter_rng.h, through Box-Muller.
 __device__ inline float dither_gauss(uint64_t seed, int frame, int i) {
-  const uint64_t ctr = ((uint64_t)(uint32_t)frame << 32) | (uint32_t)i;
-  const uint64_t r = mix64(mix64(seed ^ 0x9e3779b97f4a7c15ULL) + ctr * 0x9e3779b97f4a7c15ULL);
-  const float u1 = ((float)(uint32_t)(r >> 40) + 1.0f) * (1.0f / 16777216.0f);   // (0, 1], 24 bits
+  const uint64_t r = counter_bits(seed, (uint32_t)frame, (uint32_t)i);
+  const float u1 = counter_unit_open0(r);                                         // (0, 1], 24 bits
   const float u2 = (float)(uint32_t)((r >> 8) & 0xffffff) * (1.0f / 16777216.0f); // [0, 1)
   return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
 }
