@@ -148,6 +148,142 @@ def llr(u, n, v, psi):
     return given - without
 
 
+# ------------------------------------------------------------------------------------------------ helpers of the kernel tests
+# (tests/test_gpu_backend_kernels.py and its CPU half tests/test_backend_kernels_ref.py): inputs on which every summation order
+# gives the same bits, and np.longdouble restatements whose own error is some 2^-11 of a float64 rounding.
+def ragged_lengths(rng, allowed, total=None, count=None):
+    """Segment lengths drawn from `allowed` (which holds 1 unless `count` is given): either lengths that sum to `total`, every
+    third one followed by an empty segment, or `count` lengths.  The first and the last segment are empty either way."""
+    allowed = sorted(set(int(a) for a in allowed))
+    if count is not None:
+        assert count >= 2
+        return [0] + [int(rng.choice(allowed)) for _ in range(count - 2)] + [0]
+    lengths, left = [], int(total)
+    while left > 0:
+        k = int(rng.choice([a for a in allowed if 0 < a <= left]))
+        lengths.append(k)
+        if len(lengths) % 3 == 0:
+            lengths.append(0)
+        left -= k
+    return [0] + lengths + [0]
+
+
+def segments_of_lengths(rng, lengths, n_table):
+    """Row lists of the given lengths into a table of n_table rows: random draws, so rows repeat within and across segments;
+    every segment of four rows or more is a descending run."""
+    segs = []
+    for k in lengths:
+        idx = rng.integers(0, n_table, k)
+        segs.append([int(i) for i in (np.sort(idx)[::-1] if k >= 4 else idx)])
+    return segs
+
+
+def integer_vectors(seed, n, dim, low=-8, high=8):
+    """float32 rows of integers in [low, high]"""
+    return np.random.default_rng(seed).integers(low, high + 1, (n, dim)).astype(np.float32)
+
+
+def scatter_stats_exact(x, segments):
+    """scatter_stats of integer rows and segments whose lengths are powers of two, in int64: (s_tot, sums, s_bet, largest) as
+    float64, every one exact.  s_bet is sum_s (n_max / n_s) s s^T in int64, divided by the power of two n_max at the end.
+    `largest` is the largest absolute partial sum that any order of any of the three sums can reach, in units of the smallest
+    term (1, or 1 / n_max for s_bet): below 2^53, float64 holds every partial sum of every order exactly."""
+    xi = np.asarray(x).astype(np.int64)
+    assert np.array_equal(xi, x)
+    dim = xi.shape[1]
+    idx = np.concatenate([np.asarray(s, np.int64) for s in segments]) if len(segments) else np.zeros(0, np.int64)
+    rows = xi[idx]
+    s_tot = rows.T @ rows
+    sums = np.stack([xi[np.asarray(s, np.int64)].sum(0) for s in segments]) if len(segments) else np.zeros((0, dim), np.int64)
+    abs_sums = np.stack([np.abs(xi[np.asarray(s, np.int64)]).sum(0) for s in segments]) if len(segments) \
+        else np.zeros((0, dim), np.int64)
+    n = np.array([len(s) for s in segments], np.int64)
+    nz = n > 0
+    assert np.all(n[nz] & (n[nz] - 1) == 0), "segment lengths must be powers of two"
+    n_max = int(n.max()) if nz.any() else 1
+    w = (n_max // n[nz])[:, None]
+    scaled = (sums[nz] * w).T @ sums[nz]
+    largest = max(int((np.abs(rows).T @ np.abs(rows)).max(initial=0)), int(abs_sums.max(initial=0)),
+                  int(((np.abs(sums[nz]) * w).T @ np.abs(sums[nz])).max(initial=0)))
+    return s_tot.astype(np.float64), sums.astype(np.float64), scaled.astype(np.float64) / n_max, largest
+
+
+def sequential_sums(x, segments):
+    """sums[s]: the rows of segment s added one at a time in list order, in float64"""
+    x = np.asarray(x, np.float32)
+    out = np.zeros((len(segments), x.shape[1]))
+    for s, seg in enumerate(segments):
+        for i in seg:
+            out[s] += x[i].astype(np.float64)
+    return out
+
+
+def integer_plda_model(seed, dim, zero_every=4):
+    """(transform, offset, psi) for TransformIvector on integers: T in [-4, 4], offset in [-16, 16], psi in [0, 6] descending
+    with an exact 0 in every zero_every-th place and in the last.  Row 0 of T is even and offset[0] odd, so y[0] is odd for
+    every integer x: no transformed vector is zero."""
+    rng = np.random.default_rng(seed)
+    t = rng.integers(-4, 5, (dim, dim)).astype(np.float64)
+    t[0] = 2 * rng.integers(-2, 3, dim)
+    offset = rng.integers(-16, 17, dim).astype(np.float64)
+    offset[0] = 2 * int(rng.integers(-8, 8)) + 1
+    psi = np.sort(rng.uniform(0.0, 6.0, dim))[::-1].copy()
+    psi[zero_every - 1::zero_every] = 0.0
+    psi[-1] = 0.0
+    return t, offset, psi
+
+
+def scoring_case(seed, dim, n_u, n_v):
+    """(u, num_u, v, psi) for LogLikelihoodRatio: psi is 0 in every fourth place (and in the last when dim > 1) and in [2, 6]
+    elsewhere, num_u cycles through 1, 2.5, 3, 2, 1.5 (all in [1, 3]), u and v are float32 draws with the model's total
+    variance 1 + psi.  The kernel test's error bound rests on these ranges."""
+    rng = np.random.default_rng(seed)
+    psi = np.sort(rng.uniform(2.0, 6.0, dim))[::-1].copy()
+    psi[3::4] = 0.0
+    if dim > 1:
+        psi[-1] = 0.0
+    sd = np.sqrt(1.0 + psi)
+    u = (rng.standard_normal((n_u, dim)) * sd).astype(np.float32)
+    v = (rng.standard_normal((n_v, dim)) * sd).astype(np.float32)
+    num_u = np.array([(1.0, 2.5, 3.0, 2.0, 1.5)[k % 5] for k in range(n_u)])
+    return u, num_u, v, psi
+
+
+def transform_ivector_ld(x, transform, offset, psi, num=1, simple=False):
+    """Plda::TransformIvector in np.longdouble, on the device's own terms (offset = -T mean): (y, scale), neither rounded;
+    the normalised vector is y * scale[:, None]."""
+    L = np.longdouble
+    x = np.atleast_2d(np.asarray(x)).astype(L)
+    y = x @ np.asarray(transform).astype(L).T + np.asarray(offset).astype(L)
+    num = np.broadcast_to(np.asarray(num).astype(L), (len(x),))
+    dim = L(y.shape[1])
+    if simple:
+        scale = np.sqrt(dim) / np.sqrt((y * y).sum(1))
+    else:
+        scale = np.sqrt(dim / ((y * y) / (np.asarray(psi).astype(L)[None, :] + L(1) / num[:, None])).sum(1))
+    return y, scale
+
+
+def llr_ld(u, num_u, v, psi):
+    """Plda::LogLikelihoodRatio of every row of u (means of num_u examples) against every row of v, in np.longdouble:
+    (llr, size), both [n_u, n_v]; size = 1/2 (sum |log(1 + psi)| + sum |log var| + sum (v - m)^2 / var + sum v^2 / (1 + psi)),
+    the sum of the absolute values of the terms that llr is made of."""
+    L = np.longdouble
+    u = np.atleast_2d(np.asarray(u)).astype(L)
+    v = np.atleast_2d(np.asarray(v)).astype(L)
+    psi = np.asarray(psi).astype(L)[None, :]
+    n = np.broadcast_to(np.asarray(num_u).astype(L), (len(u),))[:, None]
+    mean = n * psi / (n * psi + 1) * u                         # [n_u, dim]
+    var = 1 + psi / (n * psi + 1)
+    quad_given = ((v[None, :, :] - mean[:, None, :]) ** 2 / var[:, None, :]).sum(2)
+    quad_without = (v * v / (1 + psi)).sum(1)[None, :]
+    log_given = np.log(var).sum(1)[:, None]
+    log_without = np.log(1 + psi).sum()
+    llr_all = -(log_given + quad_given) / 2 + (log_without + quad_without) / 2
+    size = (np.abs(np.log(var)).sum(1)[:, None] + quad_given + np.abs(np.log(1 + psi)).sum() + quad_without) / 2
+    return llr_all, size
+
+
 def eer(target, nontarget):
     """compute-eer: (EER as a fraction, threshold), on float32 scores like the tool's BaseFloat."""
     tgt = np.sort(np.asarray(target, np.float32))
