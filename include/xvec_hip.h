@@ -819,6 +819,14 @@ typedef struct {
   void* hip_stream;
 } xv_frame_output_desc;
 xv_status xv_kernel_frame_output(const xv_frame_output_desc* d);
+/* bucket_sort kernels, HOST arrays in and out (the entry owns the device buffers): the stable counting sort by key that the UBM,
+ * GMM and i-vector statistics start with.  keys [pairs], each in [0, num_keys); seg_off [num_segments + 1] rises from 0 to pairs,
+ * 1 <= num_segments <= 64.  Inside every segment [seg_off[s], seg_off[s + 1]) the pairs are bucketed by key, ascending pair
+ * index inside a bucket: sorted_out [pairs] holds the pair indices, bucket_start_out [num_segments][num_keys + 1] the absolute
+ * position of every bucket (row s runs from seg_off[s] to seg_off[s + 1]).  XV_ERR_ARG, before anything is launched, for a key
+ * out of range and for a segment table or sizes the launcher refuses. */
+xv_status xv_bucket_sort(int32_t device, const int32_t* keys, int64_t pairs, const int32_t* seg_off, int32_t num_segments,
+                         int32_t num_keys, int32_t* bucket_start_out, int32_t* sorted_out);
 
 #ifdef __cplusplus
 }

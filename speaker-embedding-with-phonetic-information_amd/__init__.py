@@ -148,7 +148,7 @@ ABI_SYMBOLS = [
     "xv_ivex_write", "xv_ivex_kernel_time",
     "xv_ivex_acc_create", "xv_ivex_acc_destroy", "xv_ivex_acc_add", "xv_ivex_acc_get", "xv_ivex_acc_pending", "xv_ivex_acc_kernel_time",
     "xv_ivex_rank_update", "xv_ivex_init", "xv_ivex_est", "xv_ivex_stats_read", "xv_ivex_stats_write",
-    "xv_kernel_first_layer", "xv_kernel_prep_input", "xv_kernel_pool_finalise", "xv_kernel_frame_output",
+    "xv_kernel_first_layer", "xv_kernel_prep_input", "xv_kernel_pool_finalise", "xv_kernel_frame_output", "xv_bucket_sort",
     "xv_wave_read", "xv_wave_free", "xv_pack_mx_residual", "xv_pack_mx_residual64", "xv_tile_mx_scales", "xv_pack_mx_weights", "xv_pack_mx_weights64",
 ]
 
@@ -2014,6 +2014,24 @@ def kernel_pool_finalise(desc):
 
 def kernel_frame_output(desc):
     _check(lib().xv_kernel_frame_output(ctypes.byref(desc)))
+
+
+def bucket_sort(keys, seg_off, num_keys, device=0, pairs=None):
+    """The stable counting sort by key of the UBM, GMM and i-vector statistics, inside every segment [seg_off[s], seg_off[s + 1])
+    of keys (int32, each in [0, num_keys)).  Returns (bucket_start [segments, num_keys + 1], sorted [pairs]): absolute positions
+    of the buckets and the pair indices, ascending inside a bucket.  pairs: len(keys) unless given."""
+    import numpy as np
+    keys = np.ascontiguousarray(keys, dtype=np.int32)
+    seg_off = np.ascontiguousarray(seg_off, dtype=np.int32)
+    n_seg = len(seg_off) - 1
+    pairs = len(keys) if pairs is None else int(pairs)
+    start = np.zeros((max(n_seg, 0), max(int(num_keys), 0) + 1), dtype=np.int32)
+    out = np.zeros(max(pairs, 0), dtype=np.int32)
+    L = lib()
+    L.xv_bucket_sort.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                 ctypes.c_void_p, ctypes.c_void_p]
+    _check(L.xv_bucket_sort(int(device), keys.ctypes.data, pairs, seg_off.ctypes.data, n_seg, int(num_keys), start.ctypes.data, out.ctypes.data))
+    return start, out
 
 
 def pack_mx_residual(w, w_hi_f16, segs, walk64=False):

@@ -2028,6 +2028,27 @@ xv_status xv_kernel_frame_output(const xv_frame_output_desc* d) {
   });
 }
 
+xv_status xv_bucket_sort(int32_t device, const int32_t* keys, int64_t pairs, const int32_t* seg_off, int32_t num_segments,
+                         int32_t num_keys, int32_t* bucket_start_out, int32_t* sorted_out) {
+  if (!seg_off || !bucket_start_out || (pairs > 0 && (!keys || !sorted_out))) return Fail(XV_ERR_ARG, "xv_bucket_sort: null argument");
+  return Guard([&] {
+    for (int64_t i = 0; i < pairs; ++i)   // the input comes from outside: the kernels index the histogram with the keys
+      if (keys[i] < 0 || keys[i] >= num_keys)
+        return Fail(XV_ERR_ARG, "xv_bucket_sort: key " + std::to_string(keys[i]) + " is outside [0, " + std::to_string(num_keys) + ")");
+    xv::UseDevice(device, "the bucket sort needs");
+    xv::DevBuf d_keys;
+    if (pairs > 0) d_keys.Upload(keys, (size_t)pairs * 4, "copy the keys");
+    xv::BucketSorter sort;
+    const hipError_t e = sort.Run(d_keys.as<int32_t>(), pairs, seg_off, num_segments, num_keys, nullptr);
+    if (e == hipErrorInvalidValue) return Fail(XV_ERR_ARG, "xv_bucket_sort: sizes or a segment table that the sort does not take");
+    if (e != hipSuccess) return Fail(XV_ERR_DEVICE, std::string("bucket_sort launch: ") + hipGetErrorString(e));
+    xv::Check(hipDeviceSynchronize(), "bucket_sort");
+    sort.start.Download(bucket_start_out, (size_t)num_segments * (num_keys + 1) * 4, "copy the bucket table");
+    if (pairs > 0) sort.sorted.Download(sorted_out, (size_t)pairs * 4, "copy the sorted pairs");
+    return XV_OK;
+  });
+}
+
 static xv_status PackMxResidualImpl(bool walk64, const float* w, const uint16_t* w_hi_f16, int32_t n_pad, int32_t nseg,
                                     const int32_t* seg_src, const int32_t* seg_shift, const int32_t* seg_klen, uint8_t* w4,
                                     uint8_t* w4_scale) {

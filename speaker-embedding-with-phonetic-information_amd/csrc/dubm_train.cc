@@ -219,8 +219,8 @@ using Impl = DgmmAccumulator::Impl;
 
 // the work items, the partial sums and the reduction on the pairs that A.Sort bucketed.  a: feats, rows, pairs, pair_frame / n, pair_w.
 float RunSparseAcc(GmmSparseAcc& A, FgmmAccArgs a, bool timed) {
-  a.sorted = A.sorted.as<int32_t>();
-  a.bucket_start = A.start.as<int32_t>();
+  a.sorted = A.sort.sorted.as<int32_t>();
+  a.bucket_start = A.sort.start.as<int32_t>();
   return A.Accumulate(
       a,
       [](int64_t bound, size_t) {
@@ -343,8 +343,8 @@ void DgmmAccAddGselect(DgmmAccumulator* acc, const UbmModel& diag, const float* 
   p.num_gauss = I.acc.num_gauss;
   p.n = n;
   p.gselect = I.gselect.as<int32_t>();
-  p.bucket_start = I.acc.start.as<int32_t>();
-  p.sorted = I.acc.sorted.as<int32_t>();
+  p.bucket_start = I.acc.sort.start.as<int32_t>();
+  p.sorted = I.acc.sort.sorted.as<int32_t>();
   p.ll = I.ll.as<float>();
   p.min_post = 0.f;
   p.out_count = I.count.as<int32_t>();

@@ -11,7 +11,7 @@
 // added in chunk order and that sum is added to the running accumulator once per call: what a call adds is a function of the call's
 // frames, pairs and model alone.  The kernels of this file (kDgmmNumKernels in the object):
 //   dgmm_sel_loglike    one thread per (frame, slot): the score of the selected Gaussian.
-//   dgmm_acc_partial    the sparse accumulator.  The pairs are bucketed by Gaussian (launch_ubm_bucket_sort) and the work items
+//   dgmm_acc_partial    the sparse accumulator.  The pairs are bucketed by Gaussian (launch_bucket_sort) and the work items
 //                       (Gaussian, chunk of kFgmmAccPairChunk pairs of its bucket) are fgmm_acc_items' (ubm_train_kernels.h), whose
 //                       contract fits as it is.  A workgroup walks its chunk in K tiles of kDgmmKTile pairs gathered into LDS;
 //                       thread c < D sums column c of the mean, thread D + c column c of the second moment and thread 2 D the

@@ -7,7 +7,6 @@
 #include <sstream>
 
 #include "gmm_sparse_acc.h"
-#include "ubm_kernels.h"
 #include "ubm_train_kernels.h"
 
 namespace xv {
@@ -251,27 +250,10 @@ int64_t GmmSparseAcc::UploadPairs(const char* who_c, const float* host_feats, in
 }
 
 float GmmSparseAcc::Sort(const int32_t* d_gauss, int64_t pairs, bool timed) {
-  UbmFullArgs s;
-  memset(&s, 0, sizeof s);
-  s.rows = pairs;
-  s.n = 1;
-  s.dim = dim;
-  s.num_gauss = num_gauss;
-  s.num_chunks = (int)((pairs + kUbmSortChunk - 1) / kUbmSortChunk);
-  const size_t hist_bytes = (size_t)num_gauss * s.num_chunks * 4;
-  rank.Reserve((size_t)pairs * 4);
-  hist.Reserve(hist_bytes);
-  start.Reserve((size_t)(num_gauss + 1) * 4);
-  sorted.Reserve((size_t)pairs * 4);
-  Check(hipMemsetAsync(hist.p, 0, hist_bytes, nullptr), "hipMemsetAsync");
-  s.gselect = d_gauss;
-  s.local_rank = rank.as<int32_t>();
-  s.chunk_hist = hist.as<int32_t>();
-  s.bucket_start = start.as<int32_t>();
-  s.sorted = sorted.as<int32_t>();
+  const int32_t seg_off[2] = {0, (int32_t)pairs};
   EventTimer tm(timed);
   tm.Start();
-  Check(launch_ubm_bucket_sort(s, nullptr), "ubm_bucket_sort launch");
+  Check(sort.Run(d_gauss, pairs, seg_off, 1, num_gauss, nullptr), "bucket_sort launch");
   return timed ? tm.Stop() : 0.f;
 }
 

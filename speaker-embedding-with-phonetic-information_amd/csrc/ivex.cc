@@ -6,6 +6,7 @@
 
 #include <algorithm>
 
+#include "bucket_sort.h"
 #include "device.h"
 #include "ivex_kernels.h"
 
@@ -13,6 +14,7 @@ namespace xv {
 namespace {
 
 const char kWhoNeeds[] = "i-vector extraction needs";
+static_assert(kIvexMaxBatch <= kBucketSortMaxSegments, "a launch group's utterances are the segments of one sort");
 
 // DP / FP (binary) or " [ rows ]" (text): one packed lower triangle appended to *packed; returns its dimension
 int ReadPackedDouble(Input& in, bool binary, std::vector<double>* packed) {
@@ -167,9 +169,10 @@ struct IvexModel::Impl {
   DevBuf sigma_inv_m, U;
   DevBuf solution;                        // [B][S] fp64, allocated by the first call that has a group hook
   // workspaces of one launch group, allocated once
-  DevBuf gamma, X, partial, linear, quadratic, work, ivec, auxf, status, bucket_start;
+  DevBuf gamma, X, partial, linear, quadratic, work, ivec, auxf, status;
   // what follows the group's frames and pairs: grown when a group needs more
-  DevBuf feats, pair_frame, pair_gauss, pair_w, pair_off, chunk_utt, chunk_begin, utt_chunk0, local_rank, chunk_hist, sorted;
+  DevBuf feats, pair_frame, pair_gauss, pair_w;
+  BucketSorter sort;   // one segment per utterance of the group
 };
 
 IvexModel::~IvexModel() {}
@@ -229,9 +232,6 @@ IvexModel* IvexCreate(int device, const IvexData& m) {
   I.ivec.Reserve(B * m.S * 4);
   I.auxf.Reserve(B * 8);
   I.status.Reserve(B * 4);
-  I.bucket_start.Reserve(B * (size_t)(m.G + 1) * 4);
-  I.pair_off.Reserve((B + 1) * 4);
-  I.utt_chunk0.Reserve((B + 1) * 4);
   return h.release();
 }
 
@@ -265,21 +265,18 @@ void IvexExtract(IvexModel& m, const float* feats, const int32_t* row_off, int n
   constexpr int64_t kBatchFrames = 1 << 16;
   const int G = I.G, D = I.D, S = I.S;
   const int64_t K = (int64_t)G * D;
-  std::vector<int32_t> pair_frame, pair_gauss, pair_off, chunk_utt, chunk_begin, utt_chunk0;
+  std::vector<int32_t> pair_frame, pair_gauss, pair_off;
   std::vector<float> pair_w;
   for (int u0 = 0; u0 < n_utts;) {
     int u1 = u0 + 1;
     while (u1 < n_utts && u1 - u0 < kIvexMaxBatch && row_off[u1 + 1] - row_off[u0] <= kBatchFrames) ++u1;
     const int B = u1 - u0;
     const int64_t r0 = row_off[u0], nr = row_off[u1] - r0;
-    // the group's pairs, scaled (step 1), and the chunks of the sort: no chunk crosses an utterance
+    // the group's pairs, scaled (step 1); pair_off: the utterances are the segments of the sort
     pair_frame.clear();
     pair_gauss.clear();
     pair_w.clear();
     pair_off.assign(1, 0);
-    chunk_utt.clear();
-    chunk_begin.clear();
-    utt_chunk0.assign(1, 0);
     for (int u = u0; u < u1; ++u) {
       const int64_t pa = post_off[row_off[u]], pb = post_off[row_off[u + 1]];
       const float scale = IvexPosteriorScale(post_w + pa, (size_t)(pb - pa), acoustic_weight, max_count, nullptr);
@@ -289,30 +286,13 @@ void IvexExtract(IvexModel& m, const float* feats, const int32_t* row_off, int n
           pair_gauss.push_back(post_idx[i]);
           pair_w.push_back(post_w[i] * scale);
         }
-      const int32_t begin = pair_off.back(), end = (int32_t)pair_frame.size();
-      for (int32_t c = begin; c < end; c += kIvexSortChunk) {
-        chunk_utt.push_back(u - u0);
-        chunk_begin.push_back(c);
-      }
-      pair_off.push_back(end);
-      utt_chunk0.push_back((int32_t)chunk_utt.size());
+      pair_off.push_back((int32_t)pair_frame.size());
     }
     const size_t pairs = pair_frame.size();
-    const int num_chunks = (int)chunk_utt.size();
-    chunk_begin.push_back((int32_t)pairs);
     I.feats.Upload(feats + (size_t)r0 * D, (size_t)nr * D * 4, "copy features");
     I.pair_frame.Upload(pair_frame, "copy the posteriors");
     I.pair_gauss.Upload(pair_gauss, "copy the posteriors");
     I.pair_w.Upload(pair_w, "copy the posteriors");
-    I.pair_off.Upload(pair_off, "copy the posteriors");
-    I.chunk_utt.Upload(chunk_utt, "copy the sort's chunks");
-    I.chunk_begin.Upload(chunk_begin, "copy the sort's chunks");
-    I.utt_chunk0.Upload(utt_chunk0, "copy the sort's chunks");
-    I.local_rank.Reserve(pairs * 4);
-    I.sorted.Reserve(pairs * 4);
-    const size_t hist_bytes = (size_t)num_chunks * G * 4;
-    I.chunk_hist.Reserve(hist_bytes);
-    Check(hipMemsetAsync(I.chunk_hist.p, 0, hist_bytes, nullptr), "hipMemsetAsync");
 
     IvexStatsArgs st;
     memset(&st, 0, sizeof st);
@@ -323,15 +303,6 @@ void IvexExtract(IvexModel& m, const float* feats, const int32_t* row_off, int n
     st.pair_frame = I.pair_frame.as<int32_t>();
     st.pair_gauss = I.pair_gauss.as<int32_t>();
     st.pair_w = I.pair_w.as<float>();
-    st.pair_off = I.pair_off.as<int32_t>();
-    st.num_chunks = num_chunks;
-    st.chunk_utt = I.chunk_utt.as<int32_t>();
-    st.chunk_begin = I.chunk_begin.as<int32_t>();
-    st.utt_chunk0 = I.utt_chunk0.as<int32_t>();
-    st.local_rank = I.local_rank.as<int32_t>();
-    st.chunk_hist = I.chunk_hist.as<int32_t>();
-    st.bucket_start = I.bucket_start.as<int32_t>();
-    st.sorted = I.sorted.as<int32_t>();
     st.gamma = I.gamma.as<double>();
     st.X = I.X.as<double>();
     IvexGemmArgs quad;
@@ -376,7 +347,9 @@ void IvexExtract(IvexModel& m, const float* feats, const int32_t* row_off, int n
 
     EventTimer tm(out.device_ms4 != nullptr, 5);
     tm.Mark();
-    Check(launch_ivex_bucket_sort(st, nullptr), "ivex_bucket_sort launch");
+    Check(I.sort.Run(st.pair_gauss, (int64_t)pairs, pair_off.data(), B, G, nullptr), "bucket_sort launch");
+    st.bucket_start = I.sort.start.as<int32_t>();   // Run sizes them
+    st.sorted = I.sort.sorted.as<int32_t>();
     Check(launch_ivex_stats(st, nullptr), "ivex_stats launch");
     tm.Mark();
     Check(launch_ivex_gemm(quad, nullptr), "ivex_gemm launch (quadratic term)");

@@ -6,11 +6,9 @@
 //   ivex_derive         one workgroup per Gaussian, plain vector fp64 (it runs once per model): SigmaInvM_g = Sigma_g^-1 M_g (j
 //                       ascending) into the [G D][S] matrix, then the packed lower triangle of M_g' SigmaInvM_g (i ascending) into
 //                       row g of U [G][P].
-//   ivex_bucket_*       a counting sort of an utterance's (frame, Gaussian, weight) pairs by Gaussian that keeps the frame order:
-//                       ranks inside chunks of kIvexSortChunk pairs (a chunk never crosses an utterance), per utterance a scan over
-//                       its chunks and one over the Gaussians, placement.  Integer work only.
-//   ivex_stats          one wave per (utterance, Gaussian): gamma = sum w and X = sum w x over the bucket front to back; lane d owns
-//                       column d.  double(w) * double(x) is exact, so the sums are one fixed set of bits.  Gaussians that were not
+//   ivex_stats          reads every utterance's (frame, Gaussian, weight) pairs bucketed by Gaussian in frame order (bucket_sort.h,
+//                       one segment per utterance).  One wave per (utterance, Gaussian): gamma = sum w and X = sum w x over the
+//                       bucket front to back; lane d owns column d.  double(w) * double(x) is exact, so the sums are one fixed set of bits.  Gaussians that were not
 //                       hit get zeros.
 //   ivex_gemm           C[B][N] = A[B][K] W[K][N] on v_mfma_f64_16x16x4_f64.  A wave owns kIvexColTile columns and every row tile
 //                       (kIvexRowTile utterances each, at most kIvexMaxRowTiles): one fetch of a W fragment feeds all of them.  K is
@@ -41,7 +39,6 @@ constexpr int kIvexKChunk = 2048;       // K per workgroup of the linear term (a
 constexpr int kIvexPanel = 32;          // block-column width of the solve
 constexpr int kIvexMaxS = 1024;         // the largest i-vector dimension
 constexpr int kIvexMaxDim = 96;         // the largest feature dimension
-constexpr int kIvexSortChunk = 1024;    // pairs per workgroup of the ranking kernel
 
 struct IvexDeriveArgs {
   const double* M;           // [G][D][S]
@@ -58,16 +55,9 @@ struct IvexStatsArgs {
   const int32_t* pair_frame;   // [pairs] row of feats
   const int32_t* pair_gauss;   // [pairs] in [0, G) (the host checks)
   const float* pair_w;         // [pairs] the scaled posterior
-  const int32_t* pair_off;     // [B + 1]
-  // the sort
-  int num_chunks;              // of the whole batch
-  const int32_t* chunk_utt;    // [num_chunks]
-  const int32_t* chunk_begin;  // [num_chunks + 1] first pair of the chunk
-  const int32_t* utt_chunk0;   // [B + 1] first chunk of the utterance
-  int32_t* local_rank;         // [pairs]
-  int32_t* chunk_hist;         // [num_chunks][G], zero before the launch; the scan turns it into offsets inside the bucket
-  int32_t* bucket_start;       // [B][G + 1] in pairs of the batch
-  int32_t* sorted;             // [pairs] pair indices, bucket after bucket
+  // the pairs sorted by Gaussian inside every utterance (bucket_sort.h, one segment per utterance)
+  const int32_t* bucket_start; // [B][G + 1] in pairs of the batch
+  const int32_t* sorted;       // [pairs] pair indices, bucket after bucket
   double* gamma;               // [B][G]
   double* X;                   // [B][G D]
 };
@@ -102,7 +92,6 @@ struct IvexSolveArgs {
 };
 
 hipError_t launch_ivex_derive(const IvexDeriveArgs& a, hipStream_t s);
-hipError_t launch_ivex_bucket_sort(const IvexStatsArgs& a, hipStream_t s);   // rank, scan, placement
 hipError_t launch_ivex_stats(const IvexStatsArgs& a, hipStream_t s);
 hipError_t launch_ivex_gemm(const IvexGemmArgs& a, hipStream_t s);
 hipError_t launch_ivex_finish_terms(const IvexFinishArgs& a, hipStream_t s);

@@ -43,76 +43,6 @@ __global__ __launch_bounds__(kIvexThreads) void ivex_derive_kernel(const IvexDer
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The counting sort of an utterance's pairs by Gaussian.
-__global__ __launch_bounds__(kIvexThreads) void ivex_bucket_rank_kernel(const IvexStatsArgs a) {
-  __shared__ int32_t gs[kIvexSortChunk];
-  const int c = blockIdx.x;
-  const int p0 = a.chunk_begin[c];
-  const int cnt = a.chunk_begin[c + 1] - p0;   // <= kIvexSortChunk
-  for (int i = threadIdx.x; i < cnt; i += kIvexThreads) gs[i] = a.pair_gauss[p0 + i];
-  __syncthreads();
-  for (int i = threadIdx.x; i < cnt; i += kIvexThreads) {
-    const int32_t g = gs[i];
-    int rank = 0, later = 0;
-    for (int j = 0; j < cnt; ++j) {
-      const int eq = gs[j] == g ? 1 : 0;
-      rank += eq & (j < i ? 1 : 0);
-      later |= eq & (j > i ? 1 : 0);
-    }
-    a.local_rank[p0 + i] = rank;
-    if (!later) a.chunk_hist[(int64_t)c * a.G + g] = rank + 1;   // the chunk's count of g, written by its last pair
-  }
-}
-
-// One workgroup per utterance: counts per Gaussian over the utterance's chunks (the histogram becomes the chunk's offset inside
-// the bucket), then the exclusive scan over the Gaussians.
-__global__ __launch_bounds__(kIvexThreads) void ivex_bucket_scan_kernel(const IvexStatsArgs a) {
-  __shared__ int32_t part[kIvexThreads];
-  const int u = blockIdx.x, tid = threadIdx.x, G = a.G;
-  const int c0 = a.utt_chunk0[u], c1 = a.utt_chunk0[u + 1];
-  int32_t* start = a.bucket_start + (int64_t)u * (G + 1);
-  for (int g = tid; g < G; g += kIvexThreads) {
-    int32_t run = 0;
-    for (int c = c0; c < c1; ++c) {
-      const int32_t v = a.chunk_hist[(int64_t)c * G + g];
-      a.chunk_hist[(int64_t)c * G + g] = run;
-      run += v;
-    }
-    start[g] = run;
-  }
-  __syncthreads();
-  const int per = (G + kIvexThreads - 1) / kIvexThreads;
-  const int lo = tid * per < G ? tid * per : G, hi = lo + per < G ? lo + per : G;
-  int32_t sum = 0;
-  for (int g = lo; g < hi; ++g) sum += start[g];
-  part[tid] = sum;
-  __syncthreads();
-  for (int step = 1; step < kIvexThreads; step <<= 1) {
-    const int32_t add = tid >= step ? part[tid - step] : 0;
-    __syncthreads();
-    part[tid] += add;
-    __syncthreads();
-  }
-  int32_t run = a.pair_off[u] + part[tid] - sum;
-  for (int g = lo; g < hi; ++g) {
-    const int32_t v = start[g];
-    start[g] = run;
-    run += v;
-  }
-  if (tid == kIvexThreads - 1) start[G] = a.pair_off[u + 1];
-}
-
-__global__ __launch_bounds__(kIvexThreads) void ivex_bucket_place_kernel(const IvexStatsArgs a) {
-  const int c = blockIdx.x;
-  const int p0 = a.chunk_begin[c];
-  const int cnt = a.chunk_begin[c + 1] - p0;
-  const int32_t* start = a.bucket_start + (int64_t)a.chunk_utt[c] * (a.G + 1);
-  for (int i = threadIdx.x; i < cnt; i += kIvexThreads) {
-    const int32_t g = a.pair_gauss[p0 + i];
-    a.sorted[start[g] + a.chunk_hist[(int64_t)c * a.G + g] + a.local_rank[p0 + i]] = p0 + i;
-  }
-}
-
 // One wave per (utterance, Gaussian); lane d owns columns d and d + 64.
 __global__ __launch_bounds__(kIvexThreads) void ivex_stats_kernel(const IvexStatsArgs a) {
   const int lane = threadIdx.x & 63;
@@ -368,19 +298,6 @@ __global__ __launch_bounds__(kIvexThreads) void ivex_solve_kernel(const IvexSolv
 
 hipError_t launch_ivex_derive(const IvexDeriveArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(ivex_derive_kernel, dim3((unsigned)a.G), dim3(kIvexThreads), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_ivex_bucket_sort(const IvexStatsArgs& a, hipStream_t s) {
-  if (a.num_chunks > 0) {
-    hipLaunchKernelGGL(ivex_bucket_rank_kernel, dim3((unsigned)a.num_chunks), dim3(kIvexThreads), 0, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(ivex_bucket_scan_kernel, dim3((unsigned)a.B), dim3(kIvexThreads), 0, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || a.num_chunks == 0) return e;
-  hipLaunchKernelGGL(ivex_bucket_place_kernel, dim3((unsigned)a.num_chunks), dim3(kIvexThreads), 0, s, a);
   return hipGetLastError();
 }
 

@@ -361,12 +361,6 @@ void UbmPostDevice::Run(const UbmModel& full, const float* host_feats, const int
   const size_t pairs = (size_t)rows * n;
   UbmFullArgs a;
   memset(&a, 0, sizeof a);
-  a.num_chunks = (int)((pairs + kUbmSortChunk - 1) / kUbmSortChunk);
-  const size_t hist_bytes = (size_t)I.num_gauss * a.num_chunks * 4;
-  rank.Reserve(pairs * 4);
-  hist.Reserve(hist_bytes);
-  start.Reserve((size_t)(I.num_gauss + 1) * 4);
-  sorted.Reserve(pairs * 4);
   ll.Reserve(pairs * 4);
   count.Reserve((size_t)rows * 4);
   idx.Reserve(pairs * 4);
@@ -375,7 +369,6 @@ void UbmPostDevice::Run(const UbmModel& full, const float* host_feats, const int
   if (with_slot_post) slot_post.Reserve(pairs * 4);
   feats.Upload(host_feats, (size_t)rows * I.dim * 4, "copy features");
   gselect.Upload(host_gselect, pairs * 4, "copy the selection");
-  Check(hipMemsetAsync(hist.p, 0, hist_bytes, nullptr), "hipMemsetAsync");
   a.feats = feats.as<float>();
   a.rows = rows;
   a.dim = I.dim;
@@ -385,10 +378,6 @@ void UbmPostDevice::Run(const UbmModel& full, const float* host_feats, const int
   a.gconst = I.gconst.as<float>();
   a.n = n;
   a.gselect = gselect.as<int32_t>();
-  a.local_rank = rank.as<int32_t>();
-  a.chunk_hist = hist.as<int32_t>();
-  a.bucket_start = start.as<int32_t>();
-  a.sorted = sorted.as<int32_t>();
   // enough workgroups per Gaussian that an average bucket is a few passes of each
   const int64_t per_gauss = (int64_t)pairs / I.num_gauss;
   a.split = (int)std::max<int64_t>(1, std::min<int64_t>(64, per_gauss / (4 * kUbmFullFrameTile)));
@@ -401,7 +390,10 @@ void UbmPostDevice::Run(const UbmModel& full, const float* host_feats, const int
   a.out_slot_post = with_slot_post ? slot_post.as<float>() : nullptr;
   EventTimer tm(device_ms3 != nullptr, 4);
   tm.Mark();
-  Check(launch_ubm_bucket_sort(a, nullptr), "ubm_bucket_sort launch");
+  const int32_t seg_off[2] = {0, (int32_t)pairs};
+  Check(sort.Run(a.gselect, (int64_t)pairs, seg_off, 1, I.num_gauss, nullptr), "bucket_sort launch");
+  a.bucket_start = sort.start.as<int32_t>();   // Run sizes them
+  a.sorted = sort.sorted.as<int32_t>();
   tm.Mark();
   Check(launch_ubm_full_loglike(a, nullptr), "ubm_full_loglike launch");
   tm.Mark();

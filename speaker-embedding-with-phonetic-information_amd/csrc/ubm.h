@@ -32,6 +32,7 @@
 #include <string>
 #include <vector>
 
+#include "bucket_sort.h"
 #include "device.h"
 #include "kio.h"
 
@@ -92,7 +93,7 @@ void UbmPost(const UbmModel& full, const float* feats, const int32_t* row_off, i
 void CheckUbmSelection(const char* who, const UbmModel& full, const int32_t* gselect, int64_t rows, int n);
 struct UbmPostDevice {
   DevBuf feats, gselect;                // the inputs of the part: [rows][dim], [rows][n]
-  DevBuf rank, hist, start, sorted;     // the sort: start [num_gauss + 1] buckets of `sorted` [rows * n] pair indices
+  BucketSorter sort;                    // its start: [num_gauss + 1] buckets of its sorted: [rows * n] pair indices
   DevBuf ll, count, idx, post, logsum;  // UbmPost's results
   DevBuf slot_post;                     // with_slot_post: [rows][n] the posterior of selection slot i at i, zeros kept
   // device_ms3 (may be null): {sort, scores, softmax} are added to it

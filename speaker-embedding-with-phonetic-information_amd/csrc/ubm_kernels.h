@@ -12,10 +12,8 @@
 //                       best and ranks the survivors together with the running list (order: score descending, then index
 //                       ascending; scores compared as order-preserving integer keys, so the order is total even with NaNs).  The
 //                       frames x Gaussians score matrix never leaves the workgroup.  n <= kUbmMaxSelect.
-//   ubm_bucket_*        a counting sort of the rows * n (frame, slot) pairs by Gaussian, ascending pair inside a bucket: ranks
-//                       inside chunks of kUbmSortChunk pairs, a scan over (Gaussian, chunk), a scan over the Gaussians, placement.
-//                       Integer work only.
-//   ubm_full_loglike    workgroup (g, s) expands Gaussian g's packed inverse covariance into LDS and takes tiles s, s + S, ... of
+//   ubm_full_loglike    reads the rows * n (frame, slot) pairs bucketed by Gaussian, ascending pair inside a bucket (bucket_sort.h).
+//                       Workgroup (g, s) expands Gaussian g's packed inverse covariance into LDS and takes tiles s, s + S, ... of
 //                       kUbmFullFrameTile frames of g's bucket: thread (frame, column group) forms y_j = sum_i x_i A_ij in ascending
 //                       i for its columns, then its share of b . x - x . y / 2; the 8 shares are added in ascending group order
 //                       to gconst and scattered back to (frame, slot).
@@ -34,7 +32,6 @@ constexpr int kUbmMaxSelect = 64;       // the largest n
 constexpr int kUbmMaxDim = 96;          // the largest feature dimension of a model on the device
 constexpr int kUbmFullFrameTile = 32;   // frames per pass of the full-covariance kernel
 constexpr int kUbmFullGroups = 8;       // column groups of that kernel (kUbmThreads / kUbmFullFrameTile)
-constexpr int kUbmSortChunk = 1024;     // pairs per workgroup of the ranking kernel
 constexpr int kDeltaRowBlock = 256;     // rows per work item of add_deltas
 constexpr int kDeltaMaxOrder = 8;
 
@@ -75,12 +72,9 @@ struct UbmFullArgs {
   const float* gconst;       // [num_gauss]
   int n;                     // pairs per frame
   const int32_t* gselect;    // [rows * n] the Gaussian of every pair, each in [0, num_gauss) (the host checks)
-  // the sort
-  int num_chunks;            // ceil(rows * n / kUbmSortChunk)
-  int32_t* local_rank;       // [rows * n]
-  int32_t* chunk_hist;       // [num_gauss][num_chunks], zero before the launch; the scan turns it into offsets inside the bucket
-  int32_t* bucket_start;     // [num_gauss + 1]
-  int32_t* sorted;           // [rows * n] pair indices, bucket after bucket
+  // the pairs sorted by Gaussian (bucket_sort.h, one segment)
+  const int32_t* bucket_start;   // [num_gauss + 1]
+  const int32_t* sorted;         // [rows * n] pair indices, bucket after bucket
   int split;                 // workgroups per Gaussian of the full-covariance kernel
   float* ll;                 // [rows * n]
   // posteriors
@@ -94,7 +88,6 @@ struct UbmFullArgs {
 
 hipError_t launch_add_deltas(const DeltaArgs& a, hipStream_t s);
 hipError_t launch_ubm_diag_gselect(const UbmDiagArgs& a, hipStream_t s);
-hipError_t launch_ubm_bucket_sort(const UbmFullArgs& a, hipStream_t s);   // rank, the two scans, placement
 hipError_t launch_ubm_full_loglike(const UbmFullArgs& a, hipStream_t s);
 hipError_t launch_ubm_post(const UbmFullArgs& a, hipStream_t s);
 

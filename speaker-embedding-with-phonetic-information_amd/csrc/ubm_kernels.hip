@@ -155,74 +155,6 @@ __global__ __launch_bounds__(kUbmThreads) void ubm_diag_gselect_kernel(const Ubm
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The counting sort of the pairs by Gaussian.
-__global__ __launch_bounds__(kUbmThreads) void ubm_bucket_rank_kernel(const UbmFullArgs a) {
-  __shared__ int32_t gs[kUbmSortChunk];
-  const int64_t total = a.rows * a.n;
-  const int64_t p0 = (int64_t)blockIdx.x * kUbmSortChunk;
-  const int cnt = total - p0 < kUbmSortChunk ? (int)(total - p0) : kUbmSortChunk;
-  for (int i = threadIdx.x; i < cnt; i += kUbmThreads) gs[i] = a.gselect[p0 + i];
-  __syncthreads();
-  for (int i = threadIdx.x; i < cnt; i += kUbmThreads) {
-    const int32_t g = gs[i];
-    int rank = 0, later = 0;
-    for (int j = 0; j < cnt; ++j) {
-      const int eq = gs[j] == g ? 1 : 0;
-      rank += eq & (j < i ? 1 : 0);
-      later |= eq & (j > i ? 1 : 0);
-    }
-    a.local_rank[p0 + i] = rank;
-    if (!later) a.chunk_hist[(int64_t)g * a.num_chunks + blockIdx.x] = rank + 1;   // the chunk's count of g, written by its last pair
-  }
-}
-
-// data[0 .. n) -> its exclusive prefix sums, in place; returns the total.  All threads of the workgroup call it.
-__device__ int block_exclusive_scan(int32_t* data, int n) {
-  __shared__ int32_t part[kUbmThreads];
-  const int tid = threadIdx.x;
-  const int per = (n + kUbmThreads - 1) / kUbmThreads;
-  const int lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
-  int32_t sum = 0;
-  for (int i = lo; i < hi; ++i) sum += data[i];
-  part[tid] = sum;
-  __syncthreads();
-  for (int step = 1; step < kUbmThreads; step <<= 1) {
-    const int32_t add = tid >= step ? part[tid - step] : 0;
-    __syncthreads();
-    part[tid] += add;
-    __syncthreads();
-  }
-  int32_t run = part[tid] - sum;
-  const int32_t all = part[kUbmThreads - 1];
-  for (int i = lo; i < hi; ++i) {
-    const int32_t v = data[i];
-    data[i] = run;
-    run += v;
-  }
-  __syncthreads();
-  return all;
-}
-
-__global__ __launch_bounds__(kUbmThreads) void ubm_bucket_scan_chunks_kernel(const UbmFullArgs a) {
-  const int g = blockIdx.x;
-  const int all = block_exclusive_scan(a.chunk_hist + (int64_t)g * a.num_chunks, a.num_chunks);
-  if (threadIdx.x == 0) a.bucket_start[g] = all;
-}
-
-__global__ __launch_bounds__(kUbmThreads) void ubm_bucket_scan_gauss_kernel(const UbmFullArgs a) {
-  const int all = block_exclusive_scan(a.bucket_start, a.num_gauss);
-  if (threadIdx.x == 0) a.bucket_start[a.num_gauss] = all;
-}
-
-__global__ __launch_bounds__(kUbmThreads) void ubm_bucket_place_kernel(const UbmFullArgs a) {
-  const int64_t p = (int64_t)blockIdx.x * kUbmThreads + threadIdx.x;
-  if (p >= a.rows * a.n) return;
-  const int32_t g = a.gselect[p];
-  const int chunk = (int)(p / kUbmSortChunk);
-  a.sorted[a.bucket_start[g] + a.chunk_hist[(int64_t)g * a.num_chunks + chunk] + a.local_rank[p]] = (int32_t)p;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
 // NC columns per thread: the LDS image of the inverse covariance is dim rows of W = 8 NC columns, zero beyond dim.
 template <int NC>
 __global__ __launch_bounds__(kUbmThreads) void ubm_full_loglike_kernel(const UbmFullArgs a) {
@@ -377,17 +309,6 @@ hipError_t launch_ubm_diag_gselect(const UbmDiagArgs& a, hipStream_t s) {
   if (blocks > INT32_MAX) return hipErrorInvalidValue;
   const size_t lds = (size_t)2 * a.dim * kUbmFrameBlock * sizeof(float);
   hipLaunchKernelGGL(ubm_diag_gselect_kernel, dim3((unsigned)blocks), dim3(kUbmThreads), lds, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_ubm_bucket_sort(const UbmFullArgs& a, hipStream_t s) {
-  if (!full_args_ok(a) || !a.local_rank || !a.chunk_hist) return hipErrorInvalidValue;
-  const int64_t total = a.rows * a.n;
-  if (a.num_chunks != (int)((total + kUbmSortChunk - 1) / kUbmSortChunk)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(ubm_bucket_rank_kernel, dim3((unsigned)a.num_chunks), dim3(kUbmThreads), 0, s, a);
-  hipLaunchKernelGGL(ubm_bucket_scan_chunks_kernel, dim3((unsigned)a.num_gauss), dim3(kUbmThreads), 0, s, a);
-  hipLaunchKernelGGL(ubm_bucket_scan_gauss_kernel, dim3(1), dim3(kUbmThreads), 0, s, a);
-  hipLaunchKernelGGL(ubm_bucket_place_kernel, dim3((unsigned)((total + kUbmThreads - 1) / kUbmThreads)), dim3(kUbmThreads), 0, s, a);
   return hipGetLastError();
 }
 

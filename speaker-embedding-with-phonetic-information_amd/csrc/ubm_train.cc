@@ -197,8 +197,8 @@ void FgmmAccAdd(FgmmAccumulator* acc, const float* feats, int64_t rows, const in
   a.pair_frame = A.frame.as<int32_t>();
   a.n = 1;
   a.pair_w = A.w.as<float>();
-  a.sorted = A.sorted.as<int32_t>();
-  a.bucket_start = A.start.as<int32_t>();
+  a.sorted = A.sort.sorted.as<int32_t>();
+  a.bucket_start = A.sort.start.as<int32_t>();
   const float ms = RunAcc(A, a, device_ms2 != nullptr);
   if (device_ms2) device_ms2[1] = ms;
   Check(hipDeviceSynchronize(), "fgmm_acc");
@@ -228,8 +228,8 @@ void FgmmAccAddGselect(FgmmAccumulator* acc, const UbmModel& full, const float* 
   a.pair_frame = nullptr;
   a.n = n;
   a.pair_w = I.post.slot_post.as<float>();
-  a.sorted = I.post.sorted.as<int32_t>();
-  a.bucket_start = I.post.start.as<int32_t>();
+  a.sorted = I.post.sort.sorted.as<int32_t>();
+  a.bucket_start = I.post.sort.start.as<int32_t>();
   const float ms = RunAcc(A, a, device_ms4 != nullptr);
   if (device_ms4) device_ms4[3] = ms;
   I.post.logsum.Download(logsum, (size_t)rows * 4, "copy the log-sums");

@@ -3,7 +3,7 @@
 //
 // fgmm_acc adds one call's posterior-weighted moments into persistent fp64 accumulators: occ [G], mean [G][D] and the packed
 // lower triangles cov [G][D (D + 1) / 2].  It gets the call's frames [rows][D] in fp32 and the pairs (frame, Gaussian, p) bucketed
-// by Gaussian, frames ascending inside a bucket (launch_ubm_bucket_sort of ubm_kernels.h: a pair's bucket is its Gaussian's).
+// by Gaussian, frames ascending inside a bucket (launch_bucket_sort of bucket_sort.h, one segment: a pair's bucket is its Gaussian's).
 // Everything is fp64 on fp32 inputs; no floating-point value goes through an atomic, and every sum has an order that is a
 // function of the call's pairs alone.
 //   fgmm_acc_items      one workgroup: item_start[g] = the exclusive prefix sums of ceil(bucket_g / kFgmmAccPairChunk), the work
