@@ -178,10 +178,19 @@ def integer_model(seed, G, D, S):
     return dict(w_vec=np.full(G, 1.0 / G), M=M, sigma_inv=sig, prior_offset=float(rng.integers(1, 4)))
 
 
-def random_model(seed, G, D, S):
-    """Sigma^-1 = A A' / D + I, M Gaussian scaled so that Q stays well conditioned"""
+def zero_leading_columns(model, s0):
+    """the model with the first s0 columns of every M_g set to zero: rows and columns below s0 of every U_g vanish, so the leading
+    s0 x s0 block of every Q is the identity, nothing couples it to the rest, and no pivot before index s0 can be bad"""
+    out = dict(model, M=np.array(model["M"], dtype=np.float64))
+    out["M"][:, :, :s0] = 0.0
+    return out
+
+
+def random_model(seed, G, D, S, m_scale=0.3):
+    """Sigma^-1 = A A' / D + I, M Gaussian scaled so that Q stays well conditioned: Q - I grows with S at a fixed scale, so a large
+    S wants a smaller m_scale (tests/ivector_cases.py's m_scale_for)"""
     rng = np.random.default_rng(seed)
-    M = rng.normal(0.0, 0.3, (G, D, S))
+    M = rng.normal(0.0, m_scale, (G, D, S))
     sig = np.zeros((G, D * (D + 1) // 2))
     for g in range(G):
         A = rng.normal(size=(D, D))

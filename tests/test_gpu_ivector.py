@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+import ivector_cases as C
 import ivector_ref as R
 import ubm_ref as UR
 from oracle import kaldi_io as kio
@@ -19,46 +20,23 @@ pytestmark = pytest.mark.gpu
 P = H.pkg()
 BIN = os.path.join(H.ROOT, H.PKG_NAME, "bin")
 
-_HDR = open(os.path.join(H.ROOT, H.PKG_NAME, "csrc", "ivex_kernels.h")).read()
-RT = int(re.search(r"kIvexRowTile = (\d+);", _HDR).group(1))
-CT = int(re.search(r"kIvexColTile = (\d+);", _HDR).group(1))
-KC = int(re.search(r"kIvexKChunk = (\d+);", _HDR).group(1))
-NB = int(re.search(r"kIvexPanel = (\d+);", _HDR).group(1))
-U53 = 2.0 ** -53
-
-
-def _shape_for(K):
-    """(G, D) with G D = K and D the largest divisor of K that a model may have"""
-    D = max(d for d in range(1, 97) if K % d == 0)
-    return K // D, D
-
-
-# (G, D, S, T, B): B around a row tile, S so that S and P fall on, below and above multiples of the column tile, G on and off
-# multiples of 4, and G D one below, at and one above the linear term's K chunk and one above two chunks
-CASES = [(37, 23, 40, 300, 1), (5, 60, 17, 64, RT + 1), (4, 1, 1, 3, RT - 1), (65, 24, 33, 500, 2 * RT + 1), (1, 23, 5, 20, RT),
-         (3, 1, CT, 10, RT + 1), (4, 60, 5, 30, RT - 1), (1, 1, 1, 1, 1)]
-CASES += [_shape_for(K) + (5, 40, b) for K, b in ((KC - 1, 1), (KC, RT), (KC + 1, RT + 1), (2 * KC + 1, 2))]
+RT, NB, MAX_S, MAX_B = C.RT, C.NB, C.MAX_S, C.MAX_B   # read from csrc/ivex_kernels.h (tests/ivector_cases.py)
+U53 = C.U53
+CASES = C.CASES
+eps_of = C.eps_of
 
 
 @functools.lru_cache(maxsize=None)
 def integer_case(G, D, S):
-    m = R.integer_model(1000 * G + 10 * D + S, G, D, S)
+    m = R.integer_model(C.integer_seed(G, D, S), G, D, S)
     return m, R.derived(m["M"], m["sigma_inv"])
 
 
-def _utterances(seed, B, T, G, D, **kw):
-    """B utterances, every one with data and a length of its own"""
-    return [R.integer_utterance(seed + 31 * u, max(1, T - 3 * u), G, D, **kw) for u in range(B)]
+_utterances = C.integer_utterances
 
 
 def _reference(m, sim_U, utts, **kw):
     return [R.extract(x, post, m["M"], m["sigma_inv"], m["prior_offset"], sim_U=sim_U, **kw) for x, post in utts]
-
-
-def eps_of(Q):
-    """Higham's bound on the backward error of Cholesky, carried to the solution: cond_2(Q) 4 S (3 S + 1) 2^-53"""
-    S = Q.shape[0]
-    return np.linalg.cond(Q, 2) * 4 * S * (3 * S + 1) * U53
 
 
 def check_solve(ref, iv, auxf, l_gpu, Q_gpu, p):
@@ -121,24 +99,56 @@ def test_integer_models_give_the_restatements_terms_bit_for_bit(G, D, S, T, B):
         assert any((r["gamma"] == 0).any() for r in ref), "no Gaussian went without a frame"
 
 
+def _assert_terms(det, ref):
+    for u, r in enumerate(ref):
+        for name in ("gamma", "X", "linear", "quadratic"):
+            assert np.array_equal(det[name][u], r[name]), (u, name)
+
+
+@pytest.mark.parametrize("G,D,S,T,B", C.LARGE_S_TERM_CASES)
+def test_integer_models_give_the_restatements_terms_bit_for_bit_at_large_s(G, D, S, T, B):
+    """The quadratic GEMM at N = P columns and the packed-index recovery of ivex_derive up to e = P - 1, P = S (S + 1) / 2, at
+    S = kIvexThreads + 1 and kIvexMaxS.  The terms only: an integer model's Q is too ill-conditioned at this size for check_solve's
+    precondition, and test_random_models_solve_within_the_bound covers the solve at these S."""
+    m, (sim, U) = integer_case(G, D, S)
+    ie = P.IvectorExtractor(**m)
+    got_sim, got_U = ie.derived()
+    assert np.array_equal(got_sim, sim) and np.array_equal(got_U, U)
+    utts = C.case_utterances(G, D, S, T, B)
+    ref = _reference(m, (sim, U), utts)
+    for (x, post), r in zip(utts, ref):
+        assert C.exact_preconditions(m, sim, U, x, post, r["gamma"])
+    iv, status, auxf, det = ie.extract([x for x, _ in utts], [p for _, p in utts], return_details=True)
+    assert not status.any() and np.isfinite(iv).all() and np.isfinite(auxf).all()
+    _assert_terms(det, ref)
+
+
+def test_a_launch_group_closed_by_its_frames_gives_the_restatements_terms_bit_for_bit():
+    """IvexExtract closes a launch group at kIvexMaxBatch utterances or at kBatchFrames frames.  Three utterances of about 30000
+    frames: the third would take the first group past kBatchFrames, so the call makes the groups {0, 1}, {2} and {3}, the last one an
+    utterance that is past the limit on its own; the frame and pair offsets of the later groups start beyond 2^16."""
+    G, D, S = C.FRAMES_SHAPE
+    m, (sim, U) = integer_case(G, D, S)
+    ie = P.IvectorExtractor(**m)
+    utts = C.frames_utterances()
+    ref = _reference(m, (sim, U), utts)
+    for (x, post), r in zip(utts, ref):
+        assert C.exact_preconditions(m, sim, U, x, post, r["gamma"])
+    iv, status, auxf, det = ie.extract([x for x, _ in utts], [p for _, p in utts], return_details=True)
+    assert not status.any()
+    _assert_terms(det, ref)
+
+
 # ------------------------------------------------------------------------------------------------------------------- the solve
-@pytest.mark.parametrize("G,D,S", [(5, 7, 17), (6, 8, NB + 1), (6, 8, 2 * NB + 3), (1, 2, 17)])
+@pytest.mark.parametrize("G,D,S", C.SOLVE_CASES)
 def test_random_models_solve_within_the_bound(G, D, S):
-    """Sigma^-1 = A A' / D + I; (1, 2, 17) is the rank-poor case: Q is the identity plus a term of rank 2."""
-    m = R.random_model(7 * S + G, G, D, S)
+    """Sigma^-1 = A A' / D + I; (1, 2, 17) is the rank-poor case: Q is the identity plus a term of rank 2.  The S above
+    2 kIvexPanel + 3 are the edges of ivex_solve_kernel's loops, each from below and from above, the recipes' 400 and 600 and the
+    limit kIvexMaxS (tests/ivector_cases.py's SOLVE_EDGES says which loop each one is for)."""
+    m = C.solve_model(G, D, S)
     ie = P.IvectorExtractor(**m)
     sim_U = R.derived(m["M"], m["sigma_inv"])
-    rng = np.random.default_rng(S)
-    utts = []
-    for u in range(3):
-        T = 50 + 17 * u
-        x = rng.normal(0.0, 2.0, (T, D)).astype(np.float32)
-        post = []
-        for t in range(T):
-            idx = rng.permutation(G)[:min(G, 3)]
-            w = rng.dirichlet(np.ones(len(idx))).astype(np.float32)
-            post.append((idx.astype(np.int32), w))
-        utts.append((x, post))
+    utts = C.solve_utterances(G, D, S, C.solve_utts_count(S))
     ref = _reference(m, sim_U, utts)
     iv, status, auxf, det = ie.extract([x for x, _ in utts], [p for _, p in utts], return_details=True)
     assert not status.any()
@@ -148,25 +158,34 @@ def test_random_models_solve_within_the_bound(G, D, S):
         check_solve(r, iv[u], auxf[u], det["linear"][u], det["quadratic"][u], m["prior_offset"])
 
 
-def test_a_q_that_is_not_positive_definite_is_flagged_and_its_neighbours_are_right():
-    """Sigma^-1 of Gaussian 0 has a negative diagonal, on purpose: an utterance that lands on it gets Q = I - 8 gamma M'M, which
-    has a negative pivot.  An arithmetic flag for that utterance, not a fault; the others of the batch are untouched."""
-    G, D, S = 2, 3, NB + 5
-    m = R.integer_model(5, G, D, S)
-    m["sigma_inv"][0] = R.pack(-8.0 * np.eye(D))
+def _not_positive_definite(S, s0):
+    G, D = 2, 3
+    m = C.not_pd_model(G, D, S, s0)
     ie = P.IvectorExtractor(**m)
     sim_U = R.derived(m["M"], m["sigma_inv"])
-    rng = np.random.default_rng(1)
-    good = lambda T: (rng.integers(-4, 5, (T, D)).astype(np.float32), [(np.array([1], np.int32), np.array([0.5], np.float32))] * T)
-    bad = (rng.integers(-4, 5, (9, D)).astype(np.float32), [(np.array([0, 1], np.int32), np.array([1.0, 0.25], np.float32))] * 9)
-    utts = [good(12), bad, good(5)]
-    assert np.linalg.eigvalsh(R.extract(*bad, m["M"], m["sigma_inv"], m["prior_offset"], sim_U=sim_U)["quadratic"]).min() < 0
+    utts = C.not_pd_utterances(D)
+    bad = utts[1]
+    bad_Q = R.extract(*bad, m["M"], m["sigma_inv"], m["prior_offset"], sim_U=sim_U)["quadratic"]
+    assert np.linalg.eigvalsh(bad_Q).min() < 0
+    assert np.array_equal(bad_Q[:s0, :s0], np.eye(s0)) and s0 <= C.first_bad_pivot(bad_Q) < S
     iv, status, auxf, det = ie.extract([x for x, _ in utts], [p for _, p in utts], return_details=True)
     assert status.tolist() == [0, 1, 0]
     assert np.isfinite(iv).all() and np.isfinite(auxf).all() and not iv[1].any() and auxf[1] == 0.0
     for u in (0, 2):
         r = R.extract(*utts[u], m["M"], m["sigma_inv"], m["prior_offset"], sim_U=sim_U)
         check_solve(r, iv[u], auxf[u], det["linear"][u], det["quadratic"][u], m["prior_offset"])
+
+
+def test_a_q_that_is_not_positive_definite_is_flagged_and_its_neighbours_are_right():
+    """Sigma^-1 of Gaussian 0 has a negative diagonal, on purpose: an utterance that lands on it gets Q = I - 8 gamma M'M, which
+    has a negative pivot.  An arithmetic flag for that utterance, not a fault; the others of the batch are untouched."""
+    _not_positive_definite(NB + 5, 0)
+
+
+def test_a_bad_pivot_in_a_late_panel_is_flagged_too():
+    """With s0 = 2 kIvexPanel + 1 leading columns of every M_g zero the leading s0 x s0 block of Q is the identity: the bad pivot
+    comes in the third panel of the factorisation or later, after block-column updates that have earlier panels to subtract."""
+    _not_positive_definite(C.LATE_S, C.LATE_S0)
 
 
 # ------------------------------------------------------------------------------------------------------------------- batches
@@ -184,8 +203,11 @@ def test_an_utterance_has_the_same_bits_alone_and_anywhere_in_a_batch():
     others = [utt(int(T)) for T in rng.integers(1, 250, RT)]   # longer and shorter ones
     iv0, st0, ax0, det0 = ie.extract([mine[0]], [mine[1]], return_details=True)
     assert st0[0] == 0
-    for k in (0, RT // 2, RT):   # first, middle and last of RT + 1
-        batch = others[:k] + [mine] + others[k:]
+    more = [utt(int(T)) for T in rng.integers(1, 250, MAX_B - RT)]
+    # first, middle and last of RT + 1; the last of the first launch group and the only one of the second, of kIvexMaxBatch + 1
+    for k, rest in [(0, others), (RT // 2, others), (RT, others), (MAX_B - 1, others + more), (MAX_B, others + more)]:
+        batch = rest[:k] + [mine] + rest[k:]
+        assert len(batch) == (RT + 1 if k <= RT else MAX_B + 1)
         iv, st, ax, det = ie.extract([x for x, _ in batch], [p for _, p in batch], return_details=True)
         assert np.array_equal(iv[k].view(np.uint32), iv0[0].view(np.uint32)), k
         assert np.array_equal(ax[k:k + 1].view(np.uint64), ax0.view(np.uint64)), k

@@ -11,17 +11,18 @@ import numpy as np
 import pytest
 
 import helpers as H
+import ivector_cases as C
 import ivector_ref as R
 import ivector_train_ref as T
 import ubm_ref as UR
 from oracle import kaldi_io as kio
-from test_gpu_ivector import eps_of
+from ivector_cases import eps_of, random_utts
 
 pytestmark = pytest.mark.gpu
 P = H.pkg()
 BIN = os.path.join(H.ROOT, H.PKG_NAME, "bin")
 U53 = 2.0 ** -53
-SLOTS = 64
+SLOTS = C.SLOTS
 KEYS = ("gamma", "Y", "R", "S", "ivector_sum", "ivector_scatter")
 
 
@@ -52,38 +53,26 @@ def test_the_rank_update_refuses_what_it_cannot_run():
 
 
 # ------------------------------------------------------------------------------------------------------------------- posterior
-def random_utts(seed, n, G, D, lo=5, hi=40, scale=1.0):
-    rng = np.random.default_rng(seed)
-    out = []
-    for _ in range(n):
-        frames = int(rng.integers(lo, hi + 1))
-        x = (rng.normal(size=(frames, D)) * scale).astype(np.float32)
-        post = []
-        for _ in range(frames):
-            k = int(rng.integers(1, min(3, G) + 1))
-            w = rng.random(k) + 0.1
-            post.append((rng.permutation(G)[:k].astype(np.int32), (w / w.sum()).astype(np.float32)))
-        out.append((x, post))
-    return out
-
-
 def feats_posts(utts):
     return [x for x, _ in utts], [p for _, p in utts]
 
 
-@pytest.mark.parametrize("shape", [(5, 7, 6), (19, 33, 17), (8, 96, 33)])
+@pytest.mark.parametrize("shape", C.POSTERIOR_CASES)
 def test_the_posterior_kernel_within_bounds_from_the_restatements_q(shape):
-    """S below, and across, the solve's panel width of 32; D at its limit.  With eps = eps_of(Q) (Higham's backward error of the
-    Cholesky factor carried to a solution, cond_2(Q) 4 S (3 S + 1) u):
+    """S below, and across, the solve's panel width of 32; D at its limit; then S around one and two wavefronts of columns of Z
+    (a wave skips the rows of Z above its lowest column, which is row 0 for the first wave), the recipes' 400, and kIvexMaxS, where
+    every thread owns a column and the packed-index recovery sees its largest argument.  With eps = eps_of(Q) (Higham's backward
+    error of the Cholesky factor carried to a solution, cond_2(Q) 4 S (3 S + 1) u):
       Var     every column of the inverse is a solve with the factor, and forming L^-T L^-1 is a second pass with the same constant:
               |Var - Q^-1| <= 2 eps |Q^-1|_2.  What the device holds is the scatter Var + m m': the solution's error eps |m| enters
               through both factors of m m', and the sum is rounded once.
       Q Var   the residual of the same inverse: |Q Var - I| <= 2 eps, plus what taking m m' off the scatter again costs.
       logdet  S logarithms summed in order, S u sum |log L_ii|, and the factor's relative error eps on each of the S diagonals."""
     G, D, S = shape
-    m = R.random_model(17 + S, G, D, S)
+    m = C.posterior_model(G, D, S)
     ie = P.IvectorExtractor(**m)
-    utts = random_utts(S, 4, G, D)
+    n = C.posterior_utts_count(S)
+    utts = random_utts(S, n, G, D)
     feats, posts = feats_posts(utts)
     before = ie.extract(feats, posts)
     acc = P.IvexAccumulator(ie)
@@ -92,7 +81,7 @@ def test_the_posterior_kernel_within_bounds_from_the_restatements_q(shape):
     after = ie.extract(feats, posts)
     for a, b in zip(before, after):   # what ivector-extract returns is what it returned before there was an accumulator
         assert a.tobytes() == b.tobytes()
-    assert pend["m"].shape == (4, S)
+    assert pend["m"].shape == (n, S)
     sim_U = R.derived(m["M"], m["sigma_inv"])
     worst = np.zeros(4)
     for u, (x, post) in enumerate(utts):
@@ -206,6 +195,20 @@ def test_how_the_utterances_are_split_over_calls_changes_no_bit():
     assert not same_bits(whole, without)
 
 
+def test_the_split_changes_no_bit_at_a_size_beyond_two_wavefronts():
+    """the same at S = 129 with 66 utterances: the posterior kernel on three wavefronts of columns, the small sums over 34
+    workgroups and a flush of 64 followed by one of two"""
+    G, D, S = C.SPLIT_SHAPE
+    m = R.random_model(21, G, D, S, m_scale=C.m_scale_for(S))
+    utts = random_utts(5, C.SPLIT_UTTS, G, D)
+    ie = P.IvectorExtractor(**m)
+    whole, status = run_acc(ie, utts, [C.SPLIT_UTTS])
+    assert not status.any() and whole["num_ivectors"] == C.SPLIT_UTTS
+    by_one, _ = run_acc(ie, utts, [1])
+    mixed, _ = run_acc(ie, utts, [7, SLOTS])
+    assert same_bits(whole, by_one) and same_bits(whole, mixed)
+
+
 def test_frames_beyond_a_block_of_the_second_moment_change_no_bit_either():
     """the frames of the accepted utterances are cut into blocks of kFgmmAccFrameBlock (16384) for S_g: 7 utterances of about
     5000 frames straddle two block boundaries"""
@@ -229,8 +232,21 @@ def test_random_models_within_the_any_order_bound_of_the_restatement(update_vari
       R, ivector_scatter   the same n; the scatter's error is the posterior test's 2 eps |Q^-1|_2 + 2 eps |m| |m_a|.
       auxf                 per utterance sums of S^2 terms and of its pairs on top of the 70: n = 70 + S^2 + max n_u; the posterior
                            part moves by 2 eps of its absolute terms."""
-    G, D, S = 7, 9, 11
-    m = R.random_model(9, G, D, S)
+    _statistics_within_the_bound(C.STATS_CASES[0], update_variances)
+
+
+@pytest.mark.parametrize("shape", C.STATS_CASES[1:])
+def test_the_small_sums_beyond_one_workgroup_stay_within_the_same_bound(shape):
+    """ivex_small_sums_kernel has one thread per element of gamma, ivector_sum, ivector_scatter and the objective, in workgroups of
+    kIvexTrainThreads: at G = 5 the elements fill one workgroup up to S = 20, S = 21 is the first with a second one, and S = 70 has
+    eleven.  70 utterances, so that the flush at kIvexTrainSlots still happens.  The bounds are those of the test above."""
+    assert (C.small_sums_elements(shape[0], shape[2]) > C.TRAIN_THREADS) == (shape != C.STATS_CASES[1])
+    _statistics_within_the_bound(shape, True)
+
+
+def _statistics_within_the_bound(shape, update_variances):
+    G, D, S = shape
+    m = R.random_model(9, G, D, S, m_scale=C.m_scale_for(S))
     ie = P.IvectorExtractor(**m)
     utts = random_utts(12, 70, G, D)
     got, _ = run_acc(ie, utts, [70], update_variances=update_variances)
