@@ -208,8 +208,7 @@ struct FeatBatchReader::Impl {
   std::unique_ptr<MatrixTableIndexer> indexer;
   std::unique_ptr<SequentialMatrixReader> seq;
   FileMapper mapper;
-  Input in;
-  std::string in_path;
+  ArchiveCursor cursor;
   // the matrix that did not fit the batch before
   bool held = false;
   std::string held_key;
@@ -229,7 +228,7 @@ struct FeatBatchReader::Impl {
         } else {
           try {
             *m = Matrix();
-            if (!mapper.View(e, m, allow_cm)) ReadIndexedMatrix(e, &in, &in_path, m);
+            if (!mapper.View(e, m, allow_cm)) ReadIndexedMatrix(e, &cursor, m);
           } catch (const std::exception& ex) {
             err = ex.what();
           }

@@ -250,7 +250,7 @@ int ApplyCmvn(const ApplyOptions& o, const std::vector<std::string>& pos) {
   std::unordered_map<std::string, std::string> utt2spk;
   if (!o.utt2spk.empty()) utt2spk = xv::ReadTokenTable(o.utt2spk);
   std::unique_ptr<xv::RandomAccessDoubleMatrixReader> table;
-  xv::RandomAccessDoubleMatrixReader::Value global;
+  xv::DoubleMatrix global;
   if (per_key) {
     table.reset(new xv::RandomAccessDoubleMatrixReader(pos[0]));
   } else {
@@ -303,7 +303,7 @@ int ApplyCmvn(const ApplyOptions& o, const std::vector<std::string>& pos) {
         ++num_err;
         continue;
       }
-      const xv::RandomAccessDoubleMatrixReader::Value& st = per_key ? table->Get(skey) : global;
+      const xv::DoubleMatrix& st = per_key ? table->Value(skey) : global;
       if (st.rows != 2 || st.cols != b.cols + 1) {
         std::ostringstream m;
         m << "Dimension mismatch: cmvn stats have dimension " << st.rows << "x" << st.cols << ", feats have dimension " << b.cols

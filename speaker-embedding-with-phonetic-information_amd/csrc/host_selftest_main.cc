@@ -11,10 +11,18 @@
 //     exactly what the sequential reader delivers, through the archive itself and through a script file of its offsets;
 // 3. replays both files truncated at `variants` positions and with 1.5 x `variants` single bits flipped: every variant must either parse or
 //    throw KioError - never crash, hang or trip a sanitizer.
+//
+//   host_selftest tables <dir>
+//
+// reads every table <dir>/cases.txt names through the reader the line names and prints one line per event - key, dimensions
+// and a 64-bit hash of the value's bytes, or the error text - so that what the table readers deliver is pinned byte for byte
+// (tests/test_table_readers.py compares the dump with the one recorded under tests/golden/table_readers/).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
 
+#include <algorithm>
 #include <fstream>
 #include <sstream>
 #include <string>
@@ -57,12 +65,8 @@ int TryArchive(const std::string& bytes) {
     xv::Input in;
     in.OpenMemory(bytes.data(), bytes.size());
     for (int n = 0; n < 100000; ++n) {
-      int c;
-      while ((c = in.Peek()) >= 0 && isspace(c)) in.Get();
-      if (c < 0) break;
       std::string key;
-      while ((c = in.Peek()) >= 0 && !isspace(c)) key.push_back((char)in.Get());
-      in.Get();
+      if (!xv::ReadKey(in, &key)) break;
       const bool binary = xv::ReadBinaryHeader(in);
       xv::Matrix m;
       xv::ReadMatrix(in, binary, &m);
@@ -84,8 +88,8 @@ int CheckIndexer(const std::string& rspec, const std::string& seq_rspec, long* v
   xv::MatrixTableIndexer idx(rspec);
   if (!idx.usable()) return 2;
   xv::SequentialMatrixReader rd(seq_rspec);
-  xv::Input in;
-  std::string in_path, key, err;
+  xv::ArchiveCursor cursor;
+  std::string key, err;
   xv::Matrix want, got;
   xv::MatrixTableIndexer::Entry e;
   for (;;) {
@@ -93,7 +97,7 @@ int CheckIndexer(const std::string& rspec, const std::string& seq_rspec, long* v
     if (a != b) return 1;
     if (!a) return 0;
     if (!e.error.empty() || !err.empty() || e.key != key) return 1;
-    xv::ReadIndexedMatrix(e, &in, &in_path, &got);
+    xv::ReadIndexedMatrix(e, &cursor, &got);
     if (got.rows != want.rows || got.cols != want.cols || got.data != want.data) return 1;
     if (e.rows >= 0 && (e.rows != want.rows || e.cols != want.cols)) return 1;
     // the VIEW of the same object in the mapped file (what the reader threads of a table job hand out): a binary float matrix
@@ -118,8 +122,7 @@ int TryIndexedFile(const std::string& path) {
   try {
     xv::MatrixTableIndexer idx("ark:" + path);
     if (!idx.usable()) return 1;
-    xv::Input in;
-    std::string in_path;
+    xv::ArchiveCursor cursor;
     xv::MatrixTableIndexer::Entry e;
     xv::Matrix m;
     xv::FileMapper mapper;
@@ -136,7 +139,7 @@ int TryIndexedFile(const std::string& path) {
           (void)last;
         }
       }
-      xv::ReadIndexedMatrix(e, &in, &in_path, &m);
+      xv::ReadIndexedMatrix(e, &cursor, &m);
     }
     return 0;
   } catch (const xv::KioError&) {
@@ -148,11 +151,220 @@ int TryIndexedFile(const std::string& path) {
   }
 }
 
+// ------------------------------------------------------------------------------------- host_selftest tables <dir>
+// FNV-1a over the value's bytes
+struct Hash {
+  uint64_t h = 1469598103934665603ull;
+  void Add(const void* p, size_t n) {
+    for (size_t i = 0; i < n; ++i) h = (h ^ ((const unsigned char*)p)[i]) * 1099511628211ull;
+  }
+  void AddInt(int32_t v) { Add(&v, 4); }
+};
+
+std::string Describe(const xv::Matrix& m) {
+  Hash h;
+  h.Add(m.Data(), (size_t)m.rows * m.cols * sizeof(float));
+  char buf[64];
+  snprintf(buf, sizeof buf, "%dx%d\t%016llx", m.rows, m.cols, (unsigned long long)h.h);
+  return buf;
+}
+std::string Describe(const std::vector<float>& v) {
+  Hash h;
+  h.Add(v.data(), v.size() * sizeof(float));
+  char buf[64];
+  snprintf(buf, sizeof buf, "%zu\t%016llx", v.size(), (unsigned long long)h.h);
+  return buf;
+}
+std::string Describe(int rows, int cols, const std::vector<double>& v) {
+  Hash h;
+  h.Add(v.data(), v.size() * sizeof(double));
+  char buf[64];
+  snprintf(buf, sizeof buf, "%dx%d\t%016llx", rows, cols, (unsigned long long)h.h);
+  return buf;
+}
+std::string Describe(const xv::IntVecVec& v) {
+  Hash h;
+  size_t total = 0;
+  for (const auto& l : v) {
+    h.AddInt((int32_t)l.size());
+    h.Add(l.data(), l.size() * 4);
+    total += l.size();
+  }
+  char buf[64];
+  snprintf(buf, sizeof buf, "%zu/%zu\t%016llx", v.size(), total, (unsigned long long)h.h);
+  return buf;
+}
+std::string Describe(const xv::Posterior& p) {
+  Hash h;
+  size_t total = 0;
+  for (const auto& frame : p) {
+    h.AddInt((int32_t)frame.size());
+    for (const auto& e : frame) {
+      h.AddInt(e.first);
+      h.Add(&e.second, 4);
+    }
+    total += frame.size();
+  }
+  char buf[64];
+  snprintf(buf, sizeof buf, "%zu/%zu\t%016llx", p.size(), total, (unsigned long long)h.h);
+  return buf;
+}
+
+void Event(const std::string& tag, const std::string& key, const std::string& what) {
+  printf("%s\t%s\t%s\n", tag.c_str(), key.c_str(), what.c_str());
+}
+
+// kSorted: the readers of Gaussian selections and posteriors also say whether the rspecifier promised sorted keys
+template <class Reader, class Value, bool kSorted = false>
+void DumpSequential(const std::string& tag, const std::string& rspec) {
+  Reader rd(rspec);
+  if constexpr (kSorted) Event(tag, "-", std::string("sorted\t") + (rd.sorted() ? "1" : "0"));
+  std::string key, err;
+  Value v;
+  while (rd.Next(&key, &v, &err)) Event(tag, key, err.empty() ? Describe(v) : "error\t" + err);
+  Event(tag, "-", "close\t" + std::to_string(rd.Close()));
+}
+
+// the index pass, the read of every entry it located and the view of the same object in the mapped file
+void DumpIndexed(const std::string& tag, const std::string& rspec) {
+  xv::MatrixTableIndexer idx(rspec);
+  Event(tag, "-", std::string("usable\t") + (idx.usable() ? "1" : "0"));
+  if (!idx.usable()) return;
+  xv::FileMapper mapper;
+  xv::ArchiveCursor cursor;
+  xv::MatrixTableIndexer::Entry e;
+  while (idx.Next(&e)) {
+    char where[96];
+    snprintf(where, sizeof where, "\toffset=%ld\trows=%d\tcols=%d", e.offset, e.rows, e.cols);
+    Event(tag, e.key, "rx=" + e.rx + where);
+    if (!e.error.empty()) {
+      Event(tag, e.key, "error\t" + e.error);
+      continue;
+    }
+    try {
+      xv::Matrix m, view;
+      xv::ReadIndexedMatrix(e, &cursor, &m);
+      Event(tag, e.key, Describe(m));
+      if (!mapper.View(e, &view, true)) {
+        Event(tag, e.key, "view\tnone");
+      } else if (view.cm) {
+        xv::Matrix full;
+        xv::ExpandCompressedView(view, &full);
+        Event(tag, e.key, "view\tcompressed\t" + Describe(full));
+      } else {
+        Event(tag, e.key, "view\tfloat\t" + Describe(view));
+      }
+    } catch (const std::exception& ex) {
+      Event(tag, e.key, std::string("thrown\t") + ex.what());
+    }
+  }
+}
+
+// ops: "has:KEY", "value:KEY", "forget:KEY", in the order given
+template <class Reader, class Fn>
+void DumpRandomAccess(const std::string& tag, const std::string& rspec, const std::vector<std::string>& ops, Fn value) {
+  Reader rd(rspec);
+  for (const std::string& op : ops) {
+    const size_t c = op.find(':');
+    const std::string what = op.substr(0, c), key = op.substr(c + 1);
+    try {
+      if (what == "has") Event(tag, key, std::string("has\t") + (rd.HasKey(key) ? "1" : "0"));
+      else Event(tag, key, what + "\t" + value(rd, what, key));
+    } catch (const std::exception& ex) {
+      Event(tag, key, what + "\tthrown\t" + ex.what());
+    }
+  }
+}
+
+template <class Map, class Fn>
+void DumpMap(const std::string& tag, const Map& table, Fn text) {
+  std::vector<std::string> keys;
+  for (const auto& kv : table) keys.push_back(kv.first);
+  std::sort(keys.begin(), keys.end());
+  for (const std::string& k : keys) Event(tag, k, text(table.at(k)));
+}
+
+std::vector<std::string> SplitTabs(const std::string& s) {
+  std::vector<std::string> out;
+  size_t a = 0;
+  for (;;) {
+    const size_t b = s.find('\t', a);
+    out.push_back(s.substr(a, b == std::string::npos ? b : b - a));
+    if (b == std::string::npos) return out;
+    a = b + 1;
+  }
+}
+
+int RunTables(const char* dir) {
+  if (chdir(dir) != 0) {
+    fprintf(stderr, "host_selftest: cannot enter %s\n", dir);
+    return 2;
+  }
+  std::ifstream cases("cases.txt");
+  if (!cases) {
+    fprintf(stderr, "host_selftest: no cases.txt in %s\n", dir);
+    return 2;
+  }
+  std::string line;
+  while (std::getline(cases, line)) {
+    if (line.empty() || line[0] == '#') continue;
+    std::vector<std::string> f = SplitTabs(line);
+    if (f.size() < 2) {
+      fprintf(stderr, "host_selftest: bad line in cases.txt: %s\n", line.c_str());
+      return 2;
+    }
+    const std::string reader = f[0], rspec = f[1], tag = reader + "\t" + rspec;
+    const std::vector<std::string> ops(f.begin() + 2, f.end());
+    try {
+      if (reader == "seq-matrix") DumpSequential<xv::SequentialMatrixReader, xv::Matrix>(tag, rspec);
+      else if (reader == "seq-vector") DumpSequential<xv::SequentialVectorReader, std::vector<float>>(tag, rspec);
+      else if (reader == "seq-gselect") DumpSequential<xv::SequentialGselectReader, xv::IntVecVec, true>(tag, rspec);
+      else if (reader == "seq-posterior") DumpSequential<xv::SequentialPosteriorReader, xv::Posterior, true>(tag, rspec);
+      else if (reader == "indexed") DumpIndexed(tag, rspec);
+      else if (reader == "ra-vector")
+        DumpRandomAccess<xv::RandomAccessVectorReader>(tag, rspec, ops, [](xv::RandomAccessVectorReader& rd, const std::string& what, const std::string& key) {
+          if (what == "forget") {
+            rd.Forget(key);
+            return std::string("done");
+          }
+          return Describe(rd.Value(key));
+        });
+      else if (reader == "ra-double-matrix")
+        DumpRandomAccess<xv::RandomAccessDoubleMatrixReader>(tag, rspec, ops, [](xv::RandomAccessDoubleMatrixReader& rd, const std::string&, const std::string& key) {
+          const auto& v = rd.Value(key);
+          return Describe(v.rows, v.cols, v.data);
+        });
+      else if (reader == "int32") DumpMap(tag, xv::ReadInt32Table(rspec), [](int32_t v) { return std::to_string(v); });
+      else if (reader == "float")
+        DumpMap(tag, xv::ReadFloatTable(rspec), [](float v) {
+          char buf[32];
+          snprintf(buf, sizeof buf, "%.9g", v);
+          return std::string(buf);
+        });
+      else if (reader == "token") DumpMap(tag, xv::ReadTokenTable(rspec), [](const std::string& v) { return v; });
+      else if (reader == "token-list")
+        for (const xv::TokenList& e : xv::ReadTokenVectorTable(rspec)) {
+          std::string all;
+          for (const std::string& t : e.tokens) all += (all.empty() ? "" : " ") + t;
+          Event(tag, e.key, std::to_string(e.tokens.size()) + "\t" + all);
+        }
+      else {
+        fprintf(stderr, "host_selftest: unknown reader %s in cases.txt\n", reader.c_str());
+        return 2;
+      }
+    } catch (const std::exception& ex) {
+      Event(tag, "-", std::string("thrown\t") + ex.what());
+    }
+  }
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc == 3 && strcmp(argv[1], "tables") == 0) return RunTables(argv[2]);
   if (argc != 4 && argc != 5) {
-    fprintf(stderr, "usage: host_selftest <model.raw> <output-node> <features.ark> [variants]\n");
+    fprintf(stderr, "usage: host_selftest <model.raw> <output-node> <features.ark> [variants]\n       host_selftest tables <dir>\n");
     return 2;
   }
   const int variants = argc == 5 ? atoi(argv[4]) : 200;

@@ -175,18 +175,8 @@ void Input::Open(const std::string& rx_in, bool drain_pipe) {
     }
     return;
   }
-  // "file:offset"
-  std::string path = rx;
-  long offset = -1;
-  size_t c = rx.rfind(':');
-  if (c != std::string::npos && c + 1 < rx.size()) {
-    bool digits = true;
-    for (size_t i = c + 1; i < rx.size(); ++i) digits = digits && isdigit((unsigned char)rx[i]);
-    if (digits) {
-      path = rx.substr(0, c);
-      offset = strtol(rx.c_str() + c + 1, nullptr, 10);
-    }
-  }
+  std::string path;
+  const long offset = SplitOffset(rx, &path);   // "file:offset"
   // A regular file is MAPPED (read-only) and read through the memory backend: the index pass of a table job skips from header
   // to header - fseek + ftell + fstat and a refill of the stdio buffer per utterance, 3 us of a 16 us host budget - and a
   // sequential reader copies straight out of the page cache.  XVEC_DEBUG=mmap=0: stdio, as before.
@@ -966,14 +956,7 @@ WspecifierOptions ParseWspecifier(const std::string& wspecifier) {
 }
 
 // ------------------------------------------------------------------------------------- readers
-SequentialMatrixReader::SequentialMatrixReader(const std::string& rspecifier) {
-  opts_ = ParseRspecifier(rspecifier);
-  in_.Open(opts_.rxfilename, /*drain_pipe=*/!opts_.is_scp);   // an archive through a pipe: the feature pipe of extract_xvectors_new.sh:79
-}
-
-SequentialMatrixReader::~SequentialMatrixReader() {}
-
-static bool ReadKey(Input& in, std::string* key) {
+bool ReadKey(Input& in, std::string* key) {
   key->clear();
   int c;
   while ((c = in.Peek()) >= 0 && isspace(c)) in.Get();
@@ -983,53 +966,7 @@ static bool ReadKey(Input& in, std::string* key) {
   return true;
 }
 
-bool SequentialMatrixReader::Next(std::string* key, Matrix* m, std::string* error) {
-  error->clear();
-  if (!opts_.is_scp) {
-    if (!ReadKey(in_, key)) return false;
-    bool binary = ReadBinaryHeader(in_);
-    ReadMatrix(in_, binary, m);  // a corrupt archive is fatal, as in Kaldi
-    return true;
-  }
-  // scp: "key rxfilename\n"
-  if (!ReadKey(in_, key)) return false;
-  std::string rx;
-  int c;
-  while ((c = in_.Get()) >= 0 && c != '\n') rx.push_back((char)c);
-  rx = Trim(rx);
-  if (rx.empty()) {
-    *error = "empty rxfilename for key " + *key;
-    return true;
-  }
-  try {
-    // fast path: consecutive entries of the same archive
-    std::string path = rx;
-    long offset = -1;
-    size_t colon = rx.rfind(':');
-    if (rx.back() != '|' && colon != std::string::npos && colon + 1 < rx.size() &&
-        std::all_of(rx.begin() + colon + 1, rx.end(), [](char ch) { return isdigit((unsigned char)ch); })) {
-      path = rx.substr(0, colon);
-      offset = strtol(rx.c_str() + colon + 1, nullptr, 10);
-    }
-    if (offset >= 0 && path == data_path_ && data_in_.IsOpen()) {
-      data_in_.Seek(offset);
-    } else {
-      data_in_.Open(rx);
-      data_path_ = offset >= 0 ? path : std::string();
-    }
-    bool binary = ReadBinaryHeader(data_in_);
-    ReadMatrix(data_in_, binary, m);
-    if (data_path_.empty()) data_in_.Close();
-  } catch (const KioError& e) {
-    *error = e.what();
-  }
-  return true;
-}
-
-int SequentialMatrixReader::Close() { return in_.Close(); }
-
-// "path:123" -> (path, 123); anything else -> offset -1
-static long SplitOffset(const std::string& rx, std::string* path) {
+long SplitOffset(const std::string& rx, std::string* path) {
   *path = rx;
   size_t colon = rx.rfind(':');
   if (!rx.empty() && rx.back() != '|' && colon != std::string::npos && colon + 1 < rx.size() &&
@@ -1039,6 +976,98 @@ static long SplitOffset(const std::string& rx, std::string* path) {
   }
   return -1;
 }
+
+bool ReadScpLine(Input& in, std::string* key, std::string* rx) {
+  if (!ReadKey(in, key)) return false;
+  rx->clear();
+  int c;
+  while ((c = in.Get()) >= 0 && c != '\n') rx->push_back((char)c);
+  *rx = Trim(*rx);
+  return true;
+}
+
+static std::string EmptyRxfilename(const std::string& key) { return "empty rxfilename for key " + key; }
+
+Input& ArchiveCursor::AtEntry(const std::string& rx) {
+  std::string path;
+  const long offset = SplitOffset(rx, &path);
+  if (offset >= 0 && Holds(path)) {
+    in_.Seek(offset);
+  } else {
+    path_.clear();
+    in_.Open(rx);   // positions itself
+    if (offset >= 0) path_ = path;
+  }
+  return in_;
+}
+
+Input& ArchiveCursor::At(const std::string& path, long offset) {
+  if (offset < 0 || !Holds(path)) {
+    path_.clear();
+    in_.Open(path);
+    if (offset >= 0) path_ = path;
+  }
+  if (offset >= 0) in_.Seek(offset);
+  return in_;
+}
+
+void ArchiveCursor::Done() {
+  if (path_.empty()) in_.Close();
+}
+
+void ArchiveCursor::Reset() {
+  in_.Close();
+  path_.clear();
+}
+
+// How a table's value is parsed: the one call of each Read function on behalf of a table reader.
+static void ReadValue(Input& in, bool binary, Matrix* m) { ReadMatrix(in, binary, m); }
+static void ReadValue(Input& in, bool binary, std::vector<float>* v) { ReadVector(in, binary, v); }
+static void ReadValue(Input& in, bool binary, DoubleMatrix* m) { ReadMatrixDouble(in, binary, &m->rows, &m->cols, &m->data); }
+static void ReadValue(Input& in, bool binary, IntVecVec* v) { ReadIntVecVec(in, binary, v); }
+static void ReadValue(Input& in, bool binary, Posterior* p) { ReadPosterior(in, binary, p); }
+
+// the object `in` stands at: its optional binary header and the value
+template <class T>
+static void ReadObject(Input& in, T* value) {
+  const bool binary = ReadBinaryHeader(in);
+  ReadValue(in, binary, value);
+}
+
+template <class T>
+SequentialTableReader<T>::SequentialTableReader(const std::string& rspecifier, bool drain_pipe, bool permissive_skips)
+    : opts_(ParseRspecifier(rspecifier)), permissive_skips_(permissive_skips) {
+  in_.Open(opts_.rxfilename, drain_pipe && !opts_.is_scp);
+}
+
+template <class T>
+bool SequentialTableReader<T>::Next(std::string* key, T* value, std::string* error) {
+  for (;;) {
+    error->clear();
+    if (!opts_.is_scp) {
+      if (!ReadKey(in_, key)) return false;
+      ReadObject(in_, value);   // a corrupt archive is fatal, as in Kaldi
+      return true;
+    }
+    std::string rx;
+    if (!ReadScpLine(in_, key, &rx)) return false;
+    try {
+      if (rx.empty()) throw KioError(EmptyRxfilename(*key));
+      ReadObject(data_.AtEntry(rx), value);
+      data_.Done();
+      return true;
+    } catch (const KioError& e) {
+      if (permissive_skips_ && opts_.permissive) continue;
+      *error = e.what();
+      return true;
+    }
+  }
+}
+
+template class SequentialTableReader<Matrix>;
+template class SequentialTableReader<std::vector<float>>;
+template class SequentialTableReader<IntVecVec>;
+template class SequentialTableReader<Posterior>;
 
 MatrixTableIndexer::MatrixTableIndexer(const std::string& rspecifier) {
   opts_ = ParseRspecifier(rspecifier);
@@ -1062,8 +1091,8 @@ MatrixTableIndexer::MatrixTableIndexer(const std::string& rspecifier) {
 
 bool MatrixTableIndexer::Next(Entry* e) {
   *e = Entry();
-  if (!ReadKey(in_, &e->key)) return false;
   if (!opts_.is_scp) {
+    if (!ReadKey(in_, &e->key)) return false;
     e->rx = in_.Name();
     {
       std::string p;
@@ -1074,51 +1103,29 @@ bool MatrixTableIndexer::Next(Entry* e) {
     SkipBinaryMatrix(in_, &e->rows, &e->cols);
     return true;
   }
-  std::string rx;
-  int c;
-  while ((c = in_.Get()) >= 0 && c != '\n') rx.push_back((char)c);
-  rx = Trim(rx);
-  if (rx.empty()) {
-    e->error = "empty rxfilename for key " + e->key;
+  if (!ReadScpLine(in_, &e->key, &e->rx)) return false;
+  if (e->rx.empty()) {
+    e->error = EmptyRxfilename(e->key);
     return true;
   }
   std::string path;
-  const long offset = SplitOffset(rx, &path);
-  e->rx = rx;
+  const long offset = SplitOffset(e->rx, &path);
   if (offset < 0) return true;   // pipe or whole file: the reading thread opens it
   try {
-    if (!(path == data_path_ && data_in_.IsOpen())) {
-      data_in_.Open(path);
-      data_path_ = path;
-    }
-    data_in_.Seek(offset);
+    Input& data = data_.At(path, offset);
     e->rx = path;
     e->offset = offset;
-    if (ReadBinaryHeader(data_in_)) SkipBinaryMatrix(data_in_, &e->rows, &e->cols);   // text objects keep rows = -1
+    if (ReadBinaryHeader(data)) SkipBinaryMatrix(data, &e->rows, &e->cols);   // text objects keep rows = -1
   } catch (const KioError& ex) {
     e->error = ex.what();
-    data_in_.Close();
-    data_path_.clear();
+    data_.Reset();
   }
   return true;
 }
 
-void ReadIndexedMatrix(const MatrixTableIndexer::Entry& e, Input* in, std::string* in_path, Matrix* m) {
-  if (e.offset < 0) {
-    Input one;
-    one.Open(e.rx);
-    const bool binary = ReadBinaryHeader(one);
-    ReadMatrix(one, binary, m);
-    one.Close();
-    return;
-  }
-  if (!(in->IsOpen() && *in_path == e.rx)) {
-    in->Open(e.rx);
-    *in_path = e.rx;
-  }
-  in->Seek(e.offset);
-  const bool binary = ReadBinaryHeader(*in);
-  ReadMatrix(*in, binary, m);
+void ReadIndexedMatrix(const MatrixTableIndexer::Entry& e, ArchiveCursor* cursor, Matrix* m) {
+  ReadObject(cursor->At(e.rx, e.offset), m);
+  cursor->Done();
 }
 
 namespace {
@@ -1215,72 +1222,56 @@ FileMapper::~FileMapper() {
     if (kv.second.base) (void)munmap((void*)kv.second.base, kv.second.size);
 }
 
-RandomAccessVectorReader::RandomAccessVectorReader(const std::string& rspecifier) {
-  RspecifierOptions o = ParseRspecifier(rspecifier);
+template <class T>
+RandomAccessTableReader<T>::RandomAccessTableReader(const std::string& rspecifier) {
+  const RspecifierOptions o = ParseRspecifier(rspecifier);
   Input in;
   in.Open(o.rxfilename);
   std::string key;
-  if (o.is_scp) {
-    while (ReadKey(in, &key)) {
-      std::string rx;
-      int c;
-      while ((c = in.Get()) >= 0 && c != '\n') rx.push_back((char)c);
-      Entry e;
-      e.key = key;
-      e.rx = Trim(rx);
-      entries_.push_back(std::move(e));
-    }
-  } else {
-    while (ReadKey(in, &key)) {
-      Entry e;
-      e.key = key;
-      bool binary = ReadBinaryHeader(in);
-      ReadVector(in, binary, &e.v);
+  for (;;) {
+    Entry e;
+    if (o.is_scp) {
+      if (!ReadScpLine(in, &key, &e.rx)) break;
+    } else {
+      if (!ReadKey(in, &key)) break;
+      ReadObject(in, &e.v);
       e.loaded = true;
-      entries_.push_back(std::move(e));
     }
+    index_.emplace(key, (int)entries_.size());   // the first entry of a key wins
+    entries_.push_back(std::move(e));
   }
 }
 
-int RandomAccessVectorReader::Find(const std::string& key) {
-  if (index_.size() != entries_.size()) {
-    index_.clear();
-    for (size_t i = 0; i < entries_.size(); ++i) index_.emplace(entries_[i].key, (int)i);   // first entry of a key wins
-  }
+template <class T>
+const T& RandomAccessTableReader<T>::Value(const std::string& key) {
   auto it = index_.find(key);
-  return it == index_.end() ? -1 : it->second;
-}
-
-SequentialVectorReader::SequentialVectorReader(const std::string& rspecifier) {
-  opts_ = ParseRspecifier(rspecifier);
-  in_.Open(opts_.rxfilename);
-}
-
-bool SequentialVectorReader::Next(std::string* key, std::vector<float>* v, std::string* error) {
-  error->clear();
-  if (!ReadKey(in_, key)) return false;
-  if (!opts_.is_scp) {
-    bool binary = ReadBinaryHeader(in_);
-    ReadVector(in_, binary, v);
-    return true;
+  if (it == index_.end()) throw KioError("key not found in table: " + key);
+  Entry& e = entries_[it->second];
+  if (!e.loaded) {
+    // "file:offset" entries (what copy-vector / compute-vad-decision write): the archive is opened - mapped - once and every
+    // lookup is a seek.  Opening it per key was 8 us per utterance in the consumer thread of a table job with a VAD table, the
+    // wall of the recipes' own pipeline once it ran on the device (100 k utt/s; profiles/r06_host_cost.md).
+    std::string path;
+    const long offset = SplitOffset(e.rx, &path);
+    ReadObject(data_.At(path, offset), &e.v);
+    data_.Done();
+    e.loaded = true;
   }
-  std::string rx;
-  int c;
-  while ((c = in_.Get()) >= 0 && c != '\n') rx.push_back((char)c);
-  rx = Trim(rx);
-  try {
-    if (rx.empty()) throw KioError("empty rxfilename for key " + *key);
-    Input data;
-    data.Open(rx);
-    bool binary = ReadBinaryHeader(data);
-    ReadVector(data, binary, v);
-  } catch (const KioError& e) {
-    *error = e.what();
-  }
-  return true;
+  return e.v;
 }
 
-int SequentialVectorReader::Close() { return in_.Close(); }
+template <class T>
+void RandomAccessTableReader<T>::Forget(const std::string& key) {
+  auto it = index_.find(key);
+  if (it == index_.end()) return;
+  Entry& e = entries_[it->second];
+  if (e.rx.empty() || !e.loaded) return;   // an archive loaded as a whole has no way to read the value again
+  e.v = T();
+  e.loaded = false;
+}
+
+template class RandomAccessTableReader<std::vector<float>>;
+template class RandomAccessTableReader<DoubleMatrix>;
 
 std::vector<TokenList> ReadTokenVectorTable(const std::string& rspecifier) {
   RspecifierOptions o = ParseRspecifier(rspecifier);
@@ -1327,24 +1318,25 @@ std::unordered_map<std::string, std::string> ReadTokenTable(const std::string& r
   return out;
 }
 
-std::unordered_map<std::string, int32_t> ReadInt32Table(const std::string& rspecifier) {
+// "key value" per entry, the value in text or as a binary object; `what` words the messages
+template <class T, class Binary, class Text>
+static std::unordered_map<std::string, T> ReadScalarTable(const std::string& rspecifier, const std::string& what, Binary binary, Text text) {
   RspecifierOptions o = ParseRspecifier(rspecifier);
-  if (o.is_scp) throw KioError("int32 tables are read from archives (ark:...), not scp: " + rspecifier);
+  if (o.is_scp) throw KioError(what + " tables are read from archives (ark:...), not scp: " + rspecifier);
   Input in;
   in.Open(o.rxfilename);
-  std::unordered_map<std::string, int32_t> out;
+  std::unordered_map<std::string, T> out;
   std::string key;
   while (ReadKey(in, &key)) {
-    int32_t v;
+    T v;
     if (in.Peek() == 0) {
       ReadBinaryHeader(in);
-      v = ReadInt32(in, true);
+      v = binary(in);
     } else {
       const std::string w = ReadTextWord(in);
       char* end = nullptr;
-      const long l = strtol(w.c_str(), &end, 10);
-      if (end == w.c_str() || *end) throw KioError("bad int32 value '" + w + "' for key " + key + " in " + rspecifier);
-      v = (int32_t)l;
+      v = text(w.c_str(), &end);
+      if (end == w.c_str() || *end) throw KioError("bad " + what + " value '" + w + "' for key " + key + " in " + rspecifier);
     }
     int c;
     while ((c = in.Peek()) >= 0 && c != '\n' && isspace(c)) in.Get();
@@ -1353,6 +1345,16 @@ std::unordered_map<std::string, int32_t> ReadInt32Table(const std::string& rspec
   }
   in.Close();
   return out;
+}
+
+std::unordered_map<std::string, int32_t> ReadInt32Table(const std::string& rspecifier) {
+  return ReadScalarTable<int32_t>(
+      rspecifier, "int32", [](Input& in) { return ReadInt32(in, true); }, [](const char* s, char** end) { return (int32_t)strtol(s, end, 10); });
+}
+
+std::unordered_map<std::string, float> ReadFloatTable(const std::string& rspecifier) {
+  return ReadScalarTable<float>(
+      rspecifier, "float", [](Input& in) { return (float)ReadFloatOrDouble(in, true); }, [](const char* s, char** end) { return strtof(s, end); });
 }
 
 void ReadVectorObject(const std::string& rxfilename, std::vector<float>* v) {
@@ -1377,94 +1379,6 @@ void WriteVectorObject(const std::string& wxfilename, bool binary, const float* 
   if (binary) out.Write("\0B", 2);
   WriteVector(out, binary, v, n);
   out.Close();
-}
-
-bool RandomAccessVectorReader::HasKey(const std::string& key) { return Find(key) >= 0; }
-
-const std::vector<float>& RandomAccessVectorReader::Value(const std::string& key) {
-  int i = Find(key);
-  if (i < 0) throw KioError("key not found in table: " + key);
-  Entry& e = entries_[i];
-  if (!e.loaded) {
-    // "file:offset" entries (what copy-vector / compute-vad-decision write): the archive is opened - mapped - once and every
-    // lookup is a seek.  Opening it per key was 8 us per utterance in the consumer thread of a table job with a VAD table, the
-    // wall of the recipes' own pipeline once it ran on the device (100 k utt/s; profiles/r06_host_cost.md).
-    std::string path;
-    const long off = SplitOffset(e.rx, &path);
-    if (off >= 0) {
-      if (!(data_in_.IsOpen() && data_path_ == path)) {
-        data_in_.Open(path);
-        data_path_ = path;
-      }
-      data_in_.Seek(off);
-      const bool binary = ReadBinaryHeader(data_in_);
-      ReadVector(data_in_, binary, &e.v);
-    } else {
-      Input in;
-      in.Open(e.rx);
-      const bool binary = ReadBinaryHeader(in);
-      ReadVector(in, binary, &e.v);
-    }
-    e.loaded = true;
-  }
-  return e.v;
-}
-
-RandomAccessDoubleMatrixReader::RandomAccessDoubleMatrixReader(const std::string& rspecifier) {
-  RspecifierOptions o = ParseRspecifier(rspecifier);
-  Input in;
-  in.Open(o.rxfilename);
-  std::string key;
-  while (ReadKey(in, &key)) {
-    Entry e;
-    if (o.is_scp) {
-      std::string rx;
-      int c;
-      while ((c = in.Get()) >= 0 && c != '\n') rx.push_back((char)c);
-      e.rx = Trim(rx);
-    } else {
-      const bool binary = ReadBinaryHeader(in);
-      ReadMatrixDouble(in, binary, &e.v.rows, &e.v.cols, &e.v.data);
-      e.loaded = true;
-    }
-    index_.emplace(key, (int)entries_.size());   // the first entry of a key wins
-    entries_.push_back(std::move(e));
-  }
-}
-
-const RandomAccessDoubleMatrixReader::Value& RandomAccessDoubleMatrixReader::Get(const std::string& key) {
-  auto it = index_.find(key);
-  if (it == index_.end()) throw KioError("key not found in table: " + key);
-  Entry& e = entries_[it->second];
-  if (!e.loaded) {
-    std::string path;
-    const long off = SplitOffset(e.rx, &path);
-    if (off >= 0) {
-      if (!(data_in_.IsOpen() && data_path_ == path)) {
-        data_in_.Open(path);
-        data_path_ = path;
-      }
-      data_in_.Seek(off);
-      const bool binary = ReadBinaryHeader(data_in_);
-      ReadMatrixDouble(data_in_, binary, &e.v.rows, &e.v.cols, &e.v.data);
-    } else {
-      Input in;
-      in.Open(e.rx);
-      const bool binary = ReadBinaryHeader(in);
-      ReadMatrixDouble(in, binary, &e.v.rows, &e.v.cols, &e.v.data);
-    }
-    e.loaded = true;
-  }
-  return e.v;
-}
-
-void RandomAccessVectorReader::Forget(const std::string& key) {
-  const int i = Find(key);
-  if (i < 0) return;
-  Entry& e = entries_[i];
-  if (e.rx.empty() || !e.loaded) return;   // an archive loaded as a whole has no way to read the value again
-  std::vector<float>().swap(e.v);
-  e.loaded = false;
 }
 
 // ------------------------------------------------------------------------------------- writer
@@ -1857,88 +1771,6 @@ void WritePosterior(Output& out, bool binary, const Posterior& p) {
     out.Puts("] ");
   }
   out.Put('\n');
-}
-
-SequentialObjectReader::SequentialObjectReader(const std::string& rspecifier) {
-  opts_ = ParseRspecifier(rspecifier);
-  in_.Open(opts_.rxfilename);
-}
-
-bool SequentialObjectReader::NextEntry(std::string* key, Input** obj, std::string* error) {
-  for (;;) {
-    error->clear();
-    if (!ReadKey(in_, key)) return false;
-    if (!opts_.is_scp) {
-      *obj = &in_;
-      return true;
-    }
-    std::string rx;
-    int c;
-    while ((c = in_.Get()) >= 0 && c != '\n') rx.push_back((char)c);
-    rx = Trim(rx);
-    try {
-      if (rx.empty()) throw KioError("empty rxfilename for key " + *key);
-      data_.Open(rx);
-      *obj = &data_;
-      return true;
-    } catch (const KioError& e) {
-      if (opts_.permissive) continue;
-      *error = e.what();
-      *obj = nullptr;
-      return true;
-    }
-  }
-}
-
-void SequentialObjectReader::DoneEntry() {
-  if (opts_.is_scp && data_.IsOpen()) data_.Close();
-}
-
-bool SequentialGselectReader::Next(std::string* key, IntVecVec* v, std::string* error) {
-  Input* obj = nullptr;
-  if (!NextEntry(key, &obj, error)) return false;
-  if (!obj) return true;
-  const bool binary = ReadBinaryHeader(*obj);
-  ReadIntVecVec(*obj, binary, v);
-  DoneEntry();
-  return true;
-}
-
-bool SequentialPosteriorReader::Next(std::string* key, Posterior* p, std::string* error) {
-  Input* obj = nullptr;
-  if (!NextEntry(key, &obj, error)) return false;
-  if (!obj) return true;
-  const bool binary = ReadBinaryHeader(*obj);
-  ReadPosterior(*obj, binary, p);
-  DoneEntry();
-  return true;
-}
-
-std::unordered_map<std::string, float> ReadFloatTable(const std::string& rspecifier) {
-  RspecifierOptions o = ParseRspecifier(rspecifier);
-  if (o.is_scp) throw KioError("float tables are read from archives (ark:...), not scp: " + rspecifier);
-  Input in;
-  in.Open(o.rxfilename);
-  std::unordered_map<std::string, float> out;
-  std::string key;
-  while (ReadKey(in, &key)) {
-    float v;
-    if (in.Peek() == 0) {
-      ReadBinaryHeader(in);
-      v = (float)ReadFloatOrDouble(in, true);
-    } else {
-      const std::string w = ReadTextWord(in);
-      char* end = nullptr;
-      v = strtof(w.c_str(), &end);
-      if (end == w.c_str() || *end) throw KioError("bad float value '" + w + "' for key " + key + " in " + rspecifier);
-    }
-    int c;
-    while ((c = in.Peek()) >= 0 && c != '\n' && isspace(c)) in.Get();
-    if (in.Peek() == '\n') in.Get();
-    out[key] = v;
-  }
-  in.Close();
-  return out;
 }
 
 }  // namespace xv

@@ -164,23 +164,66 @@ struct WspecifierOptions {
 };
 WspecifierOptions ParseWspecifier(const std::string& wspecifier);
 
-// Sequential reader of a table of float matrices ("ark:..." or "scp:...").
-class SequentialMatrixReader {
+// ---------------------------------------------------------------------------------------------
+// The pieces every table reader is made of.
+// The key of the next entry (white space before it is skipped, the one separator behind it consumed; a '\n' is left for the
+// line logic of script files); false at the end of the input.
+bool ReadKey(Input& in, std::string* key);
+// "path:123" -> (path, 123); anything else - a pipe ("cmd |", whatever it contains), a whole file, a suffix that is not all
+// digits - -> -1 with *path = rx.  The one place that knows the form; an offset of 0 is a position like any other to the
+// callers, and not a seek to Input::Open.
+long SplitOffset(const std::string& rx, std::string* path);
+// One line of a script file: the key, then the rest of the line, trimmed (empty when there is none); false at the end.
+bool ReadScpLine(Input& in, std::string* key, std::string* rx);
+
+// Where an scp entry becomes an open, positioned Input.  A cursor owns the data file it used last: an entry of the same
+// file is a seek (consecutive entries of a table usually share their archive; the file stays mapped in between), an entry of
+// another file opens - maps - that one and drops the old, and what cannot be addressed (a pipe, a whole file) is opened
+// for the one object and closed by Done().  One cursor per reading thread.
+class ArchiveCursor {
  public:
-  explicit SequentialMatrixReader(const std::string& rspecifier);
-  ~SequentialMatrixReader();
-  // Advances to the next entry; returns false at the end.  Per-entry problems in scp mode
-  // (unreadable file) are reported through `error` (non-empty) with key set, and reading continues.
-  bool Next(std::string* key, Matrix* m, std::string* error);
-  // Exit status of an input pipe (valid after the table is exhausted); 0 if not a pipe.
-  int Close();
+  // an scp entry as it is written ("path:offset", "path", "cmd |"): the sequential readers.  A file is opened under the
+  // entry's own text, which is what its errors then name.
+  Input& AtEntry(const std::string& rx);
+  // (path, offset >= 0), as SplitOffset and the indexer deliver them, or (rxfilename, -1): the file is opened under its
+  // path and errors name the archive - the indexed and the random-access readers.
+  Input& At(const std::string& path, long offset);
+  void Done();    // the object was read: closes what is not addressable, keeps an archive
+  void Reset();   // forgets the open file
+
+ private:
+  bool Holds(const std::string& path) const { return in_.IsOpen() && path_ == path; }
+  Input in_;
+  std::string path_;   // of the addressable file in_ holds; empty: none, or a one-shot input
+};
+
+// Sequential reader of a table ("ark:..." or "scp:...") of values of one type: Next() advances to the next entry and returns
+// false at the end.  A corrupt archive is fatal (KioError), as in Kaldi; a problem with one entry of a script file (an
+// unreadable file) comes back through `error` (non-empty) with the key set, and reading continues.  Close(): the exit status
+// of an input pipe (valid after the table is exhausted), 0 if not a pipe.  sorted(): the rspecifier promised sorted keys (s):
+// the caller may then merge by key instead of loading the table.  The value types: Matrix, std::vector<float>, IntVecVec and
+// Posterior (below), each parsed by its Read function.
+template <class T>
+class SequentialTableReader {
+ public:
+  // drain_pipe: an archive through a pipe is read by a second thread (Input::Open).  permissive_skips: under the rspecifier's
+  // p option an unreadable scp entry is skipped silently instead of reported.
+  explicit SequentialTableReader(const std::string& rspecifier, bool drain_pipe = false, bool permissive_skips = false);
+  bool Next(std::string* key, T* value, std::string* error);
+  bool sorted() const { return opts_.sorted; }
+  int Close() { return in_.Close(); }
 
  private:
   RspecifierOptions opts_;
-  Input in_;         // the ark stream, or the scp file
-  Input data_in_;    // scp mode: currently open data file
-  std::string data_path_;
+  bool permissive_skips_;
+  Input in_;             // the archive, or the script file
+  ArchiveCursor data_;   // scp mode: the data file of the current entry
 };
+// float matrices (features); the only table that comes through the feature pipe of extract_xvectors_new.sh:79
+struct SequentialMatrixReader : SequentialTableReader<Matrix> {
+  explicit SequentialMatrixReader(const std::string& rspecifier) : SequentialTableReader(rspecifier, /*drain_pipe=*/true) {}
+};
+typedef SequentialTableReader<std::vector<float>> SequentialVectorReader;
 
 // Index pass over a matrix table whose objects can be addressed individually: binary archives in a regular file ("ark:file")
 // and script files whose entries are "path:offset" (or plain files).  Next() yields one entry without reading its data - key,
@@ -202,13 +245,12 @@ class MatrixTableIndexer {
 
  private:
   RspecifierOptions opts_;
-  Input in_;          // the archive, or the script file
-  Input data_in_;     // scp mode: the data file of the previous entry (consecutive entries usually share it)
-  std::string data_path_;
+  Input in_;            // the archive, or the script file
+  ArchiveCursor data_;  // scp mode: the data file of the previous entry
   bool usable_ = false;
 };
-// Reads the matrix an index entry points to.  `in` / `in_path` cache the open data file between calls of one thread.
-void ReadIndexedMatrix(const MatrixTableIndexer::Entry& e, Input* in, std::string* in_path, Matrix* m);
+// Reads the matrix an index entry points to through the calling thread's cursor.
+void ReadIndexedMatrix(const MatrixTableIndexer::Entry& e, ArchiveCursor* cursor, Matrix* m);
 // The same without touching the data: for a binary FLOAT matrix ("FM") at a known offset of a regular file, *m becomes a view of
 // the file's pages (the file is mapped read-only once per FileMapper and path, and stays mapped while the FileMapper lives - a
 // job owns one, so every view dies before the mapping does and a file rewritten between two jobs of one process is mapped
@@ -235,60 +277,33 @@ class FileMapper {
   std::map<std::string, Mapped> maps_;   // by path; a file that could not be mapped is remembered with base == nullptr
 };
 
-// Sequential reader of a table of float vectors ("ark:..." or "scp:...").  A corrupt archive is fatal (KioError),
-// an unreadable scp entry is reported through `error` and reading continues.
-class SequentialVectorReader {
- public:
-  explicit SequentialVectorReader(const std::string& rspecifier);
-  bool Next(std::string* key, std::vector<float>* v, std::string* error);
-  int Close();
-
- private:
-  RspecifierOptions opts_;
-  Input in_;
+// Random-access reader of a table.  An archive is loaded as a whole; the values of a script file are read when they are
+// first asked for and kept, the archive of the previous lookup staying open - mapped - in between.  The first entry of a
+// key wins.  Float vectors: vad.scp, "scp,s,cs:..."; double-precision matrices: cmvn.scp, one per speaker (FM / DM / text).
+struct DoubleMatrix {
+  int rows = 0, cols = 0;
+  std::vector<double> data;
 };
-
-// Random-access reader over an scp (used by the front-end for vad.scp: "scp,s,cs:...").
-// Also accepts "ark:" by loading the whole archive.
-class RandomAccessVectorReader {
+template <class T>
+class RandomAccessTableReader {
  public:
-  explicit RandomAccessVectorReader(const std::string& rspecifier);
-  bool HasKey(const std::string& key);
-  const std::vector<float>& Value(const std::string& key);
+  explicit RandomAccessTableReader(const std::string& rspecifier);
+  bool HasKey(const std::string& key) const { return index_.count(key) != 0; }
+  const T& Value(const std::string& key);   // KioError: the key is not in the table
   // scp tables: gives the memory of a loaded value back (it is read again if the key is asked for once more).  A table job
   // forgets the VAD decisions of a batch once the batch is on the device: kept, a hundred thousand four-minute recordings are
-  // 10 GB of them by the end of the job.  (What Kaldi's "scp,s,cs:" options promise its reader it may do.)
+  // 10 GB of them by the end of the job.  (What Kaldi's "scp,s,cs:" options promise its reader it may do.)  A value that was
+  // loaded with its whole archive cannot be read again and stays.
   void Forget(const std::string& key);
 
  private:
-  struct Entry { std::string key, rx; std::vector<float> v; bool loaded = false; };
+  struct Entry { std::string rx; T v; bool loaded = false; };
   std::vector<Entry> entries_;
   std::unordered_map<std::string, int> index_;
-  int Find(const std::string& key);
-  // scp tables: the data file of the previous lookup stays open (mapped); consecutive keys of a job point into the same archive
-  Input data_in_;
-  std::string data_path_;
+  ArchiveCursor data_;
 };
-
-// Random-access reader of a table of double-precision matrices (cmvn.scp, "scp:$sdata/JOB/cmvn.scp"; FM / DM / text objects).
-// An archive is loaded as a whole; the values of a script file are read when they are first asked for and kept (one per speaker).
-class RandomAccessDoubleMatrixReader {
- public:
-  struct Value {
-    int rows = 0, cols = 0;
-    std::vector<double> data;
-  };
-  explicit RandomAccessDoubleMatrixReader(const std::string& rspecifier);
-  bool HasKey(const std::string& key) { return index_.count(key) != 0; }
-  const Value& Get(const std::string& key);
-
- private:
-  struct Entry { std::string rx; Value v; bool loaded = false; };
-  std::vector<Entry> entries_;
-  std::unordered_map<std::string, int> index_;
-  Input data_in_;
-  std::string data_path_;
-};
+typedef RandomAccessTableReader<std::vector<float>> RandomAccessVectorReader;
+typedef RandomAccessTableReader<DoubleMatrix> RandomAccessDoubleMatrixReader;
 
 // A text table of token lists, "key tok1 tok2 ...\n" per entry (spk2utt, "ark:$data/spk2utt").
 struct TokenList {
@@ -371,31 +386,12 @@ void WriteIntVecVec(Output& out, bool binary, const IntVecVec& v);
 void ReadPosterior(Input& in, bool binary, Posterior* p);
 void WritePosterior(Output& out, bool binary, const Posterior& p);
 
-// Sequential readers of the two tables ("ark:", "ark,s,cs:-", "scp,p:...").  sorted(): the rspecifier promised sorted keys (s): the
-// caller may then merge by key instead of loading the table.  An unreadable scp entry comes back through `error` (permissive
-// (p): it is skipped silently instead); a corrupt archive is fatal.
-class SequentialObjectReader {
- public:
-  explicit SequentialObjectReader(const std::string& rspecifier);
-  bool sorted() const { return opts_.sorted; }
-  int Close() { return in_.Close(); }
-
- protected:
-  // the next entry: *obj is where to parse it from (owned by the reader); false at the end
-  bool NextEntry(std::string* key, Input** obj, std::string* error);
-  void DoneEntry();
-  RspecifierOptions opts_;
-  Input in_, data_;
+// Sequential readers of the two tables ("ark:", "ark,s,cs:-", "scp,p:..."): the only ones that honour the p option.
+struct SequentialGselectReader : SequentialTableReader<IntVecVec> {
+  explicit SequentialGselectReader(const std::string& rspecifier) : SequentialTableReader(rspecifier, false, /*permissive_skips=*/true) {}
 };
-class SequentialGselectReader : public SequentialObjectReader {
- public:
-  using SequentialObjectReader::SequentialObjectReader;
-  bool Next(std::string* key, IntVecVec* v, std::string* error);
-};
-class SequentialPosteriorReader : public SequentialObjectReader {
- public:
-  using SequentialObjectReader::SequentialObjectReader;
-  bool Next(std::string* key, Posterior* p, std::string* error);
+struct SequentialPosteriorReader : SequentialTableReader<Posterior> {
+  explicit SequentialPosteriorReader(const std::string& rspecifier) : SequentialTableReader(rspecifier, false, /*permissive_skips=*/true) {}
 };
 // Random-access float table, text ("key 0.5") or binary entries (BaseFloatReader: the per-utterance scales of scale-post).
 std::unordered_map<std::string, float> ReadFloatTable(const std::string& rspecifier);

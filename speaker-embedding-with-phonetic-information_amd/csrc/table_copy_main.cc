@@ -163,18 +163,10 @@ int main(int argc, char** argv) {
           line.clear();
         }
       } else {
-        xv::Input in;
-        in.Open(o.rxfilename);
-        for (;;) {
-          int c;
-          while ((c = in.Peek()) >= 0 && isspace(c)) in.Get();
-          if (c < 0) break;
-          std::string key;
-          while ((c = in.Peek()) >= 0 && !isspace(c)) key.push_back((char)in.Get());
-          in.Get();
-          bool binary = xv::ReadBinaryHeader(in);
-          std::vector<float> v;
-          xv::ReadVector(in, binary, &v);
+        xv::SequentialVectorReader rd(pos[0]);
+        std::string key, err;
+        std::vector<float> v;
+        while (rd.Next(&key, &v, &err)) {
           w.WriteVec(key, v.data(), (int)v.size());
           ++n;
         }

@@ -160,8 +160,7 @@ static void SampleTable(const ExtractOptions& opt, const std::string& feat_rspec
       *strided = true;
       *n_list = (long)good.size();
       const long n = (long)good.size();
-      Input in;
-      std::string in_path;
+      ArchiveCursor cursor;
       long prev = -1;
       for (int i = 0; i < want && n > 0; ++i) {
         // centres of `want` equal slices of the list (all of it when it is shorter)
@@ -170,7 +169,7 @@ static void SampleTable(const ExtractOptions& opt, const std::string& feat_rspec
         prev = k;
         Matrix m;
         try {
-          ReadIndexedMatrix(all.entries[good[k]], &in, &in_path, &m);
+          ReadIndexedMatrix(all.entries[good[k]], &cursor, &m);
         } catch (const std::exception&) {
           continue;   // the extraction itself will report it
         }
@@ -428,8 +427,7 @@ TableExtractResult RunTableExtraction(const std::vector<Engine*>& engines, const
   const bool use_views = DebugKnobInt("mmap", 1) != 0;
   const bool cm_on_device = DebugKnobInt("cm_on_device", 1) != 0;   // compressed matrices of a front-end job: expanded on the GPU
   auto parallel_reader_body = [&] {
-    Input in;
-    std::string in_path;
+    ArchiveCursor cursor;
     for (;;) {
       PlanBatch pb;
       {
@@ -454,7 +452,7 @@ TableExtractResult RunTableExtraction(const std::vector<Engine*>& engines, const
         try {
           // a float matrix in a regular file is not read at all: the utterance is a view of the mapped archive, and its bytes
           // are touched once, by the copy into the pinned staging buffer
-          if (!use_views || !mapper.View(e, &u.feats, use_frontend && cm_on_device)) ReadIndexedMatrix(e, &in, &in_path, &u.feats);
+          if (!use_views || !mapper.View(e, &u.feats, use_frontend && cm_on_device)) ReadIndexedMatrix(e, &cursor, &u.feats);
         } catch (const std::exception& ex) {
           if (e.offset >= 0 && !opt_is_scp) {   // a damaged archive is fatal, as in the sequential reader
             std::unique_lock<std::mutex> lk(mu);
