@@ -27,11 +27,11 @@ bool ParseBoolValue(const std::string& v, bool* out) {
   return false;
 }
 
-bool ParseIntValue(const std::string& v, int* out) {
+bool ParseIntValue(const std::string& v, long lowest, int* out) {
   if (v.empty()) return false;
   char* end = nullptr;
   const long x = strtol(v.c_str(), &end, 10);
-  if (*end || x < 1 || x > 1000000) return false;
+  if (*end || x < lowest || x > 1000000) return false;
   *out = (int)x;
   return true;
 }
@@ -89,9 +89,11 @@ bool RecognizeFeaturePipeline(const std::string& rspecifier, FusedPipeline* out)
       } else if (name == "center") {
         if (!ParseBoolValue(value, &p.center)) return false;
       } else if (name == "cmn-window") {
-        if (!ParseIntValue(value, &p.cmn_window)) return false;
+        if (!ParseIntValue(value, 1, &p.cmn_window)) return false;
       } else if (name == "min-cmn-window") {
-        if (!ParseIntValue(value, &p.min_cmn_window)) return false;
+        // the tool takes this value as typed, zero and below included (no minimum then: max(t + 1, M) is t + 1), and so does the
+        // device: the fused job and the command it names run the same windows
+        if (!ParseIntValue(value, -1000000, &p.min_cmn_window)) return false;
       } else {
         return false;                                             // --max-warnings, --verbose, --config ...: run the command
       }

@@ -354,18 +354,20 @@ int main(int argc, char** argv) {
     // The feature pipeline the reference's extraction scripts build (extract_xvectors_new.sh:79: apply-cmvn-sliding |
     // select-voiced-frames, two CPU tools and two pipes) is recognised as text and run on the device instead (fuse_pipe.h) -
     // unless the caller asked for a front-end of their own, or XVEC_DEBUG=fuse_pipe=0 says to run the commands.
-    int fused_min_window = 0;
+    bool fused = false;
+    int fused_min_window = 0;   // --min-cmn-window as the pipeline has it, whatever its sign: the tool it names takes it as typed
     if (!g_frame_job && opt.cmn_window == 0 && opt.vad_rspecifier.empty() && xv::DebugKnobInt("fuse_pipe", 1) != 0) {
       xv::FusedPipeline fp;
       if (xv::RecognizeFeaturePipeline(feat_rspec, &fp)) {
         XLOG("feature pipeline recognised (apply-cmvn-sliding --norm-vars=false --center=" << (fp.center ? "true" : "false")
-             << " --cmn-window=" << fp.cmn_window << (fp.vad_rspecifier.empty() ? "" : " | select-voiced-frames " + fp.vad_rspecifier)
-             << "): it runs on the device, reading " << fp.feats_rspecifier << " directly (XVEC_DEBUG=fuse_pipe=0 runs the commands)");
+             << " --cmn-window=" << fp.cmn_window << " --min-cmn-window=" << fp.min_cmn_window
+             << (fp.vad_rspecifier.empty() ? "" : " | select-voiced-frames " + fp.vad_rspecifier) << "): it runs on the device, reading " << fp.feats_rspecifier << " directly (XVEC_DEBUG=fuse_pipe=0 runs the commands)");
         feat_rspec = fp.feats_rspecifier;
         opt.cmn_window = fp.cmn_window;
         opt.cmn_center = fp.center;
         opt.vad_rspecifier = fp.vad_rspecifier;
         fused_min_window = fp.min_cmn_window;
+        fused = true;
       }
     }
 
@@ -528,7 +530,7 @@ int main(int argc, char** argv) {
     eo.cmn_window = opt.cmn_window;
     eo.cmn_center = opt.cmn_center;
     eo.vad_rspecifier = opt.vad_rspecifier;
-    if (fused_min_window > 0) eo.cmn_min_window = fused_min_window;
+    if (fused) eo.cmn_min_window = fused_min_window;
     eo.calibrate = policy_default && opt.calibrate && !g_frame_job;   // no-op unless the context can switch (fp16mx2)
     eo.calibrate_tol = opt.calibrate_tol;
     if (policy_default && !g_frame_job) {

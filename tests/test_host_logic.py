@@ -517,6 +517,12 @@ def test_the_reference_feature_pipeline_is_recognised_as_text_and_nothing_else_i
     # variations the device front-end implements
     assert R("ark:apply-cmvn-sliding --norm-vars=false --center=false --cmn-window=200 --min-cmn-window=50 ark:/x/raw.ark ark:- |") == \
         {"feats": "ark:/x/raw.ark", "vad": "", "cmn_window": 200, "min_cmn_window": 50, "center": False}
+    # --min-cmn-window is carried as typed, zero and below included (no minimum: what the tool the string names does with it)
+    assert R("ark:apply-cmvn-sliding --norm-vars=false --center=false --cmn-window=200 --min-cmn-window=0 ark:/x/raw.ark ark:- |") == \
+        {"feats": "ark:/x/raw.ark", "vad": "", "cmn_window": 200, "min_cmn_window": 0, "center": False}
+    assert R("ark:apply-cmvn-sliding --min_cmn_window=-5 scp:f.scp ark:- |")["min_cmn_window"] == -5
+    assert R("ark:apply-cmvn-sliding --min-cmn-window=0x10 scp:f.scp ark:- |") is None
+    assert R("ark:apply-cmvn-sliding --cmn-window=0 scp:f.scp ark:- |") is None          # no window: not what the tool is for
     assert R("ark:/opt/kaldi/src/featbin/apply-cmvn-sliding --cmn_window=300 --norm_vars=false scp:f.scp ark:- | "
              "/opt/kaldi/src/ivectorbin/select-voiced-frames ark:- ark:vad.ark ark:- |")["vad"] == "ark:vad.ark"
     assert R("ark:apply-cmvn-sliding scp:f.scp ark:- |")["cmn_window"] == 600      # the tool's own defaults
