@@ -578,6 +578,26 @@ xv_status xv_fgmm_gconsts(int32_t num_gauss, int32_t dim, const float* weights, 
 xv_status xv_ubm_kernel_time(const xv_ubm* diag, const xv_ubm* full, const float* feats, const int32_t* row_off, int32_t n_utts,
                              int32_t n, float min_post, int32_t reps, float* ms5);
 
+/* ---- the GMM classifiers (fgmm-gselect --gselect=, fgmm-global-get-frame-likes, compute-vad-from-frame-likes, merge-vads;
+ * sid/gender_id.sh:88-118, sid/music_id.sh:73-104, sid/compute_vad_decision_gmm.sh:91-127).  Semantics: csrc/gmm_classify.h.
+ * Limits: n_in <= 64 preselected Gaussians, dimension <= 96, dense frame likelihoods only for models of at most 64 components. */
+/* second-stage selection by a full model: preselect [rows][n_in], every entry in [0, G); idx and loglikes (may be NULL) are
+ * [rows][min(n_out, n_in)], best first (score descending, then Gaussian ascending, then slot ascending).  The scores are bit for
+ * bit xv_ubm_post's loglikes.  n_in above 64 is XV_ERR_IO and names the limit.  device_ms3 (may be NULL): sort, scores, rerank. */
+xv_status xv_ubm_full_gselect(const xv_ubm* full, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* preselect,
+                              int32_t n_in, int32_t n_out, int32_t* idx, float* loglikes, float* device_ms3);
+/* likes [rows]: the log-sum-exp of a full model's scores over gselect [rows][n], bit for bit xv_ubm_post's logsum at min_post = 0.
+ * gselect NULL: every component is scored (n is ignored); a model of more than 64 components is then XV_ERR_IO and names the
+ * limit.  device_ms3 (may be NULL): sort, scores, softmax. */
+xv_status xv_ubm_frame_likes(const xv_ubm* full, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* gselect, int32_t n,
+                             float* likes, float* device_ms3);
+/* host only: out[t] = the first class j that maximises likes[j][t] + log(priors[j]), as map[j] if map is given.  likes: n_classes
+ * arrays of rows floats; priors (NULL: all 1) and map (NULL: the class itself): [n_classes].  A prior <= 0 is XV_ERR_IO. */
+xv_status xv_vad_from_frame_likes(int32_t n_classes, const float* const* likes, int64_t rows, const float* priors, const int32_t* map, float* out);
+/* host only: n_triples = 0: out[t] = 1 iff a[t] and b[t] are 1, else 0.  Otherwise map_triples [n_triples][3] sends the pair
+ * (a[t], b[t]) to the third entry; a pair that is not in the map is XV_ERR_IO and is named. */
+xv_status xv_merge_vads(const float* a, const float* b, int64_t rows, const int32_t* map_triples, int32_t n_triples, float* out);
+
 /* ---- full-covariance UBM training (fgmm-global-acc-stats, fgmm-global-est; sid/train_full_ubm.sh:69-118), without a model context.
  * Semantics: csrc/ubm_train.h.  The accumulators are fp64 on the device; no floating-point value goes through an atomic, and what a
  * call adds is a function of the call's frames and pairs alone.  Limits: dimension <= 96, n <= 64 selected Gaussians. */

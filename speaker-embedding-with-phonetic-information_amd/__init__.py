@@ -139,6 +139,7 @@ ABI_SYMBOLS = [
     "xv_cmvn_stats", "xv_cmvn_norm", "xv_cmvn_apply", "xv_cmvn_kernel_time",
     "xv_add_deltas", "xv_ubm_diag_create", "xv_ubm_full_create", "xv_ubm_destroy", "xv_ubm_gselect", "xv_ubm_post",
     "xv_fgmm_to_gmm", "xv_fgmm_gconsts", "xv_ubm_kernel_time",
+    "xv_ubm_full_gselect", "xv_ubm_frame_likes", "xv_vad_from_frame_likes", "xv_merge_vads",
     "xv_fgmm_acc_create", "xv_fgmm_acc_destroy", "xv_fgmm_acc_add", "xv_fgmm_acc_add_gselect", "xv_fgmm_acc_get", "xv_fgmm_est",
     "xv_fgmm_acc_kernel_time",
     "xv_logprob_to_post", "xv_logprob_to_post_kernel_time", "xv_fgmm_init_from_accs",
@@ -1299,6 +1300,104 @@ class Ubm:
         if not return_details:
             return out
         return out, [ll[off[u]:off[u + 1]].copy() for u in range(nu)], [logsum[off[u]:off[u + 1]].copy() for u in range(nu)]
+
+    def _selection(self, who, feats_list, gselect_list):
+        import numpy as np
+        packed, off, cols = _pack_matrices(feats_list, who)
+        if cols != self.dim:
+            raise XvError(XV_ERR_ARG, "%s: the features have %d columns, the model %d" % (who, cols, self.dim))
+        nu = len(off) - 1
+        if gselect_list is None:
+            return packed, off, nu, None, 0
+        gs = [np.ascontiguousarray(g, dtype=np.int32) for g in gselect_list]
+        if nu == 0 or len(gs) != nu or any(g.ndim != 2 or g.shape[0] != off[u + 1] - off[u] or g.shape[1] != gs[0].shape[1] for u, g in enumerate(gs)):
+            raise XvError(XV_ERR_ARG, "%s: one [frames, n] selection per utterance, all of one n" % who)
+        return packed, off, nu, np.ascontiguousarray(np.concatenate(gs, axis=0)), gs[0].shape[1]
+
+    def rerank(self, feats_list, gselect_list, n, return_loglikes=False, return_ms=False):
+        """Second-stage selection by a full model (fgmm-gselect --gselect=): the min(n, n_in) best of every frame's preselection,
+        best first, as a list of int32 [frames, min(n, n_in)] (and of the float32 log-likelihoods; return_ms: and the device
+        times {sort, scores, rerank} in ms)."""
+        import numpy as np
+        L = lib()
+        packed, off, nu, sel, n_in = self._selection("rerank", feats_list, gselect_list)
+        if sel is None:
+            raise XvError(XV_ERR_ARG, "rerank: a preselection is needed")
+        keep = max(1, min(n, n_in))
+        rows = packed.shape[0]
+        idx = np.zeros((rows, keep), dtype=np.int32)
+        ll = np.zeros((rows, keep), dtype=np.float32)
+        ms = (ctypes.c_float * 3)()
+        L.xv_ubm_full_gselect.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        _check(L.xv_ubm_full_gselect(self._h, packed.ctypes.data, off.ctypes.data, nu, sel.ctypes.data, n_in, n, idx.ctypes.data,
+                                     ll.ctypes.data if return_loglikes else None, ms if return_ms else None))
+        out = [[idx[off[u]:off[u + 1]].copy() for u in range(nu)]]
+        if return_loglikes:
+            out.append([ll[off[u]:off[u + 1]].copy() for u in range(nu)])
+        if return_ms:
+            out.append(dict(zip(("sort", "full", "rerank"), [float(x) for x in ms])))
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def frame_likes(self, feats_list, gselect_list=None, average=False):
+        """Per-frame log-likelihoods of a full model over each frame's selection (fgmm-global-get-frame-likes): a list of float32
+        [frames].  gselect_list None: every component, for models of at most 64.  average: one float32 per utterance instead, the
+        frames summed in float64 in frame order, divided by their number and rounded once."""
+        import numpy as np
+        L = lib()
+        packed, off, nu, sel, n = self._selection("frame_likes", feats_list, gselect_list)
+        likes = np.zeros(packed.shape[0], dtype=np.float32)
+        L.xv_ubm_frame_likes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.c_void_p]
+        _check(L.xv_ubm_frame_likes(self._h, packed.ctypes.data, off.ctypes.data, nu, None if sel is None else sel.ctypes.data, n,
+                                    likes.ctypes.data, None))
+        per_utt = [likes[off[u]:off[u + 1]].copy() for u in range(nu)]
+        if not average:
+            return per_utt
+        out = []
+        for v in per_utt:
+            tot = 0.0
+            for x in v.tolist():
+                tot += x
+            out.append(np.float32(tot / len(v)) if len(v) else np.float32(0.0))
+        return out
+
+
+def vad_from_frame_likes(likes, priors=None, map=None):
+    """compute-vad-from-frame-likes on the host: likes is one float32 [frames] array per class; frame t gets the first class j that
+    maximises likes[j][t] + log(priors[j]) (map[j] when a map, a sequence of one label per class, is given), as float32."""
+    import numpy as np
+    L = lib()
+    cls = [np.ascontiguousarray(v, dtype=np.float32) for v in likes]
+    if not cls or any(v.ndim != 1 or v.shape != cls[0].shape for v in cls):
+        raise XvError(XV_ERR_ARG, "vad_from_frame_likes: one [frames] array per class, all of one length")
+    n = len(cls)
+    pr = None if priors is None else np.ascontiguousarray(priors, dtype=np.float32)
+    mp = None if map is None else np.ascontiguousarray(map, dtype=np.int32)
+    if (pr is not None and pr.shape != (n,)) or (mp is not None and mp.shape != (n,)):
+        raise XvError(XV_ERR_ARG, "vad_from_frame_likes: %d classes need %d priors and %d map entries" % (n, n, n))
+    ptrs = (ctypes.c_void_p * n)(*[v.ctypes.data for v in cls])
+    out = np.zeros(cls[0].shape[0], dtype=np.float32)
+    L.xv_vad_from_frame_likes.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _check(L.xv_vad_from_frame_likes(n, ptrs, out.shape[0], None if pr is None else pr.ctypes.data, None if mp is None else mp.ctypes.data,
+                                     out.ctypes.data))
+    return out
+
+
+def merge_vads(a, b, map=None):
+    """merge-vads on the host: 1 where both are 1 without a map; with a map, a sequence of (a, b, c) triples, the pair (a, b)
+    gives c and a pair that is not in the map is an error that names it."""
+    import numpy as np
+    L = lib()
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    if a.ndim != 1 or a.shape != b.shape:
+        raise XvError(XV_ERR_ARG, "merge_vads: two [frames] arrays of one length")
+    tri = np.zeros((0, 3), dtype=np.int32) if map is None else np.ascontiguousarray(map, dtype=np.int32).reshape(-1, 3)
+    out = np.zeros(a.shape[0], dtype=np.float32)
+    L.xv_merge_vads.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+    _check(L.xv_merge_vads(a.ctypes.data, b.ctypes.data, a.shape[0], tri.ctypes.data if len(tri) else None, len(tri), out.ctypes.data))
+    return out
 
 
 def ubm_kernel_time(diag, full, feats_list, n=20, min_post=0.025, reps=5):

@@ -31,6 +31,7 @@
 #include "ivex.h"
 #include "ivex_train.h"
 #include "ubm.h"
+#include "gmm_classify.h"
 #include "dubm_train.h"
 #include "ubm_train.h"
 #include "ubm_train_kernels.h"
@@ -1110,6 +1111,38 @@ xv_status xv_ubm_kernel_time(const xv_ubm* diag, const xv_ubm* full, const float
       for (int i = 0; i < 5; ++i)
         if (r == 1 || (r > 1 && ms[i] < ms5[i])) ms5[i] = ms[i];
     }
+    return XV_OK;
+  });
+}
+
+xv_status xv_ubm_full_gselect(const xv_ubm* full, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* preselect,
+                              int32_t n_in, int32_t n_out, int32_t* idx, float* loglikes, float* device_ms3) {
+  if (!full || !row_off || n_utts < 0) return Fail(XV_ERR_ARG, "xv_ubm_full_gselect: bad argument");
+  return Guard([&] {
+    xv::UbmFullGselect(*full->m, feats, row_off, n_utts, preselect, n_in, n_out, idx, loglikes, device_ms3);
+    return XV_OK;
+  });
+}
+
+xv_status xv_ubm_frame_likes(const xv_ubm* full, const float* feats, const int32_t* row_off, int32_t n_utts, const int32_t* gselect, int32_t n,
+                             float* likes, float* device_ms3) {
+  if (!full || !row_off || n_utts < 0) return Fail(XV_ERR_ARG, "xv_ubm_frame_likes: bad argument");
+  return Guard([&] {
+    xv::UbmFrameLikes(*full->m, feats, row_off, n_utts, gselect, n, likes, device_ms3);
+    return XV_OK;
+  });
+}
+
+xv_status xv_vad_from_frame_likes(int32_t n_classes, const float* const* likes, int64_t rows, const float* priors, const int32_t* map, float* out) {
+  return Guard([&] {
+    xv::VadFromFrameLikes(n_classes, likes, rows, priors, map, out);
+    return XV_OK;
+  });
+}
+
+xv_status xv_merge_vads(const float* a, const float* b, int64_t rows, const int32_t* map_triples, int32_t n_triples, float* out) {
+  return Guard([&] {
+    xv::MergeVads(a, b, rows, map_triples, n_triples, out);
     return XV_OK;
   });
 }

@@ -1452,6 +1452,17 @@ void TableWriter::WriteInt32(const std::string& key, int32_t v) {
   End();
 }
 
+void TableWriter::WriteFloat(const std::string& key, float v) {
+  Begin(key);
+  if (opts_.binary) {
+    xv::WriteFloat(ark_, true, v);
+  } else {
+    PutFloatText(ark_, v);
+    ark_.Put('\n');
+  }
+  End();
+}
+
 void TableWriter::Close() {
   if (ark_.IsOpen()) ark_.Close();
   if (scp_.IsOpen()) scp_.Close();

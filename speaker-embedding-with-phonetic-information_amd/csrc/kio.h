@@ -335,6 +335,9 @@ class TableWriter {
   void WriteCompressed(const std::string& key, const char* format, const void* bytes, size_t n);
   bool binary() const { return opts_.binary; }
   void WriteInt32(const std::string& key, int32_t v);   // Int32Writer (num_utts.ark)
+  // BaseFloatWriter (the per-utterance averages of fgmm-global-get-frame-likes): text "key value\n"; binary the size byte 4 and
+  // the four bytes.  What ReadFloatTable reads.
+  void WriteFloat(const std::string& key, float v);
   // Int32VectorVectorWriter (Gaussian selection) and PosteriorWriter; the types are declared below the class
   void WriteIntVecVec(const std::string& key, const std::vector<std::vector<int32_t>>& v);
   void WritePosterior(const std::string& key, const std::vector<std::vector<std::pair<int32_t, float>>>& post);

@@ -355,18 +355,13 @@ void CheckUbmSelection(const char* who, const UbmModel& full, const int32_t* gse
       throw KioError(std::string(who) + ": the selection names Gaussian " + std::to_string(gselect[i]) + "; the model has " + std::to_string(I.num_gauss));
 }
 
-void UbmPostDevice::Run(const UbmModel& full, const float* host_feats, const int32_t* host_gselect, int64_t rows, int n, float min_post,
-                        bool with_slot_post, float* device_ms3) {
+void UbmPostDevice::Scores(const UbmModel& full, const float* host_feats, const int32_t* host_gselect, int64_t rows, int n, UbmFullArgs* out,
+                           EventTimer* tm) {
   const UbmModel::Impl& I = *full.impl_;
   const size_t pairs = (size_t)rows * n;
-  UbmFullArgs a;
+  UbmFullArgs& a = *out;
   memset(&a, 0, sizeof a);
   ll.Reserve(pairs * 4);
-  count.Reserve((size_t)rows * 4);
-  idx.Reserve(pairs * 4);
-  post.Reserve(pairs * 4);
-  logsum.Reserve((size_t)rows * 4);
-  if (with_slot_post) slot_post.Reserve(pairs * 4);
   feats.Upload(host_feats, (size_t)rows * I.dim * 4, "copy features");
   gselect.Upload(host_gselect, pairs * 4, "copy the selection");
   a.feats = feats.as<float>();
@@ -382,21 +377,33 @@ void UbmPostDevice::Run(const UbmModel& full, const float* host_feats, const int
   const int64_t per_gauss = (int64_t)pairs / I.num_gauss;
   a.split = (int)std::max<int64_t>(1, std::min<int64_t>(64, per_gauss / (4 * kUbmFullFrameTile)));
   a.ll = ll.as<float>();
+  tm->Mark();
+  const int32_t seg_off[2] = {0, (int32_t)pairs};
+  Check(sort.Run(a.gselect, (int64_t)pairs, seg_off, 1, I.num_gauss, nullptr), "bucket_sort launch");
+  a.bucket_start = sort.start.as<int32_t>();   // Run sizes them
+  a.sorted = sort.sorted.as<int32_t>();
+  tm->Mark();
+  Check(launch_ubm_full_loglike(a, nullptr), "ubm_full_loglike launch");
+  tm->Mark();
+}
+
+void UbmPostDevice::Run(const UbmModel& full, const float* host_feats, const int32_t* host_gselect, int64_t rows, int n, float min_post,
+                        bool with_slot_post, float* device_ms3) {
+  const size_t pairs = (size_t)rows * n;
+  count.Reserve((size_t)rows * 4);
+  idx.Reserve(pairs * 4);
+  post.Reserve(pairs * 4);
+  logsum.Reserve((size_t)rows * 4);
+  if (with_slot_post) slot_post.Reserve(pairs * 4);
+  EventTimer tm(device_ms3 != nullptr, 4);
+  UbmFullArgs a;
+  Scores(full, host_feats, host_gselect, rows, n, &a, &tm);
   a.min_post = min_post;
   a.out_count = count.as<int32_t>();
   a.out_idx = idx.as<int32_t>();
   a.out_post = post.as<float>();
   a.out_logsum = logsum.as<float>();
   a.out_slot_post = with_slot_post ? slot_post.as<float>() : nullptr;
-  EventTimer tm(device_ms3 != nullptr, 4);
-  tm.Mark();
-  const int32_t seg_off[2] = {0, (int32_t)pairs};
-  Check(sort.Run(a.gselect, (int64_t)pairs, seg_off, 1, I.num_gauss, nullptr), "bucket_sort launch");
-  a.bucket_start = sort.start.as<int32_t>();   // Run sizes them
-  a.sorted = sort.sorted.as<int32_t>();
-  tm.Mark();
-  Check(launch_ubm_full_loglike(a, nullptr), "ubm_full_loglike launch");
-  tm.Mark();
   Check(launch_ubm_post(a, nullptr), "ubm_post launch");
   tm.Mark();
   if (device_ms3)

@@ -91,6 +91,7 @@ void UbmPost(const UbmModel& full, const float* feats, const int32_t* row_off, i
 // upload, sort, scores, softmax.  The buffers live as long as the object and only grow.  Run checks nothing: CheckUbmSelection
 // comes first.  KioError from the check names `who`.
 void CheckUbmSelection(const char* who, const UbmModel& full, const int32_t* gselect, int64_t rows, int n);
+struct UbmFullArgs;   // ubm_kernels.h
 struct UbmPostDevice {
   DevBuf feats, gselect;                // the inputs of the part: [rows][dim], [rows][n]
   BucketSorter sort;                    // its start: [num_gauss + 1] buckets of its sorted: [rows * n] pair indices
@@ -99,6 +100,9 @@ struct UbmPostDevice {
   // device_ms3 (may be null): {sort, scores, softmax} are added to it
   void Run(const UbmModel& full, const float* host_feats, const int32_t* host_gselect, int64_t rows, int n, float min_post, bool with_slot_post,
            float* device_ms3);
+  // The first half of Run for the callers that rank the scores instead (gmm_classify.h): upload, sort, scores.  *a comes back
+  // filled up to ll; the posterior outputs are null.  tm is marked before the sort, after it and after the scores.
+  void Scores(const UbmModel& full, const float* host_feats, const int32_t* host_gselect, int64_t rows, int n, UbmFullArgs* a, EventTimer* tm);
 };
 
 }  // namespace xv
