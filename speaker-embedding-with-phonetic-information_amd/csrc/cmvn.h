@@ -18,11 +18,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "feat_batch.h"   // CmvnCompressed
 #include "kio.h"
 
 namespace xv {
@@ -38,15 +38,6 @@ int CmvnNorm(const double* stats, int cols, bool norm_means, bool norm_vars, boo
 // The value of --skip-dims: "a:b:c" -> {a, b, c}; false for anything else (an empty string is the empty list)
 bool ParseSkipDims(const std::string& value, std::vector<int>* dims);
 
-// The matrices of a device call may come as stored: "CM" objects (compress.h) back to back in `bytes`, object u at off[u]; they
-// are uploaded at one byte per element and expanded on the device (kernels.h CmExpandArgs; cols <= 64).  feats is then ignored.
-struct CmvnCompressed {
-  const uint8_t* bytes;
-  const int64_t* off;   // [n]
-  size_t nbytes;
-  int max_rows;
-};
-
 // stats: [n][2][cols + 1].  Blocking.  device_ms: the kernels' time.
 void CmvnStats(int device, const float* feats, const int32_t* row_off, int n, int cols, double* stats, float* device_ms = nullptr,
                const CmvnCompressed* cm = nullptr);
@@ -54,34 +45,5 @@ void CmvnStats(int device, const float* feats, const int32_t* row_off, int n, in
 // written).  out: [row_off[n]][cols].  Blocking.
 void CmvnApply(int device, const float* feats, const int32_t* row_off, int n, int cols, const float* norms, int n_norms,
                const int32_t* utt_norm, float* out, float* device_ms = nullptr, const CmvnCompressed* cm = nullptr);
-
-// Reads a feature table ahead in batches of one column count for the calls above.  A table whose objects can be addressed (an
-// archive in a regular file, a script file) is read through views of the mapped files, and its "CM" objects are handed on as
-// stored; anything else goes through the sequential reader.
-class FeatBatchReader {
- public:
-  struct Batch {
-    std::vector<std::string> keys;
-    std::vector<int32_t> row_off;   // [keys.size() + 1]
-    int cols = 0;
-    bool compressed = false;        // true: cm / cm_off hold the objects, feats is empty
-    std::vector<float> feats;
-    std::vector<uint8_t> cm;
-    std::vector<int64_t> cm_off;
-    int max_rows = 0;
-    CmvnCompressed View() const { return CmvnCompressed{cm.data(), cm_off.data(), cm.size(), max_rows}; }
-  };
-  struct Problem {
-    std::string key, what;   // what empty: a matrix without rows
-  };
-  FeatBatchReader(const std::string& rspecifier, int64_t max_frames, bool allow_compressed);
-  ~FeatBatchReader();
-  // false: the table is exhausted (and *b is empty).  problems: the entries met on the way that could not be read or have no rows.
-  bool Next(Batch* b, std::vector<Problem>* problems);
-
- private:
-  struct Impl;
-  std::unique_ptr<Impl> impl_;
-};
 
 }  // namespace xv

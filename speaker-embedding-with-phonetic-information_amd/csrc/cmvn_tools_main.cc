@@ -142,22 +142,6 @@ int SelectVoicedFrames(const std::vector<std::string>& pos) {
 
 constexpr int64_t kBatchFrames = 1 << 18;   // frames read ahead per device call of the two per-speaker tools
 
-// "ark:..." / "scp,p:..." is a table; anything else a file (Kaldi's ClassifyWspecifier / ClassifyRspecifier, as far as needed)
-bool IsTable(const std::string& spec) {
-  const size_t colon = spec.find(':');
-  if (colon == std::string::npos) return false;
-  const std::string kind = spec.substr(0, spec.find_first_of(",:"));
-  return kind == "ark" || kind == "scp";
-}
-
-void ReportProblems(const std::vector<xv::FeatBatchReader::Problem>& problems, long* num_err) {
-  for (const auto& p : problems) {
-    if (p.what.empty()) XWARN("Empty feature matrix for utterance " << p.key);
-    else XWARN("Failed to read features for key " << p.key << ": " << p.what);
-    ++*num_err;
-  }
-}
-
 struct StatsOptions {
   std::string spk2utt;
   bool binary = true;
@@ -166,24 +150,18 @@ struct StatsOptions {
 
 int ComputeCmvnStats(const StatsOptions& o, const std::vector<std::string>& pos) {
   const int dev = xv::PickDevice(o.device);
-  const bool table = IsTable(pos[1]);
+  const bool table = xv::IsTable(pos[1]);
   if (!o.spk2utt.empty() && !table) throw xv::KioError("--spk2utt option not compatible with wxfilename as output (did you forget ark:?)");
   std::vector<xv::TokenList> spk2utt;
   if (!o.spk2utt.empty()) spk2utt = xv::ReadTokenVectorTable(o.spk2utt);
   std::unique_ptr<xv::TableWriter> writer;
   if (table) writer.reset(new xv::TableWriter(pos[1]));
-  xv::FeatBatchReader reader(pos[0], kBatchFrames, true);
-  long num_done = 0, num_err = 0;
+  xv::FeatBatchWalk walk(pos[0], kBatchFrames, true, xv::FeatProblems::kCount);
+  long num_done = 0;
   std::unordered_map<std::string, std::vector<double>> utt_stats;   // --spk2utt: looked up by key afterwards
   std::vector<double> global;
-  xv::FeatBatchReader::Batch b;
-  std::vector<xv::FeatBatchReader::Problem> problems;
   std::vector<double> stats;
-  for (bool more = true; more;) {
-    problems.clear();
-    more = reader.Next(&b, &problems);
-    ReportProblems(problems, &num_err);
-    if (!more) break;
+  long num_err = walk.Run([&](const xv::FeatBatchReader::Batch& b) {
     const int n = (int)b.keys.size(), w = b.cols + 1;
     stats.assign((size_t)n * 2 * w, 0.0);
     const xv::CmvnCompressed cm = b.View();
@@ -202,7 +180,7 @@ int ComputeCmvnStats(const StatsOptions& o, const std::vector<std::string>& pos)
         ++num_done;
       }
     }
-  }
+  });
   if (!spk2utt.empty()) {
     for (const xv::TokenList& spk : spk2utt) {
       std::vector<double> acc;
@@ -246,7 +224,7 @@ struct ApplyOptions {
 
 int ApplyCmvn(const ApplyOptions& o, const std::vector<std::string>& pos) {
   if (o.norm_vars && !o.norm_means) throw xv::KioError("You cannot normalize the variance but not the mean.");
-  const bool per_key = IsTable(pos[0]);
+  const bool per_key = xv::IsTable(pos[0]);
   std::unordered_map<std::string, std::string> utt2spk;
   if (!o.utt2spk.empty()) utt2spk = xv::ReadTokenTable(o.utt2spk);
   std::unique_ptr<xv::RandomAccessDoubleMatrixReader> table;
@@ -262,21 +240,15 @@ int ApplyCmvn(const ApplyOptions& o, const std::vector<std::string>& pos) {
   const int dev = o.norm_means ? xv::PickDevice(o.device) : -1;
   xv::TableWriter writer(pos[2]);
   // --norm-means=false copies the features through: floats from the host readers, no device
-  xv::FeatBatchReader reader(pos[1], kBatchFrames, o.norm_means);
+  xv::FeatBatchWalk walk(pos[1], kBatchFrames, o.norm_means, xv::FeatProblems::kCount);
   long num_done = 0, num_err = 0;
-  xv::FeatBatchReader::Batch b;
-  std::vector<xv::FeatBatchReader::Problem> problems;
   std::vector<float> norms, out;
   std::vector<int32_t> utt_norm;
   // A speaker's (or the global) norm is computed once, and its flooring warning given once, however many batches its utterances
   // are spread over.  Per-utterance statistics are met once each and are not kept.
   const bool keep = !per_key || !o.utt2spk.empty();
   std::map<std::string, std::vector<float>> kept_norm;
-  for (bool more = true; more;) {
-    problems.clear();
-    more = reader.Next(&b, &problems);
-    ReportProblems(problems, &num_err);
-    if (!more) break;
+  const long unread = walk.Run([&](const xv::FeatBatchReader::Batch& b) {
     const int n = (int)b.keys.size();
     norms.clear();
     utt_norm.assign(n, -1);
@@ -342,10 +314,10 @@ int ApplyCmvn(const ApplyOptions& o, const std::vector<std::string>& pos) {
       writer.WriteMat(b.keys[u], m);
       ++num_done;
     }
-  }
+  });
   writer.Close();
   XLOG("Applied cepstral mean " << (o.norm_vars ? "and variance " : "") << "normalization to " << num_done << " utterances, errors on "
-                                << num_err);
+                                << unread + num_err);
   return num_done != 0 ? 0 : 1;
 }
 

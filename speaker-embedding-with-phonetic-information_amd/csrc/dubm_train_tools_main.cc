@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "cli.h"
-#include "cmvn.h"
+#include "feat_batch.h"
 #include "dubm_train.h"
 #include "dubm_train_kernels.h"
 #include "gmm_acc_tool.h"
@@ -26,8 +26,6 @@
 #include "ubm_kernels.h"
 
 namespace {
-
-constexpr int64_t kBatchFrames = 1 << 16;   // frames read ahead; no result depends on it
 
 std::unique_ptr<xv::UbmModel> Upload(int dev, const xv::DiagGmmData& gmm) {
   return std::unique_ptr<xv::UbmModel>(xv::UbmDiagCreate(dev, gmm.num_gauss, gmm.dim, gmm.gconsts.data(), gmm.means_invvars.data(), gmm.inv_vars.data()));
@@ -90,24 +88,18 @@ struct InitOptions {
 
 int InitFromFeats(const InitOptions& o, const std::vector<std::string>& pos) {
   if (o.num_gauss < 1 || o.num_iters < 0 || o.num_frames < 1) throw xv::KioError("--num-gauss and --num-frames must be at least 1, --num-iters not negative");
-  xv::FeatBatchReader reader(pos[0], kBatchFrames, false);
+  // (no result depends on the frames read ahead)
+  xv::FeatBatchWalk walk(pos[0], xv::kBatchFrames, false, xv::FeatProblems::kThrowUnreadable);
   xv::DgmmFrameSampler sampler;
   sampler.num_frames = o.num_frames;
   sampler.seed = o.seed;
-  xv::FeatBatchReader::Batch b;
-  std::vector<xv::FeatBatchReader::Problem> problems;
-  for (bool more = true; more;) {
-    problems.clear();
-    more = reader.Next(&b, &problems);
-    for (const auto& p : problems)
-      if (!p.what.empty()) throw xv::KioError("Failed to read features for key " + p.key + ": " + p.what);
-    if (!more) break;
+  walk.Run([&](const xv::FeatBatchReader::Batch& b) {
     if (sampler.dim == 0) sampler.dim = b.cols;
     if (b.cols != sampler.dim)
       throw xv::KioError("Features have inconsistent dims " + std::to_string(b.cols) + " vs. " + std::to_string(sampler.dim) + " (current utt is) " + b.keys[0]);
     const int64_t rows = b.row_off[b.keys.size()];
     for (int64_t t = 0; t < rows; ++t) sampler.Add(b.feats.data() + (size_t)t * b.cols);
-  }
+  });
   const int64_t T = sampler.rows();
   if (T == 0) throw xv::KioError("No frames were read from " + pos[0]);
   if (sampler.num_read < o.num_frames) {

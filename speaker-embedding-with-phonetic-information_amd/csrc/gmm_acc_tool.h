@@ -8,9 +8,8 @@
 #include <vector>
 
 #include "cli.h"
-#include "cmvn.h"
+#include "feat_join.h"
 #include "gmm_train.h"
-#include "gselect_lookup.h"
 #include "kio.h"
 #include "ubm_kernels.h"
 
@@ -39,8 +38,8 @@ inline OptionResult SetGmmAccOption(const std::string& n, const std::string& val
 // the device, logsum [rows] coming back.  get(): the device's sums into *host, once at the end.  Returns the exit status.
 template <class Accumulate, class Get>
 int GmmAccStats(const GmmAccOptions& o, const std::vector<std::string>& pos, GmmAccs* host, int frame_block, Accumulate accumulate, Get get) {
-  constexpr int64_t kBatchFrames = 1 << 16;   // frames read ahead; the accumulate calls do not depend on it
-  FeatBatchReader reader(pos[1], kBatchFrames, false);
+  // (the accumulate calls do not depend on the frames read ahead; a matrix without rows is skipped, not an error)
+  FeatBatchWalk walk(pos[1], kBatchFrames, false, FeatProblems::kCountUnreadable);
   GselectLookup gselect(o.gselect);
   long num_done = 0, num_err = 0;
   double tot_like = 0.0;
@@ -58,20 +57,7 @@ int GmmAccStats(const GmmAccOptions& o, const std::vector<std::string>& pos, Gmm
     tot_t += (int64_t)rows;
     head += rows;
   };
-  FeatBatchReader::Batch b;
-  std::vector<FeatBatchReader::Problem> problems;
-  for (bool more = true; more;) {
-    problems.clear();
-    more = reader.Next(&b, &problems);
-    for (const auto& p : problems) {
-      if (p.what.empty()) {
-        XWARN("Empty feature matrix for utterance " << p.key);   // no frames: skipped, not an error
-      } else {
-        XWARN("Failed to read features for key " << p.key << ": " << p.what);
-        ++num_err;
-      }
-    }
-    if (!more) break;
+  const long unread = walk.Run([&](const FeatBatchReader::Batch& b) {
     for (size_t u = 0; u < b.keys.size(); ++u) {
       const int rows = b.row_off[u + 1] - b.row_off[u];
       if (b.cols != D) {
@@ -80,30 +66,24 @@ int GmmAccStats(const GmmAccOptions& o, const std::vector<std::string>& pos, Gmm
         continue;
       }
       IntVecVec sel;
-      if (!gselect.Find(b.keys[u], &sel)) {
+      const Joined j = FindGselect(&gselect, b.keys[u], rows, &sel);
+      const bool usable = j.outcome == Joined::kOk && (n == 0 || j.width == n);   // one width for the whole run
+      if (j.outcome == Joined::kNotFound)
         XWARN("No gselect information for utterance " << b.keys[u]);
-        ++num_err;
-        continue;
-      }
-      if ((int)sel.size() != rows) {
-        XWARN("gselect information for utterance " << b.keys[u] << " has wrong size " << sel.size() << " vs. " << rows);
-        ++num_err;
-        continue;
-      }
-      const size_t width = sel[0].size();
-      bool same = width >= 1;
-      for (const auto& l : sel) same = same && l.size() == width;
-      if (!same || (n != 0 && (int)width != n)) {
+      else if (j.outcome == Joined::kWrongSize)
+        XWARN("gselect information for utterance " << b.keys[u] << " has wrong size " << j.size << " vs. " << rows);
+      else if (!usable)
         XWARN("The Gaussian selection of utterance " << b.keys[u] << " does not have " << (n ? "the " + std::to_string(n) + " indices per frame of the utterances before it" : "one length for every frame")
                                                     << " (skipping utterance)");
+      if (!usable) {
         ++num_err;
         continue;
       }
-      if (width > (size_t)kUbmMaxSelect)
-        throw KioError("the Gaussian selection has " + std::to_string(width) + " indices per frame; the device kernels take at most " + std::to_string(kUbmMaxSelect));
-      n = (int)width;
-      feats.insert(feats.end(), b.feats.begin() + (size_t)b.row_off[u] * D, b.feats.begin() + (size_t)b.row_off[u + 1] * D);
-      for (const auto& l : sel) gs.insert(gs.end(), l.begin(), l.end());
+      if (j.width > kUbmMaxSelect)
+        throw KioError("the Gaussian selection has " + std::to_string(j.width) + " indices per frame; the device kernels take at most " + std::to_string(kUbmMaxSelect));
+      n = j.width;
+      AppendRows(b, u, &feats);
+      Append(sel, &gs);
       while (feats.size() / D - head >= (size_t)frame_block) block((size_t)frame_block);
       if (head) {   // drop what was consumed, once per utterance that filled a block
         feats.erase(feats.begin(), feats.begin() + head * D);
@@ -114,9 +94,9 @@ int GmmAccStats(const GmmAccOptions& o, const std::vector<std::string>& pos, Gmm
       if (o.verbose >= 1 && num_done % 10 == 0)   // over the frames that have been through the device: whole blocks
         XLOG("Avg like per frame so far is " << (tot_t ? tot_like / (double)tot_t : 0.0));
     }
-  }
+  });
   if (!feats.empty()) block(feats.size() / D);
-  XLOG("Done " << num_done << " files; " << num_err << " with errors.");
+  XLOG("Done " << num_done << " files; " << unread + num_err << " with errors.");
   XLOG("Overall likelihood per frame = " << (tot_t ? tot_like / (double)tot_t : 0.0) << " over " << tot_t << " (weighted) frames.");
   get();
   WriteGmmAccsFile(pos[2], o.binary, *host);

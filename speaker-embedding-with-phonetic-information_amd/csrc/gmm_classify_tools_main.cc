@@ -10,122 +10,21 @@
 // Without --gselect the first two score every component, which the device kernels do for models of at most 64: a larger model is
 // refused by name (no script of the recipes omits --gselect).
 #include <ctype.h>
-#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 
-#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "cli.h"
-#include "cmvn.h"
+#include "feat_join.h"
 #include "gmm_classify.h"
-#include "gselect_lookup.h"
 #include "kio.h"
 #include "ubm.h"
 #include "ubm_kernels.h"
 
 namespace {
-
-constexpr int64_t kBatchFrames = 1 << 16;   // frames read ahead per device call
-
-// log sum_i exp(v_i), in fp64
-double LogSumExp(const float* v, int n) {
-  double mx = v[0];
-  for (int i = 1; i < n; ++i) mx = v[i] > mx ? v[i] : mx;
-  if (isinf(mx)) return mx;
-  double s = 0.0;
-  for (int i = 0; i < n; ++i) s += exp((double)v[i] - mx);
-  return mx + log(s);
-}
-
-// The utterances of a feature table that have a usable selection, in groups of one selection width: what the two device tools
-// walk.  Without a selection table every utterance gets the identity selection 0 .. G - 1.
-struct Group {
-  std::vector<std::string> keys;
-  std::vector<float> feats;
-  std::vector<int32_t> off, gs;
-  int n = 0;
-  void Clear() {
-    keys.clear();
-    feats.clear();
-    gs.clear();
-    off.assign(1, 0);
-  }
-};
-
-// Calls `flush` for every group; returns the number of utterances skipped with a warning.
-long ForEachGroup(const xv::FullGmmData& gmm, const std::string& feats_rspecifier, const std::string& gselect_rspecifier,
-                  const std::function<void(const Group&)>& flush) {
-  xv::FeatBatchReader reader(feats_rspecifier, kBatchFrames, false);
-  std::unique_ptr<xv::GselectLookup> gselect;
-  if (!gselect_rspecifier.empty()) gselect.reset(new xv::GselectLookup(gselect_rspecifier));
-  long num_err = 0;
-  xv::FeatBatchReader::Batch b;
-  std::vector<xv::FeatBatchReader::Problem> problems;
-  Group g;
-  for (bool more = true; more;) {
-    problems.clear();
-    more = reader.Next(&b, &problems);
-    for (const auto& p : problems) {
-      if (p.what.empty()) XWARN("Empty feature matrix for utterance " << p.key);
-      else XWARN("Failed to read features for key " << p.key << ": " << p.what);
-      ++num_err;
-    }
-    if (!more) break;
-    g.Clear();
-    g.n = 0;
-    for (size_t u = 0; u < b.keys.size(); ++u) {
-      const int rows = b.row_off[u + 1] - b.row_off[u];
-      if (b.cols != gmm.dim) {
-        XWARN("Dimension mismatch for utterance " << b.keys[u] << ": the features have " << b.cols << " columns, the model " << gmm.dim);
-        ++num_err;
-        continue;
-      }
-      int width = gmm.num_gauss;
-      xv::IntVecVec sel;
-      if (gselect) {
-        if (!gselect->Find(b.keys[u], &sel)) {
-          XWARN("No Gaussian-selection info available for utterance " << b.keys[u] << " (skipping utterance)");
-          ++num_err;
-          continue;
-        }
-        if ((int)sel.size() != rows) {
-          XWARN("Mismatch in number of frames " << rows << " for features and Gaussian selection " << sel.size() << ", for utterance " << b.keys[u]);
-          ++num_err;
-          continue;
-        }
-        const size_t w = sel[0].size();
-        bool same = w >= 1;
-        for (const auto& l : sel) same = same && l.size() == w;
-        if (!same) {
-          XWARN("The Gaussian selection of utterance " << b.keys[u] << " does not have one length for every frame (skipping utterance)");
-          ++num_err;
-          continue;
-        }
-        width = (int)w;
-      }
-      if (width != g.n && !g.keys.empty()) {
-        flush(g);
-        g.Clear();
-      }
-      g.n = width;
-      g.keys.push_back(b.keys[u]);
-      g.feats.insert(g.feats.end(), b.feats.begin() + (size_t)b.row_off[u] * b.cols, b.feats.begin() + (size_t)b.row_off[u + 1] * b.cols);
-      if (gselect) {
-        for (const auto& l : sel) g.gs.insert(g.gs.end(), l.begin(), l.end());
-      } else {
-        for (int t = 0; t < rows; ++t)
-          for (int k = 0; k < width; ++k) g.gs.push_back(k);
-      }
-      g.off.push_back(g.off.back() + rows);
-    }
-    if (!g.keys.empty()) flush(g);
-  }
-  return num_err;
-}
 
 void RefuseDense(const char* prog, const xv::FullGmmData& gmm) {
   if (gmm.num_gauss > xv::kUbmMaxSelect)
@@ -141,13 +40,14 @@ int FgmmGselect(int n_opt, const std::string& gselect_rspecifier, int device, co
   const int dev = xv::PickDevice(device);
   std::unique_ptr<xv::UbmModel> model(xv::UbmFullCreate(dev, gmm.num_gauss, gmm.dim, gmm.gconsts.data(), gmm.means_invcovars.data(), gmm.inv_covars.data()));
   xv::TableWriter writer(pos[2]);
+  xv::GselectGroupWalk groups(gmm.dim, gmm.num_gauss, pos[1], gselect_rspecifier);
   long num_done = 0;
   double tot_like = 0.0;
   int64_t tot_t = 0;
   bool warned = false;
   std::vector<int32_t> idx;
   std::vector<float> ll;
-  const long num_err = ForEachGroup(gmm, pos[1], gselect_rspecifier, [&](const Group& g) {
+  const long num_err = groups.Run([&](const xv::GselectGroup& g) {
     if (n_opt >= g.n && !warned) {
       XWARN("You asked for " << n_opt << " Gaussians but the preselection only has " << g.n
                              << ", returning this many. Note: this means the Gaussian selection is pointless.");
@@ -162,7 +62,7 @@ int FgmmGselect(int n_opt, const std::string& gselect_rspecifier, int device, co
       xv::IntVecVec out;
       for (int t = g.off[u]; t < g.off[u + 1]; ++t) {
         out.emplace_back(idx.begin() + (size_t)t * keep, idx.begin() + (size_t)(t + 1) * keep);
-        tot_like += LogSumExp(ll.data() + (size_t)t * keep, keep);
+        tot_like += xv::LogSumExp(ll.data() + (size_t)t * keep, keep);
       }
       tot_t += g.off[u + 1] - g.off[u];
       writer.WriteIntVecVec(g.keys[u], out);
@@ -182,11 +82,12 @@ int GetFrameLikes(bool average, const std::string& gselect_rspecifier, int devic
   const int dev = xv::PickDevice(device);
   std::unique_ptr<xv::UbmModel> model(xv::UbmFullCreate(dev, gmm.num_gauss, gmm.dim, gmm.gconsts.data(), gmm.means_invcovars.data(), gmm.inv_covars.data()));
   xv::TableWriter writer(pos[2]);
+  xv::GselectGroupWalk groups(gmm.dim, gmm.num_gauss, pos[1], gselect_rspecifier);
   long num_done = 0;
   double tot_like = 0.0;
   int64_t tot_t = 0;
   std::vector<float> likes;
-  const long num_err = ForEachGroup(gmm, pos[1], gselect_rspecifier, [&](const Group& g) {
+  const long num_err = groups.Run([&](const xv::GselectGroup& g) {
     const int nu = (int)g.keys.size();
     likes.resize((size_t)g.off[nu]);
     xv::UbmFrameLikes(*model, g.feats.data(), g.off.data(), nu, g.gs.data(), g.n, likes.data());

@@ -1,6 +1,6 @@
 // Host-only self test of the parsers that face untrusted input (model files, feature / vector archives), built with
 // AddressSanitizer + UndefinedBehaviorSanitizer by `make sanitize` (plain g++, no HIP: kio.cc, nnet3_raw.cc,
-// program.cc have no device dependency).  GPU AddressSanitizer is not available on the target pool, so this is where
+// program.cc, feat_batch.cc, cli.cc have no device dependency).  GPU AddressSanitizer is not available on the target pool, so this is where
 // memory errors of the host layer are caught.
 //
 //   host_selftest <model.raw> <output-node> <features.ark> [variants per kind, default 200]
@@ -11,6 +11,12 @@
 //     exactly what the sequential reader delivers, through the archive itself and through a script file of its offsets;
 // 3. replays both files truncated at `variants` positions and with 1.5 x `variants` single bits flipped: every variant must either parse or
 //    throw KioError - never crash, hang or trip a sanitizer.
+//
+//   host_selftest walk <dir>
+//
+// runs the feature-batch walk, the keyed lookups and the joins of feat_batch.h / feat_join.h over the cases <dir>/walk_cases.txt
+// names and prints one line per event - batch boundaries, join outcomes, the groups handed on (tests/test_feat_walk_host.py
+// computes the same dump from the inputs).
 //
 //   host_selftest tables <dir>
 //
@@ -28,6 +34,7 @@
 #include <string>
 #include <vector>
 
+#include "feat_join.h"
 #include "kio.h"
 #include "nnet3_raw.h"
 #include "program.h"
@@ -359,10 +366,100 @@ int RunTables(const char* dir) {
   return 0;
 }
 
+// --------------------------------------------------------------------------------------- host_selftest walk <dir>
+template <class V>
+std::string Join(const V& v) {
+  std::ostringstream o;
+  for (size_t i = 0; i < v.size(); ++i) o << (i ? "," : "") << v[i];
+  return o.str();
+}
+template <class T>
+std::string HashOf(const std::vector<T>& v) {
+  Hash h;
+  h.Add(v.data(), v.size() * sizeof(T));
+  char buf[32];
+  snprintf(buf, sizeof buf, "%016llx", (unsigned long long)h.h);
+  return buf;
+}
+std::string Outcome(const xv::Joined& j) {
+  const char* names[] = {"ok", "not-found", "wrong-size", "ragged"};
+  return std::string(names[j.outcome]) + "\tsize=" + std::to_string(j.size) + "\twidth=" + std::to_string(j.width);
+}
+
+// One case per line of <dir>/walk_cases.txt, fields separated by tabs; every case prints its line first.
+//   batches <read-ahead> <policy 0|1|2> <feats>:          the batches of the walk, then the number of entries counted as errors
+//   groups <read-ahead> <dim> <num-gauss> <feats> <gselect or ->:   the groups of the packer, then its count
+//   join-gselect <read-ahead> <feats> <gselect>:           FindGselect for every key of every batch
+//   join-post <read-ahead> <feats> <post>:                 FindFrames for every key, and per batch what Append made of the accepted
+// The warnings go to stderr, as in the tools.
+int RunWalk(const char* dir) {
+  if (chdir(dir) != 0) {
+    fprintf(stderr, "host_selftest: cannot enter %s\n", dir);
+    return 2;
+  }
+  std::ifstream cases("walk_cases.txt");
+  std::string line;
+  while (std::getline(cases, line)) {
+    if (line.empty() || line[0] == '#') continue;
+    const std::vector<std::string> f = SplitTabs(line);
+    printf("case\t%s\n", line.c_str());
+    try {
+      const int64_t ahead = f.size() > 1 ? atol(f[1].c_str()) : 0;
+      auto boundary = [](const xv::FeatBatchReader::Batch& b) {
+        printf("batch\tkeys=%s\tcols=%d\trow_off=%s\n", Join(b.keys).c_str(), b.cols, Join(b.row_off).c_str());
+      };
+      if (f[0] == "batches" && f.size() == 4) {
+        xv::FeatBatchWalk walk(f[3], ahead, false, (xv::FeatProblems)atoi(f[2].c_str()));
+        printf("errors\t%ld\n", walk.Run(boundary));
+      } else if (f[0] == "groups" && f.size() == 6) {
+        xv::GselectGroupWalk walk(atoi(f[2].c_str()), atoi(f[3].c_str()), f[4], f[5] == "-" ? "" : f[5], ahead);
+        printf("errors\t%ld\n", walk.Run([](const xv::GselectGroup& g) {
+          printf("group\twidth=%d\tkeys=%s\toff=%s\tfeats=%s\tgs=%s\n", g.n, Join(g.keys).c_str(), Join(g.off).c_str(), HashOf(g.feats).c_str(), HashOf(g.gs).c_str());
+        }));
+      } else if (f[0] == "join-gselect" && f.size() == 4) {
+        xv::FeatBatchWalk walk(f[2], ahead, false, xv::FeatProblems::kCount);
+        xv::GselectLookup table(f[3]);
+        walk.Run([&](const xv::FeatBatchReader::Batch& b) {
+          boundary(b);
+          for (size_t u = 0; u < b.keys.size(); ++u) {
+            xv::IntVecVec sel;
+            Event("join", b.keys[u], Outcome(xv::FindGselect(&table, b.keys[u], b.row_off[u + 1] - b.row_off[u], &sel)));
+          }
+        });
+      } else if (f[0] == "join-post" && f.size() == 4) {
+        xv::FeatBatchWalk walk(f[2], ahead, false, xv::FeatProblems::kCount);
+        xv::PosteriorLookup table(f[3]);
+        walk.Run([&](const xv::FeatBatchReader::Batch& b) {
+          boundary(b);
+          std::vector<int32_t> post_off(1, 0), post_idx;
+          std::vector<float> post_w, feats;
+          for (size_t u = 0; u < b.keys.size(); ++u) {
+            xv::Posterior p;
+            const xv::Joined j = xv::FindFrames(&table, b.keys[u], b.row_off[u + 1] - b.row_off[u], &p);
+            Event("join", b.keys[u], Outcome(j));
+            if (j.outcome != xv::Joined::kOk) continue;
+            xv::Append(p, &post_off, &post_idx, &post_w);
+            xv::AppendRows(b, u, &feats);
+          }
+          printf("post\tpost_off=%s\tpost_idx=%s\tpost_w=%s\tfeats=%s\n", Join(post_off).c_str(), HashOf(post_idx).c_str(), HashOf(post_w).c_str(), HashOf(feats).c_str());
+        });
+      } else {
+        fprintf(stderr, "host_selftest: bad line in walk_cases.txt: %s\n", line.c_str());
+        return 2;
+      }
+    } catch (const std::exception& ex) {
+      printf("thrown\t%s\n", ex.what());
+    }
+    fflush(stdout);
+  }
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc == 3 && strcmp(argv[1], "tables") == 0) return RunTables(argv[2]);
+  if (argc == 3 && strcmp(argv[1], "walk") == 0) return RunWalk(argv[2]);
   if (argc != 4 && argc != 5) {
     fprintf(stderr, "usage: host_selftest <model.raw> <output-node> <features.ark> [variants]\n       host_selftest tables <dir>\n");
     return 2;

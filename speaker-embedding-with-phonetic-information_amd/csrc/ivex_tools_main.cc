@@ -17,14 +17,11 @@
 #include <vector>
 
 #include "cli.h"
-#include "cmvn.h"
+#include "feat_join.h"
 #include "ivex.h"
 #include "kio.h"
-#include "posterior_lookup.h"
 
 namespace {
-
-constexpr int64_t kBatchFrames = 1 << 16;   // frames read ahead per device call
 
 struct ExtractOptions {
   bool compute_objf_change = true;
@@ -38,26 +35,16 @@ int IvectorExtract(const ExtractOptions& o, const std::vector<std::string>& pos)
   const int dev = xv::PickDevice(o.device);
   std::unique_ptr<xv::IvexModel> model(xv::IvexCreate(dev, data));
   const int D = data.D, S = data.S;
-  xv::FeatBatchReader reader(pos[1], kBatchFrames, false);
+  xv::FeatBatchWalk walk(pos[1], xv::kBatchFrames, false, xv::FeatProblems::kCount);
   xv::PosteriorLookup posts(pos[2]);
   xv::TableWriter writer(pos[3]);
   long num_done = 0, num_err = 0;
   double tot_t = 0.0, tot_auxf = 0.0;
-  xv::FeatBatchReader::Batch b;
-  std::vector<xv::FeatBatchReader::Problem> problems;
   std::vector<std::string> keys;
   std::vector<float> feats, post_w, ivectors;
   std::vector<int32_t> off, post_off, post_idx, status;
   std::vector<double> auxf, weighted;
-  for (bool more = true; more;) {
-    problems.clear();
-    more = reader.Next(&b, &problems);
-    for (const auto& p : problems) {
-      if (p.what.empty()) XWARN("Empty feature matrix for utterance " << p.key);
-      else XWARN("Failed to read features for key " << p.key << ": " << p.what);
-      ++num_err;
-    }
-    if (!more) break;
+  const long unread = walk.Run([&](const xv::FeatBatchReader::Batch& b) {
     if (b.cols != D)
       throw xv::KioError("Feature dimension mismatch: the features of " + b.keys[0] + " have " + std::to_string(b.cols) + " columns, the model " + std::to_string(D));
     keys.clear();
@@ -70,24 +57,15 @@ int IvectorExtract(const ExtractOptions& o, const std::vector<std::string>& pos)
     for (size_t u = 0; u < b.keys.size(); ++u) {
       const int rows = b.row_off[u + 1] - b.row_off[u];
       xv::Posterior p;
-      if (!posts.Find(b.keys[u], &p)) {
-        XWARN("No posteriors for utterance " << b.keys[u]);
-        ++num_err;
-        continue;
-      }
-      if ((int)p.size() != rows) {
-        XWARN("Size mismatch between posterior " << p.size() << " and features " << rows << " for utterance " << b.keys[u]);
+      const xv::Joined j = xv::FindFrames(&posts, b.keys[u], rows, &p);
+      if (j.outcome == xv::Joined::kNotFound) XWARN("No posteriors for utterance " << b.keys[u]);
+      else if (j.outcome != xv::Joined::kOk) XWARN("Size mismatch between posterior " << j.size << " and features " << rows << " for utterance " << b.keys[u]);
+      if (j.outcome != xv::Joined::kOk) {
         ++num_err;
         continue;
       }
       const size_t first = post_w.size();
-      for (const auto& frame : p) {
-        for (const auto& e : frame) {
-          post_idx.push_back(e.first);
-          post_w.push_back(e.second);
-        }
-        post_off.push_back((int32_t)post_w.size());
-      }
+      xv::Append(p, &post_off, &post_idx, &post_w);
       bool clipped = false;
       const float scale = xv::IvexPosteriorScale(post_w.data() + first, post_w.size() - first, o.acoustic_weight, o.max_count, &clipped);
       if (clipped) XLOG("Scaling stats for utterance " << b.keys[u] << " by scale " << scale << " due to --max-count=" << o.max_count);
@@ -95,10 +73,10 @@ int IvectorExtract(const ExtractOptions& o, const std::vector<std::string>& pos)
       for (size_t i = first; i < post_w.size(); ++i) t += (double)(post_w[i] * scale);
       weighted.push_back(t);
       keys.push_back(b.keys[u]);
-      feats.insert(feats.end(), b.feats.begin() + (size_t)b.row_off[u] * D, b.feats.begin() + (size_t)b.row_off[u + 1] * D);
+      xv::AppendRows(b, u, &feats);
       off.push_back(off.back() + rows);
     }
-    if (keys.empty()) continue;
+    if (keys.empty()) return;
     const int n = (int)keys.size();
     ivectors.resize((size_t)n * S);
     status.resize((size_t)n);
@@ -130,9 +108,9 @@ int IvectorExtract(const ExtractOptions& o, const std::vector<std::string>& pos)
       writer.WriteVec(keys[u], v, S);
       ++num_done;
     }
-  }
+  });
   writer.Close();
-  XLOG("Done " << num_done << " files, " << num_err << " with errors.  Total (weighted) frames " << tot_t);
+  XLOG("Done " << num_done << " files, " << unread + num_err << " with errors.  Total (weighted) frames " << tot_t);
   if (o.compute_objf_change)
     XLOG("Overall average objective-function change from estimating ivector was " << (tot_t != 0.0 ? tot_auxf / tot_t : 0.0) << " per frame  over "
                                                                                     << tot_t << " (weighted) frames.");

@@ -18,15 +18,12 @@
 #include <vector>
 
 #include "cli.h"
-#include "cmvn.h"
+#include "feat_join.h"
 #include "ivex.h"
 #include "ivex_train.h"
 #include "kio.h"
-#include "posterior_lookup.h"
 
 namespace {
-
-constexpr int64_t kBatchFrames = 1 << 16;   // frames read ahead per device call
 
 struct AccOptions {
   bool binary = true, update_variances = true, compute_auxf = true;
@@ -40,23 +37,13 @@ int AccStats(const AccOptions& o, const std::vector<std::string>& pos) {
   std::unique_ptr<xv::IvexModel> model(xv::IvexCreate(dev, data));
   std::unique_ptr<xv::IvexAccumulator> acc(xv::IvexAccCreate(model.get(), o.update_variances, o.compute_auxf));
   const int D = data.D;
-  xv::FeatBatchReader reader(pos[1], kBatchFrames, false);
+  xv::FeatBatchWalk walk(pos[1], xv::kBatchFrames, false, xv::FeatProblems::kCount);
   xv::PosteriorLookup posts(pos[2]);
   long num_done = 0, num_err = 0;
-  xv::FeatBatchReader::Batch b;
-  std::vector<xv::FeatBatchReader::Problem> problems;
   std::vector<std::string> keys;
   std::vector<float> feats, post_w;
   std::vector<int32_t> off, post_off, post_idx, status;
-  for (bool more = true; more;) {
-    problems.clear();
-    more = reader.Next(&b, &problems);
-    for (const auto& p : problems) {
-      if (p.what.empty()) XWARN("Empty feature matrix for utterance " << p.key);
-      else XWARN("Failed to read features for key " << p.key << ": " << p.what);
-      ++num_err;
-    }
-    if (!more) break;
+  const long unread = walk.Run([&](const xv::FeatBatchReader::Batch& b) {
     if (b.cols != D)
       throw xv::KioError("Feature dimension mismatch: the features of " + b.keys[0] + " have " + std::to_string(b.cols) + " columns, the model " + std::to_string(D));
     keys.clear();
@@ -68,28 +55,19 @@ int AccStats(const AccOptions& o, const std::vector<std::string>& pos) {
     for (size_t u = 0; u < b.keys.size(); ++u) {
       const int rows = b.row_off[u + 1] - b.row_off[u];
       xv::Posterior p;
-      if (!posts.Find(b.keys[u], &p)) {
-        XWARN("No posteriors for utterance " << b.keys[u]);
+      const xv::Joined j = xv::FindFrames(&posts, b.keys[u], rows, &p);
+      if (j.outcome == xv::Joined::kNotFound) XWARN("No posteriors for utterance " << b.keys[u]);
+      else if (j.outcome != xv::Joined::kOk) XWARN("Size mismatch between posterior " << j.size << " and features " << rows << " for utterance " << b.keys[u]);
+      if (j.outcome != xv::Joined::kOk) {
         ++num_err;
         continue;
       }
-      if ((int)p.size() != rows) {
-        XWARN("Size mismatch between posterior " << p.size() << " and features " << rows << " for utterance " << b.keys[u]);
-        ++num_err;
-        continue;
-      }
-      for (const auto& frame : p) {
-        for (const auto& e : frame) {
-          post_idx.push_back(e.first);
-          post_w.push_back(e.second);
-        }
-        post_off.push_back((int32_t)post_w.size());
-      }
+      xv::Append(p, &post_off, &post_idx, &post_w);
       keys.push_back(b.keys[u]);
-      feats.insert(feats.end(), b.feats.begin() + (size_t)b.row_off[u] * D, b.feats.begin() + (size_t)b.row_off[u + 1] * D);
+      xv::AppendRows(b, u, &feats);
       off.push_back(off.back() + rows);
     }
-    if (keys.empty()) continue;
+    if (keys.empty()) return;
     const int n = (int)keys.size();
     status.assign((size_t)n, 0);
     xv::IvexAccAdd(acc.get(), feats.data(), off.data(), n, post_off.data(), post_idx.data(), post_w.data(), status.data());
@@ -101,10 +79,10 @@ int AccStats(const AccOptions& o, const std::vector<std::string>& pos) {
         ++num_done;
       }
     }
-  }
+  });
   xv::IvexStats st;
   xv::IvexAccGet(acc.get(), &st);
-  XLOG("Done " << num_done << " files, " << num_err << " with errors.");
+  XLOG("Done " << num_done << " files, " << unread + num_err << " with errors.");
   if (o.compute_auxf)
     XLOG("Overall auxf/frame on training data was " << (st.frames != 0.0 ? st.auxf / st.frames : 0.0) << " per frame over " << st.frames << " frames.");
   xv::WriteIvexStatsFile(pos[3], o.binary, st);

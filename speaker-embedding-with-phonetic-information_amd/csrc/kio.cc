@@ -901,6 +901,12 @@ static std::vector<std::string> SplitComma(const std::string& s) {
   return out;
 }
 
+bool IsTable(const std::string& specifier) {
+  if (specifier.find(':') == std::string::npos) return false;
+  const std::string kind = specifier.substr(0, specifier.find_first_of(",:"));
+  return kind == "ark" || kind == "scp";
+}
+
 RspecifierOptions ParseRspecifier(const std::string& rspecifier) {
   RspecifierOptions o;
   std::string opts, rest;

@@ -163,6 +163,8 @@ struct WspecifierOptions {
   std::string ark_wxfilename, scp_wxfilename;
 };
 WspecifierOptions ParseWspecifier(const std::string& wspecifier);
+// "ark:..." / "scp,p:..." is a table; anything else a file (Kaldi's ClassifyWspecifier / ClassifyRspecifier, as far as needed)
+bool IsTable(const std::string& specifier);
 
 // ---------------------------------------------------------------------------------------------
 // The pieces every table reader is made of.

@@ -17,13 +17,12 @@
 #include <vector>
 
 #include "cli.h"
-#include "cmvn.h"
 #include "feat.h"
+#include "feat_join.h"
 #include "gmm_train.h"
 #include "kio.h"
 #include "nnet3_raw.h"
 #include "post.h"
-#include "posterior_lookup.h"
 #include "program.h"
 #include "ubm.h"
 #include "ubm_train.h"
@@ -125,9 +124,9 @@ int ParseNumComponents(const std::string& s) {
 int AccStatsPost(const AccOptions& o, const std::vector<std::string>& pos) {
   const int flags = xv::ParseGmmFlags(o.update_flags);
   const int G = ParseNumComponents(pos[1]);
-  constexpr int64_t kBatchFrames = 1 << 16;   // frames read ahead; the accumulate calls do not depend on it
   xv::PosteriorLookup posts(pos[0]);
-  xv::FeatBatchReader reader(pos[2], kBatchFrames, false);
+  // (the accumulate calls do not depend on the frames read ahead; a matrix without rows is skipped, not an error)
+  xv::FeatBatchWalk walk(pos[2], xv::kBatchFrames, false, xv::FeatProblems::kCountUnreadable);
   std::unique_ptr<xv::FgmmAccumulator> acc;
   xv::FgmmAccs host;
   int D = 0;
@@ -145,20 +144,7 @@ int AccStatsPost(const AccOptions& o, const std::vector<std::string>& pos) {
     off.erase(off.begin(), off.begin() + rows);
     for (int32_t& v : off) v -= used;
   };
-  xv::FeatBatchReader::Batch b;
-  std::vector<xv::FeatBatchReader::Problem> problems;
-  for (bool more = true; more;) {
-    problems.clear();
-    more = reader.Next(&b, &problems);
-    for (const auto& p : problems) {
-      if (p.what.empty()) {
-        XWARN("Empty feature matrix for utterance " << p.key);
-      } else {
-        XWARN("Failed to read features for key " << p.key << ": " << p.what);
-        ++num_err;
-      }
-    }
-    if (!more) break;
+  const long unread = walk.Run([&](const xv::FeatBatchReader::Batch& b) {
     for (size_t u = 0; u < b.keys.size(); ++u) {
       const int rows = b.row_off[u + 1] - b.row_off[u];
       if (!acc) {   // the first utterance gives the dimension
@@ -172,13 +158,10 @@ int AccStatsPost(const AccOptions& o, const std::vector<std::string>& pos) {
         continue;
       }
       xv::Posterior post;
-      if (!posts.Find(b.keys[u], &post)) {
-        XWARN("No posterior for utterance " << b.keys[u]);
-        ++num_err;
-        continue;
-      }
-      if ((int)post.size() != rows) {
-        XWARN("The posterior of utterance " << b.keys[u] << " has wrong size " << post.size() << " vs. " << rows);
+      const xv::Joined j = xv::FindFrames(&posts, b.keys[u], rows, &post);
+      if (j.outcome == xv::Joined::kNotFound) XWARN("No posterior for utterance " << b.keys[u]);
+      else if (j.outcome != xv::Joined::kOk) XWARN("The posterior of utterance " << b.keys[u] << " has wrong size " << j.size << " vs. " << rows);
+      if (j.outcome != xv::Joined::kOk) {
         ++num_err;
         continue;
       }
@@ -187,21 +170,14 @@ int AccStatsPost(const AccOptions& o, const std::vector<std::string>& pos) {
           if (pr.first < 0 || pr.first >= G)
             throw xv::KioError("the posterior of utterance " + b.keys[u] + " names Gaussian " + std::to_string(pr.first) + " at frame " + std::to_string(t) +
                                "; <num-components> is " + std::to_string(G));
-      feats.insert(feats.end(), b.feats.begin() + (size_t)b.row_off[u] * D, b.feats.begin() + (size_t)b.row_off[u + 1] * D);
-      for (const auto& frame : post) {
-        for (const auto& pr : frame) {
-          idx.push_back(pr.first);
-          w.push_back(pr.second);
-        }
-        if (idx.size() > (size_t)INT32_MAX) throw xv::KioError("more than 2^31 posterior pairs are pending in one block of frames");
-        off.push_back((int32_t)idx.size());
-      }
+      xv::AppendRows(b, u, &feats);
+      xv::Append(post, &off, &idx, &w);
       while (off.size() - 1 >= (size_t)xv::kFgmmAccFrameBlock) block((size_t)xv::kFgmmAccFrameBlock);
       ++num_done;
     }
-  }
+  });
   if (off.size() > 1) block(off.size() - 1);
-  XLOG("Done " << num_done << " files; " << num_err << " with errors.");
+  XLOG("Done " << num_done << " files; " << unread + num_err << " with errors.");
   if (!acc) {
     XWARN("No statistics were accumulated: nothing is written");
     return 1;

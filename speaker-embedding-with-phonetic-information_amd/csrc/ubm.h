@@ -25,6 +25,7 @@
 // On the device (ubm_kernels.h) everything is fp32 products with fp32 accumulation in an order that is a function of the frame and
 // the model alone.  A model is uploaded once, behind a UbmModel.  Limits: n <= 64 selected Gaussians, dimension <= 96.
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -82,6 +83,15 @@ UbmDiagView UbmDiagArrays(const UbmModel& diag);
 // feats: [row_off[n_utts]][dim] packed; idx: [rows][n]; ll: the same shape or null.  n <= min(64, num_gauss).  Blocking.
 void UbmGselect(const UbmModel& diag, const float* feats, const int32_t* row_off, int n_utts, int n, int32_t* idx, float* ll,
                 float* device_ms = nullptr);
+// Host only: log sum_i exp(v_i) in fp64, what the selection tools' log lines average over the frames' ll; -inf when every v_i is.
+inline double LogSumExp(const float* v, int n) {
+  double mx = v[0];
+  for (int i = 1; i < n; ++i) mx = v[i] > mx ? v[i] : mx;
+  if (isinf(mx)) return mx;
+  double s = 0.0;
+  for (int i = 0; i < n; ++i) s += exp((double)v[i] - mx);
+  return mx + log(s);
+}
 // gselect: [rows][n], every entry in [0, num_gauss).  count: [rows]; idx / post: [rows][n], the first count[t] of frame t are set.
 // ll ([rows][n], the log-likelihoods before the softmax) and logsum ([rows]) may be null.  device_ms: {sort, scores, softmax}.
 void UbmPost(const UbmModel& full, const float* feats, const int32_t* row_off, int n_utts, const int32_t* gselect, int n, float min_post,

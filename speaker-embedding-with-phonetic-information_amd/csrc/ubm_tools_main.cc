@@ -13,7 +13,6 @@
 // are read ahead in batches, so the recipes' "ark,s,cs:add-deltas ... | apply-cmvn-sliding ... | select-voiced-frames ... |" is
 // a child pipeline read front to back.  Refused by name: gmm-gselect --write-likes and --gselect.
 // ivector-extract, line 69 of that script, takes the posteriors from here: ivex_tools_main.cc.
-#include <math.h>
 #include <stdlib.h>
 
 #include <memory>
@@ -22,30 +21,13 @@
 #include <vector>
 
 #include "cli.h"
-#include "cmvn.h"
-#include "gselect_lookup.h"
+#include "feat_batch.h"
+#include "feat_join.h"
 #include "kio.h"
 #include "ubm.h"
 #include "ubm_kernels.h"
 
 namespace {
-
-constexpr int64_t kBatchFrames = 1 << 16;   // frames read ahead per device call
-
-bool IsTable(const std::string& spec) {
-  const size_t colon = spec.find(':');
-  if (colon == std::string::npos) return false;
-  const std::string kind = spec.substr(0, spec.find_first_of(",:"));
-  return kind == "ark" || kind == "scp";
-}
-
-void ReportProblems(const std::vector<xv::FeatBatchReader::Problem>& problems, long* num_err) {
-  for (const auto& p : problems) {
-    if (p.what.empty()) XWARN("Empty feature matrix for utterance " << p.key);
-    else XWARN("Failed to read features for key " << p.key << ": " << p.what);
-    ++*num_err;
-  }
-}
 
 struct DeltaOptions {
   int order = 2, window = 2, truncate = 0, device = -1;
@@ -53,17 +35,11 @@ struct DeltaOptions {
 
 int AddDeltas(const DeltaOptions& o, const std::vector<std::string>& pos) {
   const int dev = xv::PickDevice(o.device);
-  xv::FeatBatchReader reader(pos[0], kBatchFrames, false);
+  xv::FeatBatchWalk feats(pos[0], xv::kBatchFrames, false, xv::FeatProblems::kCount);
   xv::TableWriter writer(pos[1]);
-  long num_done = 0, num_err = 0;
-  xv::FeatBatchReader::Batch b;
-  std::vector<xv::FeatBatchReader::Problem> problems;
+  long num_done = 0;
   std::vector<float> out;
-  for (bool more = true; more;) {
-    problems.clear();
-    more = reader.Next(&b, &problems);
-    ReportProblems(problems, &num_err);
-    if (!more) break;
+  const long num_err = feats.Run([&](const xv::FeatBatchReader::Batch& b) {
     const int n = (int)b.keys.size();
     const int oc = (o.order + 1) * (o.truncate > 0 ? o.truncate : b.cols);
     out.resize((size_t)b.row_off[n] * oc);
@@ -76,7 +52,7 @@ int AddDeltas(const DeltaOptions& o, const std::vector<std::string>& pos) {
       writer.WriteMat(b.keys[u], m);
       ++num_done;
     }
-  }
+  });
   writer.Close();
   XLOG("Done " << num_done << " files, " << num_err << " with errors.");
   return num_done != 0 ? 0 : 1;
@@ -92,15 +68,6 @@ int FgmmToGmm(bool binary, const std::vector<std::string>& pos) {
   return 0;
 }
 
-// log sum_i exp(v_i), in fp64
-double LogSumExp(const float* v, int n) {
-  double mx = v[0];
-  for (int i = 1; i < n; ++i) mx = v[i] > mx ? v[i] : mx;
-  double s = 0.0;
-  for (int i = 0; i < n; ++i) s += exp((double)v[i] - mx);
-  return mx + log(s);
-}
-
 int GmmGselect(int n_opt, int device, const std::vector<std::string>& pos) {
   if (n_opt < 1) throw xv::KioError("--n must be at least 1");
   xv::DiagGmmData gmm;
@@ -114,26 +81,20 @@ int GmmGselect(int n_opt, int device, const std::vector<std::string>& pos) {
     throw xv::KioError("--n=" + std::to_string(n) + " is above the limit of " + std::to_string(xv::kUbmMaxSelect) + " selected Gaussians per frame of the device kernel");
   const int dev = xv::PickDevice(device);
   std::unique_ptr<xv::UbmModel> model(xv::UbmDiagCreate(dev, gmm.num_gauss, gmm.dim, gmm.gconsts.data(), gmm.means_invvars.data(), gmm.inv_vars.data()));
-  xv::FeatBatchReader reader(pos[1], kBatchFrames, false);
+  xv::FeatBatchWalk feats(pos[1], xv::kBatchFrames, false, xv::FeatProblems::kCount);
   xv::TableWriter writer(pos[2]);
   long num_done = 0, num_err = 0;
   double tot_like = 0.0;
   int64_t tot_t = 0;
-  xv::FeatBatchReader::Batch b;
-  std::vector<xv::FeatBatchReader::Problem> problems;
   std::vector<int32_t> idx;
   std::vector<float> ll;
-  for (bool more = true; more;) {
-    problems.clear();
-    more = reader.Next(&b, &problems);
-    ReportProblems(problems, &num_err);
-    if (!more) break;
+  const long unread = feats.Run([&](const xv::FeatBatchReader::Batch& b) {
     if (b.cols != gmm.dim) {
       for (const std::string& key : b.keys) {
         XWARN("Dimension mismatch for utterance " << key << ": the features have " << b.cols << " columns, the model " << gmm.dim);
         ++num_err;
       }
-      continue;
+      return;
     }
     const int nu = (int)b.keys.size();
     const size_t rows = (size_t)b.row_off[nu];
@@ -144,15 +105,15 @@ int GmmGselect(int n_opt, int device, const std::vector<std::string>& pos) {
       xv::IntVecVec gs;
       for (int t = b.row_off[u]; t < b.row_off[u + 1]; ++t) {
         gs.emplace_back(idx.begin() + (size_t)t * n, idx.begin() + (size_t)(t + 1) * n);
-        tot_like += LogSumExp(ll.data() + (size_t)t * n, n);
+        tot_like += xv::LogSumExp(ll.data() + (size_t)t * n, n);
       }
       tot_t += b.row_off[u + 1] - b.row_off[u];
       writer.WriteIntVecVec(b.keys[u], gs);
       ++num_done;
     }
-  }
+  });
   writer.Close();
-  XLOG("Done " << num_done << " files, " << num_err << " with errors, average UBM log-likelihood is " << (tot_t ? tot_like / (double)tot_t : 0.0)
+  XLOG("Done " << num_done << " files, " << unread + num_err << " with errors, average UBM log-likelihood is " << (tot_t ? tot_like / (double)tot_t : 0.0)
                << " over " << tot_t << " frames.");
   return num_done != 0 ? 0 : 1;
 }
@@ -162,88 +123,33 @@ int GselectToPost(float min_post, int device, const std::vector<std::string>& po
   xv::ReadFullGmmFile(pos[0], &gmm);
   const int dev = xv::PickDevice(device);
   std::unique_ptr<xv::UbmModel> model(xv::UbmFullCreate(dev, gmm.num_gauss, gmm.dim, gmm.gconsts.data(), gmm.means_invcovars.data(), gmm.inv_covars.data()));
-  xv::FeatBatchReader reader(pos[1], kBatchFrames, false);
-  xv::GselectLookup gselect(pos[2]);
+  xv::GselectGroupWalk groups(gmm.dim, gmm.num_gauss, pos[1], pos[2]);
   xv::TableWriter writer(pos[3]);
-  long num_done = 0, num_err = 0;
+  long num_done = 0;
   double tot_like = 0.0;
   int64_t tot_t = 0;
-  xv::FeatBatchReader::Batch b;
-  std::vector<xv::FeatBatchReader::Problem> problems;
-  std::vector<std::string> keys;
-  std::vector<float> feats, post, logsum;
-  std::vector<int32_t> off, gs, count, idx;
-  for (bool more = true; more;) {
-    problems.clear();
-    more = reader.Next(&b, &problems);
-    ReportProblems(problems, &num_err);
-    if (!more) break;
-    // the utterances of the batch that have a usable selection, grouped by the selection's width
-    keys.clear();
-    feats.clear();
-    gs.clear();
-    off.assign(1, 0);
-    int n = 0;
-    auto flush = [&] {
-      if (keys.empty()) return;
-      const int nu = (int)keys.size();
-      const size_t rows = (size_t)off[nu];
-      count.resize(rows);
-      idx.resize(rows * n);
-      post.resize(rows * n);
-      logsum.resize(rows);
-      xv::UbmPost(*model, feats.data(), off.data(), nu, gs.data(), n, min_post, count.data(), idx.data(), post.data(), nullptr, logsum.data());
-      for (int u = 0; u < nu; ++u) {
-        xv::Posterior p;
-        for (int t = off[u]; t < off[u + 1]; ++t) {
-          p.emplace_back();
-          for (int k = 0; k < count[t]; ++k) p.back().emplace_back(idx[(size_t)t * n + k], post[(size_t)t * n + k]);
-          tot_like += logsum[t];
-        }
-        tot_t += off[u + 1] - off[u];
-        writer.WritePosterior(keys[u], p);
-        ++num_done;
+  std::vector<float> post, logsum;
+  std::vector<int32_t> count, idx;
+  const long num_err = groups.Run([&](const xv::GselectGroup& g) {
+    const int nu = (int)g.keys.size(), n = g.n;
+    const size_t rows = (size_t)g.off[nu];
+    count.resize(rows);
+    idx.resize(rows * n);
+    post.resize(rows * n);
+    logsum.resize(rows);
+    xv::UbmPost(*model, g.feats.data(), g.off.data(), nu, g.gs.data(), n, min_post, count.data(), idx.data(), post.data(), nullptr, logsum.data());
+    for (int u = 0; u < nu; ++u) {
+      xv::Posterior p;
+      for (int t = g.off[u]; t < g.off[u + 1]; ++t) {
+        p.emplace_back();
+        for (int k = 0; k < count[t]; ++k) p.back().emplace_back(idx[(size_t)t * n + k], post[(size_t)t * n + k]);
+        tot_like += logsum[t];
       }
-      keys.clear();
-      feats.clear();
-      gs.clear();
-      off.assign(1, 0);
-    };
-    for (size_t u = 0; u < b.keys.size(); ++u) {
-      const int rows = b.row_off[u + 1] - b.row_off[u];
-      if (b.cols != gmm.dim) {
-        XWARN("Dimension mismatch for utterance " << b.keys[u] << ": the features have " << b.cols << " columns, the model " << gmm.dim);
-        ++num_err;
-        continue;
-      }
-      xv::IntVecVec sel;
-      if (!gselect.Find(b.keys[u], &sel)) {
-        XWARN("No Gaussian-selection info available for utterance " << b.keys[u] << " (skipping utterance)");
-        ++num_err;
-        continue;
-      }
-      if ((int)sel.size() != rows) {
-        XWARN("Mismatch in number of frames " << rows << " for features and Gaussian selection " << sel.size() << ", for utterance " << b.keys[u]);
-        ++num_err;
-        continue;
-      }
-      const size_t width = sel[0].size();
-      bool same = width >= 1;
-      for (const auto& l : sel) same = same && l.size() == width;
-      if (!same) {
-        XWARN("The Gaussian selection of utterance " << b.keys[u] << " does not have one length for every frame (skipping utterance)");
-        ++num_err;
-        continue;
-      }
-      if ((int)width != n) flush();
-      n = (int)width;
-      keys.push_back(b.keys[u]);
-      feats.insert(feats.end(), b.feats.begin() + (size_t)b.row_off[u] * b.cols, b.feats.begin() + (size_t)b.row_off[u + 1] * b.cols);
-      for (const auto& l : sel) gs.insert(gs.end(), l.begin(), l.end());
-      off.push_back(off.back() + rows);
+      tot_t += g.off[u + 1] - g.off[u];
+      writer.WritePosterior(g.keys[u], p);
+      ++num_done;
     }
-    flush();
-  }
+  });
   writer.Close();
   XLOG("Done " << num_done << " files, " << num_err << " with errors, average log-likelihood per frame is " << (tot_t ? tot_like / (double)tot_t : 0.0)
                << " over " << tot_t << " frames.");
@@ -251,7 +157,7 @@ int GselectToPost(float min_post, int device, const std::vector<std::string>& po
 }
 
 int ScalePost(const std::vector<std::string>& pos) {
-  const bool table = IsTable(pos[1]);
+  const bool table = xv::IsTable(pos[1]);
   std::unordered_map<std::string, float> scales;
   double global = 1.0;
   if (table) scales = xv::ReadFloatTable(pos[1]);

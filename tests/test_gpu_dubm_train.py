@@ -453,3 +453,33 @@ def test_train_diag_ubm_lines_run_with_the_scripts_argv(recipe):
     assert r.returncode == 0 and b"Done 6 files, 0 with errors" in r.stderr, r.stderr.decode()
     final = R.read_diag_gmm((dirr / "final.dubm").read_bytes())
     assert 1 <= len(final["weights"]) <= 8 and abs(float(final["weights"].sum()) - 1.0) < 1e-6 and np.all(np.isfinite(final["gconsts"]))
+
+
+def test_acc_stats_words_and_counts_what_it_skips(tmp_path):
+    """gmm-global-acc-stats on five utterances, one usable: a key the --gselect table does not have, a selection a frame short
+    and one of another width are warned and counted; a matrix without rows is warned and not counted."""
+    Gm, D = 4, 6
+    m = integer_model(Gm, D)
+    (tmp_path / "0.dubm").write_bytes(R.diag_gmm_bytes(np.full(Gm, 1.0 / Gm, F), m["means_invvars"], m["inv_vars"], True))
+    x = np.random.default_rng(61).integers(-4, 5, (12, D)).astype(F)
+    kio.write_ark_matrices(str(tmp_path / "f.ark"), [("a", x[0:3]), ("b", x[3:5]), ("c", x[5:8]), ("d", x[8:12]), ("e", x[:0])])
+    (tmp_path / "f.gs").write_bytes(R.gselect_table_bytes([("a", [[0, 1]] * 3), ("c", [[1, 2]] * 2), ("d", [[3]] * 4)], True))
+    r = _sh("gmm-global-acc-stats --gselect=ark,s,cs:f.gs 0.dubm ark,s,cs:f.ark f.acc", cwd=str(tmp_path))
+    log = r.stderr.decode()
+    assert r.returncode == 0, log
+    for text in (") No gselect information for utterance b\n", ") gselect information for utterance c has wrong size 2 vs. 3\n",
+                 ") The Gaussian selection of utterance d does not have the 2 indices per frame of the utterances before it (skipping utterance)\n",
+                 ") Empty feature matrix for utterance e\n", ") Done 1 files; 3 with errors.\n"):
+        assert log.count(text) == 1, log
+    assert re.search(r"Overall likelihood per frame = \S+ over 3 \(weighted\) frames\.", log), log
+
+
+def test_init_from_feats_stops_at_an_entry_it_cannot_read(tmp_path):
+    x = np.random.default_rng(62).normal(size=(8, 3)).astype(F)
+    offs = kio.write_ark_matrices(str(tmp_path / "f.ark"), [("a", x[:4]), ("c", x[4:])])
+    (tmp_path / "f.scp").write_text("a f.ark:%d\nb gone.ark:7\nc f.ark:%d\n" % (offs["a"], offs["c"]))
+    r = _sh("gmm-global-init-from-feats --num-gauss=2 --num-iters=1 scp:f.scp out.dubm", cwd=str(tmp_path))
+    log = r.stderr.decode()
+    assert r.returncode == 255, log
+    assert log.count("ERROR (gmm-global-init-from-feats) Failed to read features for key b: cannot open gone.ark for reading") == 1, log
+    assert not (tmp_path / "out.dubm").exists()

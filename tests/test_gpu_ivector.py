@@ -342,3 +342,20 @@ def test_extract_ivectors_lines_run_with_the_recipes_argv(tmp_path):
     (tmp_path / "bad.ark").write_bytes(UR.post_table_bytes(bad, True))
     r = _sh('ivector-extract %s/final.ie "%s" ark:%s/bad.ark ark:/dev/null' % (srcdir, feats, tmp_path))
     assert r.returncode == 255 and b"ERROR (ivector-extract" in r.stderr and b"name Gaussian 21" in r.stderr
+
+
+def test_a_posterior_a_frame_short_is_warned_about_and_counted(tmp_path):
+    G, D, S = 4, 6, 5
+    (tmp_path / "final.ie").write_bytes(R.ie_bytes(**R.random_model(9, G, D, S)))
+    rng = np.random.default_rng(10)
+    lens = {"a": 5, "b": 4, "c": 6}
+    kio.write_ark_matrices(str(tmp_path / "f.ark"), [(k, rng.normal(size=(n, D)).astype(np.float32)) for k, n in lens.items()])
+    post = {k: [[(int(rng.integers(0, G)), 1.0)] for _ in range(n)] for k, n in lens.items()}
+    post["b"] = post["b"][:-1]
+    (tmp_path / "p.post").write_bytes(UR.post_table_bytes(sorted(post.items()), True))
+    r = _sh("timeout -k 10 120 ivector-extract final.ie ark,s,cs:f.ark ark,s,cs:p.post ark,t:iv.ark", cwd=str(tmp_path))
+    log = r.stderr.decode()
+    assert r.returncode == 0, log
+    assert log.count(") Size mismatch between posterior 3 and features 4 for utterance b\n") == 1, log
+    assert re.search(r"LOG \(ivector-extract\S* Done 2 files, 1 with errors\.  Total \(weighted\) frames \S+\n", log), log
+    assert [k for k, _ in _read_text_vectors((tmp_path / "iv.ark").read_bytes())] == ["a", "c"]

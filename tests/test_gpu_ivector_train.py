@@ -378,3 +378,20 @@ def test_train_ivector_extractor_lines_run_with_the_recipes_argv(tmp_path):
     assert re.search(rb"Done 4 files, 0 with errors", r.stderr)
     vecs = [l for l in (d / "ivector.1.ark").read_text().splitlines() if l.strip()]
     assert len(vecs) == 4 and all(len(l.split()) == S + 3 for l in vecs)
+
+
+def test_a_posterior_a_frame_short_is_warned_about_and_counted(tmp_path):
+    G, D, S = 4, 6, 5
+    (tmp_path / "0.ie").write_bytes(R.ie_bytes(**R.random_model(9, G, D, S)))
+    rng = np.random.default_rng(10)
+    lens = {"a": 5, "b": 4, "c": 6}
+    kio.write_ark_matrices(str(tmp_path / "f.ark"), [(k, rng.normal(size=(n, D)).astype(np.float32)) for k, n in lens.items()])
+    post = {k: [[(int(rng.integers(0, G)), 1.0)] for _ in range(n)] for k, n in lens.items()}
+    post["b"] = post["b"][:-1]
+    (tmp_path / "p.post").write_bytes(UR.post_table_bytes(sorted(post.items()), True))
+    r = _sh(LIMIT + "ivector-extractor-acc-stats %s/0.ie ark,s,cs:%s/f.ark ark,s,cs:%s/p.post %s/0.acc" % ((tmp_path,) * 4))
+    log = r.stderr.decode()
+    assert r.returncode == 0, log
+    assert log.count(") Size mismatch between posterior 3 and features 4 for utterance b\n") == 1, log
+    assert re.search(r"LOG \(ivector-extractor-acc-stats\S* Done 2 files, 1 with errors\.\n", log), log
+    assert P.ivex_stats_read(str(tmp_path / "0.acc"))["num_ivectors"] == 2

@@ -262,3 +262,14 @@ def test_the_phonetic_baseline_runs_with_the_recipes_argv(tmp_path):
     vecs = [l.split() for l in (tmp_path / "ivector.1.ark").read_text().splitlines() if l.strip()]
     assert [v[0] for v in vecs] == jobs[1] and all(len(v) == S + 3 for v in vecs)
     assert np.all(np.isfinite(np.array([[float(t) for t in v[2:-1]] for v in vecs])))
+
+
+def test_a_short_posterior_is_counted_and_a_matrix_without_rows_is_not(tmp_path):
+    x, post, _ = integer_case(1)
+    write_case(tmp_path, "f", x, post, [0, 5, 9, 9, 15], ["a", "b", "c", "d"])   # c has no rows
+    (tmp_path / "p.post").write_bytes(R.post_table_bytes([("a", post[0:5]), ("b", post[5:8]), ("c", []), ("d", post[9:15])], True))
+    r = _sh(LIMIT + "fgmm-global-acc-stats-post ark,s,cs:p.post %d ark,s,cs:f.ark f.acc" % G, cwd=str(tmp_path))
+    log = r.stderr.decode()
+    assert r.returncode == 0, log
+    for text in (") The posterior of utterance b has wrong size 3 vs. 4\n", ") Empty feature matrix for utterance c\n", ") Done 2 files; 1 with errors.\n"):
+        assert log.count(text) == 1, log

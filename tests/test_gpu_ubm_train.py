@@ -275,3 +275,22 @@ def test_train_full_ubm_lines_run_with_the_recipes_argv(tmp_path):
     assert final["inv_covars"].shape == (G0 - 1, T.tri(D)) and np.all(np.isfinite(final["gconsts"]))
     sig = [np.linalg.inv(R.unpack(p, D)) for p in final["inv_covars"]]
     assert all(np.abs(s @ bb - 60.0).min() > 30.0 for s, bb in zip(sig, final["means_invcovars"].astype(np.float64)))
+
+
+def test_acc_stats_words_and_counts_what_it_skips(tmp_path):
+    """fgmm-global-acc-stats on five utterances, one usable: a key the --gselect table does not have, a selection a frame short
+    and one of another width are warned and counted; a matrix without rows is warned and not counted."""
+    Gm, D = 4, 8
+    w, means, b, ic = R.random_full_model(51, Gm, D, spread=1.0)
+    (tmp_path / "0.ubm").write_bytes(R.full_gmm_bytes(w, b, ic, True))
+    x = R.frames_around(52, means, 12)
+    kio.write_ark_matrices(str(tmp_path / "f.ark"), [("a", x[0:3]), ("b", x[3:5]), ("c", x[5:8]), ("d", x[8:12]), ("e", x[:0])])
+    (tmp_path / "f.gs").write_bytes(R.gselect_table_bytes([("a", [[0, 1]] * 3), ("c", [[1, 2]] * 2), ("d", [[3]] * 4)], True))
+    r = _sh("fgmm-global-acc-stats --gselect=ark,s,cs:f.gs 0.ubm ark,s,cs:f.ark f.acc", cwd=str(tmp_path))
+    log = r.stderr.decode()
+    assert r.returncode == 0, log
+    for text in (") No gselect information for utterance b\n", ") gselect information for utterance c has wrong size 2 vs. 3\n",
+                 ") The Gaussian selection of utterance d does not have the 2 indices per frame of the utterances before it (skipping utterance)\n",
+                 ") Empty feature matrix for utterance e\n", ") Done 1 files; 3 with errors.\n"):
+        assert log.count(text) == 1, log
+    assert re.search(r"Overall likelihood per frame = \S+ over 3 \(weighted\) frames\.", log), log
