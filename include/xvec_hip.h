@@ -499,6 +499,9 @@ xv_status xv_pack_mx_weights64(const float* w, int32_t n_pad, int32_t nseg, cons
  * epilogue (xv_gemm_desc.epilogue): n_pad * (k_len / 32) bytes.  n_pad must be a multiple of 128. */
 xv_status xv_tile_mx_scales(const uint8_t* natural, int32_t n_pad, int32_t k_len, int32_t epilogue, uint8_t* tiled);
 xv_status xv_kernel_tdnn_gemm(const xv_gemm_desc* d);
+/* Name of the kernel instantiation the calling thread's last xv_kernel_tdnn_gemm launched, e.g. "tdnn_gemm_kernel_sk<fp16x2,act,8>"
+ * ("tdnn_gemm_kernel<bf16x3,splitk>" for a split-K launch; "" before the first one).  Valid on the calling thread until its next launch. */
+const char* xv_last_gemm_kernel(void);
 
 /* ---- compressed feature matrices (copy-feats --compress=true) and stage 3 of the recipes, without a model context ------------
  * Kaldi's CompressedMatrix as csrc/compress.h restates it.  method: 1 automatic ("CM" when rows > 8, else "CM2"), 2 "CM", 3 "CM2",

@@ -131,6 +131,7 @@ ABI_SYMBOLS = [
     "xv_calibrate_table", "xv_ctx_set_calibration", "xv_ctx_model_fingerprint", "xv_ctx_share_calibration",
     "xv_ctx_set_calibration_file", "xv_calibration_file_read", "xv_calibration_file_publish", "xv_recognize_feature_pipeline", "xv_ctx_set_lite_layers", "xv_ctx_lite_layers",
     "xv_extract_table", "xv_frontend_cmvn_select", "xv_plan_chunks", "xv_ctx_create_broadcast", "xv_kernel_tdnn_gemm",
+    "xv_last_gemm_kernel",
     "xv_backend_apply", "xv_segment_mean", "xv_scatter_stats", "xv_plda_transform", "xv_plda_score", "xv_lda_estimate",
     "xv_plda_estimate", "xv_plda_adapt",
     "xv_mfcc_options_default", "xv_mfcc_num_frames", "xv_mfcc_utt_seed", "xv_mfcc_compute", "xv_mfcc_compute_i16", "xv_mfcc_kernel_time", "xv_vad_energy",
@@ -226,6 +227,8 @@ def lib():
     L.xv_ctx_create_broadcast.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int,
                                           ctypes.POINTER(ctypes.c_void_p)]
     L.xv_kernel_tdnn_gemm.argtypes = [ctypes.POINTER(GemmDesc)]
+    L.xv_last_gemm_kernel.restype = ctypes.c_char_p
+    L.xv_last_gemm_kernel.argtypes = []
     L.xv_kernel_first_layer.argtypes = [ctypes.POINTER(FirstLayerDesc)]
     L.xv_kernel_prep_input.argtypes = [ctypes.POINTER(PrepInputDesc)]
     L.xv_kernel_pool_finalise.argtypes = [ctypes.POINTER(PoolFinaliseDesc)]
@@ -2097,6 +2100,11 @@ class IvexAccumulator:
 
 def kernel_tdnn_gemm(desc):
     _check(lib().xv_kernel_tdnn_gemm(ctypes.byref(desc)))
+
+
+def last_gemm_kernel():
+    """Name of the kernel the calling thread's last kernel_tdnn_gemm launched, e.g. 'tdnn_gemm_kernel_sk<fp16x2,act,8>'."""
+    return lib().xv_last_gemm_kernel().decode()
 
 
 def kernel_first_layer(desc):

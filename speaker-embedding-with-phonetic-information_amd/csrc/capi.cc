@@ -1878,6 +1878,8 @@ xv_status xv_kernel_tdnn_gemm(const xv_gemm_desc* d) {
   });
 }
 
+const char* xv_last_gemm_kernel(void) { return xv::last_gemm_kernel(); }
+
 namespace {
 // device memory of one test entry: freed when the entry returns
 struct DevMem {

@@ -5,6 +5,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import gemm_exact_ref as R
 from helpers import pkg as _pkg
 
 pytestmark = pytest.mark.gpu
@@ -21,16 +22,22 @@ def _torch():
 F16_MODES = (2, 3, 4, 8)       # fp16, fp16x3, fp16x2, fp16x3e
 X_SPLIT = (0, 3, 8)            # modes whose activations carry a residual plane
 W_SPLIT = (0, 3, 4, 8)         # modes whose weights carry one (fp16x2: fp16 activations x split weights)
-E2M1_GRID = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
 
 
 def _decode_lo4(lo4, lo4s, n_cols):
     """4-bit residual plane [rows, n_cols / 2] + E8M0 scales [rows, n_cols / 64] -> float64 [rows, n_cols]"""
-    b = lo4.cpu().numpy()
-    nib = np.stack([b & 15, b >> 4], axis=-1).reshape(b.shape[0], n_cols)
-    val = np.where(nib & 8, -1.0, 1.0) * E2M1_GRID[nib & 7]
-    sc = 2.0 ** (lo4s.cpu().numpy()[:, :n_cols // 64].astype(np.float64) - 127)
-    return val * np.repeat(sc, 64, axis=1)
+    return R._decode_lo4(lo4.cpu().numpy(), lo4s.cpu().numpy(), n_cols)
+
+
+def _launch(P, d, kernel):
+    """the launch, and - where the test names a variant - the name of the kernel that ran (xv_last_gemm_kernel)"""
+    P.kernel_tdnn_gemm(d)
+    if kernel is not None:
+        want = R.kname(kernel[0], d.precision, d.epilogue, kernel[1])
+        assert P.last_gemm_kernel() == want, (P.last_gemm_kernel(), want)
+
+
+TILE, V2, SK8, SK4, P8 = ("", 0), ("_v2", 0), ("_sk", 8), ("_sk", 4), ("_p8", 0)     # kernel variants as (suffix, frame fragments per wave)
 
 
 def _split(t, prec, torch, split):
@@ -46,7 +53,7 @@ def _planes_value(hi, lo):
     return hi.float() + (lo.float() if lo is not None else 0)
 
 
-def _run_case(prec, epi, rows, n_pad, segs, relu, bn, seed=0, m_valid=None, p8=0, ksplit=0):
+def _run_case(prec, epi, rows, n_pad, segs, relu, bn, seed=0, m_valid=None, p8=0, ksplit=0, kernel=None):
     """segs: list of (source index, ld, row_shift, k_len).  Returns (kernel output, reference output).
     ksplit > 1: split-K over that many slices (the number the engine's rule gives for this K)."""
     torch = _torch()
@@ -109,16 +116,16 @@ def _run_case(prec, epi, rows, n_pad, segs, relu, bn, seed=0, m_valid=None, p8=0
             o4 = torch.zeros(rows, n_pad // 2, dtype=torch.uint8, device=dev)
             o4s = torch.zeros(rows, (n_pad // 64 + 3) // 4 * 4, dtype=torch.uint8, device=dev)
             d.out_lo, d.out_lo4, d.out_lo4_scale = None, o4.data_ptr(), o4s.data_ptr()
-            P.kernel_tdnn_gemm(d)
+            _launch(P, d, kernel)
             torch.cuda.synchronize()
             return oh.double().cpu().numpy() + _decode_lo4(o4, o4s, n_pad), z.cpu().numpy()
-        P.kernel_tdnn_gemm(d)
+        _launch(P, d, kernel)
         torch.cuda.synchronize()
         return _planes_value(oh, ol if prec in X_SPLIT else None).double().cpu().numpy(), z.cpu().numpy()
     if epi == P.EPI_F32:
         of = torch.full((rows, n_pad), -7.0, dtype=torch.float32, device=dev)
         d.out_f32, d.ldf, d.m_valid = of.data_ptr(), n_pad, rows if m_valid is None else m_valid
-        P.kernel_tdnn_gemm(d)
+        _launch(P, d, kernel)
         torch.cuda.synchronize()
         return of.double().cpu().numpy(), z.cpu().numpy()
     # stats
@@ -129,7 +136,7 @@ def _run_case(prec, epi, rows, n_pad, segs, relu, bn, seed=0, m_valid=None, p8=0
     gr = torch.from_numpy(np.stack([first, last], 1).copy()).to(dev)
     part = torch.zeros(ngrp, 2, n_pad, dtype=torch.float32, device=dev)
     d.partial, d.ldp, d.grp_range = part.data_ptr(), n_pad, gr.data_ptr()
-    P.kernel_tdnn_gemm(d)
+    _launch(P, d, kernel)
     torch.cuda.synchronize()
     zz = z.cpu().numpy().reshape(ngrp, 16, n_pad)
     mask = (np.arange(16)[None, :] >= first[:, None]) & (np.arange(16)[None, :] < last[:, None])
@@ -201,7 +208,7 @@ def test_gemm_stats_epilogue(prec):
 def test_gemm_even_tile_count_uses_256_row_variant(prec, epi):
     # 22 row tiles of 128 -> 11 tiles of 256 (not a multiple of 8 either); three K segments with shifts
     out, ref = _run_case(prec, epi, 22 * 128, 256, [(0, 64, -3, 64), (0, 64, 0, 64), (1, 32, 3, 32)], relu=True, bn=True,
-                         seed=6)
+                         seed=6, kernel=V2)
     if epi == 2:
         scale = np.abs(ref).max(axis=(0, 2), keepdims=True)
         assert (np.abs(out - ref) / scale).max() < 3e-5
@@ -211,7 +218,7 @@ def test_gemm_even_tile_count_uses_256_row_variant(prec, epi):
 
 def test_gemm_many_tiles_xcd_mapping():
     # 21 row tiles (not a multiple of 8) x 3 column tiles: exercises the XCD-aware block -> tile map
-    out, ref = _run_case(1, 1, 21 * 128, 384, [(0, 64, -1, 64), (0, 64, 1, 64)], relu=True, bn=False, seed=5)
+    out, ref = _run_case(1, 1, 21 * 128, 384, [(0, 64, -1, 64), (0, 64, 1, 64)], relu=True, bn=False, seed=5, kernel=TILE)
     assert np.abs(out - ref).max() / np.abs(ref).max() < 2e-5
 
 
@@ -220,8 +227,25 @@ def test_gemm_many_tiles_xcd_mapping():
 def test_gemm_stream_k_variant(prec, epi):
     # 66 x 512 rows x 4 column tiles = 264 tiles of 512 x 128 (528 of 256 x 128) for 256 workgroups: every workgroup
     # gets a head part, whole tiles and a tail part; three K segments with time offsets (partial starts inside a group)
+    # The default policy runs the single-pass and three-pass modes on the stream-K kernel only from 32 K steps on (launch_one): with
+    # these seven steps only fp16x2 runs it, bf16 and fp16x3 run tdnn_gemm_kernel_v2 - asserted by name; their stream-K launches
+    # are test_gemm_stream_k_variant_from_32_steps below
     out, ref = _run_case(prec, epi, 66 * 512, 512, [(0, 64, -3, 64), (0, 64, 0, 64), (0, 64, 3, 64), (1, 32, 1, 32)],
-                         relu=True, bn=True, seed=8)
+                         relu=True, bn=True, seed=8, kernel=SK8 if prec == 4 else V2)
+    if epi == 2:
+        scale = np.abs(ref).max(axis=(0, 2), keepdims=True)
+        assert (np.abs(out - ref) / scale).max() < 3e-5
+    else:
+        assert np.abs(out - ref).max() / np.abs(ref).max() < TOL[prec] + (OUT_Q[prec] if epi == 0 else 0)
+
+
+@pytest.mark.parametrize("prec", [1, 3])
+@pytest.mark.parametrize("epi", [0, 1, 2])
+def test_gemm_stream_k_variant_from_32_steps(prec, epi):
+    # the same walk with segments of 320 and 64 columns (32 steps): bf16 on the 512-row stream-K tiles, fp16x3 on the 256-row ones
+    # (its LDS does not hold 512)
+    out, ref = _run_case(prec, epi, 66 * 512, 512, [(0, 320, -3, 320), (0, 320, 0, 320), (0, 320, 3, 320), (1, 64, 1, 64)],
+                         relu=True, bn=True, seed=8, kernel=SK4 if prec == 3 else SK8)
     if epi == 2:
         scale = np.abs(ref).max(axis=(0, 2), keepdims=True)
         assert (np.abs(out - ref) / scale).max() < 3e-5
@@ -232,7 +256,10 @@ def test_gemm_stream_k_variant(prec, epi):
 # ---------------------------------------------------------------------------------------------------------------------
 # XV_PREC_FP16MX: fp16 product + block-scaled 4-bit residual product.  The reference below restates the arithmetic
 # exactly (what is quantised how, with which scale), so the tolerance is again fp32 accumulation order only.
-E2M1 = [0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0]
+# The restatements of the 4-bit quantisers live in gemm_exact_ref.py as numpy functions (_q_e2m1, _lo4_plane, _w4_image, _decode_lo4).
+# The two below are the same functions on device tensors, for the references of the large launches here (through numpy the 40
+# repeats of a 25600-row case took four times as long); tests/test_gemm_exact_ref.py holds them equal to the numpy ones.
+E2M1 = list(R.E2M1_GRID)
 
 
 def _q_e2m1(t, torch):
@@ -267,14 +294,7 @@ def _lo4_plane(x32, xh, torch):
 
 
 def _w4_image(W, torch):
-    """4-bit image of the weights for the second walk: per row and 32 consecutive columns the smallest power of two 2^E
-    with max |w| / 2^E <= 6, codes to nearest even - what xv_pack_mx_weights packs (values only)"""
-    n, K = W.shape
-    b = W.double().reshape(n, K // 32, 32)
-    m = b.abs().amax(dim=2, keepdim=True)
-    E = torch.ceil(torch.log2(torch.clamp(m, min=1e-300) / 6.0))
-    sc = torch.pow(torch.tensor(2.0, dtype=torch.float64, device=W.device), E)
-    return (_q_e2m1(b / sc, torch) * sc).reshape(n, K)
+    return torch.from_numpy(R._w4_image(W.double().cpu().numpy())).to(W.device)
 
 
 def _gmax_bits(plane_abs_max, torch):
@@ -282,7 +302,7 @@ def _gmax_bits(plane_abs_max, torch):
     return plane_abs_max.float().view(torch.int32)
 
 
-def _run_mx_case(epi, rows, n_pad, segs, seed=0, variant_rows=None, prec=6, p8=0, out_range=False, ksplit=0):
+def _run_mx_case(epi, rows, n_pad, segs, seed=0, variant_rows=None, prec=6, p8=0, out_range=False, ksplit=0, kernel=None):
     """out_range (epilogue 0): the launch gets a table of the rows of every 16-row group that count for its recorded maximum,
     drawn like grp_range below (some groups empty), and the expected maxima are those of the rows inside it."""
     torch = _torch()
@@ -406,12 +426,17 @@ def _run_mx_case(epi, rows, n_pad, segs, seed=0, variant_rows=None, prec=6, p8=0
             o4 = torch.zeros(rows, n_pad // 2, dtype=torch.uint8, device=dev)
             o4s = torch.zeros(rows, (n_pad // 64 + 3) // 4 * 4, dtype=torch.uint8, device=dev)
             d.out_lo4, d.out_lo4_scale = o4.data_ptr(), o4s.data_ptr()
-        P.kernel_tdnn_gemm(d)
+        _launch(P, d, kernel)
         torch.cuda.synchronize()
         # the recorded group maxima are those of the fp32 results before the fp16 rounding of the plane
         want = (z.float().abs().reshape(rows // 16, 16, -1) * counted[:, :, None]).amax(dim=(1, 2))[:run_rows // 16]
         got = gm_out.view(torch.float32)[:run_rows // 16]
         assert torch.allclose(got, want, rtol=1e-4, atol=0), (got[:4], want[:4])
+        # The consumer takes only the exponent of a maximum: the exponent fields are equal, except where the reference itself lies
+        # within its own error (the 2e-5 of the output bar) of a power of two
+        frac = want.double() / torch.pow(torch.tensor(2.0, dtype=torch.float64, device=dev), torch.floor(torch.log2(want.double().clamp(min=1e-30))))
+        clear = (want > 0) & (frac > 1 + 1e-4) & (frac < 2 - 1e-4)
+        assert torch.equal((got.view(torch.int32) >> 23)[clear], (want.view(torch.int32) >> 23)[clear])
         if out_range:   # a group without a counted row records nothing at all
             empty = ~counted.any(dim=1)[:run_rows // 16]
             assert torch.all(gm_out[:run_rows // 16][empty] == 0)
@@ -427,7 +452,7 @@ def _run_mx_case(epi, rows, n_pad, segs, seed=0, variant_rows=None, prec=6, p8=0
     gr = torch.from_numpy(np.stack([first, last], 1).copy()).to(dev)
     part = torch.zeros(ngrp, 2, n_pad, dtype=torch.float32, device=dev)
     d.partial, d.ldp, d.grp_range = part.data_ptr(), n_pad, gr.data_ptr()
-    P.kernel_tdnn_gemm(d)
+    _launch(P, d, kernel)
     torch.cuda.synchronize()
     zz = z.cpu().numpy().reshape(ngrp, 16, n_pad)
     mask = (np.arange(16)[None, :] >= first[:, None]) & (np.arange(16)[None, :] < last[:, None])
@@ -442,12 +467,12 @@ CVEC5_MX = [(0, 512, 0, 512), (1, 128, 0, 128)]      # two sources, each a whole
 @pytest.mark.parametrize("segs", [TDNN2, TDNN3, [(0, 512, 0, 512)], CVEC5_MX], ids=["tdnn2", "tdnn3", "tdnn4", "cvec5"])
 def test_gemm_mx_act_per_tile_kernel(segs):
     # 3 x 256 rows: too few tiles for the persistent grid -> the 256-row per-tile kernel
-    out, ref = _run_mx_case(0, 768, 512, segs, seed=11)
+    out, ref = _run_mx_case(0, 768, 512, segs, seed=11, kernel=V2)
     assert np.abs(out - ref).max() / np.abs(ref).max() < TOL[4] + OUT_Q[4]
 
 
 def test_gemm_mx_stats_per_tile_kernel():
-    out, ref = _run_mx_case(2, 512, 1536, [(0, 512, 0, 512)], seed=12)
+    out, ref = _run_mx_case(2, 512, 1536, [(0, 512, 0, 512)], seed=12, kernel=V2)
     scale = np.abs(ref).max(axis=(0, 2), keepdims=True)
     assert (np.abs(out - ref) / scale).max() < 3e-5
 
@@ -456,7 +481,7 @@ def test_gemm_mx_stats_per_tile_kernel():
 @pytest.mark.parametrize("segs", [TDNN3, CVEC5_MX], ids=["tdnn3", "cvec5"])
 def test_gemm_mx_stream_k(epi, segs):
     # 66 x 512 rows x 4 column tiles on 256 workgroups: heads, whole tiles and tails, cut at multiples of four steps
-    out, ref = _run_mx_case(epi, 66 * 512, 512, segs, seed=13)
+    out, ref = _run_mx_case(epi, 66 * 512, 512, segs, seed=13, kernel=SK8)
     if epi == 2:
         scale = np.abs(ref).max(axis=(0, 2), keepdims=True)
         assert (np.abs(out - ref) / scale).max() < 3e-5
@@ -480,7 +505,7 @@ CVEC5_ODD = [(0, 512, 0, 512), (1, 128, 0, 128), (2, 384, 0, 384)]   # an odd nu
 def test_gemm_mx2_stream_k(epi, segs):
     """XV_PREC_FP16MX2 on the persistent kernel: the second K walk (4-bit residual of the activations x 4-bit image of the
     weights) against an exact emulation of both 4-bit products; parts cut inside both walks."""
-    out, ref = _run_mx_case(epi, 66 * 512, 512, segs, seed=17, prec=7)
+    out, ref = _run_mx_case(epi, 66 * 512, 512, segs, seed=17, prec=7, kernel=SK8)
     if epi == 2:
         scale = np.abs(ref).max(axis=(0, 2), keepdims=True)
         assert (np.abs(out - ref) / scale).max() < 3e-5
@@ -492,7 +517,7 @@ def test_gemm_mx2_stream_k(epi, segs):
 @pytest.mark.parametrize("segs", [TDNN3, CVEC5_MX, AM_MX, CVEC5_ODD], ids=["tdnn3", "cvec5", "am768", "odd"])
 def test_gemm_mx2_per_tile_kernel(epi, segs):
     # 3 x 256 rows: too few tiles for the persistent grid -> the 256-row per-tile kernel
-    out, ref = _run_mx_case(epi, 768, 512, segs, seed=19, prec=7)
+    out, ref = _run_mx_case(epi, 768, 512, segs, seed=19, prec=7, kernel=V2)
     if epi == 2:
         scale = np.abs(ref).max(axis=(0, 2), keepdims=True)
         assert (np.abs(out - ref) / scale).max() < 3e-5
@@ -506,8 +531,9 @@ def test_gemm_mxe_is_the_mx_product_with_the_residual_plane_of_its_output(rows, 
     """Precision 9 (kPrecFp16MxE, the lite layers of a calibrated fp16mx2 context in front of a consumer that walks the
     residual plane): the 1.25-pass product - its fp16 plane is bit-identical to precision 6's - and, next to it, the 4-bit
     residual of that plane, which brings plane + residual two to three bits closer to the exact result."""
-    full, ref, hi = _run_mx_case(0, rows, 512, segs, seed=23, prec=9)
-    plain, ref6 = _run_mx_case(0, rows, 512, segs, seed=23, prec=6)
+    kernel = SK8 if rows == 66 * 512 else V2
+    full, ref, hi = _run_mx_case(0, rows, 512, segs, seed=23, prec=9, kernel=kernel)
+    plain, ref6 = _run_mx_case(0, rows, 512, segs, seed=23, prec=6, kernel=kernel)
     assert np.array_equal(hi.astype(np.float64), plain)
     assert np.abs(full - ref).max() / np.abs(ref).max() < TOL[4] + 2.0 ** -13
 
@@ -533,7 +559,7 @@ def _p8_check(out, ref, epi, tol):
 @pytest.mark.parametrize("segs", [P8_TDNN2, P8_PLAIN, P8_TWO], ids=["tdnn2", "tdnn4", "cvec5"])
 def test_gemm_p8_fp16_small_launch(epi, segs):
     # 3 row tiles x 2 column tiles on a grid of a few workgroups: whole tiles only, XCD blocks without tiles return at once
-    out, ref = _run_case(2, epi, 3 * 256, 512, segs, relu=True, bn=True, seed=21, p8=1)
+    out, ref = _run_case(2, epi, 3 * 256, 512, segs, relu=True, bn=True, seed=21, p8=1, kernel=P8)
     _p8_check(out, ref, epi, TOL[2] + OUT_Q[2])
 
 
@@ -541,21 +567,21 @@ def test_gemm_p8_fp16_small_launch(epi, segs):
 def test_gemm_p8_fp16_stream_k(epi):
     # 100 row tiles x 2 column tiles = 200 tiles of 24 K tiles on 256 workgroups: 12.5 row tiles per XCD block, 16 groups of 2
     # column lanes, every workgroup a head part, whole tiles and a tail part cut at an even K tile inside an offset group
-    out, ref = _run_case(2, epi, 100 * 256, 512, P8_TDNN3, relu=True, bn=True, seed=22, p8=1)
+    out, ref = _run_case(2, epi, 100 * 256, 512, P8_TDNN3, relu=True, bn=True, seed=22, p8=1, kernel=P8)
     _p8_check(out, ref, epi, TOL[2] + OUT_Q[2])
 
 
 @pytest.mark.parametrize("epi", [0, 2])
 @pytest.mark.parametrize("segs", [P8_TDNN2, P8_TDNN3, P8_PLAIN, P8_TWO], ids=["tdnn2", "tdnn3", "tdnn4", "cvec5"])
 def test_gemm_p8_mx_small_launch(epi, segs):
-    out, ref = _run_mx_case(epi, 3 * 256, 512, segs, seed=23, p8=1)
+    out, ref = _run_mx_case(epi, 3 * 256, 512, segs, seed=23, p8=1, kernel=P8)
     _p8_check(out, ref, epi, 2e-5 + 2.0 ** -10)
 
 
 @pytest.mark.parametrize("epi", [0, 2])
 @pytest.mark.parametrize("segs", [P8_TDNN3, P8_TWO], ids=["tdnn3", "cvec5"])
 def test_gemm_p8_mx_stream_k(epi, segs):
-    out, ref = _run_mx_case(epi, 100 * 256, 768 if segs is P8_TWO else 512, segs, seed=24, p8=1)
+    out, ref = _run_mx_case(epi, 100 * 256, 768 if segs is P8_TWO else 512, segs, seed=24, p8=1, kernel=P8)
     _p8_check(out, ref, epi, 2e-5 + 2.0 ** -10)
 
 
@@ -563,8 +589,8 @@ def test_gemm_p8_is_independent_of_the_cut():
     """The same rows as part of a large launch (stream-K cuts inside tiles) and as a launch of their own (whole tiles): same
     bits - a chunk's activations do not depend on what it is batched with."""
     torch = _torch()
-    big, _ = _run_mx_case(0, 100 * 256, 512, P8_TDNN2, seed=25, p8=1)
-    small, _ = _run_mx_case(0, 100 * 256, 512, P8_TDNN2, seed=25, p8=1, variant_rows=2 * 256)
+    big, _ = _run_mx_case(0, 100 * 256, 512, P8_TDNN2, seed=25, p8=1, kernel=P8)
+    small, _ = _run_mx_case(0, 100 * 256, 512, P8_TDNN2, seed=25, p8=1, variant_rows=2 * 256, kernel=P8)
     assert np.array_equal(big[:2 * 256], small[:2 * 256])
 
 
@@ -589,7 +615,7 @@ P8_MX2_IDS = ["tdnn2", "tdnn3", "tdnn4", "am768", "two"]
 
 
 def _p8_mx2(epi, rows, n_pad, segs, seed, **kw):
-    return _run_mx_case(epi, rows, n_pad, segs, seed=seed, prec=7, p8=1, **kw)
+    return _run_mx_case(epi, rows, n_pad, segs, seed=seed, prec=7, p8=1, kernel=P8, **kw)
 
 
 @pytest.mark.parametrize("epi", [0, 2])
@@ -650,7 +676,7 @@ def test_gemm_p8_mxe_is_the_p8_mx_product_with_the_residual_plane_of_its_output(
     the fp16 plane has the bits of precision 6 on the same kernel, and plane + 4-bit residual is two to three bits closer to the
     exact result."""
     n_pad = 768 if segs is P8_AM768 else 512
-    full, ref, hi = _run_mx_case(0, rows, n_pad, segs, seed=31, prec=9, p8=1)
-    plain, _ = _run_mx_case(0, rows, n_pad, segs, seed=31, prec=6, p8=1)
+    full, ref, hi = _run_mx_case(0, rows, n_pad, segs, seed=31, prec=9, p8=1, kernel=P8)
+    plain, _ = _run_mx_case(0, rows, n_pad, segs, seed=31, prec=6, p8=1, kernel=P8)
     assert np.array_equal(hi.astype(np.float64), plain)
     assert np.abs(full - ref).max() / np.abs(ref).max() < TOL[4] + 2.0 ** -13
