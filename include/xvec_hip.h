@@ -502,6 +502,28 @@ xv_status xv_kernel_tdnn_gemm(const xv_gemm_desc* d);
 /* Name of the kernel instantiation the calling thread's last xv_kernel_tdnn_gemm launched, e.g. "tdnn_gemm_kernel_sk<fp16x2,act,8>"
  * ("tdnn_gemm_kernel<bf16x3,splitk>" for a split-K launch; "" before the first one).  Valid on the calling thread until its next launch. */
 const char* xv_last_gemm_kernel(void);
+/* What xv_kernel_tdnn_gemm would launch for a descriptor, without launching: the launch is decided by one host function
+ * (csrc/gemm_plan.h) that this entry asks.  No device is needed, and the descriptor's pointers are only looked at for being null
+ * or equal (any distinct non-null values will do).  cus > 0: a device of that many CUs under the default XVEC_DEBUG knobs;
+ * cus <= 0: the current device and this process's knobs.  A launch the entry would refuse gives XV_OK with refused = 1. */
+typedef struct {
+  int32_t ld, ksteps, nshift, shift0, dstep, wcol0, wstride, ld4s;   /* the scalar fields of a K-walk group (csrc/kernels.h, Grp) */
+} xv_gemm_plan_group;
+typedef struct {
+  int32_t refused;
+  char kernel[96];                /* as xv_last_gemm_kernel spells it; "" when refused */
+  int32_t grid_x, grid_y, block, lds_bytes;
+  int32_t mf;                     /* stream-K: 16-row fragments per wave (4 or 8), else 0 */
+  int32_t lanes, groups_per_xcd;  /* persistent kernels (stream-K, p8): column lanes, workgroup groups per XCD block and lane */
+  int32_t sk_mtiles, p8_ktiles, p8_ktiles_lo, p8_whole, stagger_units;
+  int64_t workspace_bytes;        /* stream-K exchange workspace */
+  int32_t ngrp, ngrp_lo, lo_ksteps;   /* the K walk (not planned for split-K): grp[0 .. ngrp) the groups of the first walk, */
+  xv_gemm_plan_group grp[16];         /* grp[ngrp .. ngrp + ngrp_lo) of the second (XV_PREC_FP16MX2) */
+} xv_gemm_plan;
+xv_status xv_plan_gemm(const xv_gemm_desc* d, int32_t cus, xv_gemm_plan* out);
+/* the same under an explicit policy: the CU count and the knobs gemm_variant, sk_mf, sk_lanes, gemm_stagger (csrc/knobs.h) */
+xv_status xv_plan_gemm_policy(const xv_gemm_desc* d, int32_t cus, int32_t variant, int32_t sk_mf, int32_t sk_lanes,
+                              int32_t stagger_pct, xv_gemm_plan* out);
 
 /* ---- compressed feature matrices (copy-feats --compress=true) and stage 3 of the recipes, without a model context ------------
  * Kaldi's CompressedMatrix as csrc/compress.h restates it.  method: 1 automatic ("CM" when rows > 8, else "CM2"), 2 "CM", 3 "CM2",

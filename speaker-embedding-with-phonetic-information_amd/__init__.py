@@ -65,6 +65,19 @@ class GemmDesc(ctypes.Structure):
                 ("out_range", ctypes.c_void_p), ("ksplit", ctypes.c_int32)]
 
 
+class GemmPlanGroup(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("ld", "ksteps", "nshift", "shift0", "dstep", "wcol0", "wstride", "ld4s")]
+
+
+class GemmPlan(ctypes.Structure):
+    """xv_gemm_plan: what a kernel_tdnn_gemm call would launch (plan_gemm)"""
+    _fields_ = [("refused", ctypes.c_int32), ("kernel", ctypes.c_char * 96)] + \
+               [(n, ctypes.c_int32) for n in ("grid_x", "grid_y", "block", "lds_bytes", "mf", "lanes", "groups_per_xcd", "sk_mtiles",
+                                              "p8_ktiles", "p8_ktiles_lo", "p8_whole", "stagger_units")] + \
+               [("workspace_bytes", ctypes.c_int64), ("ngrp", ctypes.c_int32), ("ngrp_lo", ctypes.c_int32), ("lo_ksteps", ctypes.c_int32),
+                ("grp", GemmPlanGroup * 16)]
+
+
 class FirstLayerDesc(ctypes.Structure):
     """xv_first_layer_desc (row_offsets / dev_off are HOST arrays: keep the numpy arrays alive over the call)"""
     _fields_ = [("feats", ctypes.c_void_p), ("row_offsets", ctypes.c_void_p), ("dev_off", ctypes.c_void_p), ("B", ctypes.c_int32),
@@ -131,7 +144,7 @@ ABI_SYMBOLS = [
     "xv_calibrate_table", "xv_ctx_set_calibration", "xv_ctx_model_fingerprint", "xv_ctx_share_calibration",
     "xv_ctx_set_calibration_file", "xv_calibration_file_read", "xv_calibration_file_publish", "xv_recognize_feature_pipeline", "xv_ctx_set_lite_layers", "xv_ctx_lite_layers",
     "xv_extract_table", "xv_frontend_cmvn_select", "xv_plan_chunks", "xv_ctx_create_broadcast", "xv_kernel_tdnn_gemm",
-    "xv_last_gemm_kernel",
+    "xv_last_gemm_kernel", "xv_plan_gemm", "xv_plan_gemm_policy",
     "xv_backend_apply", "xv_segment_mean", "xv_scatter_stats", "xv_plda_transform", "xv_plda_score", "xv_lda_estimate",
     "xv_plda_estimate", "xv_plda_adapt",
     "xv_mfcc_options_default", "xv_mfcc_num_frames", "xv_mfcc_utt_seed", "xv_mfcc_compute", "xv_mfcc_compute_i16", "xv_mfcc_kernel_time", "xv_vad_energy",
@@ -2105,6 +2118,22 @@ def kernel_tdnn_gemm(desc):
 def last_gemm_kernel():
     """Name of the kernel the calling thread's last kernel_tdnn_gemm launched, e.g. 'tdnn_gemm_kernel_sk<fp16x2,act,8>'."""
     return lib().xv_last_gemm_kernel().decode()
+
+
+def plan_gemm(desc, cus=0, policy=None):
+    """What kernel_tdnn_gemm(desc) would launch, without a device (csrc/gemm_plan.h): a GemmPlan.  cus > 0: a device of that many
+    CUs under the default knobs, else the current device and XVEC_DEBUG.  policy: dict(variant, sk_mf, sk_lanes, stagger_pct) to
+    state the knobs (missing ones at their defaults; needs cus > 0)."""
+    L = lib()
+    out = GemmPlan()
+    if policy is None:
+        L.xv_plan_gemm.argtypes = [ctypes.POINTER(GemmDesc), ctypes.c_int32, ctypes.POINTER(GemmPlan)]
+        _check(L.xv_plan_gemm(ctypes.byref(desc), cus, ctypes.byref(out)))
+    else:
+        k = dict(dict(variant=0, sk_mf=8, sk_lanes=4, stagger_pct=85), **policy)
+        L.xv_plan_gemm_policy.argtypes = [ctypes.POINTER(GemmDesc)] + [ctypes.c_int32] * 5 + [ctypes.POINTER(GemmPlan)]
+        _check(L.xv_plan_gemm_policy(ctypes.byref(desc), cus, k["variant"], k["sk_mf"], k["sk_lanes"], k["stagger_pct"], ctypes.byref(out)))
+    return out
 
 
 def kernel_first_layer(desc):

@@ -18,6 +18,7 @@
 #include "reverb.h"
 #include "wave.h"
 #include "kernels.h"
+#include "gemm_plan.h"
 #include "calib_file.h"
 #include "fuse_pipe.h"
 #include "fuse_wav.h"
@@ -1791,65 +1792,75 @@ xv_status xv_ctx_create_broadcast(const xv_model* m, const int* devices, int n, 
   });
 }
 
+// xv_gemm_desc -> GemmArgs, for the launch entry and the plan entry: "" or what is wrong with the descriptor.  Split-K: the slices
+// are the engine's rule; splitk_ws is the caller's.
+static std::string GemmArgsFromDesc(const xv_gemm_desc* d, xv::GemmArgs* out) {
+  if (d->nseg < 1 || d->nseg > xv::kMaxSeg || d->rows % xv::kBM || d->n_pad % xv::kBN) return "bad geometry";
+  xv::GemmArgs& a = *out;
+  memset(&a, 0, sizeof a);
+  a.nseg = d->nseg;
+  for (int j = 0; j < d->nseg; ++j) {
+    if (d->seg[j].k_len % xv::kBK) return "k_len must be a multiple of 32";
+    a.seg[j].hi = (const uint16_t*)d->seg[j].hi;
+    a.seg[j].lo = (const uint16_t*)d->seg[j].lo;
+    a.seg[j].ld = d->seg[j].ld;
+    a.seg[j].row_shift = d->seg[j].row_shift;
+    a.seg[j].ksteps = d->seg[j].k_len / xv::kBK;
+    a.seg[j].gmax = (const unsigned*)d->seg[j].gmax;
+    a.seg[j].lo4 = (const uint8_t*)d->seg[j].lo4;
+    a.seg[j].lo4s = (const uint8_t*)d->seg[j].lo4_scale;
+    a.total_ksteps += a.seg[j].ksteps;
+  }
+  a.w_hi = (const uint16_t*)d->w_hi;
+  a.w_lo = (const uint16_t*)d->w_lo;
+  a.ldw = d->ldw;
+  a.m_tiles = d->rows / xv::kBM;
+  a.n_tiles = d->n_pad / xv::kBN;
+  a.relu = d->relu;
+  a.bn = d->bn;
+  a.bias = d->bias;
+  a.scale = d->scale;
+  a.offset = d->offset;
+  a.out_hi = (uint16_t*)d->out_hi;
+  a.out_lo = (uint16_t*)d->out_lo;
+  a.ldo = d->ldo;
+  a.out_f32 = d->out_f32;
+  a.ldf = d->ldf;
+  a.m_valid = d->m_valid;
+  a.partial = d->partial;
+  a.ldp = d->ldp;
+  a.grp_range = d->grp_range;
+  a.w4 = (const uint8_t*)d->w4;
+  a.ldw4 = d->ldw4;
+  a.w4_scale = (const uint8_t*)d->w4_scale;
+  a.gmax_out = (unsigned*)d->gmax_out;
+  a.w4b = (const uint8_t*)d->w4b;
+  a.ldw4b = d->ldw4b;
+  a.w4b_scale = (const uint8_t*)d->w4b_scale;
+  a.out_lo4 = (uint8_t*)d->out_lo4;
+  a.out_lo4s = (uint8_t*)d->out_lo4_scale;
+  a.p8 = d->p8;
+  a.out_range = d->out_range;
+  if (d->ksplit > 1) {
+    if (d->precision < xv::kPrecBf16x3 || d->precision > xv::kPrecFp16x3 || a.p8 ||
+        (d->epilogue != xv::kEpiAct && d->epilogue != xv::kEpiF32))
+      return "split-K needs XV_PREC_BF16X3 .. XV_PREC_FP16X3, epilogue 0 or 1 and no p8";
+    a.ksteps_per_slice = xv::SplitKStepsPerSlice(a.total_ksteps);
+    a.ksplit = (a.total_ksteps + a.ksteps_per_slice - 1) / a.ksteps_per_slice;
+    if (a.ksplit != d->ksplit)
+      return std::to_string(a.total_ksteps) + " K steps are split over " + std::to_string(a.ksplit) + " slices, not " +
+             std::to_string(d->ksplit);
+  }
+  return std::string();
+}
+
 xv_status xv_kernel_tdnn_gemm(const xv_gemm_desc* d) {
   if (!d) return Fail(XV_ERR_ARG, "xv_kernel_tdnn_gemm: null descriptor");
   return Guard([&] {
-    if (d->nseg < 1 || d->nseg > xv::kMaxSeg || d->rows % xv::kBM || d->n_pad % xv::kBN)
-      return Fail(XV_ERR_ARG, "xv_kernel_tdnn_gemm: bad geometry");
     xv::GemmArgs a;
-    memset(&a, 0, sizeof a);
-    a.nseg = d->nseg;
-    for (int j = 0; j < d->nseg; ++j) {
-      if (d->seg[j].k_len % xv::kBK) return Fail(XV_ERR_ARG, "xv_kernel_tdnn_gemm: k_len must be a multiple of 32");
-      a.seg[j].hi = (const uint16_t*)d->seg[j].hi;
-      a.seg[j].lo = (const uint16_t*)d->seg[j].lo;
-      a.seg[j].ld = d->seg[j].ld;
-      a.seg[j].row_shift = d->seg[j].row_shift;
-      a.seg[j].ksteps = d->seg[j].k_len / xv::kBK;
-      a.seg[j].gmax = (const unsigned*)d->seg[j].gmax;
-      a.seg[j].lo4 = (const uint8_t*)d->seg[j].lo4;
-      a.seg[j].lo4s = (const uint8_t*)d->seg[j].lo4_scale;
-      a.total_ksteps += a.seg[j].ksteps;
-    }
-    a.w_hi = (const uint16_t*)d->w_hi;
-    a.w_lo = (const uint16_t*)d->w_lo;
-    a.ldw = d->ldw;
-    a.m_tiles = d->rows / xv::kBM;
-    a.n_tiles = d->n_pad / xv::kBN;
-    a.relu = d->relu;
-    a.bn = d->bn;
-    a.bias = d->bias;
-    a.scale = d->scale;
-    a.offset = d->offset;
-    a.out_hi = (uint16_t*)d->out_hi;
-    a.out_lo = (uint16_t*)d->out_lo;
-    a.ldo = d->ldo;
-    a.out_f32 = d->out_f32;
-    a.ldf = d->ldf;
-    a.m_valid = d->m_valid;
-    a.partial = d->partial;
-    a.ldp = d->ldp;
-    a.grp_range = d->grp_range;
-    a.w4 = (const uint8_t*)d->w4;
-    a.ldw4 = d->ldw4;
-    a.w4_scale = (const uint8_t*)d->w4_scale;
-    a.gmax_out = (unsigned*)d->gmax_out;
-    a.w4b = (const uint8_t*)d->w4b;
-    a.ldw4b = d->ldw4b;
-    a.w4b_scale = (const uint8_t*)d->w4b_scale;
-    a.out_lo4 = (uint8_t*)d->out_lo4;
-    a.out_lo4s = (uint8_t*)d->out_lo4_scale;
-    a.p8 = d->p8;
-    a.out_range = d->out_range;
-    if (d->ksplit > 1) {
-      if (d->precision < xv::kPrecBf16x3 || d->precision > xv::kPrecFp16x3 || a.p8 ||
-          (d->epilogue != xv::kEpiAct && d->epilogue != xv::kEpiF32))
-        return Fail(XV_ERR_ARG, "xv_kernel_tdnn_gemm: split-K needs XV_PREC_BF16X3 .. XV_PREC_FP16X3, epilogue 0 or 1 and no p8");
-      a.ksteps_per_slice = xv::SplitKStepsPerSlice(a.total_ksteps);
-      a.ksplit = (a.total_ksteps + a.ksteps_per_slice - 1) / a.ksteps_per_slice;
-      if (a.ksplit != d->ksplit)
-        return Fail(XV_ERR_ARG, "xv_kernel_tdnn_gemm: " + std::to_string(a.total_ksteps) + " K steps are split over " +
-                                    std::to_string(a.ksplit) + " slices, not " + std::to_string(d->ksplit));
+    const std::string bad = GemmArgsFromDesc(d, &a);
+    if (!bad.empty()) return Fail(XV_ERR_ARG, "xv_kernel_tdnn_gemm: " + bad);
+    if (a.ksplit > 1) {
       void* ws = nullptr;
       hipError_t e = hipMalloc(&ws, (size_t)a.ksplit * d->rows * d->n_pad * 4);
       if (e != hipSuccess) return Fail(XV_ERR_DEVICE, std::string("hipMalloc(split-K workspace): ") + hipGetErrorString(e));
@@ -1876,6 +1887,59 @@ xv_status xv_kernel_tdnn_gemm(const xv_gemm_desc* d) {
     if (e != hipSuccess) return Fail(XV_ERR_DEVICE, std::string("tdnn_gemm launch: ") + hipGetErrorString(e));
     return XV_OK;
   });
+}
+
+static xv_status PlanGemmEntry(const char* who, const xv_gemm_desc* d, const xv::GemmPolicy& policy, xv_gemm_plan* out) {
+  if (!d || !out) return Fail(XV_ERR_ARG, std::string(who) + ": null argument");
+  return Guard([&] {
+    memset(out, 0, sizeof *out);
+    out->refused = 1;
+    xv::GemmArgs a;
+    if (!GemmArgsFromDesc(d, &a).empty()) return XV_OK;
+    if (a.ksplit > 1) a.splitk_ws = (float*)out;   // never read: the plan only has to know that the launch entry brings a workspace
+    const xv::GemmPlan p = xv::PlanGemm(a, d->precision, d->epilogue, policy);
+    if (!p.ok) return XV_OK;
+    const xv::GemmArgs& b = p.args;
+    const bool persistent = p.kernel == xv::kGemmSk || p.kernel == xv::kGemmP8, v2 = p.kernel == xv::kGemmV2;
+    out->refused = 0;
+    xv::GemmKernelName(p, out->kernel, sizeof out->kernel);
+    out->grid_x = p.grid_x;
+    out->grid_y = p.grid_y;
+    out->block = p.block;
+    out->lds_bytes = p.lds;
+    out->mf = p.mf;
+    out->workspace_bytes = (int64_t)p.sk_ws_bytes;
+    if (persistent) {
+      out->lanes = b.sk_lanes;
+      out->groups_per_xcd = p.grid_x / 8 / b.sk_lanes;
+      out->sk_mtiles = b.sk_mtiles;
+    }
+    if (p.kernel == xv::kGemmP8) {
+      out->p8_ktiles = b.p8_ktiles;
+      out->p8_ktiles_lo = b.p8_ktiles_lo;
+      out->p8_whole = b.p8_whole;
+    }
+    if (v2) out->stagger_units = b.stagger_units;
+    if (p.kernel != xv::kGemmSplitK) {   // (tdnn_gemm_kernel walks K segment by segment: the groups are planned, not read)
+      out->ngrp = b.ngrp;
+      out->ngrp_lo = b.ngrp_lo;
+      out->lo_ksteps = b.lo_ksteps;
+      for (int i = 0; i < b.ngrp + b.ngrp_lo; ++i) {
+        const xv::Grp& g = b.grp[i];
+        out->grp[i] = {g.ld, g.ksteps, g.nshift, g.shift0, g.dstep, g.wcol0, g.wstride, g.ld4s};
+      }
+    }
+    return XV_OK;
+  });
+}
+
+xv_status xv_plan_gemm(const xv_gemm_desc* d, int32_t cus, xv_gemm_plan* out) {
+  return PlanGemmEntry("xv_plan_gemm", d, cus > 0 ? xv::DefaultGemmPolicy(cus) : xv::CurrentGemmPolicy(), out);
+}
+
+xv_status xv_plan_gemm_policy(const xv_gemm_desc* d, int32_t cus, int32_t variant, int32_t sk_mf, int32_t sk_lanes, int32_t stagger_pct,
+                              xv_gemm_plan* out) {
+  return PlanGemmEntry("xv_plan_gemm_policy", d, xv::MakeGemmPolicy(cus, variant, sk_mf, sk_lanes, stagger_pct), out);
 }
 
 const char* xv_last_gemm_kernel(void) { return xv::last_gemm_kernel(); }

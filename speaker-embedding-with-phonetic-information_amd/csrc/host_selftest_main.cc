@@ -23,6 +23,10 @@
 // reads every table <dir>/cases.txt names through the reader the line names and prints one line per event - key, dimensions
 // and a 64-bit hash of the value's bytes, or the error text - so that what the table readers deliver is pinned byte for byte
 // (tests/test_table_readers.py compares the dump with the one recorded under tests/golden/table_readers/).
+//
+//   host_selftest gemm_plan
+//
+// sweeps the GEMM launch planner (gemm_plan.cc: plain host code, no device) over shapes, modes, CU counts and knobs.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -35,6 +39,7 @@
 #include <vector>
 
 #include "feat_join.h"
+#include "gemm_plan.h"
 #include "kio.h"
 #include "nnet3_raw.h"
 #include "program.h"
@@ -455,9 +460,91 @@ int RunWalk(const char* dir) {
   return 0;
 }
 
+// PlanGemm over walks x shapes x precisions x epilogues x p8 x split-K x CU counts x knobs: whatever it is asked, a plan stays
+// inside GemmArgs (at most 2 * kMaxSeg groups) and a launch it accepts has a grid, a block and an LDS size a CU holds.
+int RunGemmPlan() {
+  static char mem[64];   // addresses to tell sources apart by; never dereferenced
+  struct S {
+    int src, ld, shift, ksteps;
+  };
+  const std::vector<std::vector<S>> walks = {
+      {{0, 64, -3, 1}, {0, 64, 0, 1}, {0, 64, 3, 1}, {1, 96, 1, 2}},
+      {{0, 32, -4, 1}, {0, 32, 0, 1}, {1, 64, 0, 1}, {0, 32, 4, 1}, {1, 64, -2, 1}, {1, 64, 2, 1}, {1, 64, 6, 1}, {0, 32, 15, 1}},
+      {{0, 128, 0, 4}, {1, 128, 0, 4}, {2, 128, 0, 4}, {3, 128, 0, 4}, {4, 128, 0, 4}, {5, 128, 0, 4}, {6, 128, 0, 4}, {7, 128, 0, 4}},   // 8 + 8 groups
+      {{0, 256, -2, 8}, {0, 256, 2, 8}},
+      {{0, 128, -2, 4}, {0, 128, 0, 4}, {0, 128, 2, 4}, {1, 64, 1, 2}, {1, 64, 4, 2}},
+      {{0, 1536, 0, 48}},
+  };
+  long plans = 0, accepted = 0;
+  for (const auto& w : walks)
+    for (int mt : {1, 2, 3, 8, 22, 64, 300})
+      for (int nt : {1, 2, 3, 4, 6, 12})
+        for (int prec = -1; prec <= 10; ++prec)
+          for (int epi = 0; epi <= 3; ++epi)
+            for (int mode = 0; mode < 4; ++mode)   // plain, p8, split-K, planes missing
+              for (int cus : {0, 7, 8, 16, 64, 120, 256, 304})
+                for (int knobs = 0; knobs < 5; ++knobs) {
+                  xv::GemmArgs a;
+                  memset(&a, 0, sizeof a);
+                  a.nseg = (int)w.size();
+                  for (int j = 0; j < a.nseg; ++j) {
+                    a.seg[j].hi = (const uint16_t*)(mem + 8 * w[j].src);
+                    a.seg[j].ld = w[j].ld;
+                    a.seg[j].row_shift = w[j].shift;
+                    a.seg[j].ksteps = w[j].ksteps;
+                    a.total_ksteps += w[j].ksteps;
+                    if (mode != 3) {
+                      a.seg[j].gmax = (const unsigned*)mem;
+                      a.seg[j].lo4 = a.seg[j].lo4s = (const uint8_t*)mem;
+                    }
+                  }
+                  a.m_tiles = mt;
+                  a.n_tiles = nt;
+                  if (mode != 3) {
+                    a.w4 = a.w4_scale = a.w4b = a.w4b_scale = (const uint8_t*)mem;
+                    a.out_lo4 = a.out_lo4s = (uint8_t*)mem;
+                    a.ldw4 = a.ldw4b = 64;
+                  }
+                  a.p8 = mode == 1;
+                  a.p8_whole = knobs % 3;
+                  if (mode == 2) {
+                    a.ksteps_per_slice = xv::SplitKStepsPerSlice(a.total_ksteps);
+                    a.ksplit = (a.total_ksteps + a.ksteps_per_slice - 1) / a.ksteps_per_slice;
+                    a.splitk_ws = (float*)mem;
+                  }
+                  const xv::GemmPolicy pol = knobs == 0 ? xv::DefaultGemmPolicy(cus) : xv::MakeGemmPolicy(cus, knobs, 4 * (knobs & 3), knobs - 1, 50 * knobs);
+                  const xv::GemmPlan p = xv::PlanGemm(a, prec, epi, pol);
+                  ++plans;
+                  const xv::GemmArgs& b = p.args;
+                  bool ok = b.ngrp >= 0 && b.ngrp_lo >= 0 && b.ngrp + b.ngrp_lo <= 2 * xv::kMaxSeg;
+                  if (p.ok) {
+                    ++accepted;
+                    char name[96];
+                    xv::GemmKernelName(p, name, sizeof name);
+                    ok = ok && p.grid_x >= 1 && p.grid_y >= 1 && (p.block == 256 || p.block == 512) && p.lds > 0 && p.lds <= xv::kGemmMaxLds && strlen(name) > 16;
+                    if (p.sk_ws_bytes) ok = ok && cus >= 8 && p.grid_x <= cus && b.sk_lanes >= 1 && p.grid_x % (8 * b.sk_lanes) == 0 && b.sk_mtiles >= 1;
+                  }
+                  if (!ok) {
+                    fprintf(stderr, "host_selftest: bad plan (walk of %d, %d x %d tiles, precision %d, epilogue %d, mode %d, %d CUs, knobs %d)\n", a.nseg, mt,
+                            nt, prec, epi, mode, cus, knobs);
+                    return 1;
+                  }
+                }
+  // the predicates the engine calls are defined on the same group builder and must not walk past kMaxSeg segments either
+  xv::GemmArgs a;
+  memset(&a, 0, sizeof a);
+  for (int nseg : {-1, 0, 9, 1000}) {
+    a.nseg = nseg;
+    if (xv::gemm_mx_applicable(a) || xv::gemm_mx2_applicable(a) || xv::gemm_p8_applicable(a, xv::kPrecFp16)) return 1;
+  }
+  printf("host_selftest: gemm_plan ok (%ld plans, %ld accepted)\n", plans, accepted);
+  return accepted > 0 && accepted < plans ? 0 : 1;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc == 2 && strcmp(argv[1], "gemm_plan") == 0) return RunGemmPlan();
   if (argc == 3 && strcmp(argv[1], "tables") == 0) return RunTables(argv[2]);
   if (argc == 3 && strcmp(argv[1], "walk") == 0) return RunWalk(argv[2]);
   if (argc != 4 && argc != 5) {

@@ -64,6 +64,19 @@ constexpr int PrecXPlanes(int p) { return (p == kPrecBf16x3 || p == kPrecFp16x3 
 constexpr int PrecWPlanes(int p) { return (p == kPrecBf16x3 || p == kPrecFp16x3 || p == kPrecFp16x2 || p == kPrecAuto || p == kPrecFp16Mx || p == kPrecFp16Mx2 || p == kPrecFp16x3E || p == kPrecFp16MxE) ? 2 : 1; }
 constexpr int PrecPasses(int p) { return PrecXPlanes(p) + PrecWPlanes(p) - 1; }   // MFMAs per algorithmic product (Mx: 1.25)
 
+// Dynamic LDS bytes of the GEMM kernel families: what the planner (gemm_plan.cc) states and the launcher sets and launches with.
+constexpr int kGemmMaxLds = 160 * 1024;
+constexpr int kSplitKStages = 4;   // LDS ring of the split-K instantiation of tdnn_gemm_kernel
+// tdnn_gemm_kernel: stages of one 128x32 16-bit tile (8 KiB) per plane - 2, its split-K instantiation kSplitKStages
+constexpr int GemmTileLds(int p, int stages) { return kBM * kBK * 2 * (PrecXPlanes(p) + PrecWPlanes(p)) * stages; }
+constexpr int GemmV2Lds(int p) {
+  return 3 * (PrecXPlanes(p) * (256 + 16) * kBK * 2 + PrecWPlanes(p) * kBM * kBK * 2) + (PrecMx(p) ? 1536 : 0) + (PrecMx2(p) ? 3 * (256 + 16) * 4 : 0);
+}
+constexpr int GemmSkLds(int p, int mf) {   // above kGemmMaxLds: the instantiation does not exist
+  return 3 * (PrecXPlanes(p) * (64 * mf + 16) * kBK * 2 + PrecWPlanes(p) * kBM * kBK * 2) + 1536 + 2 * 1536 + (PrecMx2(p) ? 3 * (64 * mf + 16) * 4 : 0);
+}
+constexpr int GemmP8Lds() { return 2 * 65536 + 16384 + 1024 + 2 * 3072 + 2 * 2048 + 2 * 1024; }   // the layout: kernels.hip, kP8Lds
+
 enum Epilogue : int {
   kEpiAct = 0,    // bias -> ReLU? -> BatchNorm? -> split to 16-bit planes
   kEpiF32 = 1,    // bias -> ReLU? -> BatchNorm? -> fp32 rows (embedding / raw affine output)
@@ -88,7 +101,7 @@ struct Seg {
 // 4-byte LDS-DMA)
 constexpr int Lo4ScalePitch(int ld) { return ((ld >> 6) + 3) & ~3; }
 
-// A group of K segments that share one LDS activation tile (filled by the launcher, see kernels.hip).
+// A group of K segments that share one LDS activation tile (filled by the planner, see gemm_plan.cc).
 struct Grp {
   const uint16_t* hi;
   const uint16_t* lo;
@@ -108,7 +121,7 @@ struct Grp {
 
 // The order in which the GEMM kernels walk the K steps of a layer: consecutive Append() terms that read the same
 // source at uniformly spaced, increasing time offsets (total span <= 16 rows) form a group whose activation tile is
-// staged once per 32-column chunk; inside a group the walk is chunk -> offset.  Shared by the launcher (build_groups)
+// staged once per 32-column chunk; inside a group the walk is chunk -> offset.  Shared by the planner (gemm_plan.cc)
 // and by the host code that packs the 4-bit residual plane of kPrecFp16Mx in walk order (engine.cc).
 struct WalkGroup {
   int first_seg, nshift, ksteps, shift0, dstep, wcol0, wstride;
@@ -207,7 +220,7 @@ struct GemmArgs {
   Grp grp[2 * kMaxSeg];   // kPrecFp16Mx2: entries ngrp .. ngrp + ngrp_lo - 1 are the groups of the second K walk
   int ngrp;
   int total_ksteps;     // K steps of the first walk (32 columns each)
-  int ngrp_lo;          // kPrecFp16Mx2 (set by the launcher)
+  int ngrp_lo;          // kPrecFp16Mx2 (set by the planner)
   int lo_ksteps;        // K steps of the second walk (128 columns each): total_ksteps / 4
   const uint16_t* w_hi;  // [n_pad][ldw] row-major (Kaldi <LinearParams> orientation)
   const uint16_t* w_lo;
@@ -259,10 +272,10 @@ struct GemmArgs {
   int ksplit;
   int ksteps_per_slice;   // SplitKStepsPerSlice
   float* splitk_ws;
-  // start stagger of the 256x128 variant (set by the launcher): the first stagger_wgs workgroups sleep up to
+  // start stagger of the 256x128 variant (set by the planner): the first stagger_wgs workgroups sleep up to
   // stagger_units x 2048 cycles, see the kernel
   int stagger_wgs, stagger_units;
-  // stream-K variant (set by the launcher): row tiles of the launch, workspace slots of raw accumulators
+  // stream-K variant (set by the planner): row tiles of the launch, workspace slots of raw accumulators
   // [workgroup][tile rows x 128], one flag per workgroup, value a flag must hold to count for this launch
   int sk_mtiles;
   int sk_lanes;          // column lanes per workgroup group (divides n_tiles)
@@ -274,7 +287,7 @@ struct GemmArgs {
   // p8 != 0: launch that kernel - the caller's statement that this layer runs it for every launch of the mode (its sums are
   // formed in another order than the 32-column kernels') and, for kPrecFp16Mx, that w4 / w4_scale are packed in its walk order.
   int p8;
-  int p8_ktiles;         // K tiles of an output tile (set by the launcher)
+  int p8_ktiles;         // K tiles of an output tile (set by the planner)
   int p8_whole;          // partition policy (caller): 0 = K tiles dealt out evenly (stream-K exchange), 1 = whole output tiles only, 2 = whole
                          // tiles for layers of <= 8 K tiles; the launcher resolves it to 0 / 1 for the kernel
   int p8_ktiles_lo;      // kPrecFp16Mx2: tiles of the second walk (256 4-bit columns each); w4b / w4b_scale are then in ITS order
@@ -296,7 +309,8 @@ inline int SplitKStepsPerSlice(int ksteps) {
 // Pass (nullptr, nullptr) to disarm.
 void set_launch_events(hipEvent_t start, hipEvent_t stop);
 
-// Launches the spliced-affine GEMM. Returns hipSuccess or the launch error.
+// Launches the spliced-affine GEMM as PlanGemm (gemm_plan.h) decides under the current policy.  Returns hipSuccess,
+// hipErrorInvalidValue for a launch the plan refuses, or the launch error.
 hipError_t launch_tdnn_gemm(const GemmArgs& a, int precision, int epilogue, hipStream_t s);
 // Name of the kernel instantiation the calling thread's last launch_tdnn_gemm call launched, e.g.
 // "tdnn_gemm_kernel_sk<fp16mx,act,8>" (profiling labels; valid until the next launch of this thread).

@@ -30,6 +30,7 @@
 //     one frame (32-byte stores per plane); kEpiStats feeds activations as A so the 16-row
 //     reduction is 3 in-register adds + 2 cross-lane adds.
 #include "kernels.h"
+#include "gemm_plan.h"
 #include "knobs.h"
 
 #include <hip/hip_ext.h>
@@ -67,15 +68,7 @@ void set_launch_events(hipEvent_t start, hipEvent_t stop) {
 }
 static thread_local char g_last_kernel[96] = "";
 const char* last_gemm_kernel() { return g_last_kernel; }
-static const char* prec_name(int p) {
-  static const char* n[] = {"bf16x3", "bf16", "fp16", "fp16x3", "fp16x2", "auto", "fp16mx", "fp16mx2", "fp16x3e", "fp16mxe"};
-  return (p >= 0 && p <= 9) ? n[p] : "?";
-}
-static const char* epi_name(int e) { return e == kEpiAct ? "act" : e == kEpiF32 ? "f32" : e == kEpiStats ? "stats" : "splitk"; }
-static void note_kernel(const char* variant, int prec, int epi, int mf) {
-  if (mf) snprintf(g_last_kernel, sizeof g_last_kernel, "tdnn_gemm_kernel%s<%s,%s,%d>", variant, prec_name(prec), epi_name(epi), mf);
-  else snprintf(g_last_kernel, sizeof g_last_kernel, "tdnn_gemm_kernel%s<%s,%s>", variant, prec_name(prec), epi_name(epi));
-}
+static void note_kernel(const GemmPlan& p) { GemmKernelName(p, g_last_kernel, sizeof g_last_kernel); }
 #define XV_LAUNCH(kern, grid, block, lds, stream, ...)                                           \
   do {                                                                                           \
     hipEvent_t _st = g_ev_start, _sp = g_ev_stop;                                                \
@@ -715,7 +708,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[4]
 
 // (defined with the v2 kernel below: LDS-DMA from inline asm, invisible to hipcc's wait-count scoreboard)
 __device__ __forceinline__ void glds16_asm(const void* g, unsigned lds_addr);
-constexpr int kSplitKStages = 4;   // LDS ring of the split-K instantiation of tdnn_gemm_kernel
 
 template <int PREC, int EPI>
 __global__ __launch_bounds__(256, 2) void tdnn_gemm_kernel(const GemmArgs a) {
@@ -1455,129 +1447,16 @@ __global__ __launch_bounds__(512) void tdnn_gemm_kernel_v2(const GemmArgs a) {
   gemm_epilogue<PREC, EPI>(a, acc, m0 + wave_m * 64, n0 + wave_n * 64, lane, er, gm, 0);
 }
 
-// Which GEMM variant to launch: 1 = 128x128 / 2-stage, 2 = 256x128 / 3-stage ring, 4 = stream-K (persistent; falls
-// back to 2 / 1 when the launch has too few tiles or an odd shape), 0 = by precision and K length (default, see
-// launch_one).  XVEC_DEBUG=gemm_variant=... overrides.
-// (function-local static initialisers: thread-safe - the engines of a --devices job launch from a consumer thread each)
-static int gemm_variant() {
-  static const int v = [] {
-    const int x = DebugKnobInt("gemm_variant", 0);
-    return (x != 0 && x != 1 && x != 2 && x != 4) ? 0 : x;
-  }();
-  return v;
-}
-// Frame fragments per wave of the stream-K variant: 8 (512-row tiles) where the LDS allows, else 4.  XVEC_DEBUG=sk_mf=4
-// forces the 256-row tiles.
-static int sk_max_mf() {
-  static const int v = [] {
-    const int x = DebugKnobInt("sk_mf", 8);
-    return (x != 4 && x != 8) ? 8 : x;
-  }();
-  return v;
-}
-
-// The dynamic-LDS attribute of a kernel is per device: one bit per device index, so that a process driving several
-// GPUs (xv_ctx_create_broadcast) sets it on each of them.
-static bool lds_attr_needed(std::atomic<unsigned long long>* done_mask, int* dev_out) {
+// Lets kernel fn use `bytes` of dynamic LDS.  The attribute of a kernel is per device: *done holds one bit per device index,
+// so that a process driving several GPUs (xv_ctx_create_broadcast) sets it on each of them.
+static hipError_t set_dynamic_lds(const void* fn, int bytes, std::atomic<unsigned long long>* done) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  *dev_out = dev;
-  return !((done_mask->load(std::memory_order_acquire) >> (dev & 63)) & 1ull);
-}
-
-// Groups consecutive K segments that read the same source at uniformly spaced time offsets (see the v2 kernel); the
-// grouping rule itself is PlanWalkGroups (kernels.h), shared with the host code that packs weights in walk order.
-static void build_groups(GemmArgs* g) {
-  long key[kMaxSeg];
-  int shift[kMaxSeg], ksteps[kMaxSeg];
-  for (int j = 0; j < g->nseg; ++j) {
-    key[j] = j;
-    for (int k = 0; k < j; ++k)
-      if (g->seg[k].hi == g->seg[j].hi && g->seg[k].lo == g->seg[j].lo && g->seg[k].ld == g->seg[j].ld) {
-        key[j] = key[k];
-        break;
-      }
-    shift[j] = g->seg[j].row_shift;
-    ksteps[j] = g->seg[j].ksteps;
-  }
-  WalkGroup wg[kMaxSeg];
-  g->ngrp = PlanWalkGroups(g->nseg, key, shift, ksteps, wg);
-  for (int i = 0; i < g->ngrp; ++i) {
-    const Seg& s0 = g->seg[wg[i].first_seg];
-    Grp& G = g->grp[i];
-    G.hi = s0.hi;
-    G.lo = s0.lo;
-    G.ld = s0.ld;
-    G.ksteps = wg[i].ksteps;
-    G.nshift = wg[i].nshift;
-    G.shift0 = wg[i].shift0;
-    G.dstep = wg[i].dstep;
-    G.wcol0 = wg[i].wcol0;
-    G.wstride = wg[i].wstride;
-    G.pad_ = 0;
-    G.gmax = s0.gmax;
-    G.lo4s = nullptr;
-    G.ld4s = 0;
-    G.pad2_ = 0;
-  }
-  g->ngrp_lo = 0;
-  g->lo_ksteps = 0;
-}
-
-// kPrecFp16Mx2: the groups of the second K walk behind the first ones - the same sources, time offsets and order, steps of
-// 128 columns over the 4-bit residual planes (as 16-bit elements: a quarter of the row pitch and of the steps).
-static void build_lo_groups(GemmArgs* g) {
-  WalkGroup wg[kMaxSeg];
-  {
-    long key[kMaxSeg];
-    int shift[kMaxSeg], ksteps[kMaxSeg];
-    for (int j = 0; j < g->nseg; ++j) {
-      key[j] = j;
-      for (int k = 0; k < j; ++k)
-        if (g->seg[k].hi == g->seg[j].hi && g->seg[k].lo == g->seg[j].lo && g->seg[k].ld == g->seg[j].ld) {
-          key[j] = key[k];
-          break;
-        }
-      shift[j] = g->seg[j].row_shift;
-      ksteps[j] = g->seg[j].ksteps;
-    }
-    PlanWalkGroups(g->nseg, key, shift, ksteps, wg);
-  }
-  g->ngrp_lo = g->ngrp;
-  g->lo_ksteps = 0;
-  for (int i = 0; i < g->ngrp; ++i) {
-    const Seg& s0 = g->seg[wg[i].first_seg];
-    Grp& G = g->grp[g->ngrp + i];
-    G = g->grp[i];
-    G.hi = (const uint16_t*)s0.lo4;
-    G.lo = nullptr;
-    G.ld = s0.ld / 4;
-    G.ksteps = g->grp[i].ksteps / 4;
-    G.gmax = nullptr;
-    G.lo4s = s0.lo4s;
-    G.ld4s = Lo4ScalePitch(s0.ld);
-    g->lo_ksteps += G.ksteps * G.nshift;
-  }
-}
-
-bool gemm_mx2_applicable(const GemmArgs& a) {
-  if (!gemm_mx_applicable(a) || !a.w4b || !a.w4b_scale || a.ldw4b <= 0) return false;
-  GemmArgs b = a;
-  build_groups(&b);
-  for (int i = 0; i < b.ngrp; ++i)   // whole 128-column steps
-    if (b.grp[i].ksteps % 4 || b.grp[i].ld % 128) return false;
-  for (int j = 0; j < a.nseg; ++j)
-    if (!a.seg[j].lo4 || !a.seg[j].lo4s) return false;
-  return true;
-}
-
-bool gemm_mx_applicable(const GemmArgs& a) {
-  if (!a.w4 || !a.w4_scale || a.ldw4 <= 0 || (a.m_tiles & 1) || (a.total_ksteps & 3)) return false;
-  GemmArgs b = a;
-  build_groups(&b);
-  for (int i = 0; i < b.ngrp; ++i)
-    if (!b.grp[i].gmax || (b.grp[i].ksteps * b.grp[i].nshift) % 4) return false;
-  return true;
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (done->load(std::memory_order_acquire) & bit) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done->fetch_or(bit, std::memory_order_release);
+  return e;
 }
 
 // CUs of the CURRENT device (a --devices job drives several; the count is kept per ordinal, filled once under a lock)
@@ -1593,6 +1472,15 @@ static int device_cu_count() {
     count[dev] = n;
   }
   return count[dev];
+}
+
+// (function-local static initialiser: thread-safe - the engines of a --devices job launch from a consumer thread each)
+GemmPolicy CurrentGemmPolicy() {
+  static const GemmPolicy knobs = MakeGemmPolicy(0, DebugKnobInt("gemm_variant", 0), DebugKnobInt("sk_mf", 8), DebugKnobInt("sk_lanes", 4),
+                                                 DebugKnobInt("gemm_stagger", 85));
+  GemmPolicy p = knobs;
+  p.cus = device_cu_count();
+  return p;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2336,6 +2224,7 @@ constexpr int kP8PB = kP8SC + 1024;     // epilogue parameters: [part & 1][colum
 constexpr int kP8WSL = kP8PB + 2 * 3072;   // kPrecFp16Mx2, second walk: weight scales [tile & 1][128-column half of the K tile][128-column tile][512]
 constexpr int kP8XSL = kP8WSL + 2 * 2048;  // and the scales of the activation residuals, [tile & 1][frame][4]: one byte per 64 columns
 constexpr int kP8Lds = kP8XSL + 2 * 1024;
+static_assert(kP8Lds == GemmP8Lds(), "kernels.h states the size of this layout");
 
 // s_waitcnt vmcnt(n) for a wave-uniform n (the counted waits of tdnn_gemm_kernel_p8: what is in flight behind the data a wait is
 // for depends on the walk - 4-bit tiles, scale pieces, the tail of a part - and is counted as it is issued)
@@ -3200,223 +3089,6 @@ unsigned sk_take_error(hipStream_t s) {
   return v;
 }
 
-// True when the stream-K variant with MF fragments per wave can run this launch.
-template <int PREC, int MF>
-static bool sk_applicable(const GemmArgs& a) {
-  constexpr int lds = 3 * (PrecXPlanes(PREC) * (64 * MF + 16) * kBK * 2 + PrecWPlanes(PREC) * kTileBytes) + 1536 + 2 * 1536 + (PrecMx2(PREC) ? 3 * (64 * MF + 16) * 4 : 0);
-  if (lds > 160 * 1024) return false;
-  const int rows = a.m_tiles * kBM;
-  if (rows % (64 * MF)) return false;
-  const int grid = device_cu_count() / 8 * 8;
-  if (grid < 8) return false;
-  // every workgroup gets at least one tile's worth of K steps (XCD blocks are whole row tiles) ...
-  if ((long)(rows / (64 * MF) / 8) * a.n_tiles >= grid / 8) return true;
-  // ... or, on fewer workgroups (sk_groups), launches between the two regimes: at least four row tiles per XCD block, and
-  // more 256-row tiles than the per-tile kernel finishes in one round (48 and 64 chunks of 400 frames: 300 / 400 tiles of
-  // tdnn2 on 256 CUs = two rounds, 82 us for both, where one round is 42)
-  return MF == 8 && rows / (64 * MF) / 8 >= 4 && (long)(a.m_tiles / 2) * a.n_tiles > device_cu_count();
-}
-
-// Workgroup groups per XCD block and column lane: as many as the CUs allow, but not more than the block has tiles per lane
-template <int MF>
-static int sk_groups(const GemmArgs& a, int grid, int lanes) {
-  const int tiles_min = std::max(1, (a.m_tiles * kBM / (64 * MF) / 8) * (a.n_tiles / lanes));
-  return std::min(grid / 8 / lanes, tiles_min);
-}
-
-template <int PREC, int EPI, int MF>
-static hipError_t launch_one_sk(const GemmArgs& a, hipStream_t s) {
-  constexpr int lds = 3 * (PrecXPlanes(PREC) * (64 * MF + 16) * kBK * 2 + PrecWPlanes(PREC) * kTileBytes) + 1536 + 2 * 1536 + (PrecMx2(PREC) ? 3 * (64 * MF + 16) * 4 : 0);
-  if constexpr (lds > 160 * 1024) {
-    return hipErrorInvalidValue;
-  } else {
-    static std::atomic<unsigned long long> attr_done{0};
-    int attr_dev = 0;
-    if (lds_attr_needed(&attr_done, &attr_dev)) {
-      hipError_t e = hipFuncSetAttribute((const void*)tdnn_gemm_kernel_sk<PREC, EPI, MF>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return e;
-      attr_done.fetch_or(1ull << (attr_dev & 63), std::memory_order_release);
-    }
-    int grid = device_cu_count() / 8 * 8;
-    GemmArgs b = a;
-    build_groups(&b);
-    if constexpr (PrecMx2(PREC)) build_lo_groups(&b);
-    b.sk_mtiles = a.m_tiles * kBM / (64 * MF);
-    {
-      // column lanes: the largest of 4, 2, 1 that divides the column tiles and the workgroups of an XCD block
-      static const int max_lanes = [] {
-        const int x = DebugKnobInt("sk_lanes", 4);
-        return (x != 1 && x != 2 && x != 4) ? 4 : x;
-      }();
-      int l = max_lanes;
-      while (l > 1 && (a.n_tiles % l || (grid / 8) % l)) l >>= 1;
-      b.sk_lanes = l;
-      grid = 8 * l * sk_groups<MF>(a, grid, l);
-    }
-    SkWorkspace w;
-    hipError_t e = sk_workspace(s, grid, (size_t)grid * 64 * MF * kBN * sizeof(float), &w, &b.sk_epoch, &b.sk_error);
-    if (e != hipSuccess) return e;
-    b.sk_ws = w.ws;
-    b.sk_flags = w.flags;
-    note_kernel("_sk", PREC, EPI, MF);
-    XV_LAUNCH((tdnn_gemm_kernel_sk<PREC, EPI, MF>), dim3(grid), dim3(512), lds, s, b);
-    return hipGetLastError();
-  }
-}
-
-
-// tdnn_gemm_kernel_p8 can run this launch: whole 256 x 256 tiles, every K group a whole number of 64-column tiles (of
-// 128-column blocks for kPrecFp16Mx), an even number of K tiles, and for kPrecFp16Mx the residual plane in ITS walk order
-// (GemmArgs::p8 is the caller's statement that w4 / w4_scale are in that order)
-bool gemm_p8_applicable(const GemmArgs& a, int precision) {
-  if (precision == kPrecFp16MxE) precision = kPrecFp16Mx;   // the same product; its planes epilogue also writes the residual plane
-  if (precision != kPrecFp16 && precision != kPrecFp16Mx && precision != kPrecFp16Mx2) return false;
-  if ((a.m_tiles & 1) || (a.n_tiles & 1) || a.ksplit > 1) return false;
-  const bool mx = precision != kPrecFp16, mx2 = precision == kPrecFp16Mx2;
-  GemmArgs b = a;
-  build_groups(&b);
-  int t = 0;
-  for (int i = 0; i < b.ngrp; ++i) {
-    // whole K tiles: 64 columns; whole blocks of the residual product: 128; whole tiles of the second walk: 256
-    if (b.grp[i].ksteps % (mx2 ? 8 : mx ? 4 : 2) || b.grp[i].ld % (mx2 ? 256 : 64)) return false;
-    if (mx && !b.grp[i].gmax) return false;
-    t += (b.grp[i].ksteps >> 1) * b.grp[i].nshift;
-  }
-  if (t < 2 || (t & 1)) return false;
-  if (mx && (!a.w4 || !a.w4_scale || a.ldw4 <= 0)) return false;
-  if (mx2) {
-    if (!a.w4b || !a.w4b_scale || a.ldw4b <= 0) return false;
-    for (int j = 0; j < a.nseg; ++j)
-      if (!a.seg[j].lo4 || !a.seg[j].lo4s) return false;
-  }
-  return true;
-}
-
-template <int PREC, int EPI>
-static hipError_t launch_one_p8(const GemmArgs& a, hipStream_t s) {
-  if (!gemm_p8_applicable(a, PREC)) return hipErrorInvalidValue;
-  static std::atomic<unsigned long long> attr_done{0};
-  int attr_dev = 0;
-  if (lds_attr_needed(&attr_done, &attr_dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)tdnn_gemm_kernel_p8<PREC, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, kP8Lds);
-    if (e != hipSuccess) return e;
-    attr_done.fetch_or(1ull << (attr_dev & 63), std::memory_order_release);
-  }
-  GemmArgs b = a;
-  build_groups(&b);
-  b.p8_ktiles = 0;
-  for (int i = 0; i < b.ngrp; ++i) b.p8_ktiles += (b.grp[i].ksteps >> 1) * b.grp[i].nshift;
-  b.p8_ktiles_lo = 0;
-  if constexpr (PrecMx2(PREC)) {
-    build_lo_groups(&b);   // second walk: the 4-bit planes, steps of 128 columns (a tile = two of them)
-    for (int i = 0; i < b.ngrp_lo; ++i) b.p8_ktiles_lo += (b.grp[b.ngrp + i].ksteps >> 1) * b.grp[b.ngrp + i].nshift;
-  }
-  b.p8 = 1;
-  // GemmArgs::p8_whole as the caller's policy (Engine: XVEC_DEBUG=p8_whole): 0 = K tiles dealt out evenly over the workgroups (stream-K
-  // exchange; the default), 1 = whole tiles for every launch, 2 = whole tiles for layers of at most 8 K tiles per output tile
-  b.p8_whole = (a.p8_whole == 1 || (a.p8_whole == 2 && b.p8_ktiles + b.p8_ktiles_lo <= 8)) ? 1 : 0;
-  b.sk_mtiles = a.m_tiles >> 1;
-  const int nt = a.n_tiles >> 1;
-  int grid = device_cu_count() / 8 * 8;
-  if (grid < 8) return hipErrorInvalidValue;
-  // column lanes: the largest of 4, 2, 1 that divides the column tiles and the workgroups of an XCD block; groups: as many
-  // as the CUs allow, but every group's share must hold at least one whole tile
-  int l = 4;
-  while (l > 1 && (nt % l || (grid / 8) % l)) l >>= 1;
-  // Column tiles in threes (1536 = 6, 768 = 3 tiles of 256: the statistics layer, the 650-wide layers of the c-vector network):
-  // with two lanes - or one - every workgroup walks its row tile's frames once per column tile, 16 to 32 row tiles are in flight
-  // per XCD (4 - 8 MB of frames against 4 MB of L2), and every pass after the first misses: 578 MB per tdnn5 launch for a 105 MB
-  // plane (profiles/r05w_pmc_hbm.md).  As many lanes as column tiles instead: the lanes of a group walk the SAME row tile at the
-  // same time, the first brings a line into the XCD's L2 and the others find it there.  The workgroups of an XCD block are
-  // then a multiple of 3 (30 of 32 CUs); the partition is bit-identical whatever the cut.
-  // (same box, A/B: tdnn5 of the x-vector 572 -> 245 MB per launch at the same 0.205 ms; the 768-wide layers of the c-vector
-  // network 1141 -> 330 MB and 721 -> 285 MB, their launches +2.5 % on their own and the two-lane step -3.5 % - profiles/r06_lanes.md)
-  if (nt % 3 == 0 && nt <= 6 && grid / 8 >= nt) l = nt;
-  b.sk_lanes = l;
-  const int tiles_min = std::max(1, (b.sk_mtiles / 8) * (nt / l));
-  grid = 8 * l * std::min(grid / 8 / l, tiles_min);
-  SkWorkspace w;
-  hipError_t e = sk_workspace(s, grid, (size_t)grid * 256 * 256 * sizeof(float), &w, &b.sk_epoch, &b.sk_error);
-  if (e != hipSuccess) return e;
-  b.sk_ws = w.ws;
-  b.sk_flags = w.flags;
-  note_kernel("_p8", PREC, EPI, 0);
-  XV_LAUNCH((tdnn_gemm_kernel_p8<PREC, EPI>), dim3(grid), dim3(512), kP8Lds, s, b);
-  return hipGetLastError();
-}
-
-template <int PREC, int EPI>
-static hipError_t launch_one_v2(const GemmArgs& a, hipStream_t s) {
-  constexpr int lds = 3 * (PrecXPlanes(PREC) * (256 + 16) * kBK * 2 + PrecWPlanes(PREC) * kTileBytes) + (PrecMx(PREC) ? 1536 : 0) + (PrecMx2(PREC) ? 3 * (256 + 16) * 4 : 0);
-  static std::atomic<unsigned long long> attr_done{0};
-  int attr_dev = 0;
-  if (lds_attr_needed(&attr_done, &attr_dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)tdnn_gemm_kernel_v2<PREC, EPI>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_done.fetch_or(1ull << (attr_dev & 63), std::memory_order_release);
-  }
-  const int mt = a.m_tiles >> 1;
-  const int mt8 = (mt + 7) / 8 * 8;
-  dim3 grid(mt8 * a.n_tiles), block(512);
-  GemmArgs b = a;
-  build_groups(&b);
-  if constexpr (PrecMx2(PREC)) build_lo_groups(&b);
-  {
-    // stagger window = gemm_stagger (XVEC_DEBUG) percent of the modelled tile time (K steps x ~2200 cycles in split mode,
-    // ~1000 single pass, + ~14000 fixed)
-    static const int pct = DebugKnobInt("gemm_stagger", 85);
-    const int cus = device_cu_count();
-    b.stagger_wgs = cus;
-    b.stagger_units = ((int)grid.x > 2 * cus) ? (int)(((long)b.total_ksteps * (400 + 600 * PrecPasses(PREC)) + 14000) * pct / 100 / 2048) : 0;
-  }
-  note_kernel("_v2", PREC, EPI, 0);
-  XV_LAUNCH((tdnn_gemm_kernel_v2<PREC, EPI>), grid, block, lds, s, b);
-  return hipGetLastError();
-}
-
-template <int PREC, int EPI>
-static hipError_t launch_one(const GemmArgs& a, hipStream_t s) {
-  if (a.p8) {   // the caller packed / chose this layer for the 64-column K walk: no other kernel accumulates in that order
-    if constexpr (((PREC == kPrecFp16 || PREC == kPrecFp16Mx || PREC == kPrecFp16Mx2) && (EPI == kEpiAct || EPI == kEpiStats)) ||
-                  (PREC == kPrecFp16MxE && EPI == kEpiAct))
-      return launch_one_p8<PREC, EPI>(a, s);
-    else return hipErrorInvalidValue;
-  }
-  const int variant = gemm_variant();
-  // default policy (same box, 256 x 400 workload): two-pass mode - stream-K for every layer; three-pass and single-pass
-  // modes - stream-K only for the long-K layers (tdnn2 / tdnn3, 48 K steps: -5 % / -9 %), the short-K ones are faster
-  // on the per-tile kernel there (tdnn5 single-pass: 0.190 vs 0.229 ms)
-  const bool sk_default = PREC == kPrecFp16x2 || PREC == kPrecFp16Mx || a.total_ksteps >= 32;
-  if constexpr (PrecMx(PREC)) {
-    // 512-row stream-K tiles or the 256-row per-tile kernel (bit-identical); nothing else implements the mode
-    if (PrecMx2(PREC) ? !gemm_mx2_applicable(a) : !gemm_mx_applicable(a)) return hipErrorInvalidValue;
-    if (variant != 2 && variant != 1 && sk_max_mf() == 8 && sk_applicable<PREC, 8>(a)) return launch_one_sk<PREC, EPI, 8>(a, s);
-    return launch_one_v2<PREC, EPI>(a, s);
-  } else {
-    if (variant == 4 || (variant == 0 && sk_default)) {
-      if (sk_max_mf() == 8 && sk_applicable<PREC, 8>(a)) return launch_one_sk<PREC, EPI, 8>(a, s);
-      if ((variant == 4 || PrecXPlanes(PREC) == 2) && sk_applicable<PREC, 4>(a)) return launch_one_sk<PREC, EPI, 4>(a, s);
-    }
-    if (variant != 1 && (a.m_tiles & 1) == 0) return launch_one_v2<PREC, EPI>(a, s);
-    constexpr int lds = kTileBytes * (PrecXPlanes(PREC) + PrecWPlanes(PREC)) * 2;
-    static std::atomic<unsigned long long> attr_done{0};
-    int attr_dev = 0;
-    if (lds_attr_needed(&attr_done, &attr_dev)) {
-      hipError_t e = hipFuncSetAttribute((const void*)tdnn_gemm_kernel<PREC, EPI>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return e;
-      attr_done.fetch_or(1ull << (attr_dev & 63), std::memory_order_release);
-    }
-    const int mt8 = (a.m_tiles + 7) / 8 * 8;
-    dim3 grid(mt8 * a.n_tiles), block(256);
-    note_kernel("", PREC, EPI, 0);
-    XV_LAUNCH((tdnn_gemm_kernel<PREC, EPI>), grid, block, lds, s, a);
-    return hipGetLastError();
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
 // Split-K reduction: out = epilogue(sum over K slices, in slice order, + bias).  One thread = 4 columns of a row.
 template <int PREC, int EPI>
@@ -3477,67 +3149,86 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmArgs a) {
   }
 }
 
-template <int PREC, int EPI>
-static hipError_t launch_splitk(const GemmArgs& a, hipStream_t s) {
-  constexpr int lds = kTileBytes * (PrecXPlanes(PREC) + PrecWPlanes(PREC)) * kSplitKStages;
+// ---------------------------------------------------------------------------------------------
+// The launcher: carries out what PlanGemm (gemm_plan.h) decided.
+template <void (*KERN)(const GemmArgs)>
+static hipError_t launch_planned(const GemmPlan& p, hipStream_t s) {
   static std::atomic<unsigned long long> attr_done{0};
-  int attr_dev = 0;
-  if (lds_attr_needed(&attr_done, &attr_dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)tdnn_gemm_kernel<PREC, kEpiSplitK>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_done.fetch_or(1ull << (attr_dev & 63), std::memory_order_release);
-  }
-  dim3 grid(a.m_tiles * a.n_tiles, a.ksplit), block(256);
-  note_kernel("", PREC, kEpiSplitK, 0);
-  XV_LAUNCH((tdnn_gemm_kernel<PREC, kEpiSplitK>), grid, block, lds, s, a);
-  hipError_t e = hipGetLastError();
+  hipError_t e = set_dynamic_lds((const void*)KERN, p.lds, &attr_done);
   if (e != hipSuccess) return e;
-  const long total = (long)a.m_tiles * kBM * (a.n_tiles * kBN / 4);
-  XV_LAUNCH((splitk_reduce_kernel<PREC, EPI>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+  GemmArgs b = p.args;
+  if (p.sk_ws_bytes) {
+    SkWorkspace w;
+    e = sk_workspace(s, p.grid_x, p.sk_ws_bytes, &w, &b.sk_epoch, &b.sk_error);
+    if (e != hipSuccess) return e;
+    b.sk_ws = w.ws;
+    b.sk_flags = w.flags;
+  }
+  note_kernel(p);
+  XV_LAUNCH(KERN, dim3(p.grid_x, p.grid_y), dim3(p.block), p.lds, s, b);
   return hipGetLastError();
 }
 
-template <int PREC>
-static hipError_t launch_prec(const GemmArgs& a, int epi, hipStream_t s) {
-  if constexpr (PREC == kPrecFp16x3E) {   // planes out only (the layers in front of a kPrecFp16Mx2 consumer)
-    if (a.ksplit > 1 || epi != kEpiAct || !a.out_lo4 || !a.out_lo4s) return hipErrorInvalidValue;
-    return launch_one<PREC, kEpiAct>(a, s);
-  } else if constexpr (PREC == kPrecFp16MxE) {   // planes out only: the 1.25-pass product in front of a kPrecFp16Mx2 consumer
-    if (a.ksplit > 1 || epi != kEpiAct || !a.out_lo4 || !a.out_lo4s) return hipErrorInvalidValue;
-    return launch_one<PREC, kEpiAct>(a, s);
-  } else if constexpr (PrecMx(PREC)) {   // frame-level layers only: planes out or pooled statistics
-    if (a.ksplit > 1) return hipErrorInvalidValue;
-    if (epi == kEpiAct) return launch_one<PREC, kEpiAct>(a, s);
-    if (epi == kEpiStats) return launch_one<PREC, kEpiStats>(a, s);
-    return hipErrorInvalidValue;
-  } else {
-    if (a.ksplit > 1 && a.splitk_ws) {
-      if (epi == kEpiAct) return launch_splitk<PREC, kEpiAct>(a, s);
-      if (epi == kEpiF32) return launch_splitk<PREC, kEpiF32>(a, s);
-      return hipErrorInvalidValue;
-    }
-    switch (epi) {
-      case kEpiAct: return launch_one<PREC, kEpiAct>(a, s);
-      case kEpiF32: return launch_one<PREC, kEpiF32>(a, s);
-      case kEpiStats: return launch_one<PREC, kEpiStats>(a, s);
-      default: return hipErrorInvalidValue;
-    }
+// plan -> instantiation.  The guards name the instantiations that exist; PlanGemm plans no other.
+template <int PREC, int EPI>
+static hipError_t launch_plan(const GemmPlan& p, hipStream_t s) {
+  switch (p.kernel) {
+    case kGemmP8:
+      if constexpr (((PREC == kPrecFp16 || PREC == kPrecFp16Mx || PREC == kPrecFp16Mx2) && (EPI == kEpiAct || EPI == kEpiStats)) ||
+                    (PREC == kPrecFp16MxE && EPI == kEpiAct))
+        return launch_planned<tdnn_gemm_kernel_p8<PREC, EPI>>(p, s);
+      break;
+    case kGemmSk:
+      if constexpr (GemmSkLds(PREC, 8) <= kGemmMaxLds)
+        if (p.mf == 8) return launch_planned<tdnn_gemm_kernel_sk<PREC, EPI, 8>>(p, s);
+      if constexpr (!PrecMx(PREC) && GemmSkLds(PREC, 4) <= kGemmMaxLds)
+        if (p.mf == 4) return launch_planned<tdnn_gemm_kernel_sk<PREC, EPI, 4>>(p, s);
+      break;
+    case kGemmV2: return launch_planned<tdnn_gemm_kernel_v2<PREC, EPI>>(p, s);
+    case kGemmTile:
+      if constexpr (!PrecMx(PREC)) return launch_planned<tdnn_gemm_kernel<PREC, EPI>>(p, s);
+      break;
   }
+  return hipErrorInvalidValue;
+}
+
+template <int PREC>
+static hipError_t launch_plan_epi(const GemmPlan& p, hipStream_t s) {
+  if constexpr (!PrecMx(PREC) && PREC != kPrecFp16x3E)
+    if (p.kernel == kGemmSplitK) {   // the slices, then their sum in slice order with the epilogue (planes or fp32 out)
+      const hipError_t e = launch_planned<tdnn_gemm_kernel<PREC, kEpiSplitK>>(p, s);
+      if (e != hipSuccess) return e;
+      const long total = (long)p.args.m_tiles * kBM * (p.args.n_tiles * kBN / 4);
+      const dim3 grid((unsigned)((total + 255) / 256));
+      if (p.epilogue == kEpiAct) XV_LAUNCH((splitk_reduce_kernel<PREC, kEpiAct>), grid, dim3(256), 0, s, p.args);
+      else XV_LAUNCH((splitk_reduce_kernel<PREC, kEpiF32>), grid, dim3(256), 0, s, p.args);
+      return hipGetLastError();
+    }
+  switch (p.epilogue) {
+    case kEpiAct: return launch_plan<PREC, kEpiAct>(p, s);
+    case kEpiF32:
+      if constexpr (!PrecMx(PREC) && PREC != kPrecFp16x3E) return launch_plan<PREC, kEpiF32>(p, s);
+      break;
+    case kEpiStats:
+      if constexpr (PREC != kPrecFp16x3E && PREC != kPrecFp16MxE) return launch_plan<PREC, kEpiStats>(p, s);
+      break;
+  }
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_tdnn_gemm(const GemmArgs& a, int precision, int epilogue, hipStream_t s) {
-  if (a.nseg < 1 || a.nseg > kMaxSeg || a.m_tiles < 1 || a.n_tiles < 1) return hipErrorInvalidValue;
+  const GemmPlan p = PlanGemm(a, precision, epilogue, CurrentGemmPolicy());
+  if (!p.ok) return hipErrorInvalidValue;
   switch (precision) {
-    case kPrecBf16x3: return launch_prec<kPrecBf16x3>(a, epilogue, s);
-    case kPrecBf16: return launch_prec<kPrecBf16>(a, epilogue, s);
-    case kPrecFp16: return launch_prec<kPrecFp16>(a, epilogue, s);
-    case kPrecFp16x3: return launch_prec<kPrecFp16x3>(a, epilogue, s);
-    case kPrecFp16x2: return launch_prec<kPrecFp16x2>(a, epilogue, s);
-    case kPrecFp16Mx: return launch_prec<kPrecFp16Mx>(a, epilogue, s);
-    case kPrecFp16Mx2: return launch_prec<kPrecFp16Mx2>(a, epilogue, s);
-    case kPrecFp16x3E: return launch_prec<kPrecFp16x3E>(a, epilogue, s);
-    case kPrecFp16MxE: return launch_prec<kPrecFp16MxE>(a, epilogue, s);
+    case kPrecBf16x3: return launch_plan_epi<kPrecBf16x3>(p, s);
+    case kPrecBf16: return launch_plan_epi<kPrecBf16>(p, s);
+    case kPrecFp16: return launch_plan_epi<kPrecFp16>(p, s);
+    case kPrecFp16x3: return launch_plan_epi<kPrecFp16x3>(p, s);
+    case kPrecFp16x2: return launch_plan_epi<kPrecFp16x2>(p, s);
+    case kPrecFp16Mx: return launch_plan_epi<kPrecFp16Mx>(p, s);
+    case kPrecFp16Mx2: return launch_plan_epi<kPrecFp16Mx2>(p, s);
+    case kPrecFp16x3E: return launch_plan_epi<kPrecFp16x3E>(p, s);
+    case kPrecFp16MxE: return launch_plan_epi<kPrecFp16MxE>(p, s);
     default: return hipErrorInvalidValue;
   }
 }
@@ -3844,15 +3535,12 @@ hipError_t launch_tdnn_first(const FirstArgs& a, int epi_prec, hipStream_t s) {
     return hipErrorInvalidValue;
   const int dp = (a.dim + 7) & ~7;
   const int lds = 4 * 384 * 4 + 512 * 256 + 4 * (kFirstRows + 32) * dp * 2 + (96 * 4 + 8) * 16;
-  static std::atomic<unsigned long long> attr_done{0};
-  int attr_dev = 0;
-  if (lds_attr_needed(&attr_done, &attr_dev)) {
-    for (const void* f : {(const void*)tdnn_first_kernel<kPrecFp16x3>, (const void*)tdnn_first_kernel<kPrecBf16x3>,
-                          (const void*)tdnn_first_kernel<kPrecFp16x3E>, (const void*)tdnn_first_kernel<kPrecFp16x2>}) {
-      hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-    }
-    attr_done.fetch_or(1ull << (attr_dev & 63), std::memory_order_release);
+  static std::atomic<unsigned long long> attr_done[4];
+  int k = 0;
+  for (const void* f : {(const void*)tdnn_first_kernel<kPrecFp16x3>, (const void*)tdnn_first_kernel<kPrecBf16x3>,
+                        (const void*)tdnn_first_kernel<kPrecFp16x3E>, (const void*)tdnn_first_kernel<kPrecFp16x2>}) {
+    const hipError_t e = set_dynamic_lds(f, kGemmMaxLds, &attr_done[k++]);
+    if (e != hipSuccess) return e;
   }
   const int ncg = (a.g.n_tiles * kBN + 511) / 512;
   int wgs = std::min(device_cu_count() / ncg, a.nrows / kFirstRows);
