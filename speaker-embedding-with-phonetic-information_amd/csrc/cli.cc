@@ -16,6 +16,12 @@ const char* Basename(const char* path) {
   return slash ? slash + 1 : path;
 }
 
+std::string Dashes(std::string name) {
+  for (char& c : name)
+    if (c == '_') c = '-';
+  return name;
+}
+
 }  // namespace
 
 std::string ProgramName(const char* argv0) { return Basename(argv0); }
@@ -71,14 +77,6 @@ uint64_t ToSeed(const std::string& name, const std::string& v) {
   return (uint64_t)s;
 }
 
-std::string Dashes(std::string name) {
-  for (char& c : name)
-    if (c == '_') c = '-';
-  return name;
-}
-
-bool CommonOption(const std::string& n) { return n == "verbose" || n == "print-args" || n == "config"; }
-
 int PickDevice(int requested) {
   if (requested >= 0) return requested;
   const char* e = getenv("XVEC_DEVICE");
@@ -109,13 +107,59 @@ std::vector<std::pair<std::string, std::string>> ReadConfigFile(const std::strin
   return out;
 }
 
+OptionResult SetOption(const CliTool& tool, const std::string& name, const std::string& v) {
+  const std::string n = tool.underscores ? Dashes(name) : name;
+  const bool lax = tool.bad_value_line;   // a malformed value is reported by the caller, not thrown
+  for (const CliOption& o : tool.options) {
+    if (o.name != n && !(o.kind == CliOption::kCustom && o.name.empty())) continue;
+    bool b = false;
+    int i = 0;
+    double d = 0.0;
+    switch (o.kind) {
+      case CliOption::kBool:
+      case CliOption::kRefusedIfTrue:
+        if (lax && !ParseBool(v, &b)) return OptionResult::kBadValue;
+        b = ToBool(n, v);
+        if (o.kind == CliOption::kRefusedIfTrue && b) throw KioError(o.message);
+        if (o.target) *(bool*)o.target = b;
+        break;
+      case CliOption::kInt:
+      case CliOption::kRefusedIfNonZero:
+        if (lax && !ParseInt(v, &i)) return OptionResult::kBadValue;
+        i = ToInt(n, v);
+        if (o.kind == CliOption::kRefusedIfNonZero && i != 0) throw KioError(o.message);
+        if (o.target) *(int*)o.target = i;
+        break;
+      case CliOption::kFloat:
+      case CliOption::kDouble:
+        if (lax && !ParseDouble(v, &d)) return OptionResult::kBadValue;
+        d = ToDouble(n, v);
+        if (o.target && o.kind == CliOption::kFloat) *(float*)o.target = (float)d;
+        if (o.target && o.kind == CliOption::kDouble) *(double*)o.target = d;
+        break;
+      case CliOption::kString: *(std::string*)o.target = v; break;
+      case CliOption::kSeed: *(uint64_t*)o.target = ToSeed(n, v); break;
+      case CliOption::kLaxInt: *(int*)o.target = atoi(v.c_str()); break;
+      case CliOption::kIgnored: break;
+      case CliOption::kRefused: throw KioError(o.message);
+      case CliOption::kCustom:
+        if (o.custom(n, v)) break;
+        if (o.name.empty()) continue;
+        return OptionResult::kBadValue;
+    }
+    return OptionResult::kOk;
+  }
+  const bool common = !tool.config_file && (n == "verbose" || n == "print-args" || n == "config");
+  return common ? OptionResult::kOk : OptionResult::kUnknown;
+}
+
 int CliMain(int argc, char** argv, const CliTool& tool) {
   g_prog = Basename(argv[0]);
   InstallMappedFileFaultHandler(g_prog.c_str());
   const char* prog = g_prog.c_str();
   // `typed`: how an error names the option
   auto apply = [&](const std::string& name, const std::string& value, const std::string& typed) {
-    const OptionResult r = tool.set(name, value);
+    const OptionResult r = SetOption(tool, name, value);
     if (r == OptionResult::kUnknown) fprintf(stderr, "ERROR (%s) Invalid option %s\n\n%s", prog, typed.c_str(), tool.usage);
     if (r == OptionResult::kBadValue) fprintf(stderr, "ERROR (%s) Invalid value for option %s\n", prog, typed.c_str());
     return r == OptionResult::kOk;
@@ -153,7 +197,8 @@ int CliMain(int argc, char** argv, const CliTool& tool) {
     }
     for (const auto& nv : options)
       if (!apply(nv.first, nv.second, "--" + nv.first + (nv.second.empty() ? "" : "=" + nv.second))) return 255;
-    const int rc = tool.run(pos);
+    const bool count_ok = (int)pos.size() >= tool.min_pos && (tool.max_pos < 0 || (int)pos.size() <= tool.max_pos);
+    const int rc = count_ok ? tool.run(pos) : kUsageError;
     if (rc != kUsageError) return rc;
     fputs(tool.usage, stderr);
     return 1;
@@ -161,6 +206,25 @@ int CliMain(int argc, char** argv, const CliTool& tool) {
     fprintf(stderr, "ERROR (%s) %s\n", prog, e.what());
     return 255;
   }
+}
+
+int ToolsMain(int argc, char** argv, const std::vector<CliTool>& tools, NameRule rule, const char* fallback) {
+  const std::string prog = ProgramName(argv[0]);
+  const CliTool* chosen = nullptr;
+  std::string names;
+  for (const CliTool& t : tools) {
+    const bool is = rule == NameRule::kContains ? prog.find(t.match ? t.match : t.name) != std::string::npos : prog == t.name;
+    if (is && !chosen) chosen = &t;
+    names += (names.empty() ? "" : ", ") + std::string(t.name);
+  }
+  if (!chosen && fallback && rule != NameRule::kExactOrRefuse)
+    for (const CliTool& t : tools)
+      if (strcmp(t.name, fallback) == 0) chosen = &t;
+  if (!chosen) {
+    fprintf(stderr, "%s: not one of %s\n", prog.c_str(), names.c_str());
+    return 255;
+  }
+  return CliMain(argc, argv, *chosen);
 }
 
 }  // namespace xv

@@ -324,96 +324,46 @@ int ApplyCmvn(const ApplyOptions& o, const std::vector<std::string>& pos) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  const std::string prog = xv::ProgramName(argv[0]);
-  const bool select = prog.find("select") != std::string::npos;
-  const bool stats = prog.find("compute-cmvn-stats") != std::string::npos;
-  const bool apply = !stats && !select && prog.find("sliding") == std::string::npos && prog.find("apply-cmvn") != std::string::npos;
-  auto dashes = [](std::string n) {
-    for (char& c : n)
-      if (c == '_') c = '-';
-    return n;
-  };
-  if (stats) {
-    StatsOptions so;
-    xv::CliTool t;
-    t.usage = "Compute cepstral mean and variance normalization statistics, per utterance or, with --spk2utt, per speaker;\n"
-              "with a file instead of a table as the output, one global matrix.\n"
-              "Usage: compute-cmvn-stats [options] <feats-rspecifier> (<stats-wspecifier>|<stats-wxfilename>)\n"
-              "Options: --spk2utt=<rspecifier> --binary (true) --device=<gpu>\n"
-              "Not built (refused): --weights.\n";
-    t.config_file = false;
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = dashes(name);
-      if (n == "verbose" || n == "print-args" || n == "config") return xv::OptionResult::kOk;
-      if (n == "spk2utt") so.spk2utt = val;
-      else if (n == "binary") so.binary = xv::ToBool(n, val);
-      else if (n == "device") so.device = xv::ToInt(n, val);
-      else if (n == "weights") throw xv::KioError("--weights is not built: no script of the recipes passes it");
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : ComputeCmvnStats(so, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (apply) {
-    ApplyOptions ao;
-    xv::CliTool t;
-    t.usage = "Apply cepstral mean and (optionally) variance normalization, per utterance or per speaker (--utt2spk), or with\n"
-              "one global statistics matrix.\n"
-              "Usage: apply-cmvn [options] (<cmvn-stats-rspecifier>|<cmvn-stats-rxfilename>) <feats-rspecifier> <feats-wspecifier>\n"
-              "Options: --utt2spk=<rspecifier> --norm-means (true) --norm-vars (false) --skip-dims=a:b:c --reverse (false) --device=<gpu>\n";
-    t.config_file = false;
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = dashes(name);
-      if (n == "verbose" || n == "print-args" || n == "config") return xv::OptionResult::kOk;
-      if (n == "utt2spk") ao.utt2spk = val;
-      else if (n == "norm-means") ao.norm_means = xv::ToBool(n, val);
-      else if (n == "norm-vars") ao.norm_vars = xv::ToBool(n, val);
-      else if (n == "reverse") ao.reverse = xv::ToBool(n, val);
-      else if (n == "device") ao.device = xv::ToInt(n, val);
-      else if (n == "skip-dims") {
-        if (!xv::ParseSkipDims(val, &ao.skip_dims)) throw xv::KioError("Bad --skip-dims option (should be colon-separated list of integers)");
-      } else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : ApplyCmvn(ao, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
+  using Pos = std::vector<std::string>;
   CmvnOptions o;
-  xv::CliTool tool;
-  tool.usage = select ? "Select a subset of frames of the input files, based on the output of\n"
-                        "compute-vad or a similar program (a vector of length num-frames,\n"
-                        "containing 1.0 for voiced, 0.0 for unvoiced).\n"
-                        "Usage: select-voiced-frames [options] <feats-rspecifier> <vad-rspecifier> <feats-wspecifier>\n"
-                      : "Apply sliding-window cepstral mean normalization per utterance.\n"
-                        "Usage: apply-cmvn-sliding [options] <feats-rspecifier> <feats-wspecifier>\n"
-                        "Options: --center (false) --cmn-window (600) --min-cmn-window (100) --norm-vars=false --device=<gpu>\n"
-                        "Not built (refused): --norm-vars=true.\n";
-  tool.config_file = false;
-  tool.set = [&](const std::string& name, const std::string& val) {
-    std::string n = name;
-    for (char& c : n)
-      if (c == '_') c = '-';
-    if (n == "verbose" || n == "print-args" || n == "config") return xv::OptionResult::kOk;
-    if (select) return xv::OptionResult::kUnknown;
-    if (n == "norm-vars") {
-      if (xv::ToBool(n, val)) throw xv::KioError("--norm-vars=true is not built: the device front-end subtracts the sliding mean only");
-    } else if (n == "center") {
-      o.center = xv::ToBool(n, val);
-    } else if (n == "cmn-window") {
-      o.cmn_window = xv::ToInt(n, val);
-    } else if (n == "min-cmn-window") {
-      o.min_cmn_window = xv::ToInt(n, val);
-    } else if (n == "device") {
-      o.device = atoi(val.c_str());
-    } else {
-      return xv::OptionResult::kUnknown;
-    }
-    return xv::OptionResult::kOk;
+  StatsOptions so;
+  ApplyOptions ao;
+  const std::vector<xv::CliTool> tools = {
+      {"select-voiced-frames",
+       "Select a subset of frames of the input files, based on the output of\n"
+       "compute-vad or a similar program (a vector of length num-frames,\n"
+       "containing 1.0 for voiced, 0.0 for unvoiced).\n"
+       "Usage: select-voiced-frames [options] <feats-rspecifier> <vad-rspecifier> <feats-wspecifier>\n",
+       {}, 3, 3, [&](const Pos& pos) { return SelectVoicedFrames(pos); }, "select"},
+      {"compute-cmvn-stats",
+       "Compute cepstral mean and variance normalization statistics, per utterance or, with --spk2utt, per speaker;\n"
+       "with a file instead of a table as the output, one global matrix.\n"
+       "Usage: compute-cmvn-stats [options] <feats-rspecifier> (<stats-wspecifier>|<stats-wxfilename>)\n"
+       "Options: --spk2utt=<rspecifier> --binary (true) --device=<gpu>\n"
+       "Not built (refused): --weights.\n",
+       {xv::String("spk2utt", &so.spk2utt), xv::Bool("binary", &so.binary), xv::Int("device", &so.device),
+        xv::Refused("weights", "--weights is not built: no script of the recipes passes it")},
+       2, 2, [&](const Pos& pos) { return ComputeCmvnStats(so, pos); }},
+      {"apply-cmvn-sliding",
+       "Apply sliding-window cepstral mean normalization per utterance.\n"
+       "Usage: apply-cmvn-sliding [options] <feats-rspecifier> <feats-wspecifier>\n"
+       "Options: --center (false) --cmn-window (600) --min-cmn-window (100) --norm-vars=false --device=<gpu>\n"
+       "Not built (refused): --norm-vars=true.\n",
+       {xv::RefusedIfTrue("norm-vars", "--norm-vars=true is not built: the device front-end subtracts the sliding mean only"),
+        xv::Bool("center", &o.center), xv::Int("cmn-window", &o.cmn_window), xv::Int("min-cmn-window", &o.min_cmn_window),
+        xv::LaxInt("device", &o.device)},
+       2, 2, [&](const Pos& pos) { return ApplyCmvnSliding(o, pos); }, "sliding"},
+      {"apply-cmvn",
+       "Apply cepstral mean and (optionally) variance normalization, per utterance or per speaker (--utt2spk), or with\n"
+       "one global statistics matrix.\n"
+       "Usage: apply-cmvn [options] (<cmvn-stats-rspecifier>|<cmvn-stats-rxfilename>) <feats-rspecifier> <feats-wspecifier>\n"
+       "Options: --utt2spk=<rspecifier> --norm-means (true) --norm-vars (false) --skip-dims=a:b:c --reverse (false) --device=<gpu>\n",
+       {xv::String("utt2spk", &ao.utt2spk), xv::Bool("norm-means", &ao.norm_means), xv::Bool("norm-vars", &ao.norm_vars),
+        xv::Bool("reverse", &ao.reverse), xv::Int("device", &ao.device), xv::Custom("skip-dims", [&](const std::string&, const std::string& val) {
+          if (!xv::ParseSkipDims(val, &ao.skip_dims)) throw xv::KioError("Bad --skip-dims option (should be colon-separated list of integers)");
+          return true;
+        })},
+       3, 3, [&](const Pos& pos) { return ApplyCmvn(ao, pos); }},
   };
-  tool.run = [&](const std::vector<std::string>& pos) {
-    if (pos.size() != (select ? 3u : 2u)) return xv::kUsageError;
-    return select ? SelectVoicedFrames(pos) : ApplyCmvnSliding(o, pos);
-  };
-  return xv::CliMain(argc, argv, tool);
+  return xv::ToolsMain(argc, argv, tools, xv::NameRule::kContains, "apply-cmvn-sliding");
 }

@@ -147,97 +147,54 @@ int InitFromFeats(const InitOptions& o, const std::vector<std::string>& pos) {
   return 0;
 }
 
-// the four options of the M-step that gmm-global-est and gmm-global-init-from-feats share
-bool SetEstOption(const std::string& n, const std::string& val, xv::DgmmEstOptions* est) {
-  if (n == "min-gaussian-weight") est->min_gaussian_weight = xv::ToDouble(n, val);
-  else if (n == "min-gaussian-occupancy") est->min_gaussian_occupancy = xv::ToDouble(n, val);
-  else if (n == "min-variance") est->min_variance = xv::ToDouble(n, val);
-  else if (n == "remove-low-count-gaussians") est->remove_low_count_gaussians = xv::ToBool(n, val);
-  else return false;
-  return true;
+// appends the four options of the M-step that gmm-global-est and gmm-global-init-from-feats share
+void AppendEstOptions(xv::DgmmEstOptions* est, std::vector<xv::CliOption>* to) {
+  to->insert(to->end(), {xv::Double("min-gaussian-weight", &est->min_gaussian_weight), xv::Double("min-gaussian-occupancy", &est->min_gaussian_occupancy),
+                         xv::Double("min-variance", &est->min_variance), xv::Bool("remove-low-count-gaussians", &est->remove_low_count_gaussians)});
 }
 
 }  // namespace
 
 int main(int argc, char** argv) {
-  const std::string prog = xv::ProgramName(argv[0]);
-  xv::CliTool t;
-  t.config_file = false;
-  if (prog == "gmm-global-sum-accs") {
-    bool binary = true;
-    t.usage = "Sum multiple accumulated stats files for diagonal-covariance GMM training.\n"
-              "Usage: gmm-global-sum-accs [options] <stats-out> <stats-in1> <stats-in2> ...\n"
-              "Options: --binary (true)\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") binary = xv::ToBool(n, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() < 2 ? xv::kUsageError : xv::GmmSumAccs(false, binary, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog == "gmm-global-est") {
-    EstOptions o;
-    t.usage = "Estimate a diagonal-covariance GMM from the accumulated stats.\n"
-              "Usage: gmm-global-est [options] <model-in> <stats-in> <model-out>\n"
-              "Options: --binary (true) --update-flags (mvw) --min-gaussian-weight (1e-5) --min-gaussian-occupancy (10)\n"
-              "         --min-variance (0.001) --remove-low-count-gaussians (true) --mix-up (0) --perturb-factor (0.01) --seed (0)\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") o.binary = xv::ToBool(n, val);
-      else if (n == "update-flags") o.update_flags = val;
-      else if (SetEstOption(n, val, &o.est)) return xv::OptionResult::kOk;
-      else if (n == "mix-up") o.mix_up = xv::ToInt(n, val);
-      else if (n == "perturb-factor") o.perturb_factor = xv::ToDouble(n, val);
-      else if (n == "seed") o.seed = xv::ToSeed(n, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : Est(o, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog == "gmm-global-init-from-feats") {
-    InitOptions o;
-    t.usage = "This program initializes a single diagonal GMM and does multiple iterations of training from features held in memory.\n"
-              "Usage: gmm-global-init-from-feats [options] <feature-rspecifier> <model-out>\n"
-              "Options: --binary (true) --num-gauss (100) --num-gauss-init (0) --num-iters (50) --num-frames (200000)\n"
-              "         --num-threads (4; accepted and ignored) --min-gaussian-weight (1e-5) --min-gaussian-occupancy (10)\n"
-              "         --min-variance (0.001) --remove-low-count-gaussians (true) --seed (0) --verbose --device=<gpu>\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") o.binary = xv::ToBool(n, val);
-      else if (n == "num-gauss") o.num_gauss = xv::ToInt(n, val);
-      else if (n == "num-gauss-init") o.num_gauss_init = xv::ToInt(n, val);
-      else if (n == "num-iters") o.num_iters = xv::ToInt(n, val);
-      else if (n == "num-frames") o.num_frames = xv::ToInt(n, val);
-      else if (n == "num-threads") (void)xv::ToInt(n, val);
-      else if (SetEstOption(n, val, &o.est)) return xv::OptionResult::kOk;
-      else if (n == "seed") o.seed = xv::ToSeed(n, val);
-      else if (n == "device") o.device = xv::ToInt(n, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : InitFromFeats(o, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog != "gmm-global-acc-stats") {
-    fprintf(stderr, "%s: not one of gmm-global-acc-stats, gmm-global-init-from-feats, gmm-global-sum-accs, gmm-global-est\n", prog.c_str());
-    return 255;
-  }
+  using Pos = std::vector<std::string>;
+  bool binary = true;
+  EstOptions e;
+  InitOptions io;
   xv::GmmAccOptions o;
-  t.usage = "Accumulate stats for training a diagonal-covariance GMM.\n"
-            "Usage: gmm-global-acc-stats [options] --gselect=<gselect-rspecifier> <model-in> <feature-rspecifier> <stats-out>\n"
-            "Options: --binary (true) --update-flags (mvw) --gselect (required) --verbose --device=<gpu>\n"
-            "Not built (refused): running without --gselect, --weights.\n";
-  t.set = [&](const std::string& name, const std::string& val) {
-    const std::string n = xv::Dashes(name);
-    if (n == "weights") throw xv::KioError("--weights is not built: sid/train_diag_ubm.sh passes no per-frame weights");
-    return xv::SetGmmAccOption(n, val, &o);
+  std::vector<xv::CliTool> tools = {
+      {"gmm-global-acc-stats",
+       "Accumulate stats for training a diagonal-covariance GMM.\n"
+       "Usage: gmm-global-acc-stats [options] --gselect=<gselect-rspecifier> <model-in> <feature-rspecifier> <stats-out>\n"
+       "Options: --binary (true) --update-flags (mvw) --gselect (required) --verbose --device=<gpu>\n"
+       "Not built (refused): running without --gselect, --weights.\n",
+       {xv::Refused("weights", "--weights is not built: sid/train_diag_ubm.sh passes no per-frame weights")},
+       3, 3, [&](const Pos& pos) { return AccStats(o, pos); }},
+      {"gmm-global-init-from-feats",
+       "This program initializes a single diagonal GMM and does multiple iterations of training from features held in memory.\n"
+       "Usage: gmm-global-init-from-feats [options] <feature-rspecifier> <model-out>\n"
+       "Options: --binary (true) --num-gauss (100) --num-gauss-init (0) --num-iters (50) --num-frames (200000)\n"
+       "         --num-threads (4; accepted and ignored) --min-gaussian-weight (1e-5) --min-gaussian-occupancy (10)\n"
+       "         --min-variance (0.001) --remove-low-count-gaussians (true) --seed (0) --verbose --device=<gpu>\n",
+       {xv::Bool("binary", &io.binary), xv::Int("num-gauss", &io.num_gauss), xv::Int("num-gauss-init", &io.num_gauss_init),
+        xv::Int("num-iters", &io.num_iters), xv::Int("num-frames", &io.num_frames), xv::Int("num-threads", nullptr),
+        xv::Seed("seed", &io.seed), xv::Int("device", &io.device)},
+       2, 2, [&](const Pos& pos) { return InitFromFeats(io, pos); }},
+      {"gmm-global-sum-accs",
+       "Sum multiple accumulated stats files for diagonal-covariance GMM training.\n"
+       "Usage: gmm-global-sum-accs [options] <stats-out> <stats-in1> <stats-in2> ...\n"
+       "Options: --binary (true)\n",
+       {xv::Bool("binary", &binary)}, 2, -1, [&](const Pos& pos) { return xv::GmmSumAccs(false, binary, pos); }},
+      {"gmm-global-est",
+       "Estimate a diagonal-covariance GMM from the accumulated stats.\n"
+       "Usage: gmm-global-est [options] <model-in> <stats-in> <model-out>\n"
+       "Options: --binary (true) --update-flags (mvw) --min-gaussian-weight (1e-5) --min-gaussian-occupancy (10)\n"
+       "         --min-variance (0.001) --remove-low-count-gaussians (true) --mix-up (0) --perturb-factor (0.01) --seed (0)\n",
+       {xv::Bool("binary", &e.binary), xv::String("update-flags", &e.update_flags), xv::Int("mix-up", &e.mix_up),
+        xv::Double("perturb-factor", &e.perturb_factor), xv::Seed("seed", &e.seed)},
+       3, 3, [&](const Pos& pos) { return Est(e, pos); }},
   };
-  t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : AccStats(o, pos); };
-  return xv::CliMain(argc, argv, t);
+  xv::AppendGmmAccOptions(&o, &tools[0].options);
+  AppendEstOptions(&io.est, &tools[1].options);
+  AppendEstOptions(&e.est, &tools[3].options);
+  return xv::ToolsMain(argc, argv, tools, xv::NameRule::kExactOrRefuse);
 }

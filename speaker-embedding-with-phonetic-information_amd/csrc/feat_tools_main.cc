@@ -234,28 +234,26 @@ int ComputeVad(const xv_vad_options& o, int device, const std::vector<std::strin
 }  // namespace
 
 int main(int argc, char** argv) {
-  const bool vad = xv::ProgramName(argv[0]).find("vad") != std::string::npos;
+  using Pos = std::vector<std::string>;
   xv::MfccToolOptions t;
   t.mfcc = xv::MfccDefaults();
   xv_vad_options vo = xv::VadDefaults();
   int vad_device = -1;
-  xv::CliTool tool;
-  tool.usage = Usage(vad);
-  tool.config_file = true;
-  tool.set = [&](const std::string& n, const std::string& v) {
-    bool known;
-    if (!vad) {
-      known = xv::SetMfccOption(n, v, &t);
-    } else {
-      known = xv::SetVadOption(n, v, &vo) || n == "device" || n == "verbose" || n == "print-args";
-      if (n == "device") vad_device = atoi(v.c_str());
-    }
-    return known ? xv::OptionResult::kOk : xv::OptionResult::kUnknown;
+  // the options themselves are the library's (feat.h), refusals included
+  std::vector<xv::CliTool> tools = {
+      {"compute-vad", Usage(true),
+       {xv::Custom("", [&](const std::string& n, const std::string& v) { return xv::SetVadOption(n, v, &vo); }), xv::LaxInt("device", &vad_device),
+        xv::Ignored("verbose"), xv::Ignored("print-args")},
+       2, 2, [&](const Pos& pos) { return ComputeVad(vo, vad_device, pos); }, "vad"},
+      {"compute-mfcc-feats", Usage(false), {xv::Custom("", [&](const std::string& n, const std::string& v) { return xv::SetMfccOption(n, v, &t); })},
+       0, -1, [&](const Pos& pos) {
+         (void)xv::BuildMfccTables(t.mfcc);   // option errors before the argument count and before any device is touched
+         return pos.size() != 2 ? xv::kUsageError : ComputeMfcc(t, pos);
+       }},
   };
-  tool.run = [&](const std::vector<std::string>& pos) {
-    if (!vad) (void)xv::BuildMfccTables(t.mfcc);   // option errors before the argument count and before any device is touched
-    if (pos.size() != 2) return xv::kUsageError;
-    return vad ? ComputeVad(vo, vad_device, pos) : ComputeMfcc(t, pos);
-  };
-  return xv::CliMain(argc, argv, tool);
+  for (xv::CliTool& tool : tools) {
+    tool.underscores = false;
+    tool.config_file = true;
+  }
+  return xv::ToolsMain(argc, argv, tools, xv::NameRule::kContains, "compute-mfcc-feats");
 }

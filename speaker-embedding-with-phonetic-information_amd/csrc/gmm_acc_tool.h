@@ -21,16 +21,10 @@ struct GmmAccOptions {
   int device = -1, verbose = 0;
 };
 
-// The options of the two *-global-acc-stats tools but --weights, whose refusal each words itself.
-inline OptionResult SetGmmAccOption(const std::string& n, const std::string& val, GmmAccOptions* o) {
-  if (n == "verbose") o->verbose = ToInt(n, val);
-  else if (CommonOption(n)) return OptionResult::kOk;
-  else if (n == "binary") o->binary = ToBool(n, val);
-  else if (n == "update-flags") o->update_flags = val;
-  else if (n == "gselect") o->gselect = val;
-  else if (n == "device") o->device = ToInt(n, val);
-  else return OptionResult::kUnknown;
-  return OptionResult::kOk;
+// Appends the options of the two *-global-acc-stats tools but --weights, whose refusal each words itself.
+inline void AppendGmmAccOptions(GmmAccOptions* o, std::vector<CliOption>* to) {
+  to->insert(to->end(), {Int("verbose", &o->verbose), Bool("binary", &o->binary), String("update-flags", &o->update_flags),
+                         String("gselect", &o->gselect), Int("device", &o->device)});
 }
 
 // pos: <model-in> <feature-rspecifier> <stats-out>, the model already read and on the device.  host: initialised with the kind,

@@ -261,83 +261,37 @@ int FgmmInfo(const std::vector<std::string>& pos) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  const std::string prog = xv::ProgramName(argv[0]);
-  xv::CliTool t;
-  t.config_file = false;
-  if (prog.find("compute-vad-from-frame-likes") != std::string::npos) {
-    std::string map_file, priors;
-    t.usage = "Compute per-frame class decisions from the frame log-likelihoods of several models.\n"
-              "Usage: compute-vad-from-frame-likes [options] <likes-rspecifier-1> ... <likes-rspecifier-n> <vad-wspecifier>\n"
-              "Options: --map=<file of 'index label' lines> --priors=<p0,p1,...>\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "map") map_file = val;
-      else if (n == "priors") priors = val;
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() < 2 ? xv::kUsageError : VadFromFrameLikes(map_file, priors, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog.find("merge-vads") != std::string::npos) {
-    std::string map_file;
-    t.usage = "Merge two tables of per-frame decisions: 1 where both are 1, or by a map of 'a b c' lines (the pair (a, b) gives c).\n"
-              "Usage: merge-vads [options] <vad-rspecifier-1> <vad-rspecifier-2> <vad-wspecifier>\n"
-              "Options: --map=<file>\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "map") map_file = val;
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : MergeVads(map_file, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog.find("fgmm-global-info") != std::string::npos) {
-    t.usage = "Write to standard output various properties of a full-covariance GMM.\nUsage: fgmm-global-info <model-in>\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      return xv::CommonOption(xv::Dashes(name)) ? xv::OptionResult::kOk : xv::OptionResult::kUnknown;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 1 ? xv::kUsageError : FgmmInfo(pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog.find("get-frame-likes") != std::string::npos) {
-    bool average = false;
-    std::string gselect;
-    int device = -1;
-    t.usage = "Print out per-frame log-likelihoods for each utterance, as an archive of vectors of floats.  If --average=true, prints\n"
-              "out the average per-frame log-likelihood for each utterance, as a single float.\n"
-              "Usage: fgmm-global-get-frame-likes [options] <model-in> <feature-rspecifier> <likes-out-wspecifier>\n"
-              "Options: --gselect=<rspecifier> (without it: models of at most 64 components) --average (false) --device=<gpu>\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "average") average = xv::ToBool(n, val);
-      else if (n == "gselect") gselect = val;
-      else if (n == "device") device = xv::ToInt(n, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : GetFrameLikes(average, gselect, device, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
+  using Pos = std::vector<std::string>;
+  std::string map_file, priors, gselect;
+  bool average = false;
   int n_opt = 50, device = -1;
-  std::string gselect;
-  t.usage = "Precompute Gaussian indices for pruning, by the full-covariance model, usually on top of a first selection by its\n"
-            "diagonal form (--gselect).  For each frame, gives a list of the n best Gaussian indices, sorted from best to worst.\n"
-            "Usage: fgmm-gselect [options] <model-in> <feature-rspecifier> <gselect-wspecifier>\n"
-            "Options: --n (50) --gselect=<rspecifier> (at most 64 per frame; without it: models of at most 64 components) --device=<gpu>\n";
-  t.set = [&](const std::string& name, const std::string& val) {
-    const std::string n = xv::Dashes(name);
-    if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-    if (n == "n") n_opt = xv::ToInt(n, val);
-    else if (n == "gselect") gselect = val;
-    else if (n == "device") device = xv::ToInt(n, val);
-    else return xv::OptionResult::kUnknown;
-    return xv::OptionResult::kOk;
+  const std::vector<xv::CliTool> tools = {
+      {"compute-vad-from-frame-likes",
+       "Compute per-frame class decisions from the frame log-likelihoods of several models.\n"
+       "Usage: compute-vad-from-frame-likes [options] <likes-rspecifier-1> ... <likes-rspecifier-n> <vad-wspecifier>\n"
+       "Options: --map=<file of 'index label' lines> --priors=<p0,p1,...>\n",
+       {xv::String("map", &map_file), xv::String("priors", &priors)}, 2, -1, [&](const Pos& pos) { return VadFromFrameLikes(map_file, priors, pos); }},
+      {"merge-vads",
+       "Merge two tables of per-frame decisions: 1 where both are 1, or by a map of 'a b c' lines (the pair (a, b) gives c).\n"
+       "Usage: merge-vads [options] <vad-rspecifier-1> <vad-rspecifier-2> <vad-wspecifier>\n"
+       "Options: --map=<file>\n",
+       {xv::String("map", &map_file)}, 3, 3, [&](const Pos& pos) { return MergeVads(map_file, pos); }},
+      {"fgmm-global-info", "Write to standard output various properties of a full-covariance GMM.\nUsage: fgmm-global-info <model-in>\n",
+       {}, 1, 1, [&](const Pos& pos) { return FgmmInfo(pos); }},
+      {"fgmm-global-get-frame-likes",
+       "Print out per-frame log-likelihoods for each utterance, as an archive of vectors of floats.  If --average=true, prints\n"
+       "out the average per-frame log-likelihood for each utterance, as a single float.\n"
+       "Usage: fgmm-global-get-frame-likes [options] <model-in> <feature-rspecifier> <likes-out-wspecifier>\n"
+       "Options: --gselect=<rspecifier> (without it: models of at most 64 components) --average (false) --device=<gpu>\n",
+       {xv::Bool("average", &average), xv::String("gselect", &gselect), xv::Int("device", &device)},
+       3, 3, [&](const Pos& pos) { return GetFrameLikes(average, gselect, device, pos); }, "get-frame-likes"},
+      {"fgmm-gselect",
+       "Precompute Gaussian indices for pruning, by the full-covariance model, usually on top of a first selection by its\n"
+       "diagonal form (--gselect).  For each frame, gives a list of the n best Gaussian indices, sorted from best to worst.\n"
+       "Usage: fgmm-gselect [options] <model-in> <feature-rspecifier> <gselect-wspecifier>\n"
+       "Options: --n (50) --gselect=<rspecifier> (at most 64 per frame; without it: models of at most 64 components) --device=<gpu>\n",
+       {xv::Int("n", &n_opt), xv::String("gselect", &gselect), xv::Int("device", &device)},
+       3, 3, [&](const Pos& pos) { return FgmmGselect(n_opt, gselect, device, pos); }},
   };
-  t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : FgmmGselect(n_opt, gselect, device, pos); };
-  return xv::CliMain(argc, argv, t);
+  return xv::ToolsMain(argc, argv, tools, xv::NameRule::kContains, "fgmm-gselect");
 }

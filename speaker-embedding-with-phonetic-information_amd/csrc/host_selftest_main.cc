@@ -27,6 +27,12 @@
 //   host_selftest gemm_plan
 //
 // sweeps the GEMM launch planner (gemm_plan.cc: plain host code, no device) over shapes, modes, CU counts and knobs.
+//
+//   host_selftest cli <path of a config file to write>
+//
+// drives a synthetic tool table (cli.h: one option of every kind, under each combination of the tool properties) through the
+// option lookup with well-formed, malformed, empty, underscore-spelled, unknown and refused input, then through CliMain with a
+// --config file and through the three name rules of ToolsMain.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -38,6 +44,7 @@
 #include <string>
 #include <vector>
 
+#include "cli.h"
 #include "feat_join.h"
 #include "gemm_plan.h"
 #include "kio.h"
@@ -541,10 +548,128 @@ int RunGemmPlan() {
   return accepted > 0 && accepted < plans ? 0 : 1;
 }
 
+// What SetOption makes of --name=value: 'k' ok, 'u' unknown, 'b' a bad value, 't' thrown.
+char Outcome(const xv::CliTool& tool, const std::string& name, const std::string& value, std::string* what = nullptr) {
+  try {
+    const xv::OptionResult r = xv::SetOption(tool, name, value);
+    return r == xv::OptionResult::kOk ? 'k' : r == xv::OptionResult::kUnknown ? 'u' : 'b';
+  } catch (const xv::KioError& e) {
+    if (what) *what = e.what();
+    return 't';
+  }
+}
+
+int RunCli(const std::string& config_path) {
+  int failures = 0;
+  auto expect = [&](bool ok, const char* what) {
+    if (!ok) fprintf(stderr, "host_selftest: cli: %s\n", what), ++failures;
+  };
+  for (int props = 0; props < 8; ++props) {
+    bool b = false;
+    int i = 0, lax = 0, any = 0;
+    float f = 0.f;
+    double d = 0.0;
+    std::string s, last;
+    uint64_t seed = 0;
+    xv::CliTool t = {"synthetic", "Usage: synthetic\n",
+                     {xv::Bool("a-bool", &b), xv::Int("an-int", &i), xv::Float("a-float", &f), xv::Double("a-double", &d), xv::String("a-string", &s),
+                      xv::Seed("a-seed", &seed), xv::LaxInt("lax-int", &lax), xv::Ignored("ignored"), xv::Int("dropped-int", nullptr),
+                      xv::Bool("dropped-bool", nullptr), xv::Double("dropped-double", nullptr), xv::Refused("refused", "--refused is refused"),
+                      xv::RefusedIfTrue("not-true", "--not-true=true is refused"), xv::RefusedIfNonZero("only-zero", "--only-zero is refused"),
+                      xv::Custom("even", [](const std::string&, const std::string& v) { return !v.empty() && (v.back() - '0') % 2 == 0; }),
+                      xv::Custom("", [&](const std::string& n, const std::string& v) { return n.compare(0, 4, "any-") == 0 ? (last = n + "=" + v, ++any, true) : false; })},
+                     0, -1, [](const std::vector<std::string>&) { return 0; }};
+    t.underscores = (props & 1) != 0;
+    t.bad_value_line = (props & 2) != 0;
+    t.config_file = (props & 4) != 0;
+    const char bad = t.bad_value_line ? 'b' : 't';
+    // well-formed
+    expect(Outcome(t, "a-bool", "") == 'k' && b, "an empty boolean is true");
+    expect(Outcome(t, "a-bool", "false") == 'k' && !b, "a-bool=false");
+    expect(Outcome(t, "an-int", "-12") == 'k' && i == -12, "an-int=-12");
+    expect(Outcome(t, "a-float", "0.5") == 'k' && f == 0.5f, "a-float=0.5");
+    expect(Outcome(t, "a-double", "1e-3") == 'k' && d == 1e-3, "a-double=1e-3");
+    expect(Outcome(t, "a-string", "x=y") == 'k' && s == "x=y", "a-string");
+    expect(Outcome(t, "a-seed", "18446744073709551615") == 'k' && seed == UINT64_MAX, "a-seed");
+    expect(Outcome(t, "lax-int", "7up") == 'k' && lax == 7 && Outcome(t, "lax-int", "abc") == 'k' && lax == 0, "lax-int takes anything");
+    expect(Outcome(t, "ignored", "whatever") == 'k', "ignored");
+    expect(Outcome(t, "dropped-int", "3") == 'k' && Outcome(t, "dropped-bool", "t") == 'k' && Outcome(t, "dropped-double", "2.5") == 'k', "dropped, well-formed");
+    expect(Outcome(t, "not-true", "false") == 'k' && Outcome(t, "only-zero", "0") == 'k' && Outcome(t, "even", "42") == 'k', "not refused");
+    expect(Outcome(t, "any-thing", "1") == 'k' && any == 1 && last == "any-thing=1", "the nameless escape hatch");
+    // malformed and empty
+    std::string what;
+    expect(Outcome(t, "a-bool", "maybe", &what) == bad && (bad == 'b' || what == "Invalid format for boolean argument --a-bool=maybe"), "a-bool=maybe");
+    expect(Outcome(t, "an-int", "1x", &what) == bad && (bad == 'b' || what == "Invalid integer option --an-int=1x"), "an-int=1x");
+    expect(Outcome(t, "an-int", "") == bad && Outcome(t, "a-float", "") == bad && Outcome(t, "a-double", "") == bad, "empty numbers");
+    expect(Outcome(t, "a-double", "1.0.0", &what) == bad && (bad == 'b' || what == "Invalid floating-point option --a-double=1.0.0"), "a-double=1.0.0");
+    expect(Outcome(t, "dropped-int", "x") == bad && Outcome(t, "dropped-bool", "x") == bad && Outcome(t, "dropped-double", "x") == bad, "dropped, malformed");
+    expect(Outcome(t, "a-seed", "-1") == 't' && Outcome(t, "a-seed", "") == 't' && Outcome(t, "a-seed", "1e3") == 't', "a-seed, malformed");
+    expect(Outcome(t, "not-true", "perhaps") == bad && Outcome(t, "only-zero", "") == bad, "refusals check the value first");
+    expect(Outcome(t, "even", "3") == 'b', "the escape hatch's false is a bad value");
+    expect(i == -12 && f == 0.5f && d == 1e-3 && !b, "a malformed value leaves the target alone");
+    // refused
+    expect(Outcome(t, "refused", "", &what) == 't' && what == "--refused is refused", "refused");
+    expect(Outcome(t, "not-true", "true", &what) == 't' && what == "--not-true=true is refused", "not-true=true");
+    expect(Outcome(t, "only-zero", "2", &what) == 't' && what == "--only-zero is refused", "only-zero=2");
+    // underscores: read as dashes, and named with dashes in an error, only where the tool says so
+    expect(Outcome(t, "an_int", "5") == (t.underscores ? 'k' : 'u') && i == (t.underscores ? 5 : -12), "an_int=5");
+    if (t.underscores && !t.bad_value_line) expect(Outcome(t, "an_int", "x", &what) == 't' && what == "Invalid integer option --an-int=x", "an_int=x");
+    expect(Outcome(t, "any_thing", "2") == (t.underscores ? 'k' : 'u'), "any_thing=2");
+    // unknown, and the common three: after the table, and not where --config is a file
+    expect(Outcome(t, "no-such", "1") == 'u' && Outcome(t, "a-boo", "1") == 'u' && Outcome(t, "", "") == 'u', "unknown");
+    for (const char* c : {"verbose", "print-args", "config"}) expect(Outcome(t, c, "x") == (t.config_file ? 'u' : 'k'), c);
+    expect(Outcome(t, "print_args", "x") == (t.config_file || !t.underscores ? 'u' : 'k'), "print_args");
+  }
+  // a tool's own --verbose comes before the common one
+  int verbose = 0;
+  xv::CliTool v = {"verbose", "Usage: verbose\n", {xv::Int("verbose", &verbose)}, 0, 0, [](const std::vector<std::string>&) { return 0; }};
+  expect(Outcome(v, "verbose", "x") == 't' && Outcome(v, "verbose", "2") == 'k' && verbose == 2, "the tool's own --verbose");
+
+  // CliMain: the file first, the command line second; the count; kUsageError; an exception; --help
+  {
+    std::ofstream f(config_path);
+    f << "# a comment\n\n--an-int=1 # first\n--a-string=from the file\n";
+  }
+  int i = 0, ran = 0;
+  std::string s;
+  xv::CliTool c = {"synthetic", "Usage: synthetic <a> [<b>]\n", {xv::Int("an-int", &i), xv::String("a-string", &s)}, 1, 2,
+                   [&](const std::vector<std::string>& pos) { return ++ran, pos[0] == "usage" ? xv::kUsageError : pos[0] == "throw" ? throw xv::KioError("thrown") : 7; }};
+  c.config_file = true;
+  const std::string config = "--config=" + config_path;
+  auto cli = [&](std::vector<const char*> args) {
+    args.insert(args.begin(), "/somewhere/synthetic");
+    return xv::CliMain((int)args.size(), const_cast<char**>(args.data()), c);
+  };
+  expect(cli({"--an-int=2", config.c_str(), "a"}) == 7 && i == 2 && s == "from the file" && ran == 1, "the command line wins over the file");
+  expect(cli({config.c_str()}) == 1 && cli({config.c_str(), "a", "b", "c"}) == 1 && ran == 1, "a wrong count is the usage, and the tool does not run");
+  expect(cli({"a", "--an-int=x"}) == 7 && ran == 2, "an option behind a positional is a positional");
+  expect(cli({"usage"}) == 1 && cli({"throw"}) == 255 && ran == 4, "kUsageError and an exception");
+  expect(cli({"--help", "--no-such"}) == 0 && cli({"--no-such", "a"}) == 255 && cli({"--an-int=x", "a"}) == 255 && ran == 4, "--help, unknown, malformed");
+  expect(cli({"--config=/nonexistent/dir/x.conf", "a"}) == 255 && ran == 4, "a config file that is not there");
+  unlink(config_path.c_str());
+
+  // ToolsMain: every tool returns its index
+  std::vector<xv::CliTool> tools;
+  const char* names[] = {"tool-one", "tool-one-more", "other"};
+  for (int k = 0; k < 3; ++k) tools.push_back({names[k], "Usage\n", {}, 0, 0, [k](const std::vector<std::string>&) { return 10 + k; }});
+  tools[2].match = "oth";
+  auto as = [&](const char* argv0, xv::NameRule rule, const char* fallback) {
+    char* args[] = {const_cast<char*>(argv0), nullptr};
+    return xv::ToolsMain(1, args, tools, rule, fallback);
+  };
+  expect(as("bin/tool-one-more", xv::NameRule::kContains, "other") == 10, "kContains takes the first of the table that fits");
+  expect(as("x-oth.bak", xv::NameRule::kContains, "tool-one") == 12 && as("zz", xv::NameRule::kContains, "tool-one-more") == 11, "match and fallback");
+  expect(as("bin/tool-one-more", xv::NameRule::kExact, "other") == 11 && as("x-tool-one", xv::NameRule::kExact, "other") == 12, "kExact");
+  expect(as("other", xv::NameRule::kExactOrRefuse, nullptr) == 12 && as("x-other", xv::NameRule::kExactOrRefuse, nullptr) == 255, "kExactOrRefuse");
+  printf("host_selftest: cli %s\n", failures ? "FAILED" : "ok");
+  return failures ? 1 : 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc == 2 && strcmp(argv[1], "gemm_plan") == 0) return RunGemmPlan();
+  if (argc == 3 && strcmp(argv[1], "cli") == 0) return RunCli(argv[2]);
   if (argc == 3 && strcmp(argv[1], "tables") == 0) return RunTables(argv[2]);
   if (argc == 3 && strcmp(argv[1], "walk") == 0) return RunWalk(argv[2]);
   if (argc != 4 && argc != 5) {

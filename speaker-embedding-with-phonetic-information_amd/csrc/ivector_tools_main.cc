@@ -234,51 +234,41 @@ int NormalizeLength(const Args& a) {
   return n_done != 0 ? 0 : 1;
 }
 
-const char* Usage(const std::string& prog) {
-  if (prog == "ivector-subtract-global-mean")
-    return "Copies a table of iVectors but subtracts the global mean as it does so.  The mean may be specified as the first\n"
-           "argument; if not, the sum of the input iVectors is used.\n"
-           "Usage: ivector-subtract-global-mean [--subtract-mean=true] <ivector-rspecifier> <ivector-wspecifier>\n"
-           " or:   ivector-subtract-global-mean <mean-rxfilename> <ivector-rspecifier> <ivector-wspecifier>\n";
-  if (prog == "transform-vec")
-    return "This program applies a linear or affine transform to individual vectors, e.g. iVectors.\n"
-           "Usage: transform-vec [options] <transform-rxfilename> <feats-rspecifier> <feats-wspecifier>\n";
-  if (prog == "ivector-normalize-length")
-    return "Normalize length of iVectors to equal sqrt(feature-dimension)\n"
-           "Usage: ivector-normalize-length [--normalize=true] [--scaleup=true] <ivector-rspecifier> <ivector-wspecifier>\n";
-  return "With 3 or 4 arguments, averages iVectors over all the utterances of each speaker using the spk2utt file.\n"
-         "With 2 arguments, averages all the iVectors of the input and writes the mean as a single vector.\n"
-         "Usage: ivector-mean <spk2utt-rspecifier> <ivector-rspecifier> <ivector-wspecifier> [<num-utt-wspecifier>]\n"
-         " or:   ivector-mean [--binary=true] <ivector-rspecifier> <mean-wxfilename>\n";
-}
-
-// All four tools know all of these; --config, --verbose and --print-args are accepted and have no effect.
-xv::OptionResult SetOption(const std::string& name, const std::string& val, Args* a) {
-  bool ok = true;
-  if (name == "binary") ok = xv::ParseBool(val, &a->binary);
-  else if (name == "normalize") ok = xv::ParseBool(val, &a->normalize);
-  else if (name == "scaleup") ok = xv::ParseBool(val, &a->scaleup);
-  else if (name == "subtract-mean") ok = xv::ParseBool(val, &a->subtract_mean);
-  else if (name == "device") a->device = atoi(val.c_str());
-  else if (name != "verbose" && name != "print-args" && name != "config") return xv::OptionResult::kUnknown;
-  return ok ? xv::OptionResult::kOk : xv::OptionResult::kBadValue;
-}
-
 }  // namespace
 
 int main(int argc, char** argv) {
-  const std::string prog = xv::ProgramName(argv[0]);
   Args a;
-  xv::CliTool tool;
-  tool.usage = Usage(prog);
-  tool.config_file = false;
-  tool.set = [&](const std::string& name, const std::string& val) { return SetOption(name, val, &a); };
-  tool.run = [&](const std::vector<std::string>& pos) {
-    a.pos = pos;
-    if (prog == "ivector-subtract-global-mean") return SubtractGlobalMean(a);
-    if (prog == "transform-vec") return TransformVec(a);
-    if (prog == "ivector-normalize-length") return NormalizeLength(a);
-    return IvectorMean(a);
+  auto tool = [&](const char* name, const char* usage, int (*run)(const Args&)) {
+    // All four tools know all of these, and count their arguments themselves.
+    xv::CliTool t = {name, usage,
+                     {xv::Bool("binary", &a.binary), xv::Bool("normalize", &a.normalize), xv::Bool("scaleup", &a.scaleup),
+                      xv::Bool("subtract-mean", &a.subtract_mean), xv::LaxInt("device", &a.device)},
+                     0, -1, [&a, run](const std::vector<std::string>& pos) { return a.pos = pos, run(a); }};
+    t.underscores = false;
+    t.bad_value_line = true;
+    return t;
   };
-  return xv::CliMain(argc, argv, tool);
+  const std::vector<xv::CliTool> tools = {
+      tool("ivector-mean",
+           "With 3 or 4 arguments, averages iVectors over all the utterances of each speaker using the spk2utt file.\n"
+           "With 2 arguments, averages all the iVectors of the input and writes the mean as a single vector.\n"
+           "Usage: ivector-mean <spk2utt-rspecifier> <ivector-rspecifier> <ivector-wspecifier> [<num-utt-wspecifier>]\n"
+           " or:   ivector-mean [--binary=true] <ivector-rspecifier> <mean-wxfilename>\n",
+           IvectorMean),
+      tool("ivector-subtract-global-mean",
+           "Copies a table of iVectors but subtracts the global mean as it does so.  The mean may be specified as the first\n"
+           "argument; if not, the sum of the input iVectors is used.\n"
+           "Usage: ivector-subtract-global-mean [--subtract-mean=true] <ivector-rspecifier> <ivector-wspecifier>\n"
+           " or:   ivector-subtract-global-mean <mean-rxfilename> <ivector-rspecifier> <ivector-wspecifier>\n",
+           SubtractGlobalMean),
+      tool("transform-vec",
+           "This program applies a linear or affine transform to individual vectors, e.g. iVectors.\n"
+           "Usage: transform-vec [options] <transform-rxfilename> <feats-rspecifier> <feats-wspecifier>\n",
+           TransformVec),
+      tool("ivector-normalize-length",
+           "Normalize length of iVectors to equal sqrt(feature-dimension)\n"
+           "Usage: ivector-normalize-length [--normalize=true] [--scaleup=true] <ivector-rspecifier> <ivector-wspecifier>\n",
+           NormalizeLength),
+  };
+  return xv::ToolsMain(argc, argv, tools, xv::NameRule::kExact, "ivector-mean");
 }

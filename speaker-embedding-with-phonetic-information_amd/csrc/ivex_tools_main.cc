@@ -128,41 +128,24 @@ int ExtractorCopy(bool binary, const std::vector<std::string>& pos) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  const std::string prog = xv::ProgramName(argv[0]);
-  xv::CliTool t;
-  t.config_file = false;
-  if (prog.find("ivector-extractor-copy") != std::string::npos) {
-    bool binary = true;
-    t.usage = "Copy the i-vector extractor to a different file (possibly changing binary/text format).\n"
-              "Usage: ivector-extractor-copy [options] <ivector-extractor-in> <ivector-extractor-out>\nOptions: --binary (true)\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") binary = xv::ToBool(n, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : ExtractorCopy(binary, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
+  using Pos = std::vector<std::string>;
+  bool binary = true;
   ExtractOptions o;
-  t.usage = "Extract iVectors for utterances, using a trained iVector extractor, and features and Gaussian-level posteriors.\n"
-            "Usage: ivector-extract [options] <model-in> <feature-rspecifier> <posterior-rspecifier> <ivector-wspecifier>\n"
-            "e.g.: fgmm-global-gselect-to-post 1.ubm '$feats' 'ark:gunzip -c gselect.1.gz|' ark:- | ivector-extract final.ie '$feats' ark,s,cs:- ark,t:ivectors.1.ark\n"
-            "Options: --compute-objf-change (true) --acoustic-weight (1.0) --max-count (0) --num-threads (accepted, ignored) --verbose --device=<gpu>\n"
-            "Limits: i-vector dimension <= 1024, feature dimension <= 96.  Not built (refused): --spk2utt, models with i-vector-dependent weights.\n";
-  t.set = [&](const std::string& name, const std::string& val) {
-    const std::string n = xv::Dashes(name);
-    if (n == "print-args" || n == "config" || n == "num-threads") return xv::OptionResult::kOk;
-    if (n == "verbose") o.verbose = xv::ToInt(n, val);
-    else if (n == "compute-objf-change") o.compute_objf_change = xv::ToBool(n, val);
-    else if (n == "acoustic-weight") o.acoustic_weight = xv::ToDouble(n, val);
-    else if (n == "max-count") o.max_count = xv::ToDouble(n, val);
-    else if (n == "device") o.device = xv::ToInt(n, val);
-    else if (n == "spk2utt") throw xv::KioError("--spk2utt is not built: no script of the recipes passes it (they average per speaker with ivector-mean)");
-    else return xv::OptionResult::kUnknown;
-    return xv::OptionResult::kOk;
+  const std::vector<xv::CliTool> tools = {
+      {"ivector-extractor-copy",
+       "Copy the i-vector extractor to a different file (possibly changing binary/text format).\n"
+       "Usage: ivector-extractor-copy [options] <ivector-extractor-in> <ivector-extractor-out>\nOptions: --binary (true)\n",
+       {xv::Bool("binary", &binary)}, 2, 2, [&](const Pos& pos) { return ExtractorCopy(binary, pos); }},
+      {"ivector-extract",
+       "Extract iVectors for utterances, using a trained iVector extractor, and features and Gaussian-level posteriors.\n"
+       "Usage: ivector-extract [options] <model-in> <feature-rspecifier> <posterior-rspecifier> <ivector-wspecifier>\n"
+       "e.g.: fgmm-global-gselect-to-post 1.ubm '$feats' 'ark:gunzip -c gselect.1.gz|' ark:- | ivector-extract final.ie '$feats' ark,s,cs:- ark,t:ivectors.1.ark\n"
+       "Options: --compute-objf-change (true) --acoustic-weight (1.0) --max-count (0) --num-threads (accepted, ignored) --verbose --device=<gpu>\n"
+       "Limits: i-vector dimension <= 1024, feature dimension <= 96.  Not built (refused): --spk2utt, models with i-vector-dependent weights.\n",
+       {xv::Ignored("num-threads"), xv::Int("verbose", &o.verbose), xv::Bool("compute-objf-change", &o.compute_objf_change),
+        xv::Double("acoustic-weight", &o.acoustic_weight), xv::Double("max-count", &o.max_count), xv::Int("device", &o.device),
+        xv::Refused("spk2utt", "--spk2utt is not built: no script of the recipes passes it (they average per speaker with ivector-mean)")},
+       4, 4, [&](const Pos& pos) { return IvectorExtract(o, pos); }},
   };
-  t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 4 ? xv::kUsageError : IvectorExtract(o, pos); };
-  return xv::CliMain(argc, argv, t);
+  return xv::ToolsMain(argc, argv, tools, xv::NameRule::kContains, "ivector-extract");
 }

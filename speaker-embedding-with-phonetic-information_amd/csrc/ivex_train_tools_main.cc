@@ -143,83 +143,47 @@ int Est(bool binary, const xv::IvexEstOptions& o, const std::vector<std::string>
 }  // namespace
 
 int main(int argc, char** argv) {
-  const std::string prog = xv::ProgramName(argv[0]);
-  xv::CliTool t;
-  t.config_file = false;
+  using Pos = std::vector<std::string>;
   bool binary = true;
-  if (prog == "ivector-extractor-init") {
-    int ivector_dim = 400;
-    uint64_t seed = 0;
-    t.usage = "Initialize an iVector extractor from a full-covariance UBM.\n"
-              "Usage: ivector-extractor-init [options] <fgmm-in> <ivector-extractor-out>\n"
-              "Options: --binary (true) --ivector-dim (400) --seed (0: the generator of the projections; not an upstream option)\n"
-              "Limits: i-vector dimension <= 1024, feature dimension <= 96.  Not built (refused): --use-weights=true.\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") binary = xv::ToBool(n, val);
-      else if (n == "ivector-dim") ivector_dim = xv::ToInt(n, val);
-      else if (n == "seed") seed = (uint64_t)(int64_t)xv::ToInt(n, val);
-      else if (n == "use-weights") {
-        if (xv::ToBool(n, val))
-          throw xv::KioError("--use-weights=true is not built: no recipe trains a model with i-vector-dependent weights, and ivector-extract refuses one");
-      } else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : Init(binary, ivector_dim, seed, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog == "ivector-extractor-sum-accs") {
-    t.usage = "Sum statistics for iVector extractor training; the output is the last argument.\n"
-              "Usage: ivector-extractor-sum-accs [options] <stats-in1> <stats-in2> ... <stats-inN> <stats-out>\n"
-              "Options: --binary (true) --parallel (accepted; the inputs are read one after another either way)\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") binary = xv::ToBool(n, val);
-      else if (n == "parallel") (void)xv::ToBool(n, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() < 2 ? xv::kUsageError : SumAccs(binary, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog == "ivector-extractor-est") {
-    xv::IvexEstOptions o;
-    t.usage = "Do model re-estimation of an iVector extractor.\n"
-              "Usage: ivector-extractor-est [options] <model-in> <stats-in> <model-out>\n"
-              "Options: --binary (true) --num-threads (1) --variance-floor-factor (0.1) --gaussian-min-count (100) --diagonalize (true)\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") binary = xv::ToBool(n, val);
-      else if (n == "num-threads") o.num_threads = xv::ToInt(n, val);
-      else if (n == "variance-floor-factor") o.variance_floor_factor = xv::ToDouble(n, val);
-      else if (n == "gaussian-min-count") o.gaussian_min_count = xv::ToDouble(n, val);
-      else if (n == "diagonalize") o.diagonalize = xv::ToBool(n, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : Est(binary, o, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
+  int ivector_dim = 400;
+  uint64_t seed = 0;
+  xv::IvexEstOptions e;
   AccOptions o;
-  t.usage = "Accumulate stats for iVector extractor training, from features and Gaussian-level posteriors.\n"
-            "Usage: ivector-extractor-acc-stats [options] <model-in> <feature-rspecifier> <posterior-rspecifier> <stats-out>\n"
-            "Options: --binary (true) --update-variances (true) --compute-auxf (true) --verbose --device=<gpu>; --num-threads,\n"
-            "--num-samples-for-weights and --cache-size are accepted and ignored.\n"
-            "Limits: i-vector dimension <= 1024, feature dimension <= 96.\n";
-  t.set = [&](const std::string& name, const std::string& val) {
-    const std::string n = xv::Dashes(name);
-    if (n == "print-args" || n == "config" || n == "num-threads" || n == "num-samples-for-weights" || n == "cache-size") return xv::OptionResult::kOk;
-    if (n == "verbose") o.verbose = xv::ToInt(n, val);
-    else if (n == "binary") o.binary = xv::ToBool(n, val);
-    else if (n == "update-variances") o.update_variances = xv::ToBool(n, val);
-    else if (n == "compute-auxf") o.compute_auxf = xv::ToBool(n, val);
-    else if (n == "device") o.device = xv::ToInt(n, val);
-    else return xv::OptionResult::kUnknown;
-    return xv::OptionResult::kOk;
+  const std::vector<xv::CliTool> tools = {
+      {"ivector-extractor-init",
+       "Initialize an iVector extractor from a full-covariance UBM.\n"
+       "Usage: ivector-extractor-init [options] <fgmm-in> <ivector-extractor-out>\n"
+       "Options: --binary (true) --ivector-dim (400) --seed (0: the generator of the projections; not an upstream option)\n"
+       "Limits: i-vector dimension <= 1024, feature dimension <= 96.  Not built (refused): --use-weights=true.\n",
+       {xv::Bool("binary", &binary), xv::Int("ivector-dim", &ivector_dim),
+        xv::Custom("seed", [&](const std::string& n, const std::string& val) {   // an int, negative ones included
+          seed = (uint64_t)(int64_t)xv::ToInt(n, val);
+          return true;
+        }),
+        xv::RefusedIfTrue("use-weights", "--use-weights=true is not built: no recipe trains a model with i-vector-dependent weights, and ivector-extract refuses one")},
+       2, 2, [&](const Pos& pos) { return Init(binary, ivector_dim, seed, pos); }},
+      {"ivector-extractor-sum-accs",
+       "Sum statistics for iVector extractor training; the output is the last argument.\n"
+       "Usage: ivector-extractor-sum-accs [options] <stats-in1> <stats-in2> ... <stats-inN> <stats-out>\n"
+       "Options: --binary (true) --parallel (accepted; the inputs are read one after another either way)\n",
+       {xv::Bool("binary", &binary), xv::Bool("parallel", nullptr)}, 2, -1, [&](const Pos& pos) { return SumAccs(binary, pos); }},
+      {"ivector-extractor-est",
+       "Do model re-estimation of an iVector extractor.\n"
+       "Usage: ivector-extractor-est [options] <model-in> <stats-in> <model-out>\n"
+       "Options: --binary (true) --num-threads (1) --variance-floor-factor (0.1) --gaussian-min-count (100) --diagonalize (true)\n",
+       {xv::Bool("binary", &binary), xv::Int("num-threads", &e.num_threads), xv::Double("variance-floor-factor", &e.variance_floor_factor),
+        xv::Double("gaussian-min-count", &e.gaussian_min_count), xv::Bool("diagonalize", &e.diagonalize)},
+       3, 3, [&](const Pos& pos) { return Est(binary, e, pos); }},
+      {"ivector-extractor-acc-stats",
+       "Accumulate stats for iVector extractor training, from features and Gaussian-level posteriors.\n"
+       "Usage: ivector-extractor-acc-stats [options] <model-in> <feature-rspecifier> <posterior-rspecifier> <stats-out>\n"
+       "Options: --binary (true) --update-variances (true) --compute-auxf (true) --verbose --device=<gpu>; --num-threads,\n"
+       "--num-samples-for-weights and --cache-size are accepted and ignored.\n"
+       "Limits: i-vector dimension <= 1024, feature dimension <= 96.\n",
+       {xv::Ignored("num-threads"), xv::Ignored("num-samples-for-weights"), xv::Ignored("cache-size"), xv::Int("verbose", &o.verbose),
+        xv::Bool("binary", &o.binary), xv::Bool("update-variances", &o.update_variances), xv::Bool("compute-auxf", &o.compute_auxf),
+        xv::Int("device", &o.device)},
+       4, 4, [&](const Pos& pos) { return AccStats(o, pos); }},
   };
-  t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 4 ? xv::kUsageError : AccStats(o, pos); };
-  return xv::CliMain(argc, argv, t);
+  return xv::ToolsMain(argc, argv, tools, xv::NameRule::kExact, "ivector-extractor-acc-stats");
 }

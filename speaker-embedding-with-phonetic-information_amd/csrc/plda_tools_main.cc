@@ -447,75 +447,61 @@ int ComputeEer(const Args& a) {
   return 0;
 }
 
-const char* Usage(const std::string& prog) {
-  if (prog == "ivector-compute-lda")
-    return "Compute an LDA matrix for iVector system.  Reads in iVectors per utterance, and an utt2spk file which it uses to\n"
-           "help work out the within-speaker and between-speaker covariance matrices.  Outputs an LDA projection to a\n"
-           "specified dimension.  By default it will normalize so that the projected within-class covariance is unit.\n"
-           "Usage: ivector-compute-lda [options] <ivector-rspecifier> <utt2spk-rspecifier> <lda-matrix-out>\n"
-           "Options: --dim=100 --total-covariance-factor=0.0 --covariance-floor=1e-06 --binary=true\n";
-  if (prog == "ivector-compute-plda")
-    return "Computes a Plda object (for Probabilistic Linear Discriminant Analysis) from a set of iVectors.\n"
-           "Usage: ivector-compute-plda [options] <spk2utt-rspecifier> <ivector-rspecifier> <plda-out>\n"
-           "Options: --num-em-iters=10 --binary=true\n";
-  if (prog == "ivector-copy-plda")
-    return "Copy a PLDA object, possibly applying smoothing to the within-class covariance\n"
-           "Usage: ivector-copy-plda [--smoothing=0.0] [--binary=true] <plda-in> <plda-out>\n";
-  if (prog == "ivector-adapt-plda")
-    return "Adapt a PLDA object using unsupervised adaptation-data iVectors from a different domain to the training data.\n"
-           "Usage: ivector-adapt-plda [options] <plda-in> <ivectors-rspecifier> <plda-out>\n"
-           "e.g.: ivector-adapt-plda plda ark:ivectors.ark plda.adapted\n"
-           "Options: --mean-diff-scale=1.0 --within-covar-scale=0.3 --between-covar-scale=0.7 --binary=true\n";
-  if (prog == "compute-eer")
-    return "Computes Equal Error Rate.  Input is a series of lines, each with two fields: the score and 'target' or\n"
-           "'nontarget'.  The EER is printed in percent on the standard output.\n"
-           "Usage: compute-eer <scores-in>\n"
-           "e.g.: compute-eer -\n";
-  return "Computes log-likelihood ratios for trials using PLDA model.  The trials file has lines 'key1 key2' (speaker,\n"
-         "utterance); the output has lines 'key1 key2 score'.\n"
-         "Usage: ivector-plda-scoring <plda> <train-ivector-rspecifier> <test-ivector-rspecifier>\n"
-         "                            <trials-rxfilename> <scores-wxfilename>\n"
-         "Options: --num-utts=<rspecifier> --normalize-length=true --simple-length-normalization=false\n";
-}
-
-// Every tool knows --binary and its own options only: a sibling's option is an unknown one.  --config, --verbose and
-// --print-args are accepted and have no effect.
-xv::OptionResult SetOption(const std::string& prog, const std::string& name, const std::string& val, Args* a) {
-  bool ok = true;
-  if (name == "binary") ok = xv::ParseBool(val, &a->binary);
-  else if (name == "dim" && prog == "ivector-compute-lda") ok = xv::ParseInt(val, &a->lda_dim);
-  else if (name == "total-covariance-factor" && prog == "ivector-compute-lda") ok = xv::ParseDouble(val, &a->total_covariance_factor);
-  else if (name == "covariance-floor" && prog == "ivector-compute-lda") ok = xv::ParseDouble(val, &a->covariance_floor);
-  else if (name == "num-em-iters" && prog == "ivector-compute-plda") ok = xv::ParseInt(val, &a->num_em_iters) && a->num_em_iters >= 0;
-  else if (name == "smoothing" && prog == "ivector-copy-plda") ok = xv::ParseDouble(val, &a->smoothing);
-  else if (name == "mean-diff-scale" && prog == "ivector-adapt-plda") ok = xv::ParseDouble(val, &a->mean_diff_scale);
-  else if (name == "within-covar-scale" && prog == "ivector-adapt-plda") ok = xv::ParseDouble(val, &a->within_covar_scale);
-  else if (name == "between-covar-scale" && prog == "ivector-adapt-plda") ok = xv::ParseDouble(val, &a->between_covar_scale);
-  else if (name == "normalize-length" && prog == "ivector-plda-scoring") ok = xv::ParseBool(val, &a->normalize_length);
-  else if (name == "simple-length-normalization" && prog == "ivector-plda-scoring") ok = xv::ParseBool(val, &a->simple_length_norm);
-  else if (name == "num-utts" && prog == "ivector-plda-scoring") a->num_utts = val;
-  else if (name == "device") a->device = atoi(val.c_str());
-  else if (name != "verbose" && name != "print-args" && name != "config") return xv::OptionResult::kUnknown;
-  return ok ? xv::OptionResult::kOk : xv::OptionResult::kBadValue;
-}
-
 }  // namespace
 
 int main(int argc, char** argv) {
-  const std::string prog = xv::ProgramName(argv[0]);
   Args a;
-  xv::CliTool tool;
-  tool.usage = Usage(prog);
-  tool.config_file = false;
-  tool.set = [&](const std::string& name, const std::string& val) { return SetOption(prog, name, val, &a); };
-  tool.run = [&](const std::vector<std::string>& pos) {
-    a.pos = pos;
-    if (prog == "ivector-compute-lda") return ComputeLda(a);
-    if (prog == "ivector-compute-plda") return ComputePlda(a);
-    if (prog == "ivector-copy-plda") return CopyPlda(a);
-    if (prog == "ivector-adapt-plda") return AdaptPlda(a);
-    if (prog == "compute-eer") return ComputeEer(a);
-    return PldaScoring(a);
+  // Every tool knows --binary, --device and its own options only: a sibling's option is an unknown one.
+  auto tool = [&](const char* name, const char* usage, std::vector<xv::CliOption> own, int (*run)(const Args&)) {
+    xv::CliTool t = {name, usage, {xv::Bool("binary", &a.binary)}, 0, -1, [&a, run](const std::vector<std::string>& pos) { return a.pos = pos, run(a); }};
+    t.options.insert(t.options.end(), own.begin(), own.end());
+    t.options.push_back(xv::LaxInt("device", &a.device));
+    t.underscores = false;
+    t.bad_value_line = true;
+    return t;
   };
-  return xv::CliMain(argc, argv, tool);
+  const std::vector<xv::CliTool> tools = {
+      tool("ivector-compute-lda",
+           "Compute an LDA matrix for iVector system.  Reads in iVectors per utterance, and an utt2spk file which it uses to\n"
+           "help work out the within-speaker and between-speaker covariance matrices.  Outputs an LDA projection to a\n"
+           "specified dimension.  By default it will normalize so that the projected within-class covariance is unit.\n"
+           "Usage: ivector-compute-lda [options] <ivector-rspecifier> <utt2spk-rspecifier> <lda-matrix-out>\n"
+           "Options: --dim=100 --total-covariance-factor=0.0 --covariance-floor=1e-06 --binary=true\n",
+           {xv::Int("dim", &a.lda_dim), xv::Double("total-covariance-factor", &a.total_covariance_factor), xv::Double("covariance-floor", &a.covariance_floor)},
+           ComputeLda),
+      tool("ivector-compute-plda",
+           "Computes a Plda object (for Probabilistic Linear Discriminant Analysis) from a set of iVectors.\n"
+           "Usage: ivector-compute-plda [options] <spk2utt-rspecifier> <ivector-rspecifier> <plda-out>\n"
+           "Options: --num-em-iters=10 --binary=true\n",
+           {xv::Custom("num-em-iters", [&](const std::string&, const std::string& v) { return xv::ParseInt(v, &a.num_em_iters) && a.num_em_iters >= 0; })},
+           ComputePlda),
+      tool("ivector-copy-plda",
+           "Copy a PLDA object, possibly applying smoothing to the within-class covariance\n"
+           "Usage: ivector-copy-plda [--smoothing=0.0] [--binary=true] <plda-in> <plda-out>\n",
+           {xv::Double("smoothing", &a.smoothing)}, CopyPlda),
+      tool("ivector-adapt-plda",
+           "Adapt a PLDA object using unsupervised adaptation-data iVectors from a different domain to the training data.\n"
+           "Usage: ivector-adapt-plda [options] <plda-in> <ivectors-rspecifier> <plda-out>\n"
+           "e.g.: ivector-adapt-plda plda ark:ivectors.ark plda.adapted\n"
+           "Options: --mean-diff-scale=1.0 --within-covar-scale=0.3 --between-covar-scale=0.7 --binary=true\n",
+           {xv::Double("mean-diff-scale", &a.mean_diff_scale), xv::Double("within-covar-scale", &a.within_covar_scale),
+            xv::Double("between-covar-scale", &a.between_covar_scale)},
+           AdaptPlda),
+      tool("compute-eer",
+           "Computes Equal Error Rate.  Input is a series of lines, each with two fields: the score and 'target' or\n"
+           "'nontarget'.  The EER is printed in percent on the standard output.\n"
+           "Usage: compute-eer <scores-in>\n"
+           "e.g.: compute-eer -\n",
+           {}, ComputeEer),
+      tool("ivector-plda-scoring",
+           "Computes log-likelihood ratios for trials using PLDA model.  The trials file has lines 'key1 key2' (speaker,\n"
+           "utterance); the output has lines 'key1 key2 score'.\n"
+           "Usage: ivector-plda-scoring <plda> <train-ivector-rspecifier> <test-ivector-rspecifier>\n"
+           "                            <trials-rxfilename> <scores-wxfilename>\n"
+           "Options: --num-utts=<rspecifier> --normalize-length=true --simple-length-normalization=false\n",
+           {xv::Bool("normalize-length", &a.normalize_length), xv::Bool("simple-length-normalization", &a.simple_length_norm),
+            xv::String("num-utts", &a.num_utts)},
+           PldaScoring),
+  };
+  return xv::ToolsMain(argc, argv, tools, xv::NameRule::kExact, "ivector-plda-scoring");
 }

@@ -301,86 +301,51 @@ int Nnet3Info(const std::string& rxfilename) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  const std::string prog = xv::ProgramName(argv[0]);
-  xv::CliTool t;
-  t.config_file = false;
-  if (prog == "nnet3-info") {
-    t.usage = "Print some text information about 'raw' nnet3 neural network, to standard output\n"
-              "Usage: nnet3-info <raw-nnet-rxfilename>\n"
-              "e.g.: nnet3-info \"nnet3-am-copy --raw=true final.mdl - |\"\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      return xv::CommonOption(xv::Dashes(name)) ? xv::OptionResult::kOk : xv::OptionResult::kUnknown;
-    };
-    t.run = [&](const std::vector<std::string>& pos) {
-      // sid/init_full_ubm_from_nnet3.sh:91 passes $nnet_raw unquoted: the words of "nnet3-am-copy --raw=true final.mdl - |" arrive
-      // one by one, and are put together again
-      std::string rx = pos.empty() ? "" : pos[0];
-      if (pos.size() > 1 && pos.back() == "|")
-        for (size_t i = 1; i < pos.size(); ++i) rx += " " + pos[i];
-      else if (pos.size() != 1) return (int)xv::kUsageError;
-      return Nnet3Info(rx);
-    };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog == "fgmm-global-init-from-accs") {
-    bool binary = true, remove_low_count = true;
-    t.usage = "Initialize a full-covariance GMM from the accumulated stats.\n"
-              "Usage: fgmm-global-init-from-accs [options] <stats-in> <number-of-components> <model-out>\n"
-              "Options: --binary (true) --remove-low-count-gaussians (true)\n"
-              "Accepted and without effect here, as in fgmm-global-est's option set: --update-flags --min-gaussian-weight\n"
-              "         --min-gaussian-occupancy --variance-floor --max-condition\n"
-              "Not built (refused): --mix-up other than 0.\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") binary = xv::ToBool(n, val);
-      else if (n == "remove-low-count-gaussians") remove_low_count = xv::ToBool(n, val);
-      else if (n == "update-flags") xv::ParseGmmFlags(val);
-      else if (n == "min-gaussian-weight" || n == "min-gaussian-occupancy" || n == "variance-floor" || n == "max-condition") xv::ToDouble(n, val);
-      else if (n == "mix-up") {
-        if (xv::ToInt(n, val) != 0) throw xv::KioError("--mix-up is not built: no script of the recipes increases the number of Gaussians here");
-      } else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : InitFromAccs(binary, remove_low_count, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog == "fgmm-global-acc-stats-post") {
-    AccOptions o;
-    t.usage = "Accumulate stats for training a full-covariance GMM, given posteriors\n"
-              "Usage: fgmm-global-acc-stats-post [options] <posterior-rspecifier> <number-of-components> <feature-rspecifier> <stats-out>\n"
-              "Options: --binary (true) --update-flags (mvw) --device=<gpu>\n"
-              "Not built (refused): --weights.\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") o.binary = xv::ToBool(n, val);
-      else if (n == "update-flags") o.update_flags = val;
-      else if (n == "device") o.device = xv::ToInt(n, val);
-      else if (n == "weights") throw xv::KioError("--weights is not built: no script of the recipes passes per-frame weights");
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 4 ? xv::kUsageError : AccStatsPost(o, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog != "logprob-to-post") {
-    fprintf(stderr, "%s: not one of logprob-to-post, fgmm-global-acc-stats-post, fgmm-global-init-from-accs, nnet3-info\n", prog.c_str());
-    return 255;
-  }
-  PostOptions o;
-  t.usage = "Convert a matrix of log-probabilities (e.g. from nnet-logprob) to posteriors\n"
-            "Usage: logprob-to-post [options] <logprob-matrix-rspecifier> <posteriors-wspecifier>\n"
-            "Options: --min-post (0.01) --random-prune (true) --device=<gpu>\n";
-  t.set = [&](const std::string& name, const std::string& val) {
-    const std::string n = xv::Dashes(name);
-    if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-    if (n == "min-post") o.min_post = xv::ToFloat(n, val);
-    else if (n == "random-prune") o.random_prune = xv::ToBool(n, val);
-    else if (n == "device") o.device = xv::ToInt(n, val);
-    else return xv::OptionResult::kUnknown;
-    return xv::OptionResult::kOk;
+  using Pos = std::vector<std::string>;
+  bool binary = true, remove_low_count = true;
+  PostOptions p;
+  AccOptions o;
+  const char* no_mix_up = "--mix-up is not built: no script of the recipes increases the number of Gaussians here";
+  const std::vector<xv::CliTool> tools = {
+      {"logprob-to-post",
+       "Convert a matrix of log-probabilities (e.g. from nnet-logprob) to posteriors\n"
+       "Usage: logprob-to-post [options] <logprob-matrix-rspecifier> <posteriors-wspecifier>\n"
+       "Options: --min-post (0.01) --random-prune (true) --device=<gpu>\n",
+       {xv::Float("min-post", &p.min_post), xv::Bool("random-prune", &p.random_prune), xv::Int("device", &p.device)},
+       2, 2, [&](const Pos& pos) { return LogprobToPost(p, pos); }},
+      {"fgmm-global-acc-stats-post",
+       "Accumulate stats for training a full-covariance GMM, given posteriors\n"
+       "Usage: fgmm-global-acc-stats-post [options] <posterior-rspecifier> <number-of-components> <feature-rspecifier> <stats-out>\n"
+       "Options: --binary (true) --update-flags (mvw) --device=<gpu>\n"
+       "Not built (refused): --weights.\n",
+       {xv::Bool("binary", &o.binary), xv::String("update-flags", &o.update_flags), xv::Int("device", &o.device),
+        xv::Refused("weights", "--weights is not built: no script of the recipes passes per-frame weights")},
+       4, 4, [&](const Pos& pos) { return AccStatsPost(o, pos); }},
+      {"fgmm-global-init-from-accs",
+       "Initialize a full-covariance GMM from the accumulated stats.\n"
+       "Usage: fgmm-global-init-from-accs [options] <stats-in> <number-of-components> <model-out>\n"
+       "Options: --binary (true) --remove-low-count-gaussians (true)\n"
+       "Accepted and without effect here, as in fgmm-global-est's option set: --update-flags --min-gaussian-weight\n"
+       "         --min-gaussian-occupancy --variance-floor --max-condition\n"
+       "Not built (refused): --mix-up other than 0.\n",
+       {xv::Bool("binary", &binary), xv::Bool("remove-low-count-gaussians", &remove_low_count),
+        xv::Custom("update-flags", [](const std::string&, const std::string& val) { return xv::ParseGmmFlags(val), true; }),
+        xv::Double("min-gaussian-weight", nullptr), xv::Double("min-gaussian-occupancy", nullptr), xv::Double("variance-floor", nullptr),
+        xv::Double("max-condition", nullptr), xv::RefusedIfNonZero("mix-up", no_mix_up)},
+       3, 3, [&](const Pos& pos) { return InitFromAccs(binary, remove_low_count, pos); }},
+      {"nnet3-info",
+       "Print some text information about 'raw' nnet3 neural network, to standard output\n"
+       "Usage: nnet3-info <raw-nnet-rxfilename>\n"
+       "e.g.: nnet3-info \"nnet3-am-copy --raw=true final.mdl - |\"\n",
+       {}, 0, -1, [&](const Pos& pos) {
+         // sid/init_full_ubm_from_nnet3.sh:91 passes $nnet_raw unquoted: the words of "nnet3-am-copy --raw=true final.mdl - |" arrive
+         // one by one, and are put together again
+         std::string rx = pos.empty() ? "" : pos[0];
+         if (pos.size() > 1 && pos.back() == "|")
+           for (size_t i = 1; i < pos.size(); ++i) rx += " " + pos[i];
+         else if (pos.size() != 1) return (int)xv::kUsageError;
+         return Nnet3Info(rx);
+       }},
   };
-  t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : LogprobToPost(o, pos); };
-  return xv::CliMain(argc, argv, t);
+  return xv::ToolsMain(argc, argv, tools, xv::NameRule::kExactOrRefuse);
 }

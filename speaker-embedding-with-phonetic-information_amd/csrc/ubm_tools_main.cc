@@ -238,114 +238,52 @@ int CopyGselect(int n, const std::vector<std::string>& pos) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  const std::string prog = xv::ProgramName(argv[0]);
-  xv::CliTool t;
-  t.config_file = false;
-  if (prog.find("add-deltas") != std::string::npos) {
-    DeltaOptions o;
-    t.usage = "Add deltas (typically to raw mfcc or plp features).\n"
-              "Usage: add-deltas [options] <feats-rspecifier> <feats-wspecifier>\n"
-              "Options: --delta-order (2) --delta-window (2) --truncate (0) --device=<gpu>\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "delta-order") o.order = xv::ToInt(n, val);
-      else if (n == "delta-window") o.window = xv::ToInt(n, val);
-      else if (n == "truncate") o.truncate = xv::ToInt(n, val);
-      else if (n == "device") o.device = xv::ToInt(n, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : AddDeltas(o, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog.find("fgmm-global-to-gmm") != std::string::npos) {
-    bool binary = true;
-    t.usage = "Convert single full-covariance GMM to single diagonal-covariance GMM.\n"
-              "Usage: fgmm-global-to-gmm [options] <full-gmm-in> <diag-gmm-out>\n"
-              "Options: --binary (true)\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") binary = xv::ToBool(n, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : FgmmToGmm(binary, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog.find("gmm-global-copy") != std::string::npos) {   // fgmm-global-copy as well
-    const bool full = prog.find("fgmm-global-copy") != std::string::npos;
-    bool binary = true;
-    t.usage = full ? "Copy a full-covariance GMM.\nUsage: fgmm-global-copy [options] <model-in> <model-out>\nOptions: --binary (true)\n"
-                   : "Copy a diagonal-covariance GMM.\nUsage: gmm-global-copy [options] <model-in> <model-out>\nOptions: --binary (true)\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") binary = xv::ToBool(n, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : GmmCopy(full, binary, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog.find("copy-gselect") != std::string::npos) {
-    int n = -1;
-    t.usage = "Copy Gaussian indices for pruning, possibly making the lists shorter.\n"
-              "Usage: copy-gselect [options] <gselect-rspecifier> <gselect-wspecifier>\nOptions: --n (-1)\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string nm = xv::Dashes(name);
-      if (xv::CommonOption(nm)) return xv::OptionResult::kOk;
-      if (nm == "n") n = xv::ToInt(nm, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : CopyGselect(n, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog.find("gselect-to-post") != std::string::npos) {
-    float min_post = 0.f;
-    int device = -1;
-    t.usage = "Given features and Gaussian-selection (gselect) information for a full-covariance GMM, output per-frame posteriors\n"
-              "for the selected indices.\n"
-              "Usage: fgmm-global-gselect-to-post [options] <full-gmm-in> <feats-rspecifier> <gselect-rspecifier> <post-wspecifier>\n"
-              "Options: --min-post (0.0) --device=<gpu>\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "min-post") min_post = xv::ToFloat(n, val);
-      else if (n == "device") device = xv::ToInt(n, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 4 ? xv::kUsageError : GselectToPost(min_post, device, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog.find("gmm-gselect") != std::string::npos) {
-    int n_opt = 50, device = -1;
-    t.usage = "Precompute Gaussian indices for pruning (e.g. in training UBMs, SGMMs, tied-mixture systems).\n"
-              "For each frame, gives a list of the n best Gaussian indices, sorted from best to worst.\n"
-              "Usage: gmm-gselect [options] <model-in> <feature-rspecifier> <gselect-wspecifier>\n"
-              "Options: --n (50; at most 64) --device=<gpu>\n"
-              "Not built (refused): --write-likes, --gselect.\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "n") n_opt = xv::ToInt(n, val);
-      else if (n == "device") device = xv::ToInt(n, val);
-      else if (n == "write-likes") throw xv::KioError("--write-likes is not built: no script of the recipes passes it");
-      else if (n == "gselect") throw xv::KioError("--gselect is not built: no script of the recipes passes it");
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : GmmGselect(n_opt, device, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  t.usage = "Scale all the posteriors of a table, by one scale or by a scale per utterance.\n"
-            "Usage: scale-post <post-rspecifier> (<scale-rspecifier>|<scale>) <post-wspecifier>\n";
-  t.set = [&](const std::string& name, const std::string& val) {
-    return xv::CommonOption(xv::Dashes(name)) ? xv::OptionResult::kOk : xv::OptionResult::kUnknown;
+  using Pos = std::vector<std::string>;
+  DeltaOptions d;
+  bool binary = true;
+  int copy_n = -1, select_n = 50, device = -1;
+  float min_post = 0.f;
+  const std::vector<xv::CliTool> tools = {
+      {"add-deltas",
+       "Add deltas (typically to raw mfcc or plp features).\n"
+       "Usage: add-deltas [options] <feats-rspecifier> <feats-wspecifier>\n"
+       "Options: --delta-order (2) --delta-window (2) --truncate (0) --device=<gpu>\n",
+       {xv::Int("delta-order", &d.order), xv::Int("delta-window", &d.window), xv::Int("truncate", &d.truncate), xv::Int("device", &d.device)},
+       2, 2, [&](const Pos& pos) { return AddDeltas(d, pos); }},
+      {"fgmm-global-to-gmm",
+       "Convert single full-covariance GMM to single diagonal-covariance GMM.\n"
+       "Usage: fgmm-global-to-gmm [options] <full-gmm-in> <diag-gmm-out>\n"
+       "Options: --binary (true)\n",
+       {xv::Bool("binary", &binary)}, 2, 2, [&](const Pos& pos) { return FgmmToGmm(binary, pos); }},
+      {"fgmm-global-copy", "Copy a full-covariance GMM.\nUsage: fgmm-global-copy [options] <model-in> <model-out>\nOptions: --binary (true)\n",
+       {xv::Bool("binary", &binary)}, 2, 2, [&](const Pos& pos) { return GmmCopy(true, binary, pos); }},
+      {"gmm-global-copy", "Copy a diagonal-covariance GMM.\nUsage: gmm-global-copy [options] <model-in> <model-out>\nOptions: --binary (true)\n",
+       {xv::Bool("binary", &binary)}, 2, 2, [&](const Pos& pos) { return GmmCopy(false, binary, pos); }},
+      {"copy-gselect",
+       "Copy Gaussian indices for pruning, possibly making the lists shorter.\n"
+       "Usage: copy-gselect [options] <gselect-rspecifier> <gselect-wspecifier>\nOptions: --n (-1)\n",
+       {xv::Int("n", &copy_n)}, 2, 2, [&](const Pos& pos) { return CopyGselect(copy_n, pos); }},
+      {"fgmm-global-gselect-to-post",
+       "Given features and Gaussian-selection (gselect) information for a full-covariance GMM, output per-frame posteriors\n"
+       "for the selected indices.\n"
+       "Usage: fgmm-global-gselect-to-post [options] <full-gmm-in> <feats-rspecifier> <gselect-rspecifier> <post-wspecifier>\n"
+       "Options: --min-post (0.0) --device=<gpu>\n",
+       {xv::Float("min-post", &min_post), xv::Int("device", &device)}, 4, 4, [&](const Pos& pos) { return GselectToPost(min_post, device, pos); },
+       "gselect-to-post"},
+      {"gmm-gselect",
+       "Precompute Gaussian indices for pruning (e.g. in training UBMs, SGMMs, tied-mixture systems).\n"
+       "For each frame, gives a list of the n best Gaussian indices, sorted from best to worst.\n"
+       "Usage: gmm-gselect [options] <model-in> <feature-rspecifier> <gselect-wspecifier>\n"
+       "Options: --n (50; at most 64) --device=<gpu>\n"
+       "Not built (refused): --write-likes, --gselect.\n",
+       {xv::Int("n", &select_n), xv::Int("device", &device), xv::Refused("write-likes", "--write-likes is not built: no script of the recipes passes it"),
+        xv::Refused("gselect", "--gselect is not built: no script of the recipes passes it")},
+       3, 3, [&](const Pos& pos) { return GmmGselect(select_n, device, pos); }},
+      {"scale-post",
+       "Scale all the posteriors of a table, by one scale or by a scale per utterance.\n"
+       "Usage: scale-post <post-rspecifier> (<scale-rspecifier>|<scale>) <post-wspecifier>\n",
+       {}, 3, 3, [&](const Pos& pos) { return ScalePost(pos); }},
   };
-  t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : ScalePost(pos); };
-  return xv::CliMain(argc, argv, t);
+  // in this order: a name that holds "fgmm-global-gselect-to-post" holds "gmm-gselect" too
+  return xv::ToolsMain(argc, argv, tools, xv::NameRule::kContains, "scale-post");
 }

@@ -134,95 +134,48 @@ int Est(const EstOptions& o, const std::vector<std::string>& pos) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  const std::string prog = xv::ProgramName(argv[0]);
-  xv::CliTool t;
-  t.config_file = false;
-  if (prog == "gmm-global-to-fgmm") {
-    bool binary = true;
-    t.usage = "Convert single diagonal-covariance GMM to single full-covariance GMM.\n"
-              "Usage: gmm-global-to-fgmm [options] <diag-gmm-in> <full-gmm-out>\n"
-              "Options: --binary (true)\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") binary = xv::ToBool(n, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 ? xv::kUsageError : GmmToFgmm(binary, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog == "subsample-feats") {
-    int n = 1, offset = 0;
-    t.usage = "Sub-samples features by taking every n'th frame.  With negative values of n, will repeat each frame n times\n"
-              "(e.g. --n=-2 will repeat each frame twice)\n"
-              "Usage: subsample-feats [options] <in-rspecifier> <out-wspecifier>\n"
-              "Options: --n (1) --offset (0; must be 0 with a negative --n)\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string nm = xv::Dashes(name);
-      if (xv::CommonOption(nm)) return xv::OptionResult::kOk;
-      if (nm == "n") n = xv::ToInt(nm, val);
-      else if (nm == "offset") offset = xv::ToInt(nm, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 2 || n == 0 ? xv::kUsageError : SubsampleFeats(n, offset, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog == "fgmm-global-sum-accs") {
-    bool binary = true;
-    t.usage = "Sum multiple accumulated stats files for full-covariance GMM training.\n"
-              "Usage: fgmm-global-sum-accs [options] <stats-out> <stats-in1> <stats-in2> ...\n"
-              "Options: --binary (true)\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") binary = xv::ToBool(n, val);
-      else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() < 2 ? xv::kUsageError : xv::GmmSumAccs(true, binary, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog == "fgmm-global-est") {
-    EstOptions o;
-    t.usage = "Estimate a full-covariance GMM from the accumulated stats.\n"
-              "Usage: fgmm-global-est [options] <model-in> <stats-in> <model-out>\n"
-              "Options: --binary (true) --update-flags (mvw) --min-gaussian-weight (1e-5) --min-gaussian-occupancy (100)\n"
-              "         --variance-floor (0.001) --max-condition (1e5) --remove-low-count-gaussians (true)\n"
-              "Not built (refused): --mix-up other than 0.\n";
-    t.set = [&](const std::string& name, const std::string& val) {
-      const std::string n = xv::Dashes(name);
-      if (xv::CommonOption(n)) return xv::OptionResult::kOk;
-      if (n == "binary") o.binary = xv::ToBool(n, val);
-      else if (n == "update-flags") o.update_flags = val;
-      else if (n == "min-gaussian-weight") o.est.min_gaussian_weight = xv::ToDouble(n, val);
-      else if (n == "min-gaussian-occupancy") o.est.min_gaussian_occupancy = xv::ToDouble(n, val);
-      else if (n == "variance-floor") o.est.variance_floor = xv::ToDouble(n, val);
-      else if (n == "max-condition") o.est.max_condition = xv::ToDouble(n, val);
-      else if (n == "remove-low-count-gaussians") o.est.remove_low_count_gaussians = xv::ToBool(n, val);
-      else if (n == "mix-up") {
-        if (xv::ToInt(n, val) != 0) throw xv::KioError("--mix-up is not built: no script of the recipes increases the number of Gaussians here");
-      } else return xv::OptionResult::kUnknown;
-      return xv::OptionResult::kOk;
-    };
-    t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : Est(o, pos); };
-    return xv::CliMain(argc, argv, t);
-  }
-  if (prog != "fgmm-global-acc-stats") {
-    fprintf(stderr, "%s: not one of fgmm-global-acc-stats, gmm-global-to-fgmm, subsample-feats, fgmm-global-sum-accs, fgmm-global-est\n", prog.c_str());
-    return 255;
-  }
+  using Pos = std::vector<std::string>;
+  bool binary = true;
+  int n = 1, offset = 0;
+  EstOptions e;
   xv::GmmAccOptions o;
-  t.usage = "Accumulate stats for training a full-covariance GMM.\n"
-            "Usage: fgmm-global-acc-stats [options] --gselect=<gselect-rspecifier> <model-in> <feature-rspecifier> <stats-out>\n"
-            "Options: --binary (true) --update-flags (mvw) --gselect (required) --verbose --device=<gpu>\n"
-            "Not built (refused): running without --gselect, --weights.\n";
-  t.set = [&](const std::string& name, const std::string& val) {
-    const std::string n = xv::Dashes(name);
-    if (n == "weights") throw xv::KioError("--weights is not built: no script of the recipes passes per-frame weights");
-    return xv::SetGmmAccOption(n, val, &o);
+  std::vector<xv::CliTool> tools = {
+      {"fgmm-global-acc-stats",
+       "Accumulate stats for training a full-covariance GMM.\n"
+       "Usage: fgmm-global-acc-stats [options] --gselect=<gselect-rspecifier> <model-in> <feature-rspecifier> <stats-out>\n"
+       "Options: --binary (true) --update-flags (mvw) --gselect (required) --verbose --device=<gpu>\n"
+       "Not built (refused): running without --gselect, --weights.\n",
+       {xv::Refused("weights", "--weights is not built: no script of the recipes passes per-frame weights")},
+       3, 3, [&](const Pos& pos) { return AccStats(o, pos); }},
+      {"gmm-global-to-fgmm",
+       "Convert single diagonal-covariance GMM to single full-covariance GMM.\n"
+       "Usage: gmm-global-to-fgmm [options] <diag-gmm-in> <full-gmm-out>\n"
+       "Options: --binary (true)\n",
+       {xv::Bool("binary", &binary)}, 2, 2, [&](const Pos& pos) { return GmmToFgmm(binary, pos); }},
+      {"subsample-feats",
+       "Sub-samples features by taking every n'th frame.  With negative values of n, will repeat each frame n times\n"
+       "(e.g. --n=-2 will repeat each frame twice)\n"
+       "Usage: subsample-feats [options] <in-rspecifier> <out-wspecifier>\n"
+       "Options: --n (1) --offset (0; must be 0 with a negative --n)\n",
+       {xv::Int("n", &n), xv::Int("offset", &offset)}, 2, 2,
+       [&](const Pos& pos) { return n == 0 ? xv::kUsageError : SubsampleFeats(n, offset, pos); }},
+      {"fgmm-global-sum-accs",
+       "Sum multiple accumulated stats files for full-covariance GMM training.\n"
+       "Usage: fgmm-global-sum-accs [options] <stats-out> <stats-in1> <stats-in2> ...\n"
+       "Options: --binary (true)\n",
+       {xv::Bool("binary", &binary)}, 2, -1, [&](const Pos& pos) { return xv::GmmSumAccs(true, binary, pos); }},
+      {"fgmm-global-est",
+       "Estimate a full-covariance GMM from the accumulated stats.\n"
+       "Usage: fgmm-global-est [options] <model-in> <stats-in> <model-out>\n"
+       "Options: --binary (true) --update-flags (mvw) --min-gaussian-weight (1e-5) --min-gaussian-occupancy (100)\n"
+       "         --variance-floor (0.001) --max-condition (1e5) --remove-low-count-gaussians (true)\n"
+       "Not built (refused): --mix-up other than 0.\n",
+       {xv::Bool("binary", &e.binary), xv::String("update-flags", &e.update_flags), xv::Double("min-gaussian-weight", &e.est.min_gaussian_weight),
+        xv::Double("min-gaussian-occupancy", &e.est.min_gaussian_occupancy), xv::Double("variance-floor", &e.est.variance_floor),
+        xv::Double("max-condition", &e.est.max_condition), xv::Bool("remove-low-count-gaussians", &e.est.remove_low_count_gaussians),
+        xv::RefusedIfNonZero("mix-up", "--mix-up is not built: no script of the recipes increases the number of Gaussians here")},
+       3, 3, [&](const Pos& pos) { return Est(e, pos); }},
   };
-  t.run = [&](const std::vector<std::string>& pos) { return pos.size() != 3 ? xv::kUsageError : AccStats(o, pos); };
-  return xv::CliMain(argc, argv, t);
+  xv::AppendGmmAccOptions(&o, &tools[0].options);
+  return xv::ToolsMain(argc, argv, tools, xv::NameRule::kExactOrRefuse);
 }

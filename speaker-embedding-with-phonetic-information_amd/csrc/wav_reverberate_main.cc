@@ -54,27 +54,6 @@ struct Tool {
   int verbose = 0, device = -1;
 };
 
-bool SetOption(const std::string& n, const std::string& v, Tool* t) {
-  if (n == "impulse-response") t->impulse_response = v;
-  else if (n == "additive-signals") t->additive_signals = v;
-  else if (n == "snrs") t->snrs = v;
-  else if (n == "start-times") t->start_times = v;
-  else if (n == "shift-output") t->o.shift_output = xv::ToBool(n, v);
-  else if (n == "normalize-output") t->o.normalize_output = xv::ToBool(n, v);
-  else if (n == "duration") t->o.duration = xv::ToFloat(n, v);
-  else if (n == "volume") t->o.volume = xv::ToFloat(n, v);
-  else if (n == "input-wave-channel") t->o.input_wave_channel = xv::ToInt(n, v);
-  else if (n == "rir-channel") t->o.rir_channel = xv::ToInt(n, v);
-  else if (n == "noise-channel") t->o.noise_channel = xv::ToInt(n, v);
-  else if (n == "multi-channel-output") {
-    if (xv::ToBool(n, v)) throw xv::KioError("--" + n + "=" + v + " is not supported: one output channel is written");
-  } else if (n == "verbose") t->verbose = xv::ToInt(n, v);
-  else if (n == "device") t->device = xv::ToInt(n, v);
-  else if (n == "print-args") (void)xv::ToBool(n, v);
-  else return false;
-  return true;
-}
-
 // One channel of a wave file, as float; the channel must exist (Kaldi asserts it).
 int ReadChannel(const std::string& rx, int channel, const char* what, std::vector<float>* out) {
   xv::Input in;
@@ -164,12 +143,22 @@ int Run(const Tool& t, const std::vector<std::string>& pos) {
 
 int main(int argc, char** argv) {
   Tool t;
-  xv::CliTool tool;
-  tool.usage = kUsage;
-  tool.config_file = true;
-  tool.set = [&](const std::string& n, const std::string& v) {
-    return SetOption(n, v, &t) ? xv::OptionResult::kOk : xv::OptionResult::kUnknown;
+  auto flag = [](const char* name, int32_t* to) {   // a boolean kept as the C interface's int32_t
+    return xv::Custom(name, [to](const std::string& n, const std::string& v) { return *to = xv::ToBool(n, v), true; });
   };
-  tool.run = [&](const std::vector<std::string>& pos) { return pos.size() == 2 ? Run(t, pos) : xv::kUsageError; };
-  return xv::CliMain(argc, argv, tool);
+  xv::CliTool tool = {
+      "wav-reverberate", kUsage,
+      {xv::String("impulse-response", &t.impulse_response), xv::String("additive-signals", &t.additive_signals), xv::String("snrs", &t.snrs),
+       xv::String("start-times", &t.start_times), flag("shift-output", &t.o.shift_output), flag("normalize-output", &t.o.normalize_output),
+       xv::Float("duration", &t.o.duration), xv::Float("volume", &t.o.volume), xv::Int("input-wave-channel", &t.o.input_wave_channel),
+       xv::Int("rir-channel", &t.o.rir_channel), xv::Int("noise-channel", &t.o.noise_channel),
+       xv::Custom("multi-channel-output", [](const std::string& n, const std::string& v) {   // the refusal quotes the value
+         if (xv::ToBool(n, v)) throw xv::KioError("--" + n + "=" + v + " is not supported: one output channel is written");
+         return true;
+       }),
+       xv::Int("verbose", &t.verbose), xv::Int("device", &t.device), xv::Bool("print-args", nullptr)},
+      2, 2, [&](const std::vector<std::string>& pos) { return Run(t, pos); }};
+  tool.underscores = false;
+  tool.config_file = true;
+  return xv::ToolsMain(argc, argv, {tool}, xv::NameRule::kExact, "wav-reverberate");   // under any name
 }

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/cli_transcripts/cases.json: exit status, stdout and stderr of the small drop-in tools (the four
-multi-tool executables behind csrc/cli.h) on command lines that end before any device call - --help, wrong argument counts,
+"""Generates tests/golden/cli_transcripts/*.json: exit status, stdout and stderr of the small drop-in tools (the twelve
+executables behind csrc/cli.h) on command lines that end before any device call - --help, wrong argument counts,
 unknown, misplaced and malformed options, --config files, refused options.  tests/test_cli_transcripts.py replays them.
+cases.json holds the four executables that came first (13 tools); each of the other eight has a file of its own, which adds
+an option in underscore spelling, one own option of every sibling tool, and the executable under a foreign name (a symlink;
+"argv0" in the case record).  foreign_argv0.json holds those foreign names for the executables of cases.json.
 
 The fixture is written by this project's own programs (build them first); every case runs without a device
 (HIP_VISIBLE_DEVICES=-1 ROCR_VISIBLE_DEVICES=) in a scratch directory that holds FILES, so no path of this machine is recorded.
@@ -67,6 +70,118 @@ TOOLS.update({"compute-mfcc-feats": (MFCC, 2), "compute-vad": (VAD, 2), "wav-rev
 READS_CONFIG = {"compute-mfcc-feats": "mfcc.conf", "compute-vad": "vad.conf", "wav-reverberate": "reverb.conf"}
 OVERRIDES = {"compute-mfcc-feats": "--num-ceps=13", "compute-vad": "--vad-energy-threshold=6", "wav-reverberate": "--volume=0.25"}
 
+# The other eight executables.  SEED: a non-negative decimal integer (ToSeed).
+SEED = "seed"
+COMMON = [("verbose", S, "1"), ("print-args", S, "false"), ("config", S, "x.conf")]
+DEV = ("device", I, "0")
+BIN_OPT = ("binary", B, "false")
+GMM_ACC = [BIN_OPT, ("update-flags", S, "mv"), ("gselect", S, "ark:g.ark"), ("verbose", I, "1"), DEV, ("print-args", S, "false"), ("config", S, "x.conf")]
+DGMM_EST = [("min-gaussian-weight", F, "1e-5"), ("min-gaussian-occupancy", F, "10"), ("min-variance", F, "0.001"), ("remove-low-count-gaussians", B, "true")]
+FGMM_EST = [("update-flags", S, "mvw"), ("min-gaussian-weight", F, "1e-5"), ("min-gaussian-occupancy", F, "100"), ("variance-floor", F, "0.001"),
+            ("max-condition", F, "1e5")]
+# file -> {tool: (its options, the positional arguments it takes (0: any number from two on), further command lines)};
+# the first tool of a file is the one the Makefile links, the others are its copies
+EXECUTABLES = {
+    "cmvn": {
+        "apply-cmvn-sliding": ([("norm-vars", B, "false"), ("center", B, "true"), ("cmn-window", I, "300"), ("min-cmn-window", I, "50"),
+                                ("device", S, "0")] + COMMON, 2, [["--norm-vars=true"]]),
+        "select-voiced-frames": (COMMON, 3, []),
+        "compute-cmvn-stats": ([("spk2utt", S, "ark:s2u"), BIN_OPT, DEV] + COMMON, 2, [["--weights=ark:w.ark"]]),
+        "apply-cmvn": ([("utt2spk", S, "ark:u2s"), ("norm-means", B, "true"), ("norm-vars", B, "false"), ("reverse", B, "false"),
+                        ("skip-dims", S, "0:2"), DEV] + COMMON, 3, [["--skip-dims=a:b"], ["--skip-dims="], ["--norm-vars=true"]]),
+    },
+    "ubm": {
+        "add-deltas": ([("delta-order", I, "2"), ("delta-window", I, "2"), ("truncate", I, "0"), DEV] + COMMON, 2, []),
+        "fgmm-global-to-gmm": ([BIN_OPT] + COMMON, 2, []),
+        "gmm-gselect": ([("n", I, "50"), DEV] + COMMON, 3, [["--write-likes=ark:l.ark"], ["--gselect=ark:g.ark"]]),
+        "fgmm-global-gselect-to-post": ([("min-post", F, "0.025"), DEV] + COMMON, 4, []),
+        "scale-post": (COMMON, 3, []),
+        "fgmm-global-copy": ([BIN_OPT] + COMMON, 2, []),
+        "gmm-global-copy": ([BIN_OPT] + COMMON, 2, []),
+        "copy-gselect": ([("n", I, "20")] + COMMON, 2, []),
+    },
+    "ivex": {
+        "ivector-extract": ([("compute-objf-change", B, "true"), ("acoustic-weight", F, "0.5"), ("max-count", F, "100"), ("num-threads", S, "4"),
+                             ("verbose", I, "1"), DEV, ("print-args", S, "false"), ("config", S, "x.conf")], 4, [["--spk2utt=ark:s2u"]]),
+        "ivector-extractor-copy": ([BIN_OPT] + COMMON, 2, []),
+    },
+    "ubm_train": {
+        "fgmm-global-acc-stats": (GMM_ACC, 3, [["--weights=ark:w.ark"], ["final.ubm", "scp:f.scp", "out.acc"]]),
+        "gmm-global-to-fgmm": ([BIN_OPT] + COMMON, 2, []),
+        "subsample-feats": ([("n", I, "2"), ("offset", I, "1")] + COMMON, 2, [["--n=0", "ark:a", "ark:b"]]),
+        "fgmm-global-sum-accs": ([BIN_OPT] + COMMON, 0, [["out.acc", "nosuch.acc"]]),
+        "fgmm-global-est": ([BIN_OPT] + FGMM_EST + [("remove-low-count-gaussians", B, "true"), ("mix-up", I, "0")] + COMMON, 3, [["--mix-up=1"]]),
+    },
+    "dubm_train": {
+        "gmm-global-acc-stats": (GMM_ACC, 3, [["--weights=ark:w.ark"], ["final.dubm", "scp:f.scp", "out.acc"]]),
+        "gmm-global-init-from-feats": ([BIN_OPT, ("num-gauss", I, "8"), ("num-gauss-init", I, "4"), ("num-iters", I, "2"), ("num-frames", I, "1000"),
+                                        ("num-threads", I, "4")] + DGMM_EST + [("seed", SEED, "3"), DEV] + COMMON, 2, []),
+        "gmm-global-sum-accs": ([BIN_OPT] + COMMON, 0, [["out.acc", "nosuch.acc"]]),
+        "gmm-global-est": ([BIN_OPT, ("update-flags", S, "mvw")] + DGMM_EST + [("mix-up", I, "16"), ("perturb-factor", F, "0.01"), ("seed", SEED, "3")]
+                           + COMMON, 3, []),
+    },
+    "ivex_train": {
+        "ivector-extractor-acc-stats": ([BIN_OPT, ("update-variances", B, "true"), ("compute-auxf", B, "true"), ("verbose", I, "1"), DEV,
+                                         ("num-threads", S, "4"), ("num-samples-for-weights", S, "3"), ("cache-size", S, "100"),
+                                         ("print-args", S, "false"), ("config", S, "x.conf")], 4, []),
+        "ivector-extractor-init": ([BIN_OPT, ("ivector-dim", I, "8"), ("seed", I, "3"), ("use-weights", B, "false")] + COMMON, 2,
+                                   [["--use-weights=true"], ["--seed=-1"]]),
+        "ivector-extractor-sum-accs": ([BIN_OPT, ("parallel", B, "true")] + COMMON, 0, []),
+        "ivector-extractor-est": ([BIN_OPT, ("num-threads", I, "1"), ("variance-floor-factor", F, "0.1"), ("gaussian-min-count", F, "100"),
+                                   ("diagonalize", B, "true")] + COMMON, 3, []),
+    },
+    "post": {
+        "logprob-to-post": ([("min-post", F, "0.01"), ("random-prune", B, "true"), DEV] + COMMON, 2, []),
+        "fgmm-global-acc-stats-post": ([BIN_OPT, ("update-flags", S, "mv"), DEV] + COMMON, 4, [["--weights=ark:w.ark"]]),
+        "fgmm-global-init-from-accs": ([BIN_OPT, ("remove-low-count-gaussians", B, "true")] + FGMM_EST + [("mix-up", I, "0")] + COMMON, 3,
+                                       [["--mix-up=1"], ["--update-flags=xyz"], ["--update-flags="]]),
+        "nnet3-info": (COMMON, 1, []),
+    },
+    "gmm_classify": {
+        "fgmm-gselect": ([("n", I, "20"), ("gselect", S, "ark:g.ark"), DEV] + COMMON, 3, []),
+        "fgmm-global-get-frame-likes": ([("average", B, "true"), ("gselect", S, "ark:g.ark"), DEV] + COMMON, 3, []),
+        "compute-vad-from-frame-likes": ([("map", S, "m.txt"), ("priors", S, "0.5,0.5")] + COMMON, 0, []),
+        "merge-vads": ([("map", S, "m.txt")] + COMMON, 3, []),
+        "fgmm-global-info": (COMMON, 1, []),
+    },
+}
+FIRST = list(TOOLS)   # cases.json
+for _tools in EXECUTABLES.values():
+    TOOLS.update({t: v[:2] for t, v in _tools.items()})
+# Names no tool has, names that merely contain a tool's, and for the ubm executable names that contain two
+FOREIGN = ["zz-other"]
+FOREIGN_CONTAINS = {"cmvn": ["x-select-voiced-frames.bak", "x-apply-cmvn.bak"], "ubm": ["x-gmm-gselect.bak", "fgmm-global-gselect-to-post.gmm-gselect",
+                    "x-fgmm-global-copy.bak", "x-gmm-global-copy.bak"], "ivex": ["x-ivector-extractor-copy.bak"], "ubm_train": ["x-subsample-feats.bak"],
+                    "dubm_train": ["x-gmm-global-est.bak"], "ivex_train": ["x-ivector-extractor-est.bak"], "post": ["x-nnet3-info.bak"],
+                    "gmm_classify": ["x-merge-vads.bak", "x-fgmm-global-info.bak"]}
+# ... and the executables of cases.json, by the tool the Makefile links
+FOREIGN_FIRST = {"ivector-mean": ["x-transform-vec.bak"], "ivector-compute-lda": ["x-compute-eer.bak"], "compute-mfcc-feats": ["x-compute-vad.bak"],
+                 "wav-reverberate": ["x-wav-reverberate.bak"]}
+_COMMON_NAMES = {"verbose", "print-args", "config", "device"}
+
+
+def own_options(opts):
+    return [o for o in opts if o[0] not in _COMMON_NAMES]
+
+
+def new_command_lines(tool, siblings):
+    """What the eight later files add to command_lines(tool)."""
+    opts, _, extra = siblings[tool]
+    for line in extra:
+        yield line
+    for n, kind, _ in opts:
+        if kind == SEED:
+            for bad in ("abc", "", "-1"):
+                yield ["--%s=%s" % (n, bad)]
+    # one option in underscore spelling: the first own one that has a dash, else --print_args
+    n, _, v = next((o for o in own_options(opts) if "-" in o[0]), ("print-args", S, "false"))
+    yield ["--%s=%s" % (n.replace("-", "_"), v)]
+    # one own option of each sibling that this tool does not have
+    for sibling, (sopts, _, _) in siblings.items():
+        other = [o for o in own_options(sopts) if o[0] not in {x[0] for x in opts}]
+        if sibling != tool and other:
+            yield ["--%s=%s" % (other[0][0], other[0][2])]
+
 
 def command_lines(tool):
     opts, npos = TOOLS[tool]
@@ -78,7 +193,7 @@ def command_lines(tool):
     yield ["--"]
     yield ["--%s=%s" % (n, v) for n, _, v in opts]
     for n, kind, _ in opts:
-        for bad in {B: ["maybe"], I: ["abc", ""], F: ["abc", ""], S: []}[kind]:
+        for bad in {B: ["maybe"], I: ["abc", ""], F: ["abc", ""], S: [], SEED: []}[kind]:
             yield ["--%s=%s" % (n, bad)]
     yield ["--device=abc"]
     if tool == "ivector-compute-plda":
@@ -113,41 +228,72 @@ def command_lines(tool):
         yield ["--multi-channel-output=true"]
 
 
-def run(tool, args, cwd):
+def run(tool, args, cwd, argv0=None):
     env = {k: v for k, v in os.environ.items() if k != "XVEC_DEVICE"}
     env.update(HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="")
-    r = subprocess.run([os.path.join(BIN, tool)] + args, cwd=cwd, env=env, stdin=subprocess.DEVNULL, stdout=subprocess.PIPE,
+    program = os.path.join(BIN, tool)
+    if argv0 is not None:   # the same executable under another name
+        program = os.path.join(cwd, argv0)
+        if os.path.lexists(program):
+            os.remove(program)
+        os.symlink(os.path.join(BIN, tool), program)
+    r = subprocess.run([program] + args, cwd=cwd, env=env, stdin=subprocess.DEVNULL, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=120)
     return r.returncode, r.stdout.decode(), r.stderr.decode()
 
 
+def record(tool, lines, cwd):
+    """The cases of one tool; its usage is spelt out by the --help case alone."""
+    usage = run(tool, ["--help"], cwd)[2]
+    assert "Usage" in usage, (tool, usage)
+    seen = set()
+    for args in lines:
+        if tuple(args) in seen:
+            continue
+        seen.add(tuple(args))
+        rc, out, err = run(tool, args, cwd)
+        assert rc in (0, 1, 255) and "HIP" not in err and "hip" not in err, (tool, args, rc, err)
+        if args != ["--help"]:
+            err = err.replace(usage, USAGE_MARK)
+        case = {"tool": tool, "args": args, "rc": rc, "err": err}
+        if out:
+            case["out"] = out
+        yield case
+
+
+def record_foreign(tool, names, cwd):
+    """--help and no arguments of `tool`'s executable under each of `names`, in full."""
+    for argv0 in names:
+        for args in (["--help"], []):
+            rc, out, err = run(tool, args, cwd, argv0)
+            assert rc in (0, 1, 255) and "HIP" not in err and "hip" not in err, (tool, argv0, args, rc, err)
+            case = {"tool": tool, "argv0": argv0, "args": args, "rc": rc, "err": err}
+            if out:
+                case["out"] = out
+            yield case
+
+
+def write(name, cases):
+    path = os.path.join(HERE, "cli_transcripts", name + ".json")
+    with open(path, "w") as f:
+        json.dump({"usage_mark": USAGE_MARK, "files": FILES, "cases": cases}, f, separators=(",", ":"))
+    print("%s: wrote %d cases, %d bytes" % (name, len(cases), os.path.getsize(path)))
+
+
 def main():
-    cases = []
+    os.makedirs(os.path.join(HERE, "cli_transcripts"), exist_ok=True)
     with tempfile.TemporaryDirectory() as d:
         for name, text in FILES.items():
             with open(os.path.join(d, name), "w") as f:
                 f.write(text)
-        for tool in TOOLS:
-            usage = run(tool, ["--help"], d)[2]
-            assert "Usage" in usage, (tool, usage)
-            seen = set()
-            for args in command_lines(tool):
-                if tuple(args) in seen:
-                    continue
-                seen.add(tuple(args))
-                rc, out, err = run(tool, args, d)
-                assert rc in (0, 1, 255) and "HIP" not in err and "hip" not in err, (tool, args, rc, err)
-                if args != ["--help"]:
-                    err = err.replace(usage, USAGE_MARK)
-                case = {"tool": tool, "args": args, "rc": rc, "err": err}
-                if out:
-                    case["out"] = out
-                cases.append(case)
-    os.makedirs(os.path.join(HERE, "cli_transcripts"), exist_ok=True)
-    path = os.path.join(HERE, "cli_transcripts", "cases.json")
-    with open(path, "w") as f:
-        json.dump({"usage_mark": USAGE_MARK, "files": FILES, "cases": cases}, f, separators=(",", ":"))
-    print("wrote %d cases, %d bytes" % (len(cases), os.path.getsize(path)))
+        write("cases", [c for tool in FIRST for c in record(tool, command_lines(tool), d)])
+        write("foreign_argv0", [c for tool, names in FOREIGN_FIRST.items() for c in record_foreign(tool, FOREIGN + names, d)])
+        for name, siblings in EXECUTABLES.items():
+            cases = []
+            for tool in siblings:
+                cases += record(tool, list(command_lines(tool)) + list(new_command_lines(tool, siblings)), d)
+            cases += record_foreign(next(iter(siblings)), FOREIGN + FOREIGN_CONTAINS[name], d)
+            write(name, cases)
 
 
 if __name__ == "__main__":

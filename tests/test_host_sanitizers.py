@@ -40,3 +40,13 @@ def test_parsers_survive_damaged_input_under_asan_ubsan(selftest, tmp_path, bina
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert "host_selftest: ok" in r.stdout
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
+def test_the_tool_tables_option_lookup_under_asan_ubsan(selftest, tmp_path):
+    """`host_selftest cli`: a synthetic tool table (csrc/cli.h) with one option of every kind, under every combination of the
+    tool properties, through the lookup, CliMain with a --config file and the three name rules of ToolsMain."""
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([selftest, "cli", str(tmp_path / "synthetic.conf")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                       env=env, timeout=300)
+    assert r.returncode == 0 and "host_selftest: cli ok" in r.stdout, (r.stdout + r.stderr)[-3000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
