@@ -9,9 +9,9 @@ namespace {
 static_assert(kRerankThreads == 64 * kRerankFramesPerBlock, "one wave per frame");
 static_assert(kUbmMaxSelect <= 64, "a slot per lane");
 
-// float -> unsigned key with the same order (and a place for every NaN): ubm_diag_gselect's
+// float -> unsigned key with the same order (and a place for every NaN): ubm_diag_gselect's, the two zeros one score
 __device__ inline uint32_t score_key(float x) {
-  const uint32_t b = __float_as_uint(x);
+  const uint32_t b = __float_as_uint(x + 0.f);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 

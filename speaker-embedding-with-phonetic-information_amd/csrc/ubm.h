@@ -10,12 +10,17 @@
 //   0 skipped; the output has (order + 1) * D columns; truncate = n > 0 keeps the first n input columns.
 // Diagonal model, per frame x and Gaussian g:
 //   loglike = gconst_g + sum_d (mu / sigma^2)_gd x_d - 1/2 sum_d (1 / sigma^2)_gd x_d^2
-//   Selection keeps the n largest per frame in descending order (equal scores: the lower index first).
+//   Selection keeps the n largest per frame in descending order (equal scores: the lower index first).  -0 and +0 are equal
+//   scores: the order is that of score + 0, here and in the second-stage selection of gmm_classify.h.  -infinity is below every
+//   finite score; a frame that holds a NaN scores NaN everywhere and selects n distinct Gaussians, which ones is not stated.
 // Full model, on the selected Gaussians only:
 //   loglike = gconst_g + (Sigma^-1 mu)_g . x - 1/2 x' Sigma_g^-1 x
 //   posteriors = softmax over the selected set (its log-sum is what the log line averages).  min_post != 0: remember the arg-max,
 //   zero every posterior < min_post, and if nothing is left give the arg-max 1, else scale by 1 / (what is left).  The entries
-//   that are not 0 are emitted as (index, posterior) in selection order.
+//   that are not 0 are emitted as (index, posterior) in selection order.  A selected Gaussian that scores -infinity has posterior 0.
+//   A frame whose largest selected log-likelihood is not finite has no posterior.  It has zero entries, every slot posterior is 0,
+//   and the log-sum is that largest value as computed (-infinity or NaN).  That is a frame whose selected gconsts are all
+//   -infinity, or one that holds a NaN; the accumulators of ubm_train.h and dubm_train.h, which skip weights of 0, leave it out.
 // Gconsts are recomputed (fp64, stored as float) after every read of a model, whether the file has <GCONSTS> or not:
 //   diagonal:  log w_g - 1/2 (D log 2 pi - sum_d log (1/sigma^2)_gd + sum_d (mu/sigma^2)_gd^2 / (1/sigma^2)_gd)
 //   full:      log w_g - 1/2 (D log 2 pi + log det Sigma_g + (Sigma^-1 mu)' Sigma (Sigma^-1 mu))

@@ -10,14 +10,16 @@
 //                       tiles of kUbmGaussTile: thread (Gaussian of the tile, half of the frames) adds gconst + sum_d (m x + v x^2)
 //                       in ascending d.  The tile's scores go to LDS; per frame one wave keeps what beats the frame's current n-th
 //                       best and ranks the survivors together with the running list (order: score descending, then index
-//                       ascending; scores compared as order-preserving integer keys, so the order is total even with NaNs).  The
-//                       frames x Gaussians score matrix never leaves the workgroup.  n <= kUbmMaxSelect.
+//                       ascending; scores compared as order-preserving integer keys of score + 0, so the two zeros are equal and
+//                       the order is total even with NaNs).  The frames x Gaussians score matrix never leaves the workgroup.
+//                       n <= kUbmMaxSelect.
 //   ubm_full_loglike    reads the rows * n (frame, slot) pairs bucketed by Gaussian, ascending pair inside a bucket (bucket_sort.h).
 //                       Workgroup (g, s) expands Gaussian g's packed inverse covariance into LDS and takes tiles s, s + S, ... of
 //                       kUbmFullFrameTile frames of g's bucket: thread (frame, column group) forms y_j = sum_i x_i A_ij in ascending
 //                       i for its columns, then its share of b . x - x . y / 2; the 8 shares are added in ascending group order
 //                       to gconst and scattered back to (frame, slot).
-//   ubm_post            one thread per frame: softmax over the n log-likelihoods, the min-post rule, compaction.
+//   ubm_post            one thread per frame: softmax over the n log-likelihoods, the min-post rule, compaction.  A frame whose
+//                       largest log-likelihood is not finite gets count 0, slot posteriors of 0 and that value as its log-sum.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

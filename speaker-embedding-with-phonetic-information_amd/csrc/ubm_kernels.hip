@@ -40,9 +40,10 @@ __global__ __launch_bounds__(kUbmThreads) void add_deltas_kernel(const DeltaArgs
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// float -> unsigned key with the same order (and a place for every NaN), and back
+// float -> unsigned key with the same order (and a place for every NaN), and back.  The key is that of x + 0: -0 + 0 is +0, so
+// the two zeros are one score and their Gaussians go by index (ubm.h).
 __device__ inline uint32_t score_key(float x) {
-  const uint32_t b = __float_as_uint(x);
+  const uint32_t b = __float_as_uint(x + 0.f);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 __device__ inline float key_score(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
@@ -117,7 +118,8 @@ __global__ __launch_bounds__(kUbmThreads) void ubm_diag_gselect_kernel(const Ubm
       for (int h = 0; h < kUbmGaussTile / 64; ++h) {
         const int gs = h * 64 + lane, gg = g0 + gs;
         const uint32_t key = score_key(sc[f][gs]);
-        // a tile's indices are above every index already in the list: at equal score the newcomer loses
+        // a tile's indices are above every index already in the list: at equal score the newcomer loses.  The compare only spares
+        // the ranking below a candidate; admitted, an equal score would rank behind the list's by its index and fall out at n.
         const bool ok = gg < a.num_gauss && (open || key > thr);
         const unsigned long long mask = __ballot(ok);
         if (ok) {
@@ -234,12 +236,22 @@ __global__ __launch_bounds__(kUbmThreads) void ubm_post_kernel(const UbmFullArgs
       mx = ll[i];
       arg = i;
     }
+  float* post = a.out_post + t * n;
+  int32_t* idx = a.out_idx + t * n;
+  if (!isfinite(mx)) {   // no posterior (ubm.h): every score is -inf, or the first one is a NaN, as all are for a frame that holds one
+    if (a.out_logsum) a.out_logsum[t] = mx;
+    a.out_count[t] = 0;
+    for (int i = 0; i < n; ++i) {
+      idx[i] = -1;
+      post[i] = 0.f;
+      if (a.out_slot_post) a.out_slot_post[t * n + i] = 0.f;
+    }
+    return;
+  }
   float sum = 0.f;
   for (int i = 0; i < n; ++i) sum = sum + expf(ll[i] - mx);
   if (a.out_logsum) a.out_logsum[t] = mx + logf(sum);
   const float inv = 1.f / sum;
-  float* post = a.out_post + t * n;
-  int32_t* idx = a.out_idx + t * n;
   int count = 0;
   if (a.min_post != 0.f) {
     // what survives min-post is renormalised; nothing survives: the arg-max takes everything

@@ -15,8 +15,9 @@ F = np.float32
 
 # ------------------------------------------------------------------------------------------------------------------- ranking
 def score_key(scores):
-    """float32 -> uint32 with the same order, -inf below every finite score and a place for every NaN (the device's key)"""
-    b = np.ascontiguousarray(scores, F).view(np.uint32)
+    """float32 -> uint32 with the same order, -inf below every finite score and a place for every NaN (the device's key).  The key
+    is that of score + 0: the two zeros are one score"""
+    b = (np.ascontiguousarray(scores, F) + F(0)).view(np.uint32)
     return np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
 
 

@@ -52,9 +52,13 @@ def test_minus_infinity_ranks_last_and_n_out_above_n_in_keeps_all():
     assert idx.shape == (1, 4)
     assert idx.tolist() == [[2, 1, 0, 3]]
     assert out[0, :2].tolist() == [0.0, np.float32(-1e30)] and np.all(np.isneginf(out[0, 2:]))
-    # negative zero is below positive zero in the key order, as on the device; NaNs have a place (a positive one above +inf)
+    # the two zeros are one score, as on the device (the key of score + 0); NaNs have a place (a positive one above +inf)
     key = C.score_key(np.array([-INF, -1.0, -0.0, 0.0, 1.0, INF, np.nan], np.float32))
-    assert np.all(np.diff(key.astype(np.int64)) > 0)
+    assert np.diff(key.astype(np.int64)).tolist()[2] == 0 and np.all(np.delete(np.diff(key.astype(np.int64)), 2) > 0)
+    # so equal zeros of either sign go by Gaussian, then slot, like any other tie
+    idx, out = C.rerank(np.array([[0.0, -0.0, 0.0, -1.0]], np.float32), np.array([[5, 2, 1, 0]], np.int32), 4)
+    assert idx.tolist() == [[1, 2, 5, 0]] and out.tolist() == [[0.0, 0.0, 0.0, -1.0]]
+    assert np.signbit(out[0]).tolist() == [False, True, False, True]   # the scores themselves come back as they were
 
 
 def test_logsumexp_and_average():

@@ -71,6 +71,36 @@ def test_posteriors_sum_to_one_and_follow_the_min_post_rule():
     assert p.tolist() == [[1.0, 0.0, 0.0, 0.0]]
 
 
+def test_a_frame_whose_largest_score_is_not_finite_has_no_posterior():
+    """csrc/ubm.h: such a frame has zero entries, every slot posterior is 0 and the log-sum is the largest value as computed;
+    every other row, one that mixes -inf with finite scores included, is what it is without the bad rows."""
+    inf = np.inf
+    good = np.log(np.array([[0.5, 0.3, 0.15, 0.05], [0.4, 0.3, 0.2, 0.1], [0.97, 0.01, 0.01, 0.01]])) + 7.0
+    mixed = np.array([[-inf, 2.0, -inf, 1.0]])
+    ll = np.concatenate([good[:1], np.full((1, 4), -inf), good[1:2], [[1.0, np.nan, 2.0, 3.0]], mixed, np.full((1, 4), np.nan), good[2:]])
+    bad = [1, 3, 5]
+    rest = np.delete(ll, bad, axis=0)
+    for min_post in (0.0, 0.12, 0.6):
+        with np.errstate(all="raise"):   # the rule is stated, not an accident of inf - inf
+            p, logsum = R.posteriors(ll, min_post)
+            p_rest, logsum_rest = R.posteriors(rest, min_post)
+        assert p.shape == ll.shape and not np.isnan(p).any()
+        assert not p[bad].any()
+        assert np.isneginf(logsum[1]) and np.isnan(logsum[3]) and np.isnan(logsum[5])
+        assert np.array_equal(np.delete(p, bad, axis=0), p_rest) and np.array_equal(np.delete(logsum, bad), logsum_rest)
+        np.testing.assert_allclose(p_rest.sum(1), 1.0, rtol=1e-14)
+    # the -inf slots of a mixed row are at 0 and the log-sum is that of the finite ones
+    p, logsum = R.posteriors(mixed)
+    e = np.exp(-1.0)
+    np.testing.assert_allclose(p[0], [0.0, 1.0 / (1.0 + e), 0.0, e / (1.0 + e)], rtol=1e-14)
+    assert p[0, 0] == 0.0 and p[0, 2] == 0.0
+    np.testing.assert_allclose(logsum, 2.0 + np.log1p(e), rtol=1e-14)
+    # a batch without a bad row takes the old path: the same values as before the rule
+    p, logsum = R.posteriors(good, 0.12)
+    np.testing.assert_allclose(p[0], np.array([0.5, 0.3, 0.15, 0.0]) / 0.95, rtol=1e-12)
+    np.testing.assert_allclose(logsum, 7.0, rtol=1e-14)
+
+
 def test_the_files_round_trip_through_the_restatement():
     w, means, b, ic = R.random_full_model(3, 3, 4)
     for binary in (True, False):

@@ -122,9 +122,17 @@ def gamma(m):
 
 
 def posteriors(loglikes, min_post=0.0):
-    """[T, n] float64 posteriors with the pruned ones at 0, and the per-frame log-sums"""
+    """[T, n] float64 posteriors with the pruned ones at 0, and the per-frame log-sums.  A frame whose largest selected
+    log-likelihood is not finite has no posterior: every slot is 0 and the log-sum is that largest value (-inf, or NaN)."""
     ll = np.asarray(loglikes, np.float64)
-    mx = ll.max(1, keepdims=True)
+    mx = ll.max(1, keepdims=True)   # a NaN in the row makes it NaN
+    bad = ~np.isfinite(mx[:, 0])
+    if bad.any():
+        good = np.where(bad[:, None], 0.0, ll)
+        p, logsum = posteriors(good, min_post)
+        p[bad] = 0.0
+        logsum[bad] = mx[bad, 0]
+        return p, logsum
     e = np.exp(ll - mx)
     s = e.sum(1, keepdims=True)
     p = e / s
