@@ -562,6 +562,18 @@ xv_status xv_cmvn_norm(const double* stats, int32_t cols, int32_t norm_means, in
  * on their own; matrix u takes norm utt_norm[u] (>= 0) of norms[..][2][cols].  out has the shape of feats. */
 xv_status xv_cmvn_apply(int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t cols, const float* norms,
                         const int32_t* utt_norm, float* out);
+/* host buffers, blocking: the same map behind a row selection, as one launch: out[i][d] = feats[sel_row[i]][d] * scale + offset with
+ * norm utt_norm[sel_utt[i]] of norms[n_norms][2][cols] - bit for bit the rows sel_row of what xv_cmvn_apply writes.  sel_row:
+ * absolute rows of feats, each inside utterance sel_utt[i] (the layout of xv_frontend_cmvn_select); an utterance without a selected
+ * row may have utt_norm = -1.  Any cols >= 1.  out: [n_out][cols].  A table that does not check out is XV_ERR_IO. */
+xv_status xv_cmvn_apply_select(int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t cols, const float* norms,
+                               int32_t n_norms, const int32_t* utt_norm, const int32_t* sel_row, const int32_t* sel_utt, int32_t n_out,
+                               float* out);
+/* host only: whether a feature rspecifier is the per-speaker pipeline nnet3-compute runs on the device instead of as commands
+ * ("ark[,letters]:apply-cmvn [--norm-means=B] [--norm-vars=B] [--utt2spk=ark:FILE] <stats> <feats> ark:- | [select-voiced-frames
+ * ark:- <vad> ark:- |]", csrc/fuse_pipe.h); *found = 0 / 1 and, when found, description receives "name=value" lines: stats,
+ * stats-is-table, feats, vad, utt2spk, norm-means, norm-vars. */
+xv_status xv_recognize_cmvn_pipeline(const char* rspecifier, int32_t* found, char* description, size_t description_cap);
 /* the kernels' times of one statistics call and one application in ms: the best of reps runs after one that warms up */
 xv_status xv_cmvn_kernel_time(int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t cols, int32_t reps,
                               float* stats_ms, float* apply_ms);

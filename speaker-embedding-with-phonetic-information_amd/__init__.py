@@ -150,7 +150,7 @@ ABI_SYMBOLS = [
     "xv_mfcc_options_default", "xv_mfcc_num_frames", "xv_mfcc_utt_seed", "xv_mfcc_compute", "xv_mfcc_compute_i16", "xv_mfcc_kernel_time", "xv_vad_energy",
     "xv_reverb_options_default", "xv_reverb_output_length", "xv_wav_reverberate", "xv_reverb_kernel_time", "xv_wave_write", "xv_recognize_wav_pipeline",
     "xv_compressed_size", "xv_compress_matrices", "xv_compress_kernel_time", "xv_cmvn_sliding",
-    "xv_cmvn_stats", "xv_cmvn_norm", "xv_cmvn_apply", "xv_cmvn_kernel_time",
+    "xv_cmvn_stats", "xv_cmvn_norm", "xv_cmvn_apply", "xv_cmvn_apply_select", "xv_recognize_cmvn_pipeline", "xv_cmvn_kernel_time",
     "xv_add_deltas", "xv_ubm_diag_create", "xv_ubm_full_create", "xv_ubm_destroy", "xv_ubm_gselect", "xv_ubm_post",
     "xv_fgmm_to_gmm", "xv_fgmm_gconsts", "xv_ubm_kernel_time",
     "xv_ubm_full_gselect", "xv_ubm_frame_likes", "xv_vad_from_frame_likes", "xv_merge_vads",
@@ -914,6 +914,20 @@ def write_wave(wxfilename, samples, rate):
     return clipped.value
 
 
+def recognize_cmvn_pipeline(rspecifier):
+    """None, or the fields of the per-speaker feature pipeline nnet3-compute runs on the device instead of as commands
+    (xv_recognize_cmvn_pipeline, csrc/fuse_pipe.h; host only): {"stats", "stats-is-table", "feats", "vad", "utt2spk", "norm-means",
+    "norm-vars"}, all strings ("vad" / "utt2spk" empty when the string has none)."""
+    L = lib()
+    L.xv_recognize_cmvn_pipeline.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_size_t]
+    found = ctypes.c_int32(0)
+    buf = ctypes.create_string_buffer(1 << 16)
+    _check(L.xv_recognize_cmvn_pipeline(rspecifier.encode(), ctypes.byref(found), buf, len(buf)))
+    if not found.value:
+        return None
+    return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
+
+
 def recognize_wav_pipeline(rxfilename):
     """None, or the fields of the wav-reverberate line compute-mfcc-feats would take over instead of running it
     (xv_recognize_wav_pipeline; host only): a dict of the "name=value" lines, e.g. "source", "impulse-response", "duration",
@@ -1173,6 +1187,31 @@ def apply_cmvn(feats_list, norms, utt_norm, device=0):
     _check(L.xv_cmvn_apply(device, packed.ctypes.data if packed.size else None, off.ctypes.data, n, max(cols, 1), nm.ctypes.data,
                            un.ctypes.data, out.ctypes.data if out.size else None))
     return [out[off[u]:off[u + 1]].copy() for u in range(n)]
+
+
+def apply_cmvn_select(feats_list, norms, utt_norm, sel_row, sel_utt, device=0):
+    """The same map behind a row selection, as one launch (xv_cmvn_apply_select): row i of the result is row sel_row[i] of the
+    packed matrices (an absolute row, inside matrix sel_utt[i]) times the scale plus the offset of norms[utt_norm[sel_utt[i]]].  A
+    matrix without a selected row may have utt_norm -1.  Returns one float32 [len(sel_row), cols] matrix."""
+    import numpy as np
+    L = lib()
+    packed, off, cols = _pack_matrices(feats_list, "apply_cmvn_select")
+    n = len(off) - 1
+    cols = max(cols, 1)
+    nm = np.ascontiguousarray(norms, dtype=np.float32)
+    un = np.ascontiguousarray(utt_norm, dtype=np.int32)
+    sr = np.ascontiguousarray(sel_row, dtype=np.int32)
+    su = np.ascontiguousarray(sel_utt, dtype=np.int32)
+    if un.shape != (n,) or nm.ndim != 3 or nm.shape[1:] != (2, cols) or sr.ndim != 1 or sr.shape != su.shape:
+        raise XvError(XV_ERR_ARG, "apply_cmvn_select: norms are [n_norms][2][cols], utt_norm has one entry per matrix, sel_row and sel_utt one per kept row")
+    out = np.empty((sr.size, cols), dtype=np.float32)
+    L.xv_cmvn_apply_select.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                       ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+    _check(L.xv_cmvn_apply_select(device, packed.ctypes.data if packed.size else None, off.ctypes.data, n, cols,
+                                  nm.ctypes.data if nm.size else None, int(nm.shape[0]), un.ctypes.data if un.size else None,
+                                  sr.ctypes.data if sr.size else None, su.ctypes.data if su.size else None, int(sr.size),
+                                  out.ctypes.data if out.size else None))
+    return out
 
 
 def add_deltas(feats_list, order=2, window=2, truncate=0, device=0):

@@ -783,6 +783,20 @@ xv_status xv_wave_write(const char* wxfilename, int32_t rate, const float* sampl
   });
 }
 
+xv_status xv_recognize_cmvn_pipeline(const char* rspecifier, int32_t* found, char* description, size_t description_cap) {
+  if (!rspecifier || !found) return Fail(XV_ERR_ARG, "xv_recognize_cmvn_pipeline: null argument");
+  return Guard([&] {
+    xv::FusedCmvnPipeline p;
+    *found = xv::RecognizeCmvnPipeline(rspecifier, &p) ? 1 : 0;
+    if (*found && description) {
+      const std::string d = xv::DescribeFusedCmvn(p);
+      if (d.size() + 1 > description_cap) return Fail(XV_ERR_ARG, "xv_recognize_cmvn_pipeline: output buffer too small");
+      memcpy(description, d.c_str(), d.size() + 1);
+    }
+    return XV_OK;
+  });
+}
+
 xv_status xv_recognize_wav_pipeline(const char* rxfilename, int32_t* found, char* description, size_t description_cap) {
   if (!rxfilename || !found) return Fail(XV_ERR_ARG, "xv_recognize_wav_pipeline: null argument");
   return Guard([&] {
@@ -969,6 +983,16 @@ xv_status xv_cmvn_apply(int device, const float* feats, const int32_t* row_off, 
   }
   return Guard([&] {
     xv::CmvnApply(device, feats, row_off, n_utts, cols, norms, n_norms, utt_norm, out);
+    return XV_OK;
+  });
+}
+
+xv_status xv_cmvn_apply_select(int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t cols, const float* norms,
+                               int32_t n_norms, const int32_t* utt_norm, const int32_t* sel_row, const int32_t* sel_utt, int32_t n_out,
+                               float* out) {
+  if (n_utts < 0 || cols < 1 || !row_off || n_norms < 0 || n_out < 0) return Fail(XV_ERR_ARG, "xv_cmvn_apply_select: bad argument");
+  return Guard([&] {
+    xv::CmvnApplySelect(device, feats, row_off, n_utts, cols, norms, n_norms, utt_norm, sel_row, sel_utt, n_out, out);
     return XV_OK;
   });
 }

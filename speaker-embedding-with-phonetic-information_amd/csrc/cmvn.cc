@@ -201,4 +201,45 @@ void CmvnApply(int device, const float* feats, const int32_t* row_off, int n, in
   }
 }
 
+void CmvnApplySelect(int device, const float* feats, const int32_t* row_off, int n, int cols, const float* norms, int n_norms,
+                     const int32_t* utt_norm, const int32_t* sel_row, const int32_t* sel_utt, int n_out, float* out, float* device_ms) {
+  if (device_ms) *device_ms = 0.f;
+  if (n < 0 || cols < 1 || !row_off || n_norms < 0 || n_out < 0 || (n > 0 && !utt_norm) || (n_out > 0 && (!sel_row || !sel_utt || !out)))
+    throw KioError("cmvn-apply-select: bad argument");
+  const int64_t rows = CheckOffsets("cmvn-apply-select", row_off, n);
+  if (rows > 0 && !feats) throw KioError("cmvn-apply-select: null input");
+  if (n_norms > 0 && !norms) throw KioError("cmvn-apply-select: null norm table");
+  // the kernel trusts its tables: every kept row is a row of its utterance, and that utterance has a norm
+  for (int i = 0; i < n_out; ++i) {
+    const int u = sel_utt[i];
+    if (u < 0 || u >= n || sel_row[i] < row_off[u] || sel_row[i] >= row_off[u + 1])
+      throw KioError("cmvn-apply-select: a selected row is not a row of its utterance");
+    if (utt_norm[u] < 0 || utt_norm[u] >= n_norms) throw KioError("cmvn-apply-select: a selected row's utterance names no norm of the table");
+  }
+  if (n_out == 0) return;
+  UseDevice(device, kWhoNeeds);
+  DevBuf d_feats, d_norms, d_utt_norm, d_row, d_utt, d_out;
+  d_feats.Upload(feats, (size_t)rows * cols * 4, "copy features");
+  d_norms.Upload(norms, (size_t)n_norms * 2 * cols * 4, "copy norms");
+  d_utt_norm.Upload(utt_norm, (size_t)n * 4, "copy norm indices");
+  d_row.Upload(sel_row, (size_t)n_out * 4, "copy selected rows");
+  d_utt.Upload(sel_utt, (size_t)n_out * 4, "copy selected rows");
+  d_out.Alloc((size_t)n_out * cols * 4);
+  CmvnSelectArgs a;
+  a.raw = d_feats.as<float>();
+  a.cols = cols;
+  a.norms = d_norms.as<float>();
+  a.utt_norm = d_utt_norm.as<int32_t>();
+  a.sel_row = d_row.as<int32_t>();
+  a.sel_utt = d_utt.as<int32_t>();
+  a.n_out = n_out;
+  a.out = d_out.as<float>();
+  EventTimer tm(device_ms != nullptr);
+  tm.Start();
+  Check(launch_cmvn_apply_select(a, nullptr), "cmvn_apply_select launch");
+  if (device_ms) *device_ms = tm.Stop();
+  Check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+  d_out.Download(out, (size_t)n_out * cols * 4, "copy normalised features");
+}
+
 }  // namespace xv

@@ -45,5 +45,12 @@ void CmvnStats(int device, const float* feats, const int32_t* row_off, int n, in
 // written).  out: [row_off[n]][cols].  Blocking.
 void CmvnApply(int device, const float* feats, const int32_t* row_off, int n, int cols, const float* norms, int n_norms,
                const int32_t* utt_norm, float* out, float* device_ms = nullptr, const CmvnCompressed* cm = nullptr);
+// The same behind a row selection, as one launch (cmvn_kernels.h cmvn_apply_select; what nnet3-compute runs in front of the
+// network for the per-speaker pipeline, fuse_pipe.h): out[i] = feats[sel_row[i]] * scale + offset with the norm of utterance
+// sel_utt[i].  sel_row: absolute rows of feats, each inside its utterance; every utterance that has a selected row has
+// utt_norm >= 0 (the others may be -1 and are not touched).  out: [n_out][cols].  Blocking; KioError on a bad table.
+void CmvnApplySelect(int device, const float* feats, const int32_t* row_off, int n, int cols, const float* norms, int n_norms,
+                     const int32_t* utt_norm, const int32_t* sel_row, const int32_t* sel_utt, int n_out, float* out,
+                     float* device_ms = nullptr);
 
 }  // namespace xv

@@ -13,6 +13,9 @@
 //                       and columns alone, so a matrix's statistics are the same bits in whatever batch it lands.
 //   cmvn_apply          out = x * scale + offset per item, the norm of matrix u being row utt_norm[u] of the table.  fp32, the
 //                       product and the sum each rounded on their own (the file is compiled with contraction off).
+//   cmvn_apply_select   (cmvn_select_kernel.hip) the same map behind a row selection, for the front-end of nnet3-compute (fuse_pipe.h): out[i] = raw[sel_row[i]]
+//                       * scale + offset with the norm of utterance sel_utt[i]; one launch, one thread per kept element.  A kept
+//                       row is bit for bit what cmvn_apply writes for it: selection commutes with an element-wise map.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -41,7 +44,23 @@ struct CmvnArgs {
   float* out;                  // [row_off[n]][cols]
 };
 
+constexpr int kCmvnSelectRows = 64;   // output rows per workgroup of cmvn_apply_select
+
+// sel_row / sel_utt as FrontEndArgs (kernels.h) has them.  The kernel checks nothing: every sel_row is a row of raw, every
+// sel_utt an utterance whose utt_norm is a row of norms (utterances without statistics are filtered out by the host).
+struct CmvnSelectArgs {
+  const float* raw;            // [raw rows][cols]
+  int cols;                    // >= 1
+  const float* norms;          // [n_norms][2][cols]: row 0 the offset, row 1 the scale
+  const int32_t* utt_norm;     // [n_utts] in [0, n_norms)
+  const int32_t* sel_row;      // [n_out] absolute raw row of every kept frame
+  const int32_t* sel_utt;      // [n_out] its utterance
+  int n_out;
+  float* out;                  // [n_out][cols]
+};
+
 hipError_t launch_cmvn_stats(const CmvnArgs& a, hipStream_t s);    // partial + reduce
 hipError_t launch_cmvn_apply(const CmvnArgs& a, hipStream_t s);
+hipError_t launch_cmvn_apply_select(const CmvnSelectArgs& a, hipStream_t s);   // n_out == 0: nothing to do
 
 }  // namespace xv

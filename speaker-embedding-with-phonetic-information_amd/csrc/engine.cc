@@ -1,5 +1,6 @@
 // Device engine.  See engine.h.
 #include "engine.h"
+#include "cmvn_kernels.h"
 #include "knobs.h"
 
 #include <stddef.h>
@@ -1995,6 +1996,110 @@ void Engine::ForwardHost(const float* feats, const int32_t* row_offsets, int B, 
   // plan offsets are absolute; shift the device base so that offset row_offsets[0] lands on byte 0
   const float* dev_feats = (const float*)feats_stage_.p - (size_t)row_offsets[0] * info_.input_dim;
   Forward(*plan, dev_feats, (float*)out_stage_.p, info_.output_dim, stream_);
+  Check(hipMemcpyAsync(out, out_stage_.p, obytes, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(out)");
+  Check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+  CheckKernelFaults();
+}
+
+void Engine::ForwardFrontHost(const FrontEndInput& fe, const int32_t* row_offsets, int B, float* out) {
+  Check(hipSetDevice(device_), "hipSetDevice");
+  const int D = info_.input_dim;
+  const bool cm = fe.raw == nullptr;
+  if (B <= 0 || fe.n_utts <= 0 || fe.n_out <= 0 || !fe.raw_off || !fe.sel_row || !fe.sel_utt || row_offsets[0] != 0 ||
+      row_offsets[B] != fe.n_out || (cm && (!fe.cm || !fe.cm_off || D > 64)) || (fe.norms && (!fe.utt_norm || fe.n_norms <= 0)))
+    throw EngineError("ForwardFrontHost: bad argument");
+  const long raw_rows = fe.raw_off[fe.n_utts];
+  // the kernels trust their tables
+  for (int i = 0; i < fe.n_out; ++i) {
+    const int u = fe.sel_utt[i];
+    if (u < 0 || u >= fe.n_utts || fe.sel_row[i] < fe.raw_off[u] || fe.sel_row[i] >= fe.raw_off[u + 1])
+      throw EngineError("ForwardFrontHost: a selected row is not a row of its utterance");
+  }
+  for (int u = 0; fe.norms && u < fe.n_utts; ++u)
+    if (fe.utt_norm[u] < 0 || fe.utt_norm[u] >= fe.n_norms) throw EngineError("ForwardFrontHost: an utterance names no norm of the table");
+  for (int u = 0; cm && u < fe.n_utts; ++u) {
+    const size_t need = 16 + (size_t)D * 8 + (size_t)(fe.raw_off[u + 1] - fe.raw_off[u]) * D;
+    if (fe.cm_off[u] < 0 || (size_t)fe.cm_off[u] + need > fe.cm_bytes) throw EngineError("ForwardFrontHost: compressed object out of bounds");
+    int32_t rc[2];
+    memcpy(rc, fe.cm + fe.cm_off[u] + 8, 8);
+    if (rc[0] != fe.raw_off[u + 1] - fe.raw_off[u] || rc[1] != D || rc[0] > fe.max_rows)
+      throw EngineError("ForwardFrontHost: compressed object does not have the shape of its utterance");
+  }
+  std::shared_ptr<Plan> plan = MakePlan(row_offsets, B);
+  const size_t fbytes = (size_t)fe.n_out * D * 4;
+  const size_t obytes = (size_t)(frame_mode_ ? plan->n_out : B) * info_.output_dim * 4;
+  // one table image: raw_off | sel_row | sel_utt | cm_off | utt_norm | norms
+  const size_t o_off = 0, o_row = Align256((size_t)(fe.n_utts + 1) * 4), o_utt = Align256(o_row + (size_t)fe.n_out * 4);
+  const size_t o_cm = Align256(o_utt + (size_t)fe.n_out * 4), o_un = Align256(o_cm + (cm ? (size_t)fe.n_utts * 8 : 0));
+  const size_t o_norm = Align256(o_un + (fe.norms ? (size_t)fe.n_utts * 4 : 0));
+  const size_t tab = Align256(o_norm + (fe.norms ? (size_t)fe.n_norms * 2 * D * 4 : 0));
+  const size_t pbytes = fe.norms ? 0 : (size_t)(raw_rows + fe.n_utts) * D * 8;
+  // (re)allocation frees device memory the stream may still read
+  if (feats_stage_.bytes < fbytes || out_stage_.bytes < obytes || fe_raw_.bytes < (size_t)raw_rows * D * 4 || fe_tab_.bytes < tab ||
+      fe_prefix_.bytes < pbytes || (cm && fe_cm_.bytes < fe.cm_bytes))
+    Check(hipStreamSynchronize(stream_), "sync");
+  auto grow = [&](Buf* b, size_t need) {
+    if (b->bytes < need || !b->p) Ensure(b, need + need / 4 + 256, false);
+  };
+  grow(&feats_stage_, fbytes);
+  grow(&out_stage_, obytes);
+  grow(&fe_raw_, (size_t)raw_rows * D * 4);
+  grow(&fe_tab_, tab);
+  if (pbytes) grow(&fe_prefix_, pbytes);
+  if (cm) grow(&fe_cm_, fe.cm_bytes);
+  std::vector<uint8_t> host(tab, 0);
+  memcpy(host.data() + o_off, fe.raw_off, (size_t)(fe.n_utts + 1) * 4);
+  memcpy(host.data() + o_row, fe.sel_row, (size_t)fe.n_out * 4);
+  memcpy(host.data() + o_utt, fe.sel_utt, (size_t)fe.n_out * 4);
+  if (cm) memcpy(host.data() + o_cm, fe.cm_off, (size_t)fe.n_utts * 8);
+  if (fe.norms) {
+    memcpy(host.data() + o_un, fe.utt_norm, (size_t)fe.n_utts * 4);
+    memcpy(host.data() + o_norm, fe.norms, (size_t)fe.n_norms * 2 * D * 4);
+  }
+  const uint8_t* dt = (const uint8_t*)fe_tab_.p;
+  Check(hipMemcpyAsync(fe_tab_.p, host.data(), tab, hipMemcpyHostToDevice, stream_), "hipMemcpyAsync(front-end tables)");
+  if (cm) {   // one byte per element goes up; the float rows are made here
+    Check(hipMemcpyAsync(fe_cm_.p, fe.cm, fe.cm_bytes, hipMemcpyHostToDevice, stream_), "hipMemcpyAsync(compressed feats)");
+    CmExpandArgs ca;
+    ca.cm = (const uint8_t*)fe_cm_.p;
+    ca.cm_off = (const int64_t*)(dt + o_cm);
+    ca.raw_off = (const int32_t*)(dt + o_off);
+    ca.n_utts = fe.n_utts;
+    ca.dim = D;
+    ca.max_rows = fe.max_rows;
+    ca.out = (float*)fe_raw_.p;
+    Check(launch_cm_expand(ca, stream_), "cm_expand launch");
+  } else {
+    Check(hipMemcpyAsync(fe_raw_.p, fe.raw, (size_t)raw_rows * D * 4, hipMemcpyHostToDevice, stream_), "hipMemcpyAsync(raw feats)");
+  }
+  if (fe.norms) {
+    CmvnSelectArgs sa;
+    sa.raw = (const float*)fe_raw_.p;
+    sa.cols = D;
+    sa.norms = (const float*)(dt + o_norm);
+    sa.utt_norm = (const int32_t*)(dt + o_un);
+    sa.sel_row = (const int32_t*)(dt + o_row);
+    sa.sel_utt = (const int32_t*)(dt + o_utt);
+    sa.n_out = fe.n_out;
+    sa.out = (float*)feats_stage_.p;
+    Check(launch_cmvn_apply_select(sa, stream_), "cmvn_apply_select launch");
+  } else {
+    FrontEndArgs fa;
+    fa.raw = (const float*)fe_raw_.p;
+    fa.raw_off = (const int32_t*)(dt + o_off);
+    fa.prefix = (double*)fe_prefix_.p;
+    fa.n_utts = fe.n_utts;
+    fa.dim = D;
+    fa.sel_row = (const int32_t*)(dt + o_row);
+    fa.sel_utt = (const int32_t*)(dt + o_utt);
+    fa.n_out = fe.n_out;
+    fa.cmn_window = fe.cmn_window;
+    fa.center = fe.center ? 1 : 0;
+    fa.min_window = fe.min_window;
+    fa.out = (float*)feats_stage_.p;
+    Check(launch_frontend(fa, stream_), "front-end launch");
+  }
+  Forward(*plan, (const float*)feats_stage_.p, (float*)out_stage_.p, info_.output_dim, stream_);
   Check(hipMemcpyAsync(out, out_stage_.p, obytes, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(out)");
   Check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
   CheckKernelFaults();

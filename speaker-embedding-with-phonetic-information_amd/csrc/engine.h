@@ -88,6 +88,32 @@ class Engine {
   // Host convenience: H2D, forward, D2H, synchronise.  Segment-level output: out is [B][output_dim]; frame-level
   // output: out is [sum of chunk lengths][output_dim] (one row per input frame), chunk b starting at OutRowOffset.
   void ForwardHost(const float* feats, const int32_t* row_offsets, int B, float* out);
+  // ForwardHost with the network's input made on the device (nnet3-compute's fused feature pipelines, fuse_pipe.h): the raw rows
+  // go up - float rows, or stored "CM" objects that are expanded on the device as SubmitHost does - one front-end stage makes
+  // the rows the network reads (the sliding-CMN front-end, or the per-speaker affine map behind the row selection,
+  // cmvn_kernels.h), and then come the very launches of ForwardHost: MakePlan, Forward on the engine's stream, the copy of the
+  // output.  Everything on stream_, blocking.  row_offsets describe the KEPT rows (row_offsets[0] == 0, row_offsets[B] == n_out).
+  struct FrontEndInput {
+    const float* raw = nullptr;       // [raw_off[n_utts]][input_dim] float rows; null: compressed objects below
+    const int32_t* raw_off = nullptr; // [n_utts + 1]
+    int n_utts = 0;
+    const int32_t* sel_row = nullptr; // [n_out] absolute raw row of every kept frame, ascending
+    const int32_t* sel_utt = nullptr; // [n_out] its utterance
+    int n_out = 0;
+    const uint8_t* cm = nullptr;      // the "CM" objects back to back (input_dim <= 64), object u at cm_off[u]
+    const int64_t* cm_off = nullptr;  // [n_utts]
+    size_t cm_bytes = 0;
+    int max_rows = 0;                 // the longest utterance (compressed input)
+    // the stage: norms != null: out = x * scale + offset with norms[utt_norm[u]] ([n_norms][2][input_dim], every utt_norm in
+    // range); else the sliding front-end (cmn_window <= 0: selection only)
+    const float* norms = nullptr;
+    int n_norms = 0;
+    const int32_t* utt_norm = nullptr;   // [n_utts]
+    int cmn_window = 0;
+    bool center = false;
+    int min_window = 100;
+  };
+  void ForwardFrontHost(const FrontEndInput& fe, const int32_t* row_offsets, int B, float* out);
   // Asynchronous host path (table jobs): kNumHostSlots batches queued or in flight, each with its own pinned staging
   // buffers, device staging and plan tables; batch number `seq` runs on the stream of lane (seq % lanes), so
   // consecutive batches alternate lanes while a third one is already queued behind them.  Usage per slot:
@@ -309,6 +335,7 @@ class Engine {
   size_t next_lane_ = 0;
   Buf feats_stage_, out_stage_;
   Buf fe_raw_, fe_tab_, fe_prefix_, fe_out_;
+  Buf fe_cm_;   // ForwardFrontHost: the uploaded compressed objects
   std::map<std::vector<int32_t>, std::shared_ptr<Plan>> plan_cache_;
   bool prof_on_ = false;
   std::vector<std::string> prof_labels_;

@@ -18,7 +18,8 @@
 //   engines_on_one_device (n, 0)      test knob: n engines on ONE device behind the several-engine table loop
 //   bn_fold (0 | 1, 0)  bn_fold_mask (bits)   the opt-in lowering of DESIGN.md section 3.5
 //   tail_over_tol (factor, 1.10)      study knob of tools/tail_error.py: the calibration's projected-tail condition
-//   fuse_pipe (0 | 1, 1)              0: the reference's feature pipeline (fuse_pipe.h) is run as commands, not on the device
+//   fuse_pipe (0 | 1, 1)              0: the reference's feature pipelines (fuse_pipe.h: the sliding-CMN one of both tools, the
+//                                     per-speaker apply-cmvn one of nnet3-compute) are run as commands, not on the device
 //   fuse_wav (0 | 1, 1)               0: wav-reverberate lines of a wav.scp (fuse_wav.h) are run as commands, not taken into the batch
 //   reverb_group_blocks (n, 16384)    test knob: FFT blocks of signal spectra held at once by the reverberation (reverb.cc)
 //   calib_fail (0 | 1 | 2 | 3, 0)     fault injection: the first / every Engine::Calibrate of the process throws; 3: the first one

@@ -113,7 +113,10 @@ const char* kUsage =
     "                                   (A features rspecifier that IS the recipes' pipeline - 'ark:apply-cmvn-sliding\n"
     "                                   --norm-vars=false --center=.. --cmn-window=.. <table> ark:- | select-voiced-frames ark:-\n"
     "                                   <vad table> ark:- |', extract_xvectors_new.sh:79 - is recognised and run this way by\n"
-    "                                   itself; the log says so.  Anything else in a pipe is run as a command.)\n"
+    "                                   itself; the log says so.  Anything else in a pipe is run as a command.\n"
+    "                                   nnet3-compute recognises the same string and the per-speaker one of the\n"
+    "                                   acoustic-model scripts, 'ark,s,cs:apply-cmvn [--norm-vars=..] --utt2spk=ark:<file>\n"
+    "                                   <stats> <table> ark:- | [select-voiced-frames ...|]', extract_bn.sh:59.)\n"
     "  --backend-mean=<vec> --backend-transform=<mat> --backend-normalize-length=true|false [--backend-scaleup=true]\n"
     "                                   apply ivector-subtract-global-mean | transform-vec | ivector-normalize-length\n"
     "                                   on the device to every embedding before it is written\n"
@@ -354,20 +357,45 @@ int main(int argc, char** argv) {
     // The feature pipeline the reference's extraction scripts build (extract_xvectors_new.sh:79: apply-cmvn-sliding |
     // select-voiced-frames, two CPU tools and two pipes) is recognised as text and run on the device instead (fuse_pipe.h) -
     // unless the caller asked for a front-end of their own, or XVEC_DEBUG=fuse_pipe=0 says to run the commands.
+    // nnet3-compute does the same with that string (extract_log_post.sh:68-70) and with the per-speaker one of the acoustic-model
+    // scripts (extract_bn.sh:59: apply-cmvn --utt2spk ... [| select-voiced-frames]), each in front of its frame-level forward pass.
     bool fused = false;
     int fused_min_window = 0;   // --min-cmn-window as the pipeline has it, whatever its sign: the tool it names takes it as typed
-    if (!g_frame_job && opt.cmn_window == 0 && opt.vad_rspecifier.empty() && xv::DebugKnobInt("fuse_pipe", 1) != 0) {
+    xv::ComputeFrontEnd front;  // the frame-level job's fused pipeline (kNone: the rspecifier is read as it is)
+    if (opt.cmn_window == 0 && opt.vad_rspecifier.empty() && xv::DebugKnobInt("fuse_pipe", 1) != 0) {
       xv::FusedPipeline fp;
+      xv::FusedCmvnPipeline cp;
       if (xv::RecognizeFeaturePipeline(feat_rspec, &fp)) {
         XLOG("feature pipeline recognised (apply-cmvn-sliding --norm-vars=false --center=" << (fp.center ? "true" : "false")
              << " --cmn-window=" << fp.cmn_window << " --min-cmn-window=" << fp.min_cmn_window
              << (fp.vad_rspecifier.empty() ? "" : " | select-voiced-frames " + fp.vad_rspecifier) << "): it runs on the device, reading " << fp.feats_rspecifier << " directly (XVEC_DEBUG=fuse_pipe=0 runs the commands)");
-        feat_rspec = fp.feats_rspecifier;
-        opt.cmn_window = fp.cmn_window;
-        opt.cmn_center = fp.center;
-        opt.vad_rspecifier = fp.vad_rspecifier;
-        fused_min_window = fp.min_cmn_window;
-        fused = true;
+        if (g_frame_job) {
+          front.kind = xv::ComputeFrontEnd::kSliding;
+          front.feats_rspecifier = fp.feats_rspecifier;
+          front.vad_rspecifier = fp.vad_rspecifier;
+          front.cmn_window = fp.cmn_window;
+          front.min_window = fp.min_cmn_window;
+          front.center = fp.center;
+        } else {
+          feat_rspec = fp.feats_rspecifier;
+          opt.cmn_window = fp.cmn_window;
+          opt.cmn_center = fp.center;
+          opt.vad_rspecifier = fp.vad_rspecifier;
+          fused_min_window = fp.min_cmn_window;
+          fused = true;
+        }
+      } else if (g_frame_job && xv::RecognizeCmvnPipeline(feat_rspec, &cp) && cp.norm_means) {
+        // (--norm-means=false makes apply-cmvn a copy, which x * 1 + 0 is not for a negative zero: that one is run as commands)
+        XLOG("feature pipeline recognised (apply-cmvn --norm-means=true --norm-vars=" << (cp.norm_vars ? "true" : "false")
+             << (cp.utt2spk_rspecifier.empty() ? "" : " --utt2spk=" + cp.utt2spk_rspecifier) << " " << cp.stats_rxfilename
+             << (cp.vad_rspecifier.empty() ? "" : " | select-voiced-frames " + cp.vad_rspecifier) << "): it runs on the device, reading " << cp.feats_rspecifier << " directly (XVEC_DEBUG=fuse_pipe=0 runs the commands)");
+        front.kind = xv::ComputeFrontEnd::kPerSpeaker;
+        front.feats_rspecifier = cp.feats_rspecifier;
+        front.vad_rspecifier = cp.vad_rspecifier;
+        front.stats_rxfilename = cp.stats_rxfilename;
+        front.stats_is_table = cp.stats_is_table;
+        front.utt2spk_rspecifier = cp.utt2spk_rspecifier;
+        front.norm_vars = cp.norm_vars;
       }
     }
 
@@ -514,7 +542,9 @@ int main(int argc, char** argv) {
     if (g_frame_job) {
       xv::TableExtractResult fr = xv::RunTableCompute(
           &engine, opt.batch_frames, g_apply_exp, feat_rspec, vec_wspec,
-          [](const char* level, const std::string& m) { LogLine(level, 0, m); });
+          [](const char* level, const std::string& m) { LogLine(level, 0, m); }, &front);
+      // (a feature command that failed left a table that may lack utterances: Kaldi's reader ends such a job with an error)
+      if (fr.reader_status != 0) throw xv::KioError("feature input command exited with status " + std::to_string(fr.reader_status));
       XLOG("Time taken " << fr.seconds << "s: real-time factor assuming 100 frames/sec is "
                          << (fr.seconds * 100.0 / std::max(fr.frames, 1.0)));
       XLOG("Done " << fr.num_success << " utterances, failed for " << fr.num_fail);

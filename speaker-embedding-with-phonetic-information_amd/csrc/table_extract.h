@@ -59,7 +59,24 @@ Engine::Calibration CalibrateOnTable(Engine* engine, const ExtractOptions& opt, 
 // nnet3-compute style job: one output MATRIX per utterance (a row per input frame) from a frame-level model
 // (reference call sites: sid/nnet3_cvector/cvector/extract_log_post.sh:77-84, sid/nnet3_cvector/am/extract_bn.sh:68,
 // steps/nnet3/make_bottleneck_features_new.sh:109).  apply_exp turns log-posteriors into posteriors (--apply-exp).
+// The loop is three stages on three threads (stage_pipeline.h): the next batch is read while the device works on one and the
+// previous one is written; the table's order is kept.  front (optional, kind != kNone): the feature rspecifier was one of the
+// recipes' pipelines (fuse_pipe.h) and is run on the device instead: the job reads front->feats_rspecifier itself, stored "CM"
+// bytes kept as they are, joins it with the side tables, and reports what the tools it replaces report, in their words - their
+// per-utterance warnings, fatal errors (statistics of another width, a count below 1) and closing lines.  Batches close on
+// the rows that reach the network, so they are those of the job run as commands.
+struct ComputeFrontEnd {
+  enum Kind { kNone, kSliding, kPerSpeaker } kind = kNone;
+  std::string feats_rspecifier;
+  std::string vad_rspecifier;       // empty: every row is kept
+  // kSliding: apply-cmvn-sliding --norm-vars=false
+  int cmn_window = 600, min_window = 100;
+  bool center = false;
+  // kPerSpeaker: apply-cmvn --norm-means=true
+  std::string stats_rxfilename, utt2spk_rspecifier;
+  bool stats_is_table = true, norm_vars = false;
+};
 TableExtractResult RunTableCompute(Engine* engine, int max_batch_rows, bool apply_exp, const std::string& feature_rspecifier,
-                                   const std::string& matrix_wspecifier, const LogFn& log);
+                                   const std::string& matrix_wspecifier, const LogFn& log, const ComputeFrontEnd* front = nullptr);
 
 }  // namespace xv
