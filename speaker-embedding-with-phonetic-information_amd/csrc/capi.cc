@@ -12,6 +12,7 @@
 #include "backend.h"
 #include "cmvn.h"
 #include "compress.h"
+#include "device.h"
 #include "engine.h"
 #include "extractor.h"
 #include "feat.h"
@@ -728,13 +729,9 @@ xv_status xv_mfcc_kernel_time(int device, const xv_mfcc_options* opts, const int
     std::vector<float> feats;
     std::vector<int32_t> row_off(n_utts + 1);
     std::vector<uint64_t> seeds(n_utts, 1);
-    float best = 0.f;
-    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
-      float ms = 0.f;
-      mc.Compute(samples, true, sample_offsets, n_utts, seeds.data(), &feats, row_off.data(), &ms);
-      if (r == 1 || (r > 1 && ms < best)) best = ms;
-    }
-    *kernel_ms = best;
+    xv::BestOfReps(reps, 1, kernel_ms, [&](int, float* ms) {
+      mc.Compute(samples, true, sample_offsets, n_utts, seeds.data(), &feats, row_off.data(), ms);
+    });
     return XV_OK;
   });
 }
@@ -879,23 +876,16 @@ xv_status xv_reverb_kernel_time(int device, const xv_reverb_options* opts, float
     FillReverbBatch(&b, sample_rate, samples, samples_are_i16, sample_offsets, n_utts, rirs, rir_offsets, n_rirs,
                                             utt_rir, noises, noise_offsets, n_noises, utt_add_offsets, add_noise, add_snr, add_start);
     std::vector<int64_t> off(n_utts + 1);
-    std::vector<float> out;
-    float best = 0.f;
-    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
-      if (r == 0) {
-        int64_t total = 0;
-        for (int u = 0; u < n_utts; ++u) {
-          const int ri = b.utt_rir ? b.utt_rir[u] : -1;
-          const int64_t rl = ri >= 0 && ri < n_rirs ? rir_offsets[ri + 1] - rir_offsets[ri] : 0;
-          total += std::max<int64_t>(0, xv::ReverbOutputLength(*opts, sample_rate, sample_offsets[u + 1] - sample_offsets[u], rl));
-        }
-        out.resize((size_t)total + 1);
-      }
-      float ms = 0.f;
-      xv::Reverberate(device, *opts, b, off.data(), out.data(), nullptr, nullptr, &ms);
-      if (r == 1 || (r > 1 && ms < best)) best = ms;
+    int64_t total = 0;
+    for (int u = 0; u < n_utts; ++u) {
+      const int ri = b.utt_rir ? b.utt_rir[u] : -1;
+      const int64_t rl = ri >= 0 && ri < n_rirs ? rir_offsets[ri + 1] - rir_offsets[ri] : 0;
+      total += std::max<int64_t>(0, xv::ReverbOutputLength(*opts, sample_rate, sample_offsets[u + 1] - sample_offsets[u], rl));
     }
-    *kernel_ms = best;
+    std::vector<float> out((size_t)total + 1);
+    xv::BestOfReps(reps, 1, kernel_ms, [&](int, float* ms) {
+      xv::Reverberate(device, *opts, b, off.data(), out.data(), nullptr, nullptr, ms);
+    });
     return XV_OK;
   });
 }
@@ -931,13 +921,9 @@ xv_status xv_compress_kernel_time(int device, const float* feats, const int32_t*
       total += nb;
     }
     std::vector<uint8_t> out(total + 1);
-    float best = 0.f;
-    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
-      float ms = 0.f;
-      xv::CompressMatrices(device, feats, row_off, n, cols, method, out.data(), off.data(), nullptr, &ms);
-      if (r == 1 || (r > 1 && ms < best)) best = ms;
-    }
-    *kernel_ms = best;
+    xv::BestOfReps(reps, 1, kernel_ms, [&](int, float* ms) {
+      xv::CompressMatrices(device, feats, row_off, n, cols, method, out.data(), off.data(), nullptr, ms);
+    });
     return XV_OK;
   });
 }
@@ -1005,21 +991,18 @@ xv_status xv_cmvn_kernel_time(int device, const float* feats, const int32_t* row
     std::vector<double> stats((size_t)n_utts * 2 * (cols + 1));
     std::vector<float> norms((size_t)n_utts * 2 * cols), out((size_t)row_off[n_utts] * cols);
     std::vector<int32_t> utt_norm(n_utts);
-    float best_s = 0.f, best_a = 0.f;
-    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
-      float ms = 0.f;
-      xv::CmvnStats(device, feats, row_off, n_utts, cols, stats.data(), &ms);
-      if (r == 1 || (r > 1 && ms < best_s)) best_s = ms;
+    float best[2];
+    xv::BestOfReps(reps, 2, best, [&](int r, float* ms) {
+      xv::CmvnStats(device, feats, row_off, n_utts, cols, stats.data(), &ms[0]);
       if (r == 0)
         for (int u = 0; u < n_utts; ++u) {
           utt_norm[u] = u;
           xv::CmvnNorm(stats.data() + (size_t)u * 2 * (cols + 1), cols, true, true, false, nullptr, 0, norms.data() + (size_t)u * 2 * cols);
         }
-      xv::CmvnApply(device, feats, row_off, n_utts, cols, norms.data(), n_utts, utt_norm.data(), out.data(), &ms);
-      if (r == 1 || (r > 1 && ms < best_a)) best_a = ms;
-    }
-    *stats_ms = best_s;
-    *apply_ms = best_a;
+      xv::CmvnApply(device, feats, row_off, n_utts, cols, norms.data(), n_utts, utt_norm.data(), out.data(), &ms[1]);
+    });
+    *stats_ms = best[0];
+    *apply_ms = best[1];
     return XV_OK;
   });
 }
@@ -1128,14 +1111,11 @@ xv_status xv_ubm_kernel_time(const xv_ubm* diag, const xv_ubm* full, const float
     const int dim = diag->m->dim();
     std::vector<int32_t> gs(rows * n), count(rows), idx(rows * n);
     std::vector<float> post(rows * n), deltas(dim % 3 == 0 ? rows * dim : 0);
-    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
-      float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    xv::BestOfReps(reps, 5, ms5, [&](int, float* ms) {
       if (dim % 3 == 0) xv::AddDeltas(diag->m->device(), feats, row_off, n_utts, dim, 2, 3, dim / 3, deltas.data(), &ms[0]);
       xv::UbmGselect(*diag->m, feats, row_off, n_utts, n, gs.data(), nullptr, &ms[1]);
       xv::UbmPost(*full->m, feats, row_off, n_utts, gs.data(), n, min_post, count.data(), idx.data(), post.data(), nullptr, nullptr, &ms[2]);
-      for (int i = 0; i < 5; ++i)
-        if (r == 1 || (r > 1 && ms[i] < ms5[i])) ms5[i] = ms[i];
-    }
+    });
     return XV_OK;
   });
 }
@@ -1286,12 +1266,9 @@ xv_status xv_fgmm_acc_kernel_time(xv_fgmm_acc* a, const xv_ubm* full, const floa
   if (!a || !full || !feats || !gselect || rows < 1 || reps < 1 || !ms4) return Fail(XV_ERR_ARG, "xv_fgmm_acc_kernel_time: bad argument");
   return Guard([&] {
     std::vector<float> logsum((size_t)rows);
-    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
-      float ms[4];
+    xv::BestOfReps(reps, 4, ms4, [&](int, float* ms) {
       xv::FgmmAccAddGselect(a->a.get(), *full->m, feats, rows, gselect, n, logsum.data(), ms);
-      for (int i = 0; i < 4; ++i)
-        if (r == 1 || (r > 1 && ms[i] < ms4[i])) ms4[i] = ms[i];
-    }
+    });
     return XV_OK;
   });
 }
@@ -1330,12 +1307,11 @@ xv_status xv_logprob_to_post_kernel_time(int device, const float* logprobs, int3
   return Guard([&] {
     const int32_t row_off[2] = {0, rows};
     const uint64_t seed = xv::UttSeed(key);
-    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
+    xv::BestOfReps(reps, 3, ms4, [&](int, float* ms) {
       xv::LogprobPostResult res;
       xv::LogprobToPost(device, logprobs, row_off, 1, cols, &seed, min_post, random_prune != 0, rows, true, &res);
-      for (int i = 0; i < 3; ++i)
-        if (r == 1 || (r > 1 && res.ms[i] < ms4[i])) ms4[i] = res.ms[i];
-    }
+      std::copy(res.ms, res.ms + 3, ms);
+    });
     ms4[3] = xv::DeviceCopyMs(device, (size_t)rows * cols * 4, reps);
     return XV_OK;
   });
@@ -1466,14 +1442,10 @@ xv_status xv_dgmm_acc_kernel_time(xv_dgmm_acc* a, const xv_ubm* diag, const floa
   if (!a || !diag || !feats || rows < 1 || reps < 1 || !ms7) return Fail(XV_ERR_ARG, "xv_dgmm_acc_kernel_time: bad argument");
   return Guard([&] {
     std::vector<float> logsum((size_t)rows);
-    for (int i = 0; i < 7; ++i) ms7[i] = 0.f;
-    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
-      float ms[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    xv::BestOfReps(reps, 7, ms7, [&](int, float* ms) {
       if (gselect) xv::DgmmAccAddGselect(a->a.get(), *diag->m, feats, rows, gselect, n, nullptr, logsum.data(), ms);
       if (dense) xv::DgmmAccAddDense(a->a.get(), *diag->m, feats, rows, logsum.data(), ms + 4);
-      for (int i = 0; i < 7; ++i)
-        if (r == 1 || (r > 1 && ms[i] < ms7[i])) ms7[i] = ms[i];
-    }
+    });
     return XV_OK;
   });
 }
@@ -1594,17 +1566,14 @@ xv_status xv_ivex_kernel_time(xv_ivex* m, const float* feats, const int32_t* row
     std::vector<float> iv((size_t)n_utts * S);
     std::vector<int32_t> status((size_t)n_utts);
     std::vector<double> auxf((size_t)n_utts);
-    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
-      float ms[4] = {0.f, 0.f, 0.f, 0.f};
+    xv::BestOfReps(reps, 4, ms5, [&](int, float* ms) {
       xv::IvexOutputs o;
       o.ivectors = iv.data();
       o.status = status.data();
       o.auxf_change = auxf.data();
       o.device_ms4 = ms;
       xv::IvexExtract(*m->m, feats, row_off, n_utts, post_off, post_idx, post_w, 1.0, 0.0, o);
-      for (int i = 0; i < 4; ++i)
-        if (r == 1 || (r > 1 && ms[i] < ms5[i])) ms5[i] = ms[i];
-    }
+    });
     ms5[4] = m->m->derive_ms();
     return XV_OK;
   });
@@ -1695,15 +1664,12 @@ xv_status xv_ivex_acc_kernel_time(xv_ivex_acc* a, const float* feats, const int3
   if (!a || !feats || !row_off || !post_off || n_utts < 1 || reps < 1 || !ms3) return Fail(XV_ERR_ARG, "xv_ivex_acc_kernel_time: bad argument");
   return Guard([&] {
     xv::IvexStats st;
-    for (int r = 0; r <= reps; ++r) {   // the first pass warms up
+    xv::BestOfReps(reps, 3, ms3, [&](int, float* ms) {
       float add[3], get[3];
       xv::IvexAccAdd(a->a.get(), feats, row_off, n_utts, post_off, post_idx, post_w, nullptr, add);
       xv::IvexAccGet(a->a.get(), &st, get);
-      for (int i = 0; i < 3; ++i) {
-        const float ms = add[i] + get[i];
-        if (r == 1 || (r > 1 && ms < ms3[i])) ms3[i] = ms;
-      }
-    }
+      for (int i = 0; i < 3; ++i) ms[i] = add[i] + get[i];
+    });
     return XV_OK;
   });
 }

@@ -131,6 +131,20 @@ class EventTimer {
   size_t used_ = 0;
 };
 
+// The loop of every entry point that reports kernel times: pass(r, ms) runs the work once and leaves its n times in ms (zero on
+// entry), for r = 0 .. reps.  The first pass warms up; best[i] is the smallest ms[i] of the others.
+template <class Pass>
+void BestOfReps(int reps, int n, float* best, Pass pass) {
+  std::vector<float> ms((size_t)n);
+  for (int i = 0; i < n; ++i) best[i] = 0.f;
+  for (int r = 0; r <= reps; ++r) {
+    ms.assign((size_t)n, 0.f);
+    pass(r, ms.data());
+    for (int i = 0; i < n; ++i)
+      if (r == 1 || (r > 1 && ms[i] < best[i])) best[i] = ms[i];
+  }
+}
+
 // Work items (unit, block) of one launch: a unit is a matrix or an utterance, and takes as many workgroups as it has blocks.
 struct WorkItems {
   std::vector<int32_t> unit, blk;

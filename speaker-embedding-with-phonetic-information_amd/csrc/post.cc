@@ -99,12 +99,11 @@ float DeviceCopyMs(int device, size_t bytes, int reps) {
   Check(hipMemset(src.p, 0, bytes), "hipMemset");
   EventTimer tm(true);
   float best = 0.f;
-  for (int r = 0; r <= reps; ++r) {
+  BestOfReps(reps, 1, &best, [&](int, float* ms) {
     tm.Start();
     Check(hipMemcpyAsync(dst.p, src.p, bytes, hipMemcpyDeviceToDevice, nullptr), "hipMemcpyAsync");
-    const float ms = tm.Stop();
-    if (r == 1 || (r > 1 && ms < best)) best = ms;
-  }
+    *ms = tm.Stop();
+  });
   return best;
 }
 

@@ -41,8 +41,6 @@ REFUSED = {
 
 
 def _child():
-    import ctypes
-
     import numpy as np
     P = H.pkg()
     x = np.ones((2, 4), np.float32)
@@ -52,8 +50,6 @@ def _child():
 
     def cmvn_stats_bad():
         L = P.lib()
-        L.xv_cmvn_stats.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                    ctypes.c_void_p]
         off = np.zeros(2, np.int32)
         st = np.zeros((1, 2, 6))
         P._check(L.xv_cmvn_stats(0, m.ctypes.data, off.ctypes.data, -1, 5, st.ctypes.data, None))

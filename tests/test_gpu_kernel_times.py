@@ -32,8 +32,6 @@ def test_mfcc():
     samples = np.concatenate(waves)
     off = np.array([0, 400, 1400], np.int64)
     ms = ctypes.c_float(0)
-    L.xv_mfcc_kernel_time.argtypes = [ctypes.c_int, ctypes.POINTER(P.MfccOptions), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                      ctypes.c_int32, ctypes.POINTER(ctypes.c_float)]
     P._check(L.xv_mfcc_kernel_time(0, ctypes.byref(o), samples.ctypes.data, off.ctypes.data, 2, 2, ctypes.byref(ms)))
     print("mfcc %.4f ms" % ms.value)
     assert _valid(ms.value)

@@ -50,8 +50,6 @@ def main():
     off = np.array([0, T], np.int32)
     idx = np.zeros((T, n), np.int32)
     best = None
-    L.xv_ubm_gselect.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                 ctypes.c_void_p]
     for r in range(a.reps + 1):
         ms = ctypes.c_float()
         assert L.xv_ubm_gselect(diag._h, x.ctypes.data, off.ctypes.data, 1, n, idx.ctypes.data, None, ctypes.byref(ms)) == 0

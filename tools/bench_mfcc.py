@@ -40,8 +40,6 @@ def main():
         frames = sum(P.mfcc_num_frames(len(w), options=o) for w in waves)
         nbytes = samples.nbytes + frames * o.num_ceps * 4
         ms = ctypes.c_float(0)
-        L.xv_mfcc_kernel_time.argtypes = [ctypes.c_int, ctypes.POINTER(P.MfccOptions), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                          ctypes.c_int32, ctypes.POINTER(ctypes.c_float)]
         P._check(L.xv_mfcc_kernel_time(0, ctypes.byref(o), samples.ctypes.data, off.ctypes.data, n_utts, 5, ctypes.byref(ms)))
         P.mfcc(waves[:4], options=o)
         t0 = time.perf_counter()
