@@ -44,6 +44,7 @@
 #include <string>
 #include <vector>
 
+#include "batch_source.h"
 #include "cli.h"
 #include "feat_join.h"
 #include "gemm_plan.h"
@@ -665,9 +666,47 @@ int RunCli(const std::string& config_path) {
   return failures ? 1 : 0;
 }
 
+// ---------------------------------------------------- host_selftest batches <rspecifier> <readers> <views 0|1>
+// The table loop's batch source (batch_source.h) with limits of 16 rows and 4 utterances: one line per batch - keys with their
+// row counts, a hash of the rows - then the read-failure count, the pipe's status and the error; warnings go to stderr.
+int RunBatches(const std::string& rspec, int readers, bool views) {
+  xv::BatchSourceOptions o;
+  o.max_rows = 16;
+  o.max_utts = 4;
+  o.n_readers = readers;
+  o.views = views;
+  std::mutex warn_mu;
+  try {
+    xv::BatchSource src(rspec, o, [&warn_mu](const std::string& m) {
+      std::lock_guard<std::mutex> lk(warn_mu);
+      fprintf(stderr, "WARNING %s\n", m.c_str());
+    });
+    printf("addressable\t%d\n", src.addressable() ? 1 : 0);
+    src.Start();
+    xv::Batch b;
+    while (src.Next(&b)) {
+      Hash h;
+      std::string keys;
+      for (const xv::Utt& u : b.utts) {
+        keys += (keys.empty() ? "" : ",") + u.key + ":" + std::to_string(u.feats.rows) + "x" + std::to_string(u.feats.cols);
+        h.Add(u.feats.Data(), (size_t)u.feats.rows * u.feats.cols * sizeof(float));
+      }
+      printf("batch\t%s\t%016llx%s\n", keys.c_str(), (unsigned long long)h.h, b.last ? "\tlast" : "");
+      src.Recycle(std::move(b));
+      b = xv::Batch();
+    }
+    src.Finish();
+    printf("fail_read\t%ld\nstatus\t%d\nerror\t%s\n", src.num_fail_read(), src.reader_status(), src.error().c_str());
+  } catch (const std::exception& ex) {
+    printf("thrown\t%s\n", ex.what());
+  }
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc == 5 && strcmp(argv[1], "batches") == 0) return RunBatches(argv[2], atoi(argv[3]), atoi(argv[4]) != 0);
   if (argc == 2 && strcmp(argv[1], "gemm_plan") == 0) return RunGemmPlan();
   if (argc == 3 && strcmp(argv[1], "cli") == 0) return RunCli(argv[2]);
   if (argc == 3 && strcmp(argv[1], "tables") == 0) return RunTables(argv[2]);

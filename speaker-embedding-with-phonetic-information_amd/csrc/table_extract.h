@@ -12,6 +12,8 @@
 
 namespace xv {
 
+struct TableIndex;   // batch_source.h
+
 struct TableExtractResult {
   long num_success = 0;
   long num_fail = 0;
@@ -47,12 +49,7 @@ Engine::Calibration CalibrateOnUtterances(Engine* engine, const ExtractOptions& 
 // whole list and the choice is applied on every rank, so that an N-way sharded job computes what the 1-way job does.
 // `index` (optional): receives the index of an addressable table that the sample was drawn from - every entry, those with an
 // error included, and the message of whatever stopped the indexing early - so that the extraction's batching pass can reuse it
-// instead of visiting every header a second time.
-struct TableIndex {
-  bool valid = false;
-  std::vector<MatrixTableIndexer::Entry> entries;
-  std::string error;
-};
+// instead of visiting every header a second time (TableIndex: batch_source.h).
 Engine::Calibration CalibrateOnTable(Engine* engine, const ExtractOptions& opt, const std::string& feature_rspecifier,
                                      const LogFn& log, TableIndex* index = nullptr);
 

@@ -1,4 +1,4 @@
-"""nnet3-compute with the recipes' feature pipelines run on the device (csrc/fuse_pipe.h, table_extract.cc RunTableCompute): every
+"""nnet3-compute with the recipes' feature pipelines run on the device (csrc/fuse_pipe.h, table_compute.cc RunTableCompute): every
 case is the tool's command line run twice - as it is, where the pipeline is recognised and fused, and under XVEC_DEBUG=fuse_pipe=0,
 where the commands it names are run - and the two must write the same bytes, skip the same utterances with the same words and end
 with the same status.  The network is the "am" one of tests/helpers.py; --batch-frames=256 makes every job several batches."""

@@ -392,3 +392,42 @@ def test_cli_several_engines_threaded_consumers_write_the_one_engine_archive(tmp
     ref = dict(kio.read_ark(str(tmp_path / "one4096.ark"), "vector"))
     for k, v in got:
         np.testing.assert_array_equal(v, ref[k])
+
+
+def test_cli_every_ingestion_path_and_engine_count_writes_the_same_archive(tmp_path):
+    """The pieces of the table loop against each other: the stream reader, the index pass with one and with three readers, views of
+    the mapped archive and copies, one consumer on the calling thread and two consumer threads.  63 short utterances at
+    --batch-frames=256 are at least 14 batches, so every host slot of both engines is reused.  Archive, closing line and the set
+    of warnings are those of the default one-engine job."""
+    net, line = H.synth_model("v2_xvector")
+    (tmp_path / "final.raw").write_bytes(net.to_bytes(True))
+    rng = np.random.default_rng(17)
+    utts = [("utt%02d" % i, H.features(300 + i, int(T))) for i, T in enumerate(rng.integers(26, 121, 60))]
+    utts[20:20] = [("zero_len", np.zeros((0, 23), np.float32)), ("nine", H.features(7, 9)), ("bad_dim", np.ones((40, 24), np.float32))]
+    assert sum(x.shape[0] for _, x in utts if x.shape[1] == 23) >= 14 * 256   # at least 14 batches
+    kio.write_ark_matrices(str(tmp_path / "feats.ark"), utts, scp_path=str(tmp_path / "feats.scp"))
+    exe = os.path.join(H.ROOT, H.PKG_NAME, "bin", "nnet3-xvector-compute")
+    ark, scp = "ark:%s/feats.ark" % tmp_path, "scp:%s/feats.scp" % tmp_path
+    runs = [("ref", ark, ""), ("r1", ark, "readers=1"), ("scp3", scp, "readers=3,engines_on_one_device=2"),
+            ("pipe", "ark:cat %s/feats.ark |" % tmp_path, "engines_on_one_device=2"), ("nomap", ark, "mmap=0,engines_on_one_device=2")]
+    seen = {}
+    for tag, rspec, knobs in runs:   # (a failing run ends the test: nothing more is started)
+        env = dict(os.environ, XVEC_DEBUG=knobs) if knobs else dict(os.environ)
+        r = subprocess.run([exe, "--use-gpu=yes", "--min-chunk-size=25", "--chunk-size=10000", "--output-node=tdnn6.affine", "--batch-frames=256",
+                            str(tmp_path / "final.raw"), rspec, "ark:%s/%s.ark" % (tmp_path, tag)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, env=env)
+        assert r.returncode == 0, (tag, r.stderr[-2000:])
+        lines = r.stderr.splitlines()
+        seen[tag] = ((tmp_path / ("%s.ark" % tag)).read_bytes(), [l for l in lines if "Done " in l][-1].split("Done")[-1],
+                     sorted(l.split("WARNING")[-1] for l in lines if "WARNING" in l))
+        if "engines_on_one_device=2" in knobs:
+            assert "2 engines on device" in r.stderr, r.stderr[-2000:]
+        assert seen[tag][0] == seen["ref"][0], tag
+        assert seen[tag][1] == seen["ref"][1], (tag, seen[tag][1], seen["ref"][1])
+        assert seen[tag][2] == seen["ref"][2], (tag, seen[tag][2], seen["ref"][2])
+    # what the reference run itself must show: the empty and the wrong-width utterance are refused with a warning each, the one of
+    # 9 frames is padded to the minimum chunk (--pad-input is on by default) and written with the 60 others
+    warned = seen["ref"][2]
+    assert len(warned) == 2 and "Zero-length utterance: zero_len" in warned[0] and "utterance bad_dim does not match" in warned[1], warned
+    assert seen["ref"][1] == " 61 utterances, failed for 2", seen["ref"][1]
+    assert b"nine " in seen["ref"][0] and b"zero_len " not in seen["ref"][0] and b"bad_dim " not in seen["ref"][0]
