@@ -7,7 +7,8 @@ computed here from the two restatements.  A case is one utterance: one (impulse 
 compared and asserted on its own samples.  The
 kernel's partition size is 2048 taps and filters of up to 64 taps are convolved directly, so the RIR lengths stand below, at
 and above both.  int16 parity of the tool's file: no sample further than 1 from trunc(ref64), and the share of differing
-samples at most 4 x the share by which trunc(ref32) differs, with a floor of 1e-4."""
+samples at most 4 x the share by which trunc(ref32) differs, with a floor of 1e-4.
+The kernels' own edges (partitions, early slice, chunks, saturation thresholds, group cap): tests/test_gpu_reverb_edges.py."""
 import os
 import subprocess
 
