@@ -310,7 +310,8 @@ xv_status xv_segment_mean(int device, const float* x, int32_t n, int32_t dim, co
  *                      (Kaldi's defaults 1.0, 0.3, 0.7); mean_out[dim], transform_out[dim][dim], psi_out[dim] (descending);
  *                      s_out (optional, [dim]) = eigenvalues of the adaptation covariance in the space where the model's
  *                      total covariance is I, descending.
- * The device entries fail with XV_ERR_DEVICE when no gfx950 device is usable. */
+ * The device entries fail with XV_ERR_DEVICE when no gfx950 device is usable.
+ * Score normalisation on top of xv_plda_score (all pairs, top-N statistics) is declared in xvec_hip_asnorm.h. */
 xv_status xv_scatter_stats(int device, const float* x, int32_t n, int32_t dim, const int32_t* seg_off, const int32_t* idx,
                            int32_t n_seg, double* s_tot, double* sums, double* s_bet, float* device_ms);
 xv_status xv_plda_transform(int device, const float* x, int32_t n, int32_t dim, const double* transform, const double* offset,

@@ -291,6 +291,15 @@ SIGNATURES = {
 }
 ABI_SYMBOLS = list(SIGNATURES)
 
+# The same for include/xvec_hip_asnorm.h, the companion header of score normalisation (tests/test_plda_dense_host.py holds this
+# table to that header).
+ASNORM_SIGNATURES = {
+    "xv_plda_score_dense": (ST, [c_int, VP, VP, I32, VP, I32, I32, VP, VP, VP]),
+    "xv_topn_stats": (ST, [c_int, VP, I64, I32, I32, VP, VP, VP]),
+    "xv_plda_cohort_stats": (ST, [c_int, VP, VP, I32, VP, I32, I32, VP, I32, I32, VP, VP, VP]),
+    "xv_plda_dense_plan": (ST, [I64, I64, I32, I64, PI64, PI64, PI64]),
+}
+
 _lib = None
 
 
@@ -312,10 +321,10 @@ def lib():
         except Exception:
             pass
     L = ctypes.CDLL(LIB_PATH)
-    missing = [s for s in SIGNATURES if not hasattr(L, s)]
+    missing = [s for s in list(SIGNATURES) + list(ASNORM_SIGNATURES) if not hasattr(L, s)]
     if missing:
         raise ImportError("%s does not export: %s" % (LIB_PATH, missing))
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(ASNORM_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype = restype
         fn.argtypes = argtypes

@@ -1,4 +1,4 @@
-// extern "C" boundary of libxvec_hip.so - see include/xvec_hip.h.
+// extern "C" boundary of libxvec_hip.so - see include/xvec_hip.h and include/xvec_hip_asnorm.h.
 #include <dlfcn.h>
 #include <stdlib.h>
 #include <string.h>
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/xvec_hip.h"
+#include "../../include/xvec_hip_asnorm.h"
 #include "backend.h"
 #include "cmvn.h"
 #include "compress.h"
@@ -27,6 +28,7 @@
 #include "nnet3_raw.h"
 #include "plda.h"
 #include "plda_kernels.h"
+#include "plda_dense_kernels.h"
 #include "post.h"
 #include "program.h"
 #include "table_extract.h"
@@ -608,6 +610,67 @@ xv_status xv_plda_score(int device, const float* u, const double* num_u, int32_t
     xv::PldaScore(device, u, num_u, n_u, v, n_v, dim, psi, trials, (long)n_trials, scores, device_ms);
     return XV_OK;
   });
+}
+
+xv_status xv_plda_score_dense(int device, const float* u, const double* num_u, int32_t n_u, const float* v, int32_t n_v, int32_t dim,
+                              const double* psi, double* scores, float* device_ms) {
+  if (n_u < 0 || n_v < 0 || dim < 1 || !psi || (n_u > 0 && (!u || !num_u)) || (n_v > 0 && !v) || (n_u > 0 && n_v > 0 && !scores))
+    return Fail(XV_ERR_ARG, "xv_plda_score_dense: bad argument");
+  if (dim > xv::kPldaMaxDim) return Fail(XV_ERR_ARG, "xv_plda_score_dense: dimension larger than " + std::to_string(xv::kPldaMaxDim));
+  for (int32_t k = 0; k < n_u; ++k)
+    if (!(num_u[k] > 0)) return Fail(XV_ERR_ARG, "xv_plda_score_dense: example counts must be positive");
+  return Guard([&] {
+    xv::PldaScoreDense(device, u, num_u, n_u, v, n_v, dim, psi, scores, device_ms);
+    return XV_OK;
+  });
+}
+
+// XV_ERR_ARG unless 2 <= n <= cols <= kTopnMaxCols
+static xv_status CheckTopn(const char* who, int64_t cols, int32_t n) {
+  if (cols > xv::kTopnMaxCols)
+    return Fail(XV_ERR_ARG, std::string(who) + ": " + std::to_string(cols) + " columns are more than kTopnMaxCols = " +
+                                std::to_string(xv::kTopnMaxCols));
+  if (cols < 2) return Fail(XV_ERR_ARG, std::string(who) + ": the statistics need at least two columns");
+  if (n < 2 || n > cols)
+    return Fail(XV_ERR_ARG, std::string(who) + ": N = " + std::to_string(n) + " is out of range [2, " + std::to_string(cols) + "]");
+  return XV_OK;
+}
+
+xv_status xv_topn_stats(int device, const double* scores, int64_t rows, int32_t cols, int32_t n, double* mean, double* std,
+                        float* device_ms) {
+  if (rows < 0 || rows > 0x7fffffffll || (rows > 0 && (!scores || !mean || !std))) return Fail(XV_ERR_ARG, "xv_topn_stats: bad argument");
+  if (const xv_status st = CheckTopn("xv_topn_stats", cols, n)) return st;
+  return Guard([&] {
+    xv::TopnStats(device, scores, rows, cols, n, mean, std, device_ms);
+    return XV_OK;
+  });
+}
+
+xv_status xv_plda_cohort_stats(int device, const float* u, const double* num_u, int32_t n_u, const float* v, int32_t n_v, int32_t dim,
+                               const double* psi, int32_t by_column, int32_t n, double* mean, double* std, float* device_ms) {
+  const int32_t rows = by_column ? n_v : n_u;
+  if (n_u < 0 || n_v < 0 || dim < 1 || !psi || (n_u > 0 && (!u || !num_u)) || (n_v > 0 && !v) || (rows > 0 && (!mean || !std)))
+    return Fail(XV_ERR_ARG, "xv_plda_cohort_stats: bad argument");
+  if (dim > xv::kPldaMaxDim) return Fail(XV_ERR_ARG, "xv_plda_cohort_stats: dimension larger than " + std::to_string(xv::kPldaMaxDim));
+  if (const xv_status st = CheckTopn("xv_plda_cohort_stats", by_column ? n_u : n_v, n)) return st;
+  for (int32_t k = 0; k < n_u; ++k)
+    if (!(num_u[k] > 0)) return Fail(XV_ERR_ARG, "xv_plda_cohort_stats: example counts must be positive");
+  return Guard([&] {
+    xv::PldaCohortStats(device, u, num_u, n_u, v, n_v, dim, psi, by_column != 0, n, mean, std, device_ms);
+    return XV_OK;
+  });
+}
+
+xv_status xv_plda_dense_plan(int64_t rows, int64_t cols, int32_t dim, int64_t workspace_bytes, int64_t* rows_per_chunk,
+                             int64_t* n_chunks, int64_t* chunk_bytes) {
+  xv::DensePlan plan;
+  std::string why;
+  if (!xv::PlanPldaDense(rows, cols, dim, workspace_bytes > 0 ? workspace_bytes : xv::kDenseDefaultWorkspace, &plan, &why))
+    return Fail(XV_ERR_ARG, "xv_plda_dense_plan: " + why);
+  if (rows_per_chunk) *rows_per_chunk = plan.rows_per_chunk;
+  if (n_chunks) *n_chunks = plan.n_chunks;
+  if (chunk_bytes) *chunk_bytes = plan.chunk_bytes;
+  return XV_OK;
 }
 
 xv_status xv_lda_estimate(int32_t dim, int64_t n, const double* s_tot, const double* s_bet, const float* mean,

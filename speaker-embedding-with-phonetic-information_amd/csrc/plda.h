@@ -25,6 +25,29 @@ void PldaTransform(int device, const float* x, int n, int dim, const double* tra
 void PldaScore(int device, const float* u, const double* num_u, int n_u, const float* v, int n_v, int dim,
                const double* psi, const int32_t* trials, long n_trials, double* scores, float* device_ms = nullptr);
 
+// ---- adaptive score normalisation (plda_dense.cc, plda_dense_kernels.h)
+// Plda::LogLikelihoodRatio of every pair (row i of u with num_u[i] examples, row j of v): scores [n_u][n_v].
+void PldaScoreDense(int device, const float* u, const double* num_u, int n_u, const float* v, int n_v, int dim, const double* psi,
+                    double* scores, float* device_ms = nullptr);
+// Mean and population standard deviation of the n largest values of every row of scores [rows][cols] (finite values).
+void TopnStats(int device, const double* scores, int64_t rows, int cols, int n, double* mean, double* std, float* device_ms = nullptr);
+// TopnStats of PldaScoreDense without the matrix leaving the device: per row of u over all of v, or (by_column) per row of v
+// over all of u.  The matrix exists one row chunk at a time in a workspace of at most DenseWorkspaceCap() bytes.
+void PldaCohortStats(int device, const float* u, const double* num_u, int n_u, const float* v, int n_v, int dim, const double* psi,
+                     bool by_column, int n, double* mean, double* std, float* device_ms = nullptr);
+// The chunks of a rows x cols score matrix (host only, pure): rows_per_chunk is the largest count of rows whose scores fit
+// the workspace, a multiple of the scoring kernel's row tile where it holds a tile at all, and at most what one launch's grid
+// covers; chunk c is rows [c rows_per_chunk, min(rows, (c + 1) rows_per_chunk)).  false with *why: a bad argument, or a
+// workspace that does not hold one row.
+struct DensePlan {
+  int64_t rows_per_chunk = 0, n_chunks = 0;
+  int64_t chunk_bytes = 0;   // what the driver allocates: min(rows, rows_per_chunk) rows
+};
+bool PlanPldaDense(int64_t rows, int64_t cols, int dim, int64_t workspace_bytes, DensePlan* out, std::string* why);
+constexpr int64_t kDenseDefaultWorkspace = (int64_t)256 << 20;
+// kDenseDefaultWorkspace, or the bytes that the environment variable XVEC_PLDA_DENSE_WORKSPACE names (tests: small chunks)
+int64_t DenseWorkspaceCap();
+
 // ---- the model: <Plda> mean transform psi </Plda>
 struct Plda {
   int dim = 0;

@@ -1,4 +1,5 @@
-// ivector-compute-lda / ivector-compute-plda / ivector-copy-plda / ivector-adapt-plda / ivector-plda-scoring / compute-eer -
+// ivector-compute-lda / ivector-compute-plda / ivector-copy-plda / ivector-adapt-plda / ivector-plda-scoring /
+// ivector-plda-scoring-asnorm / compute-eer -
 // drop-in command lines for the back-end stage of the recipes (stage 7 of egs/sre/v2/run_sre10.sh:221-252;
 // v5/run_sre10.sh:105-137, stage 2 of v2/run_sre16.sh:76-175), one executable dispatching on its name:
 //   ivector-compute-lda [--dim=100 --total-covariance-factor=0.0 --covariance-floor=1e-6 --binary=true]
@@ -10,6 +11,9 @@
 //   ivector-plda-scoring [--normalize-length=true --simple-length-normalization=false --num-utts=<rspecifier>]
 //                        <plda> <train-ivector-rspecifier> <test-ivector-rspecifier> <trials-rxfilename> <scores-wxfilename>
 //                                                                                                           :240-246
+//   ivector-plda-scoring-asnorm [the options of ivector-plda-scoring, --top-n=300 --train-stats=<wx> --test-stats=<wx>]
+//                        <plda> <train-ivector-rspecifier> <test-ivector-rspecifier> <cohort-ivector-rspecifier>
+//                        <trials-rxfilename> <scores-wxfilename>          (not in the recipes: INTEGRATION.md)
 //   compute-eer <scores-rxfilename>    ("score target|nontarget" lines; the EER in percent on stdout)           :252
 // The statistics over the vectors (for the adaptation: one segment that lists every vector), the PLDA transform of the
 // vectors and the per-trial scores run on the HIP device (plda.h); without a GPU these tools fail (exit 255).  compute-eer
@@ -22,6 +26,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <map>
 #include <numeric>
 #include <sstream>
@@ -50,6 +55,8 @@ struct Args {
   bool normalize_length = true;         // ivector-plda-scoring
   bool simple_length_norm = false;
   std::string num_utts;
+  int top_n = 300;                      // ivector-plda-scoring-asnorm
+  std::string train_stats, test_stats;
   int device = -1;
 };
 
@@ -280,110 +287,122 @@ class LineReader {
   size_t pos_ = 0, len_ = 0;
 };
 
-int PldaScoring(const Args& a) {
-  if (a.pos.size() != 5) return xv::kUsageError;
-  const int dev = xv::PickDevice(a.device);
-  xv::Plda plda;
-  xv::ReadPlda(a.pos[0], &plda);
-  const int dim = plda.dim;
-  std::unordered_map<std::string, int32_t> num_utts;
-  if (!a.num_utts.empty()) num_utts = xv::ReadInt32Table(a.num_utts);
+// One table of ivector-plda-scoring and its kin, transformed by the model: the rows that are kept, in table order.
+struct Side {
+  xv::Packed p;
+  std::vector<double> num;
+  std::vector<float> y;
+  std::unordered_map<std::string, int> row;
+};
+enum class SideKind { kTrain, kTest, kCohort };
 
-  // one table -> transformed vectors on the device
-  struct Side {
-    xv::Packed p;
-    std::vector<double> num;
-    std::vector<float> y;
-    std::unordered_map<std::string, int> row;
-  } train, test;
-  auto load = [&](const std::string& rspec, bool is_train, Side* s, long* n_err) {
-    xv::Packed raw;
-    long read_err = 0;
-    ReadAll(rspec, &raw, &read_err);
-    if (raw.n() > 0 && raw.dim != dim)
-      throw xv::KioError("iVector dimension " + std::to_string(raw.dim) + " does not match the PLDA dimension " + std::to_string(dim));
-    s->p.dim = dim;
-    for (int i = 0; i < raw.n(); ++i) {
-      const std::string& key = raw.keys[i];
-      if (s->row.count(key))
-        throw xv::KioError(std::string("Duplicate ") + (is_train ? "training iVector found for speaker " : "test iVector found for utterance ") + key);
-      double n = 1.0;
-      if (is_train && !a.num_utts.empty()) {
-        auto it = num_utts.find(key);
-        if (it == num_utts.end()) {
-          XWARN("Number of utterances not given for speaker " << key);
-          ++*n_err;
-          continue;
-        }
-        n = it->second;
-        if (n < 1) throw xv::KioError("number of utterances for speaker " + key + " is not positive");
+// Reads a table and transforms it on the device; returns the sum of the renormalisation scales.  A training table takes its
+// example counts from num_utts when --num-utts is given (a key without one is skipped and counted in *n_err).  finite_only:
+// a value that is not finite is an error.
+double LoadSide(const Args& a, int dev, const xv::Plda& plda, const std::unordered_map<std::string, int32_t>& num_utts,
+                const std::string& rspec, SideKind kind, bool finite_only, Side* s, long* n_err) {
+  const int dim = plda.dim;
+  const bool is_train = kind == SideKind::kTrain;
+  xv::Packed raw;
+  long read_err = 0;
+  ReadAll(rspec, &raw, &read_err);
+  if (raw.n() > 0 && raw.dim != dim)
+    throw xv::KioError("iVector dimension " + std::to_string(raw.dim) + " does not match the PLDA dimension " + std::to_string(dim));
+  s->p.dim = dim;
+  for (int i = 0; i < raw.n(); ++i) {
+    const std::string& key = raw.keys[i];
+    if (s->row.count(key))
+      throw xv::KioError(std::string("Duplicate ") + (is_train ? "training iVector found for speaker "
+                                                       : kind == SideKind::kTest ? "test iVector found for utterance "
+                                                                                 : "cohort iVector found for utterance ") + key);
+    if (finite_only)
+      for (int d = 0; d < dim; ++d)
+        if (!std::isfinite(raw.data[(size_t)i * dim + d])) throw xv::KioError("iVector " + key + " of " + rspec + " has a value that is not finite");
+    double n = 1.0;
+    if (is_train && !a.num_utts.empty()) {
+      auto it = num_utts.find(key);
+      if (it == num_utts.end()) {
+        XWARN("Number of utterances not given for speaker " << key);
+        ++*n_err;
+        continue;
       }
-      s->row.emplace(key, s->p.n());
-      s->p.keys.push_back(key);
-      s->p.data.insert(s->p.data.end(), raw.data.begin() + (size_t)i * dim, raw.data.begin() + (size_t)(i + 1) * dim);
-      s->num.push_back(n);
+      n = it->second;
+      if (n < 1) throw xv::KioError("number of utterances for speaker " + key + " is not positive");
     }
-    std::vector<double> scale(s->p.n());
-    s->y.resize(s->p.data.size());
-    xv::PldaTransform(dev, s->p.data.data(), s->p.n(), dim, plda.transform.data(), plda.offset.data(), plda.psi.data(),
-                      s->num.data(), a.normalize_length, a.simple_length_norm, s->y.data(), scale.data());
-    double tot = 0;
-    for (double x : scale) tot += x;
-    return tot;
-  };
+    s->row.emplace(key, s->p.n());
+    s->p.keys.push_back(key);
+    s->p.data.insert(s->p.data.end(), raw.data.begin() + (size_t)i * dim, raw.data.begin() + (size_t)(i + 1) * dim);
+    s->num.push_back(n);
+  }
+  std::vector<double> scale(s->p.n());
+  s->y.resize(s->p.data.size());
+  xv::PldaTransform(dev, s->p.data.data(), s->p.n(), dim, plda.transform.data(), plda.offset.data(), plda.psi.data(),
+                    s->num.data(), a.normalize_length, a.simple_length_norm, s->y.data(), scale.data());
+  double tot = 0;
+  for (double x : scale) tot += x;
+  return tot;
+}
+
+// The training and the test table, with the log lines of ivector-plda-scoring.
+void LoadTrainAndTest(const Args& a, int dev, const xv::Plda& plda, const std::unordered_map<std::string, int32_t>& num_utts,
+                      bool finite_only, Side* train, Side* test) {
   long n_train_err = 0, n_test_err = 0;
   XLOG("Reading train iVectors");
-  const double train_scale = load(a.pos[1], true, &train, &n_train_err);
-  XLOG("Read " << train.p.n() << " training iVectors, errors on " << n_train_err);
-  if (train.p.n() == 0) throw xv::KioError("No training iVectors present.");
-  XLOG("Average renormalization scale on training iVectors was " << train_scale / train.p.n());
+  const double train_scale = LoadSide(a, dev, plda, num_utts, a.pos[1], SideKind::kTrain, finite_only, train, &n_train_err);
+  XLOG("Read " << train->p.n() << " training iVectors, errors on " << n_train_err);
+  if (train->p.n() == 0) throw xv::KioError("No training iVectors present.");
+  XLOG("Average renormalization scale on training iVectors was " << train_scale / train->p.n());
   XLOG("Reading test iVectors");
-  const double test_scale = load(a.pos[2], false, &test, &n_test_err);
-  XLOG("Read " << test.p.n() << " test iVectors.");
-  if (test.p.n() == 0) throw xv::KioError("No test iVectors present.");
-  XLOG("Average renormalization scale on test iVectors was " << test_scale / test.p.n());
+  const double test_scale = LoadSide(a, dev, plda, num_utts, a.pos[2], SideKind::kTest, finite_only, test, &n_test_err);
+  XLOG("Read " << test->p.n() << " test iVectors.");
+  if (test->p.n() == 0) throw xv::KioError("No test iVectors present.");
+  XLOG("Average renormalization scale on test iVectors was " << test_scale / test->p.n());
+}
 
-  // trials, in input order; lines whose keys are missing are skipped
-  using Clock = std::chrono::steady_clock;
-  auto secs = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-  const Clock::time_point t0 = Clock::now();
-  LineReader lr(a.pos[3]);
-  std::string line;
-  std::vector<std::string> f;
-  std::vector<int32_t> pairs;
-  std::vector<size_t> line_of;      // trial -> index into names
+// The trials of an rxfilename, in input order; lines whose keys are missing are skipped and counted.
+struct Trials {
+  std::vector<int32_t> pairs;       // (training row, test row) of every scored trial
   std::vector<std::string> names;   // "key1 key2 " of every scored trial
   long n_err = 0;
+  long n() const { return (long)names.size(); }
+};
+
+void ReadTrials(const std::string& rx, const Side& train, const Side& test, Trials* t) {
+  LineReader lr(rx);
+  std::string line;
+  std::vector<std::string> f;
   while (lr.Next(&line)) {
     SplitFields(line, &f);
     if (f.size() != 2)
-      throw xv::KioError("Bad line " + std::to_string(names.size() + n_err) + " in input (expected two fields: key1 key2): " + line);
+      throw xv::KioError("Bad line " + std::to_string(t->names.size() + t->n_err) + " in input (expected two fields: key1 key2): " + line);
     auto i1 = train.row.find(f[0]);
     if (i1 == train.row.end()) {
       XWARN("Key " << f[0] << " not present in training iVectors.");
-      ++n_err;
+      ++t->n_err;
       continue;
     }
     auto i2 = test.row.find(f[1]);
     if (i2 == test.row.end()) {
       XWARN("Key " << f[1] << " not present in test iVectors.");
-      ++n_err;
+      ++t->n_err;
       continue;
     }
-    pairs.push_back(i1->second);
-    pairs.push_back(i2->second);
-    names.push_back(f[0] + " " + f[1] + " ");
+    t->pairs.push_back(i1->second);
+    t->pairs.push_back(i2->second);
+    t->names.push_back(f[0] + " " + f[1] + " ");
   }
   const int st = lr.Close();
-  if (st != 0) throw xv::KioError("the trials command of " + a.pos[3] + " exited with status " + std::to_string(st));
+  if (st != 0) throw xv::KioError("the trials command of " + rx + " exited with status " + std::to_string(st));
+}
+
+using Clock = std::chrono::steady_clock;
+double Secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+
+// "<names[i]><score as BaseFloat>" lines (the stream's default 6 significant digits) and the log line of their statistics.
+void WriteScores(const std::string& wx, const std::vector<std::string>& names, const std::vector<double>& scores) {
   const long n_done = (long)names.size();
-  const Clock::time_point t1 = Clock::now();
-  std::vector<double> scores(n_done);
-  xv::PldaScore(dev, train.y.data(), train.num.data(), train.p.n(), test.y.data(), test.p.n(), dim, plda.psi.data(),
-                pairs.data(), n_done, scores.data());
-  const Clock::time_point t2 = Clock::now();
   xv::Output out;
-  out.Open(a.pos[4]);
+  out.Open(wx);
   double sum = 0, sumsq = 0;
   std::ostringstream o;
   for (long i = 0; i < n_done; ++i) {
@@ -397,14 +416,139 @@ int PldaScoring(const Args& a) {
     }
   }
   out.Close();
-  const Clock::time_point t3 = Clock::now();
   if (n_done != 0) {
     const float mean = (float)(sum / n_done), scatter = (float)(sumsq / n_done), var = scatter - mean * mean;
     XLOG("Mean score was " << mean << ", standard deviation was " << sqrtf(var > 0 ? var : 0));
   }
+}
+
+int PldaScoring(const Args& a) {
+  if (a.pos.size() != 5) return xv::kUsageError;
+  const int dev = xv::PickDevice(a.device);
+  xv::Plda plda;
+  xv::ReadPlda(a.pos[0], &plda);
+  const int dim = plda.dim;
+  std::unordered_map<std::string, int32_t> num_utts;
+  if (!a.num_utts.empty()) num_utts = xv::ReadInt32Table(a.num_utts);
+  Side train, test;
+  LoadTrainAndTest(a, dev, plda, num_utts, /*finite_only=*/false, &train, &test);
+
+  const Clock::time_point t0 = Clock::now();
+  Trials tr;
+  ReadTrials(a.pos[3], train, test, &tr);
+  const long n_done = tr.n();
+  const Clock::time_point t1 = Clock::now();
+  std::vector<double> scores(n_done);
+  xv::PldaScore(dev, train.y.data(), train.num.data(), train.p.n(), test.y.data(), test.p.n(), dim, plda.psi.data(),
+                tr.pairs.data(), n_done, scores.data());
+  const Clock::time_point t2 = Clock::now();
+  WriteScores(a.pos[4], tr.names, scores);
+  const Clock::time_point t3 = Clock::now();
+  XLOG("Processed " << n_done << " trials, " << tr.n_err << " had errors.");
+  XLOG("Timing: trials read in " << Secs(t0, t1) << " s, scored on the device in " << Secs(t1, t2) << " s, written in "
+                                 << Secs(t2, t3) << " s");
+  return n_done != 0 ? 0 : 1;
+}
+
+// "key mean std" lines, one per listed row, in table order.
+void WriteStats(const std::string& wx, const Side& s, const std::vector<int32_t>& rows, const std::vector<double>& mean,
+                const std::vector<double>& std) {
+  xv::Output out;
+  out.Open(wx);
+  std::ostringstream o;
+  o.precision(17);
+  for (size_t i = 0; i < rows.size(); ++i) o << s.p.keys[rows[i]] << ' ' << mean[i] << ' ' << std[i] << '\n';
+  out.Puts(o.str());
+  out.Close();
+}
+
+// Adaptive symmetric score normalisation: every trial's raw score s is ivector-plda-scoring's; the
+// enrolment row e and the test row t of the trial are each scored against the whole cohort on the device, S_e[c] = LLR(e with
+// num_e examples, c) and S_t[c] = LLR(c with one example, t), and the mean and standard deviation of the --top-n largest of
+// each give 1/2 ((s - mu_e) / sigma_e + (s - mu_t) / sigma_t).
+int PldaScoringAsnorm(const Args& a) {
+  if (a.pos.size() != 6) return xv::kUsageError;
+  if (a.top_n < 2) throw xv::KioError("--top-n=" + std::to_string(a.top_n) + " is out of range: the statistics need at least two scores");
+  const int dev = xv::PickDevice(a.device);
+  xv::Plda plda;
+  xv::ReadPlda(a.pos[0], &plda);
+  const int dim = plda.dim;
+  std::unordered_map<std::string, int32_t> num_utts;
+  if (!a.num_utts.empty()) num_utts = xv::ReadInt32Table(a.num_utts);
+  Side train, test, cohort;
+  LoadTrainAndTest(a, dev, plda, num_utts, /*finite_only=*/true, &train, &test);
+  XLOG("Reading cohort iVectors");
+  long n_cohort_err = 0;
+  const double cohort_scale = LoadSide(a, dev, plda, num_utts, a.pos[3], SideKind::kCohort, true, &cohort, &n_cohort_err);
+  XLOG("Read " << cohort.p.n() << " cohort iVectors.");
+  const int n_cohort = cohort.p.n();
+  if (n_cohort < 2) throw xv::KioError("The cohort has " + std::to_string(n_cohort) + " iVectors: score normalisation needs at least two.");
+  XLOG("Average renormalization scale on cohort iVectors was " << cohort_scale / n_cohort);
+  int top_n = a.top_n;
+  if (top_n > n_cohort) {
+    XLOG("--top-n=" << top_n << " is more than the cohort holds: using all " << n_cohort << " cohort scores (S-norm).");
+    top_n = n_cohort;
+  }
+
+  const Clock::time_point t0 = Clock::now();
+  Trials tr;
+  ReadTrials(a.pos[4], train, test, &tr);
+  const long n_read = tr.n();
+  const Clock::time_point t1 = Clock::now();
+  std::vector<double> raw(n_read);
+  xv::PldaScore(dev, train.y.data(), train.num.data(), train.p.n(), test.y.data(), test.p.n(), dim, plda.psi.data(),
+                tr.pairs.data(), n_read, raw.data());
+  // the rows that occur in a scored trial, in table order, and their place among those
+  auto used = [&](const Side& s, int which, std::vector<int32_t>* rows, std::vector<int32_t>* place) {
+    place->assign(s.p.n(), -1);
+    for (long i = 0; i < n_read; ++i) (*place)[tr.pairs[2 * i + which]] = 0;
+    for (int r = 0; r < s.p.n(); ++r)
+      if ((*place)[r] == 0) {
+        (*place)[r] = (int32_t)rows->size();
+        rows->push_back(r);
+      }
+  };
+  auto gather = [&](const Side& s, const std::vector<int32_t>& rows, std::vector<float>* y, std::vector<double>* num) {
+    for (int32_t r : rows) {
+      y->insert(y->end(), s.y.begin() + (size_t)r * dim, s.y.begin() + (size_t)(r + 1) * dim);
+      num->push_back(s.num[r]);
+    }
+  };
+  std::vector<int32_t> e_rows, e_place, t_rows, t_place;
+  used(train, 0, &e_rows, &e_place);
+  used(test, 1, &t_rows, &t_place);
+  std::vector<float> e_y, t_y;
+  std::vector<double> e_num, t_num;
+  gather(train, e_rows, &e_y, &e_num);
+  gather(test, t_rows, &t_y, &t_num);
+  std::vector<double> e_mean(e_rows.size()), e_std(e_rows.size()), t_mean(t_rows.size()), t_std(t_rows.size());
+  xv::PldaCohortStats(dev, e_y.data(), e_num.data(), (int)e_rows.size(), cohort.y.data(), n_cohort, dim, plda.psi.data(),
+                      /*by_column=*/false, top_n, e_mean.data(), e_std.data());
+  xv::PldaCohortStats(dev, cohort.y.data(), cohort.num.data(), n_cohort, t_y.data(), (int)t_rows.size(), dim, plda.psi.data(),
+                      /*by_column=*/true, top_n, t_mean.data(), t_std.data());
+  std::vector<std::string> names;
+  std::vector<double> scores;
+  long n_err = tr.n_err;
+  for (long i = 0; i < n_read; ++i) {
+    const int e = e_place[tr.pairs[2 * i]], t = t_place[tr.pairs[2 * i + 1]];
+    if (e_std[e] == 0.0 || t_std[t] == 0.0) {
+      XWARN("The cohort scores of " << (e_std[e] == 0.0 ? train.p.keys[tr.pairs[2 * i]] : test.p.keys[tr.pairs[2 * i + 1]])
+                                   << " have standard deviation 0: not normalising trial " << tr.names[i]);
+      ++n_err;
+      continue;
+    }
+    names.push_back(tr.names[i]);
+    scores.push_back(0.5 * ((raw[i] - e_mean[e]) / e_std[e] + (raw[i] - t_mean[t]) / t_std[t]));
+  }
+  const long n_done = (long)names.size();
+  const Clock::time_point t2 = Clock::now();
+  WriteScores(a.pos[5], names, scores);
+  if (!a.train_stats.empty()) WriteStats(a.train_stats, train, e_rows, e_mean, e_std);
+  if (!a.test_stats.empty()) WriteStats(a.test_stats, test, t_rows, t_mean, t_std);
+  const Clock::time_point t3 = Clock::now();
   XLOG("Processed " << n_done << " trials, " << n_err << " had errors.");
-  XLOG("Timing: trials read in " << secs(t0, t1) << " s, scored on the device in " << secs(t1, t2) << " s, written in "
-                                 << secs(t2, t3) << " s");
+  XLOG("Timing: trials read in " << Secs(t0, t1) << " s, scored and normalised on the device in " << Secs(t1, t2) << " s, written in "
+                                 << Secs(t2, t3) << " s");
   return n_done != 0 ? 0 : 1;
 }
 
@@ -502,6 +646,19 @@ int main(int argc, char** argv) {
            {xv::Bool("normalize-length", &a.normalize_length), xv::Bool("simple-length-normalization", &a.simple_length_norm),
             xv::String("num-utts", &a.num_utts)},
            PldaScoring),
+      tool("ivector-plda-scoring-asnorm",
+           "Computes log-likelihood ratios for trials using PLDA model, as ivector-plda-scoring does, and normalises each with the\n"
+           "statistics of its two sides against a cohort (adaptive symmetric normalisation, AS-norm): the mean and standard\n"
+           "deviation of the --top-n highest scores of the speaker against the cohort, and of the cohort against the utterance.\n"
+           "The output has lines 'key1 key2 normalised-score'.\n"
+           "Usage: ivector-plda-scoring-asnorm [options] <plda> <train-ivector-rspecifier> <test-ivector-rspecifier>\n"
+           "                                   <cohort-ivector-rspecifier> <trials-rxfilename> <scores-wxfilename>\n"
+           "Options: --num-utts=<rspecifier> --normalize-length=true --simple-length-normalization=false --top-n=300\n"
+           "         --train-stats=<wxfilename> --test-stats=<wxfilename>  ('key mean std' of every speaker / utterance in a trial)\n",
+           {xv::Bool("normalize-length", &a.normalize_length), xv::Bool("simple-length-normalization", &a.simple_length_norm),
+            xv::String("num-utts", &a.num_utts), xv::Int("top-n", &a.top_n), xv::String("train-stats", &a.train_stats),
+            xv::String("test-stats", &a.test_stats)},
+           PldaScoringAsnorm),
   };
   return xv::ToolsMain(argc, argv, tools, xv::NameRule::kExact, "ivector-plda-scoring");
 }
