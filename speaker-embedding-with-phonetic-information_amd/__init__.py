@@ -8,7 +8,8 @@ library is missing or no gfx950 device is present, calls fail loudly.
 
 _abi.py states the ABI once (constants, struct mirrors, every function's signature) and loads the library; the
 other modules hold the wrappers, one module per stage of the C sources.  Every public name lives here, except those of
-score normalisation, which came later and stay in their module (asnorm, for include/xvec_hip_asnorm.h).
+score normalisation and of nnet-am-compute, which came later and stay in their modules (asnorm, for include/xvec_hip_asnorm.h;
+nnet2, for include/xvec_hip_nnet2.h).
 """
 import os
 import subprocess
@@ -26,6 +27,7 @@ from ._abi import (ABI_SYMBOLS, EPI_ACT, EPI_F32, EPI_STATS, MFMA_PASSES, PREC_A
                    ReverbOptions, SegDesc, VadOptions, XvError, _check, lib)
 from ._marshal import _segments  # noqa: E402,F401
 from . import asnorm  # noqa: E402,F401  (score normalisation: a module of its own, as its header is)
+from . import nnet2  # noqa: E402,F401  (nnet-am-compute: the same)
 from .backend import (backend_apply, lda_estimate, plda_adapt, plda_estimate, plda_score, plda_transform, scatter_stats,  # noqa: E402,F401
                       segment_mean)
 from .extractor import (Context, Model, Watchdog, calibration_file_publish, calibration_file_read, create_broadcast,  # noqa: E402,F401

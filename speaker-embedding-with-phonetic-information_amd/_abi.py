@@ -300,6 +300,29 @@ ASNORM_SIGNATURES = {
     "xv_plda_dense_plan": (ST, [I64, I64, I32, I64, PI64, PI64, PI64]),
 }
 
+
+class Nnet2Info(ctypes.Structure):
+    """xv_nnet2_info_t (include/xvec_hip_nnet2.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("num_components", "num_updatable_components", "left_context", "right_context", "input_dim",
+                                              "output_dim", "softmax_dim", "prior_dim", "num_layers", "max_plane_cols", "max_pre_cols",
+                                              "halo")] + [("parameter_dim", ctypes.c_int64)]
+
+
+# The same for include/xvec_hip_nnet2.h, the companion header of nnet-am-compute (tests/test_nnet2_abi_table.py holds this table to
+# that header).
+NNET2_SIGNATURES = {
+    "xv_nnet2_open": (ST, [STR, PVP]),
+    "xv_nnet2_close": (None, [VP]),
+    "xv_nnet2_get_info": (ST, [VP, POINTER(Nnet2Info)]),
+    "xv_nnet2_plan": (ST, [POINTER(Nnet2Info), I64, I64, I64, PI64, PI64, PI64]),
+    "xv_nnet2_compute": (ST, [VP, c_int, VP, VP, I32, I32, I64, VP, PF32]),
+    "xv_nnet2_compute_layers": (ST, [VP, c_int, VP, VP, I32, I32, I64, VP, VP]),
+    "xv_nnet2_kernel_affine": (ST, [c_int, VP, I32, I32, VP, I32, VP, VP, I32, VP]),
+    "xv_nnet2_kernel_row": (ST, [c_int, VP, I32, I32, I32, I32, I32, VP, VP]),
+    "xv_nnet2_kernel_head": (ST, [c_int, VP, I32, I32, VP, I32, VP, I32, VP]),
+}
+COMPANION_SIGNATURES = dict(ASNORM_SIGNATURES, **NNET2_SIGNATURES)
+
 _lib = None
 
 
@@ -321,10 +344,10 @@ def lib():
         except Exception:
             pass
     L = ctypes.CDLL(LIB_PATH)
-    missing = [s for s in list(SIGNATURES) + list(ASNORM_SIGNATURES) if not hasattr(L, s)]
+    missing = [s for s in list(SIGNATURES) + list(COMPANION_SIGNATURES) if not hasattr(L, s)]
     if missing:
         raise ImportError("%s does not export: %s" % (LIB_PATH, missing))
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(ASNORM_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(COMPANION_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype = restype
         fn.argtypes = argtypes

@@ -4,12 +4,14 @@
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/xvec_hip.h"
 #include "../../include/xvec_hip_asnorm.h"
+#include "../../include/xvec_hip_nnet2.h"
 #include "backend.h"
 #include "cmvn.h"
 #include "compress.h"
@@ -25,6 +27,8 @@
 #include "fuse_pipe.h"
 #include "fuse_wav.h"
 #include "multi_gpu.h"
+#include "nnet2.h"
+#include "nnet2_kernels.h"
 #include "nnet3_raw.h"
 #include "plda.h"
 #include "plda_kernels.h"
@@ -671,6 +675,111 @@ xv_status xv_plda_dense_plan(int64_t rows, int64_t cols, int32_t dim, int64_t wo
   if (n_chunks) *n_chunks = plan.n_chunks;
   if (chunk_bytes) *chunk_bytes = plan.chunk_bytes;
   return XV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// nnet-am-compute (xvec_hip_nnet2.h)
+struct xv_nnet2 {
+  std::unique_ptr<xv::Nnet2> net;
+};
+
+xv_status xv_nnet2_open(const char* model_rxfilename, xv_nnet2** out) {
+  if (!model_rxfilename || !out) return Fail(XV_ERR_ARG, "xv_nnet2_open: bad argument");
+  *out = nullptr;
+  return Guard([&] {
+    std::unique_ptr<xv_nnet2> m(new xv_nnet2);
+    m->net.reset(new xv::Nnet2(model_rxfilename));
+    *out = m.release();
+    return XV_OK;
+  });
+}
+
+void xv_nnet2_close(xv_nnet2* m) { delete m; }
+
+xv_status xv_nnet2_get_info(const xv_nnet2* m, xv_nnet2_info_t* info) {
+  if (!m || !info) return Fail(XV_ERR_ARG, "xv_nnet2_get_info: bad argument");
+  const xv::Nnet2Model& mod = m->net->model();
+  const xv::Nnet2Dims& d = m->net->dims();
+  memset(info, 0, sizeof *info);
+  info->num_components = (int32_t)mod.components.size();
+  info->num_updatable_components = mod.num_updatable;
+  info->left_context = d.left_context;
+  info->right_context = d.right_context;
+  info->input_dim = d.input_dim;
+  info->output_dim = d.output_dim;
+  info->softmax_dim = d.softmax_dim;
+  info->prior_dim = (int32_t)mod.priors.size();
+  info->num_layers = (int32_t)mod.layers.size();
+  info->max_plane_cols = d.max_plane_cols;
+  info->max_pre_cols = d.max_pre_cols;
+  info->halo = d.halo;
+  info->parameter_dim = mod.parameter_dim;
+  return XV_OK;
+}
+
+xv_status xv_nnet2_plan(const xv_nnet2_info_t* info, int64_t rows, int64_t block_rows, int64_t workspace_bytes, int64_t* rows_per_block,
+                        int64_t* n_blocks, int64_t* bytes) {
+  if (!info) return Fail(XV_ERR_ARG, "xv_nnet2_plan: bad argument");
+  xv::Nnet2Dims d;
+  d.input_dim = info->input_dim;
+  d.output_dim = info->output_dim;
+  d.softmax_dim = info->softmax_dim;
+  d.left_context = info->left_context;
+  d.right_context = info->right_context;
+  d.max_plane_cols = info->max_plane_cols;
+  d.max_pre_cols = info->max_pre_cols;
+  d.halo = info->halo;
+  xv::Nnet2BlockPlan plan;
+  std::string why;
+  if (!xv::Nnet2Plan(d, rows, block_rows, workspace_bytes, &plan, &why)) return Fail(XV_ERR_ARG, "xv_nnet2_plan: " + why);
+  if (rows_per_block) *rows_per_block = plan.rows_per_block;
+  if (n_blocks) *n_blocks = plan.n_blocks;
+  if (bytes) *bytes = plan.bytes;
+  return XV_OK;
+}
+
+// The stage checks its own arguments (nnet2.cc) and says so with Nnet2ArgError.
+static xv_status Nnet2Guard(const std::function<void()>& f) {
+  return Guard([&] {
+    try {
+      f();
+    } catch (const xv::Nnet2ArgError& e) {
+      return Fail(XV_ERR_ARG, e.what());
+    }
+    return XV_OK;
+  });
+}
+
+static xv_status Nnet2ComputeCommon(xv_nnet2* m, int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t flags,
+                                    int64_t block_rows, float* out, float* device_ms, float* layer_ms) {
+  if (!m) return Fail(XV_ERR_ARG, "xv_nnet2_compute: bad argument");
+  return Nnet2Guard([&] { m->net->Compute(device, feats, row_off, n_utts, flags, block_rows, out, device_ms, layer_ms); });
+}
+
+xv_status xv_nnet2_compute(xv_nnet2* m, int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t flags,
+                           int64_t block_rows, float* out, float* device_ms) {
+  return Nnet2ComputeCommon(m, device, feats, row_off, n_utts, flags, block_rows, out, device_ms, nullptr);
+}
+
+xv_status xv_nnet2_compute_layers(xv_nnet2* m, int device, const float* feats, const int32_t* row_off, int32_t n_utts, int32_t flags,
+                                  int64_t block_rows, float* out, float* layer_ms) {
+  if (!layer_ms) return Fail(XV_ERR_ARG, "xv_nnet2_compute_layers: bad argument");
+  return Nnet2ComputeCommon(m, device, feats, row_off, n_utts, flags, block_rows, out, nullptr, layer_ms);
+}
+
+xv_status xv_nnet2_kernel_affine(int device, const float* x, int32_t rows, int32_t k, const int32_t* context, int32_t n_ctx, const float* w,
+                                 const float* bias, int32_t n, float* out) {
+  return Nnet2Guard([&] { xv::Nnet2KernelAffine(device, x, rows, k, context, n_ctx, w, bias, n, out); });
+}
+
+xv_status xv_nnet2_kernel_row(int device, const float* pre, int32_t rows, int32_t in_dim, int32_t out_dim, int32_t nonlin, int32_t normalize,
+                              uint16_t* hi, uint16_t* lo) {
+  return Nnet2Guard([&] { xv::Nnet2KernelRow(device, pre, rows, in_dim, out_dim, nonlin, normalize != 0, hi, lo); });
+}
+
+xv_status xv_nnet2_kernel_head(int device, const float* logits, int32_t rows, int32_t n, const int32_t* sizes, int32_t n_groups,
+                               const float* priors, int32_t apply_log, float* out) {
+  return Nnet2Guard([&] { xv::Nnet2KernelHead(device, logits, rows, n, sizes, n_groups, priors, apply_log != 0, out); });
 }
 
 xv_status xv_lda_estimate(int32_t dim, int64_t n, const double* s_tot, const double* s_bet, const float* mean,
